@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — fp64 CSR SpMV throughput of the HIP path on 1..N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3] [--kernel ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3] [--kernel ...] [--full] [--dump-outputs DIR]
+
+A plain run does only what its headline needs: set-up, W warm-up steps, K timed steps, the result line.  `--full` adds
+everything else the line can carry, each measured or checked after the timed region: parity against the CPU oracle, the
+CPU baselines and the PCIe-inclusive calls, the cold / in-pipeline / value-update / stream-read figures (N = 1), and for
+N > 1 the compute-only overlap and the one-process form.  `--dump-outputs DIR` writes what the last timed step handed its
+caller as DIR/<name>.npy (float64; `dump_outputs`).
 
 With --gpus N > 1 and no torchrun environment (RANK unset) the script starts its N ranks ITSELF, as a child process
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, decided before anything touches the GPU), relays the
@@ -67,6 +73,24 @@ WORKLOADS = {
     "fe_spmm8": dict(kind="fe", n=4 * 69 ** 3, k=1, cells=68, bcsr=True, spmm=8, desc="the FE matrix as BCSR 4x4, Y = A X for 8 column vectors in one launch (spmm_avx2.c)"),
     "fe_bcsr": dict(kind="fe", n=4 * 69 ** 3, k=1, cells=68, bcsr=True, desc="same FE matrix as BCSR 4x4 (SpMV_BCSR path, mpk/SpMV.cpp:90-219), y=Ax"),
 }
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array as dirname/<name>.npy, float64.  Where the arrays hold more than `limit` bytes in all, each one
+    is cut to a fixed sample of its entries (flattened, indices drawn from a generator seeded 0x5EED and sorted), the same on
+    every run with the same arguments, so that two builds can be compared entry for entry."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit:
+            keep = max(1, a.size * limit // total)
+            idx = np.sort(np.random.default_rng(0x5EED).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def algorithmic_bytes(n, nnz):
@@ -240,11 +264,13 @@ def single_process_main(args):
         step()
     D.synchronize()
     wall = time.perf_counter() - t0
+    got = [t.get() for t in outs] if (args.dump_outputs or (args.full and not args.no_parity)) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y" if k == 1 else f"y{i + 1}": got[i] for i in range(k)})
     parity = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         from oracle import oracle as O  # checker only
         Y = O.spmk_chain(k, p, c, v, x_host)
-        got = [t.get() for t in outs]
         parity = dict(rel_error=max(O.rel_error(Y[i], got[i]) for i in range(k)),
                       bitwise=all(np.array_equal(Y[i].view(np.uint64), got[i].view(np.uint64)) for i in range(k)),
                       against="oracle/cpu_ref.c fma chain (= reference SpMV_CSR_OPT/_FMA), full vectors gathered from the ranks")
@@ -281,7 +307,7 @@ def run_single_process_child(args, timeout_s=240):
     env = {k_: v_ for k_, v_ in os.environ.items() if k_ not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
                                                                   "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--single-process", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--workload", args.workload]
+           "--workload", args.workload, "--full"]
     if "MI355_FORCE_DEVICE" in os.environ:  # development: every rank on one card
         env["MI355_DIST_DEVICES"] = os.environ["MI355_FORCE_DEVICE"]
     try:
@@ -322,7 +348,14 @@ def main():
                     "single-process harnesses reach through the shim with MI355_NGPUS=N) instead of one process per GPU")
     ap.add_argument("--no-single-process-extra", action="store_true", help="N > 1: do not also time the one-process form (a child process of rank 0, "
                     "after the timed region; reported as `single_process`, never as `value`)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline (parity, CPU baselines, cold / pipeline / "
+                    "value-update / stream-read figures, PCIe-inclusive calls; N > 1: compute-only overlap, the one-process form); the --no-* options "
+                    "above switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed, the arrays its caller receives, "
+                    "as DIR/<name>.npy (float64; a fixed seeded sample where they exceed 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.single_process:
         return single_process_main(args)
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -606,25 +639,32 @@ def main():
             if ex != chosen:
                 alive.pop(ex)[0].close()
         dc, step, x_ext, y, pbufs = alive[chosen]
-        # what the same rank's kernels cost WITHOUT any exchange (pack + interior rows + boundary rows, back to back), slowest rank
-        L_ = mpk.lib()
-        ybuf = dc.new_y()
-        sbuf = torch.empty(max(dc.n_send, 1), dtype=torch.float64, device="cuda")
-        vp_ = _ct.c_void_p
+        us_step = probes[chosen]["step_us"]
+        overlap = dict(step_us=us_step)
+        if args.full:
+            # what the same rank's kernels cost WITHOUT any exchange (pack + interior rows + boundary rows, back to back), slowest rank
+            L_ = mpk.lib()
+            ybuf = dc.new_y()
+            sbuf = torch.empty(max(dc.n_send, 1), dtype=torch.float64, device="cuda")
+            vp_ = _ct.c_void_p
 
-        def compute_only():
-            for _ in range(k):
-                mpk.check(L_.mi_part_pack_dev(dc._h, vp_(x_ext.data_ptr()), vp_(sbuf.data_ptr()), sp))
-                mpk.check(L_.mi_part_spmv_interior_dev(dc._h, vp_(x_ext.data_ptr()), vp_(ybuf.data_ptr()), sp))
-                mpk.check(L_.mi_part_spmv_boundary_dev(dc._h, vp_(x_ext.data_ptr()), vp_(ybuf.data_ptr()), sp))
-        for _ in range(3):
-            compute_only()
-        us_compute = timed_max_us(compute_only, probe_steps)
+            def compute_only():
+                for _ in range(k):
+                    mpk.check(L_.mi_part_pack_dev(dc._h, vp_(x_ext.data_ptr()), vp_(sbuf.data_ptr()), sp))
+                    mpk.check(L_.mi_part_spmv_interior_dev(dc._h, vp_(x_ext.data_ptr()), vp_(ybuf.data_ptr()), sp))
+                    mpk.check(L_.mi_part_spmv_boundary_dev(dc._h, vp_(x_ext.data_ptr()), vp_(ybuf.data_ptr()), sp))
+            for _ in range(3):
+                compute_only()
+            us_compute = timed_max_us(compute_only, probe_steps)
+            overlap.update(compute_only_us=round(us_compute, 2), exchange_exposed_us=round(us_step - us_compute, 2),
+                           compute_over_step=round(us_compute / us_step, 4),
+                           note="compute_only = pack + interior rows + boundary rows of the same rank with NO exchange, slowest rank; "
+                                "exposed = what the exchange adds to the step (negative: the one-launch step is cheaper than the three kernels it replaces)")
+            del ybuf, sbuf
         tb = torch.tensor([8.0 * dc.n_send * k, 8.0 * dc.n_halo * k], dtype=torch.float64, device=red_dev0)
         tb_max = tb.clone()
         dist.all_reduce(tb, op=dist.ReduceOp.SUM)
         dist.all_reduce(tb_max, op=dist.ReduceOp.MAX)
-        us_step = probes[chosen]["step_us"]
         halo_info = dict(n_halo=dc.n_halo, n_send=dc.n_send, interior_rows=dc.n_interior, boundary_rows=dc.n_boundary,
                          exchange=("peer push over HIP IPC windows, no RCCL (mi_part_spmv_push_dev), " + probes[chosen]["form"]) if chosen == "push"
                          else ("native RCCL send/recv (mi_part_spmv_dev)" if chosen == "native" else
@@ -633,14 +673,10 @@ def main():
                          exchanges=probes,
                          exchange_bytes_per_step=dict(sent_all_ranks=int(tb[0]), received_all_ranks=int(tb[1]), sent_max_rank=int(tb_max[0]),
                                                       received_max_rank=int(tb_max[1]), note="8 B per halo entry, once per product"),
-                         overlap=dict(step_us=us_step, compute_only_us=round(us_compute, 2), exchange_exposed_us=round(us_step - us_compute, 2),
-                                      compute_over_step=round(us_compute / us_step, 4),
-                                      note="compute_only = pack + interior rows + boundary rows of the same rank with NO exchange, slowest rank; "
-                                           "exposed = what the exchange adds to the step (negative: the one-launch step is cheaper than the three kernels it replaces)"),
+                         overlap=overlap,
                          rccl_ranks=rccl_ranks, torch_backend=backend, torch_world=world,
                          probe_seconds=dict(phase_s, note="wall seconds per candidate exchange on rank 0: DistCSR create (partition, pieces, their create-time "
                                                           "measurements, the exchange's set-up and bitwise self-check) + dry run + timing"))
-        del ybuf, sbuf
     torch.cuda.synchronize()
     t_setup = time.perf_counter() - t_setup
 
@@ -684,9 +720,21 @@ def main():
             print(f"[rank {rank}] {e}", file=sys.stderr, flush=True)
         if agree_min(fine) == 0:
             sys.exit("a halo wait gave up during the timed region: no number to report")
-    # ---- the same kernel in two other regimes (N = 1, y = A x workloads only; never `value`) -------------------
+    # ---- what the last timed step handed its caller (--dump-outputs) -----------------------------------------
+    if args.dump_outputs:
+        if world == 1 and bcsr and W.get("spmm"):
+            outputs = {"Y": Yd.cpu().numpy()}
+        elif world == 1:
+            outputs = {("y" if k == 1 else f"y{i + 1}"): t.cpu().numpy() for i, t in enumerate(ys)}
+        elif k == 1:
+            outputs = {f"y_rank{rank}": y.cpu().numpy()}
+        else:
+            outputs = {f"y{i + 1}_rank{rank}": pbufs[i][: dc.n_local].cpu().numpy() for i in range(k)}
+        dump_outputs(args.dump_outputs, outputs, limit=DUMP_LIMIT_BYTES // world)
+        del outputs
+    # ---- the same kernel in two other regimes (N = 1, y = A x workloads only; --full; never `value`) -------------
     extra = {}
-    if world == 1 and k == 1 and not args.cold and not args.no_extras and not W.get("spmm") and not args.internal:
+    if world == 1 and k == 1 and args.full and not args.cold and not args.no_extras and not W.get("spmm") and not args.internal:
         # (1) cold single shot: L2s and the 256 MiB Infinity Cache evicted before EVERY launch (the reference's own
         #     protocol: flush_cache() before each timed call, mpk/SpM2V.cpp:895-904)
         #     Two forms: the eviction ENQUEUED in front of the launch (cold caches, GPU never idle: what "cold cache" means on
@@ -745,7 +793,7 @@ def main():
     # (3) what a Newton iteration pays beside its products (src/solve_newton.c:1245-1247: the Jacobian's VALUES change every iteration, the
     #     pattern never): mi_csr_update_values_dev on the benched handle — CSR values, the sliced copy the headline kernel streams and the
     #     blocked copy where there is one, refilled on the update's stream — and what the handle keeps allocated on the device.
-    if world == 1 and not args.no_extras and k == 1 and not W.get("spmm"):
+    if world == 1 and args.full and not args.no_extras and k == 1 and not W.get("spmm"):
         vdev = torch.from_numpy(np.ascontiguousarray(bv if bcsr else v)).cuda()  # the same values: the parity check below still sees the timed region's result
         for _ in range(2):
             A.update_values(vdev)
@@ -766,7 +814,7 @@ def main():
 
     # ---- parity of what was just timed (rank-local rows, against the oracle) ---------------------
     parity = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         from oracle import oracle as O  # checker only
         if world == 1 and bcsr and W.get("spmm"):
             got = Yd.cpu().numpy()
@@ -872,7 +920,7 @@ def main():
         roofline["frac_note"] = ("frac = algorithmic bytes / launch time / peak (the contract's definition); frac_on_traffic = the profiled fabric traffic of this kernel "
                                  "(FETCH_SIZE x 2 + WRITE_SIZE) over the same time: what actually moved, as a fraction of the 8 TB/s peak — a frac above 1.0 means the "
                                  "kernel's format holds fewer bytes than the CSR model charges for, not that memory ran above its peak")
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         # this box's own streaming rate: a plain read sweep over as many bytes as the kernel's format holds (MI355X boxes of one
         # pool differ by 10-20 % in it); NOT the roofline's peak — `frac` stays priced against the 8 TB/s spec
         us_stream = mpk.stream_read_us(B_exec)
@@ -971,13 +1019,13 @@ def main():
     # (the one-process extra costs another mi_dist_create over all N devices: skipped — collectively, by rank 0's clock — when this run has
     # already used more than 120 s, so that the whole command stays well inside the driver's window)
     sp_budget_ok = True
-    if world > 1:
+    if world > 1 and args.full:
         used = torch.tensor([time.time() - (float(os.environ.get("MI355_BENCH_T0", "0")) or t_wall0)], dtype=torch.float64, device=red_dev)
         dist.broadcast(used, src=0)
         sp_budget_ok = float(used) <= float(os.environ.get("MI355_BENCH_SP_BUDGET_S", "120"))
         if not sp_budget_ok and rank == 0 and not args.no_single_process_extra:
             out["single_process"] = dict(ok=False, skipped=True, note=f"skipped: the process-per-GPU path had used {float(used):.0f} s of wall time (> 120 s) when it was its turn")
-    if world > 1 and sp_budget_ok and not args.no_single_process_extra and kind in ("s15", "fe") and not args.cold:
+    if world > 1 and args.full and sp_budget_ok and not args.no_single_process_extra and kind in ("s15", "fe") and not args.cold:
         # the same workload through ONE process (mi_dist_*), as a child of rank 0.  The other ranks wait on the HOST — a key in the
         # process group's own TCP store — so that no collective kernel spins on their GPUs while the child measures; everything here
         # is bounded (child: 200 s; the wait: 260 s) and a failure costs the line nothing but the field.
@@ -1005,7 +1053,7 @@ def main():
                 store.wait([key], datetime.timedelta(seconds=260))
             except Exception:  # noqa: BLE001 — rank 0 never got there: nothing to wait for any longer
                 pass
-    if rank == 0 and world == 1 and not bcsr and k == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and not bcsr and k == 1 and args.full and not args.no_cpu_baseline:
         # the reference's calling convention (host pointers): x H2D + kernel + y D2H per call; never `value`
         xh, yh = x_host, np.empty(n)
         mpk.SpMV_CSR(yh, xh, A)
@@ -1015,7 +1063,7 @@ def main():
         t1 = (time.perf_counter() - t1) / 3
         out["pcie_inclusive"] = dict(gflops=round(2.0 * nnz_global / t1 / 1e9, 2), ms_per_call=round(t1 * 1e3, 3),
                                      note="mi_spmv with host vectors (pageable numpy): x in, y out over PCIe every call")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(p, c, v, x_host)
         out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
         out["gpu_over_cpu_all_cores"] = round(value / out["cpu_baseline"]["all_cores"]["value"], 1)

@@ -6,6 +6,7 @@ proper: they call the HIP path through the C-ABI on cuda:0 and compare with the
 oracle.  Nothing here reads /root/reference at run time; tests that compare the
 oracle with the real reference object code skip when oracle/_ref is absent.
 """
+import hashlib
 import os
 import subprocess
 import sys
@@ -57,3 +58,13 @@ def assert_bit_equal(a, b, what=""):
     assert a.shape == b.shape, f"{what}: shape {a.shape} vs {b.shape}"
     bad = np.nonzero(bits(a) != bits(b))[0]
     assert bad.size == 0, f"{what}: {bad.size} of {a.size} entries differ bitwise, first at {bad[:5]}: {a.reshape(-1)[bad[:5]]} vs {b.reshape(-1)[bad[:5]]}"
+
+
+def digest(a):
+    """sha256 of an array's shape and values (float64 bits, int64 for integer arrays): equal digests = bit-equal arrays.
+    The reference's recorded outputs (tests/golden/ref_digests.json) are kept in this form."""
+    a = np.asarray(a)
+    a = np.ascontiguousarray(a, dtype=np.int64 if np.issubdtype(a.dtype, np.integer) else np.float64)
+    h = hashlib.sha256(repr(a.shape).encode())
+    h.update(a.tobytes())
+    return h.hexdigest()

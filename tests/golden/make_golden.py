@@ -10,6 +10,7 @@ files hold DATA only: inputs and expected outputs as raw float64/int32.
 
     python tests/golden/make_golden.py
 """
+import json
 import os
 import sys
 
@@ -17,6 +18,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))  # the test modules name their cases; conftest.digest
 from navierstokes_amd import synth  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
@@ -98,9 +100,80 @@ def blas1_case(name, n, m, alpha, seed):
     print(name, "n", n, "m", m)
 
 
+def ref_digests():
+    """tests/test_oracle_vs_reference.py: every output of the reference's object code on that module's cases, as
+    conftest.digest values (a few KB instead of megabytes of vectors)."""
+    import test_oracle_vs_reference as T
+    from conftest import digest
+    d = {}
+    for kind, n, w in T.SPMV_CASES:
+        p, c, v = synth.rows(kind, n, w=w)
+        x = synth.x_sin(0, n)
+        for var in ("opt", "fma", "scalar"):
+            d[T.case_id("spmv", kind, n, w, var)] = digest(O.ref_spmv(p, c, v, x, var))
+    for kind, n, w in T.POWERS_CASES:
+        p, c, v = synth.rows(kind, n, w=w)
+        x = synth.x_ones(n)
+        d[T.case_id("powers", kind, n, w, "layer1")] = digest(O.ref_gen_layer1(p, c))
+        y, z = O.ref_spm2v(p, c, v, x, "opt")
+        d[T.case_id("powers", kind, n, w, "spm2v_opt_y")], d[T.case_id("powers", kind, n, w, "spm2v_opt_z")] = digest(y), digest(z)
+        for k in (2, 3, 4):
+            d[T.case_id("powers", kind, n, w, f"powers{k}")] = digest(O.ref_powers(k, p, c, v, x))
+    for nrow, ir, jc, va in T.coo_inputs():
+        for name, arrs in (("csr", O.ref_coo2csr(nrow, ir, jc, va)), ("bcsr4", O.ref_coo2bcsr4(nrow, ir, jc, va))):
+            for i, a in enumerate(arrs):
+                d[T.case_id("coo", nrow, name, i)] = digest(a)
+    for n, b, x1, B in T.blas1_inputs():
+        d[T.case_id("blas1", n, "orthogonalize3")] = digest(O.ref_orthogonalize3(b, x1, 0.37))
+        d[T.case_id("blas1", n, "orthogonalize_inplace")] = digest(O.ref_orthogonalize_inplace(b, x1, 0.37))
+        d[T.case_id("blas1", n, "mgs")] = digest(O.ref_mgs(B, x1))
+    for kind, n, w in T.LAYER_CASES:
+        p, c, v = synth.rows(kind, n, w=w)
+        lay = O.ref_gen_layers(p, c)
+        for name in lay:
+            d[T.case_id("layers", kind, n, w, name)] = digest(lay[name])
+        d[T.case_id("layers", kind, n, w, "keys")] = sorted(lay)
+        d[T.case_id("layers", kind, n, w, "spm4v_avx2")] = digest(O.ref_spm4v_avx2(p, c, v, synth.x_sin(0, n)))
+    with open(os.path.join(OUT, "ref_digests.json"), "w") as f:
+        json.dump(d, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("ref_digests", len(d), "entries")
+
+
+def fe_ref_blocks():
+    """tests/test_fe_matrix.py: the node blocks composed from the reference's src/integration.c object code for the
+    seeded tetrahedra of test_element_blocks_vs_reference_object_code."""
+    import test_fe_matrix as T
+    tets = np.array(T.positive_tets(T.REF_TETS, T.REF_TETS_SEED))
+    blocks = np.array([T.reference_blocks(a, T.REF_RE, T.REF_DELTA) for a in tets])
+    np.savez(os.path.join(OUT, "fe_ref_blocks.npz"), tets=tets, blocks=blocks, Re=T.REF_RE, delta=T.REF_DELTA)
+    print("fe_ref_blocks", blocks.shape)
+
+
+def ref_symbols():
+    """tests/test_capi_symbols.py: the function symbols the reference's objects define (oracle/_ref/libref_*.so): mangled
+    for SpMV.cpp + utils.cpp, demangled names for the matrix-powers drivers' objects."""
+    import subprocess
+
+    def nm(path, *flags):
+        return subprocess.check_output(["nm", "-D", "--defined-only", *flags, path], text=True)
+    d = {"libref_spmv_mangled": sorted({ln.split()[-1] for ln in nm(os.path.join(ROOT, "oracle", "_ref", "libref_spmv.so")).splitlines()
+                                        if " T " in ln and ln.split()[-1].startswith("_Z")})}
+    for lib in ("spm2v", "multi0", "2spmv", "multi1"):
+        dem = nm(os.path.join(ROOT, "oracle", "_ref", f"libref_{lib}.so"), "-C")
+        d[f"libref_{lib}_functions"] = sorted({ln.split(" T ", 1)[1].split("(")[0] for ln in dem.splitlines() if " T " in ln and "(" in ln})
+    with open(os.path.join(OUT, "ref_symbols.json"), "w") as f:
+        json.dump(d, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("ref_symbols", {k: len(v) for k, v in d.items()})
+
+
 def main():
     if not O.have_ref():
         sys.exit("oracle/_ref is not built: run `make -C oracle` where /root/reference exists")
+    ref_digests()
+    fe_ref_blocks()
+    ref_symbols()
     csr_case("s15_n512", "s15", 512, 40, "sin")
     csr_case("svar_n400", "svar", 400, 30, "sin")
     csr_case("sfe_n268", "sfe", 268, 40, "ones")  # 268 rows = mat/matrix1 (mpk/log/log_SPMV.txt:1)

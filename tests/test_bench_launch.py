@@ -28,7 +28,7 @@ def test_bench_gpus_2_on_one_card_prints_one_json_line():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(MI355_FORCE_DEVICE="0", MI355_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "10", "--warmup", "3"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "10", "--warmup", "3", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -61,7 +61,7 @@ def test_bench_single_process_prints_one_json_line():
     """`python3 bench.py --gpus 3 --single-process`: one process, three ranks behind a mi_dist handle (all on cuda:0 here), k = 4 powers."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--single-process", "--workload", "c3", "--steps", "5", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--single-process", "--workload", "c3", "--steps", "5", "--warmup", "2", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -92,3 +92,57 @@ def test_roofline_traffic_comes_from_a_committed_profile_of_the_same_kernel_fami
     assert srcb.endswith("_bench_fe_bcsr_pmc.json") and tb > 0
     assert bench.load_traffic("c4", "some_other_kernel<1>") == (None, None)
     assert bench.load_traffic("no_such_workload", "spmv_sstream<8, true, 0>") == (None, None)
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_writes_float64_and_a_fixed_sample_above_the_limit(tmp_path):
+    """--dump-outputs: arrays within the limit are written whole; above it every array is cut to the same seeded sample on every call."""
+    import numpy as np
+    bench = _load_bench()
+    y = np.sin(np.arange(1000.0))
+    Y = np.cos(np.arange(3000.0)).reshape(3, 1000)
+    bench.dump_outputs(str(tmp_path / "whole"), {"y": y, "Y": Y}, limit=1 << 20)
+    assert np.array_equal(np.load(tmp_path / "whole" / "y.npy"), y)
+    got = np.load(tmp_path / "whole" / "Y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, Y)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"y": y, "Y": Y}, limit=8 * 400)
+    a, b = np.load(tmp_path / "a" / "Y.npy"), np.load(tmp_path / "b" / "Y.npy")
+    assert np.array_equal(a, b) and a.dtype == np.float64
+    assert a.nbytes + np.load(tmp_path / "a" / "y.npy").nbytes <= 8 * 400
+    assert np.isin(a, Y).all()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_what_it_timed(tmp_path):
+    """A plain run prints the headline line without the --full measurements and checks; --dump-outputs leaves y = A x of the
+    last timed step, bitwise what the oracle computes for the same seeded inputs."""
+    import json
+    import numpy as np
+    from navierstokes_amd import synth
+    from oracle import oracle as O
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "GFLOP/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    for moved in ("parity", "cpu_baseline", "pcie_inclusive"):
+        assert moved not in d, moved
+    assert not {"cold_single_shot", "in_pipeline", "newton_refresh", "this_box_stream_read"} & set(d["roofline"])
+    n = d["config"]["n"]
+    y = np.load(out / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (n,)
+    p, c, v = synth.rows("s15", n)
+    ref = O.spmk_chain(1, p, c, v, synth.x_sin(0, n))[0]
+    assert np.array_equal(ref.view(np.uint64), y.view(np.uint64))

@@ -1,6 +1,6 @@
 """FE matrix generator (navierstokes_amd/csrc/fe_matrix.c): element blocks against the
-reference's src/integration.c object code (live when oracle/_ref is built, else the committed
-goldens), assembly rule, structure, and GPU parity on the assembled matrix."""
+reference's src/integration.c object code (its outputs recorded under tests/golden/, and live in
+the assembly check when oracle/_ref is built), assembly rule, structure, and GPU parity on the assembled matrix."""
 import ctypes
 import os
 
@@ -12,6 +12,7 @@ from navierstokes_amd import synth
 from oracle import oracle as O
 
 REFLIB = os.path.join(ROOT, "oracle", "_ref", "libref_integration.so")
+REF_TETS, REF_TETS_SEED, REF_RE, REF_DELTA = 300, 11, 100.0, 0.05  # the cases of tests/golden/fe_ref_blocks.npz
 
 
 def reference_blocks(a, Re, delta):
@@ -71,11 +72,14 @@ def test_element_blocks_golden():
     assert np.abs(mine - g["unit_blocks"]).max() <= 1e-13 * np.abs(g["unit_blocks"]).max()
 
 
-@pytest.mark.skipif(not os.path.exists(REFLIB), reason="oracle/_ref/libref_integration.so not built")
 def test_element_blocks_vs_reference_object_code():
-    for a in positive_tets(300, 11):
-        ref = reference_blocks(a, 100.0, 0.05)
-        mine = synth.fe_element_blocks(a, 100.0, 0.05)
+    """Against the blocks reference_blocks composed from the reference's object code for these tetrahedra, recorded in
+    tests/golden/fe_ref_blocks.npz (tests/golden/make_golden.py)."""
+    g = np.load(os.path.join(GOLDEN, "fe_ref_blocks.npz"))
+    tets = positive_tets(REF_TETS, REF_TETS_SEED)
+    assert float(g["Re"]) == REF_RE and float(g["delta"]) == REF_DELTA and np.array_equal(np.array(tets), g["tets"])
+    for a, ref in zip(tets, g["blocks"]):
+        mine = synth.fe_element_blocks(a, REF_RE, REF_DELTA)
         assert np.abs(mine - ref).max() <= 1e-12 * np.abs(ref).max()
 
 

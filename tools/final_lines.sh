@@ -11,17 +11,17 @@ run() { # args of bench.py
   [ $rc -ge 124 ] && exit $rc
   return 0
 }
-run
-run --workload c2
-run --workload c3
-run --workload fe
-run --workload fe_bcsr
-run --workload fe_spmm4
-run --workload fe_spmm8
-run --workload mesh
-run --workload c2_perm
-run --workload c2_perm --internal
-run --workload fe_perm
-run --workload mesh_perm --internal
-run --cold --steps 30 --warmup 3 --no-cpu-baseline
+run --full
+run --full --workload c2
+run --full --workload c3
+run --full --workload fe
+run --full --workload fe_bcsr
+run --full --workload fe_spmm4
+run --full --workload fe_spmm8
+run --full --workload mesh
+run --full --workload c2_perm
+run --full --workload c2_perm --internal
+run --full --workload fe_perm
+run --full --workload mesh_perm --internal
+run --full --cold --steps 30 --warmup 3 --no-cpu-baseline
 echo FINAL_DONE
