@@ -98,7 +98,8 @@ int mi_flush_cache_async(mi_stream_t s);
 /* Upload a csrmatrix (mpk/SpMV.h:18-24: n, ptrow[n+1], indcol, coef; nnz taken
  * from ptrow[n], not from the possibly stale csrmatrix::nnz — mpk/utils.cpp:100).
  * ncols = length of the x vectors (n for the reference's square matrices).
- * Host pointers. */
+ * Host pointers.  The handle is complete on return and usable from any stream,
+ * non-blocking ones included (so are mi_csr_create_mapped's and mi_csr_set_kernel's). */
 int mi_csr_create(int n, int ncols, const int* ptrow, const int* indcol, const double* coef, mi_csr_t* out);
 /* Same, for a row subset whose results are scattered: row r of this matrix
  * writes y[rowmap[r]] (rowmap == NULL: y[r]).  Used for the interior/boundary
@@ -349,6 +350,7 @@ int mi_rel_error_dev(int n, const double* d_ref, const double* d_test, double* d
 int mi_gather_dev(int m, const int* d_idx, const double* d_src, double* d_dst, mi_stream_t s);
 
 /* ---- BCSR 4x4 (SpMV_BCSR*, mpk/SpMV.cpp:90-219; row-major blocks) ------- */
+/* The handle is complete on return and usable from any stream, non-blocking ones included. */
 int mi_bcsr4_create(int nbrows, int nbcols, const int* ptrow, const int* indcol, const double* coef,
                     mi_bcsr4_t* out);
 int mi_bcsr4_destroy(mi_bcsr4_t A);

@@ -183,6 +183,11 @@ extern "C" int mi_bcsr4_create(int nbrows, int nbcols, const int* ptrow, const i
             }
         }
     }
+    // the handle is complete on return (the sliced values are filled on the null stream, which a non-blocking stream does not wait for)
+    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) {
+        mi_bcsr4_destroy(A);
+        return fail(MI_ERR_HIP, std::string("mi_bcsr4_create: ") + hipGetErrorString(e));
+    }
     *out = A;
     return MI_OK;
 }

@@ -850,6 +850,9 @@ int csr_create_impl(int n, int ncols, const int* ptrow, const int* indcol, const
             if (rcp == MI_OK && A->kept_x == tx) tx = ty = nullptr; // the handle keeps the pair (mi_vec_alloc_placed's first candidate)
         }
     }
+    // the handle is complete on return: the fills, zeroed paddings and uploads queued on the null stream above are done, so the first
+    // product may come on any stream (a non-blocking one is not ordered behind the null stream)
+    TRY_OR_CLEAN(hipStreamSynchronize(nullptr));
 #undef TRY_OR_CLEAN
     *out = A;
     return MI_OK;
@@ -981,7 +984,8 @@ extern "C" int mi_csr_create(int n, int ncols, const int* ptrow, const int* indc
     // (placement draws deferred: a handle that maybe_reorder replaces by its relabelled twin would draw for arrays it is about to release)
     int rc = csr_create_impl(n, ncols, ptrow, indcol, coef, nullptr, out, 0, 0, true);
     if (rc) return rc;
-    if ((rc = maybe_reorder(*out, ptrow, indcol, coef)) || (!(*out)->inner && (rc = placement_draws(*out, nullptr, nullptr, n == ncols)))) {
+    if ((rc = maybe_reorder(*out, ptrow, indcol, coef)) || (!(*out)->inner && (rc = placement_draws(*out, nullptr, nullptr, n == ncols))) ||
+        (hipStreamSynchronize(nullptr) != hipSuccess && (rc = fail(MI_ERR_HIP, "mi_csr_create: synchronize")))) {
         mi_csr_destroy(*out);
         *out = nullptr;
     }
@@ -1744,7 +1748,6 @@ extern "C" int mi_csr_set_kernel(mi_csr_t A, int kernel_id)
         HIP_TRY(hipMemcpy(back.data(), A->d_indcol, sizeof(int) * (size_t)A->nnz, hipMemcpyDeviceToHost));
         if ((rc = build_sstream(A, A->h_ptrow.data(), back.data(), A->ghost_lo, A->ghost_hi))) return rc;
         A->ss.asked = true;
-        HIP_TRY(hipStreamSynchronize(nullptr)); // (the sliced values were filled on the null stream)
     }
     if (kernel_id == MI_KERNEL_SSTREAM && !A->ss.dev.val)
         return fail(MI_ERR_UNSUPPORTED, "MI_KERNEL_SSTREAM: the handle holds no sliced copy (the matrix pads too much or its rows do "
@@ -1762,6 +1765,7 @@ extern "C" int mi_csr_set_kernel(mi_csr_t A, int kernel_id)
         if ((rc = build_mring(A, nullptr, large_row_align(A->nnz)))) return rc;
     }
     A->kernel = kernel_id;
+    HIP_TRY(hipStreamSynchronize(nullptr)); // (whatever a plan built on request queued on the null stream: usable from any stream on return)
     return MI_OK;
 }
 

@@ -84,6 +84,7 @@ static int spmk_setup(mi_csr_t H)
     hipError_t e;
     const size_t nflag = (size_t)R.wgs * kSpmkFlagStride;
     if ((e = hipMalloc(&H->d_kflags, sizeof(unsigned) * nflag)) != hipSuccess || (e = hipMemset(H->d_kflags, 0, sizeof(unsigned) * nflag)) != hipSuccess ||
+        (e = hipStreamSynchronize(nullptr)) != hipSuccess || // (the zeroed flags, before the first step on the caller's stream reads them)
         (e = hipMalloc(&H->d_kdep_ptr, sizeof(int) * R.h_dep_ptr.size())) != hipSuccess ||
         (e = hipMalloc(&H->d_kdep_run, sizeof(int) * std::max<size_t>(1, R.h_dep_run.size()))) != hipSuccess ||
         (e = hipMemcpy(H->d_kdep_ptr, R.h_dep_ptr.data(), sizeof(int) * R.h_dep_ptr.size(), hipMemcpyHostToDevice)) != hipSuccess ||

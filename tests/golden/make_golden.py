@@ -134,6 +134,15 @@ def ref_digests():
             d[T.case_id("layers", kind, n, w, name)] = digest(lay[name])
         d[T.case_id("layers", kind, n, w, "keys")] = sorted(lay)
         d[T.case_id("layers", kind, n, w, "spm4v_avx2")] = digest(O.ref_spm4v_avx2(p, c, v, synth.x_sin(0, n)))
+    for pat, name, p, c, v, x, block, _ in T.ieee_inputs():
+        key = lambda what: T.case_id("ieee", pat, name, what)
+        for var in ("opt", "fma"):
+            d[key("spmv_" + var)] = digest(T.canon_nan(O.ref_spmv(p, c, v, x, var)))
+        if block == 4:
+            bp, bc, bv = synth.csr_to_bcsr4(p, c, v)
+            d[key("spmv_bcsr_fma")] = digest(T.canon_nan(O.ref_spmv_bcsr(bp, bc, bv, x, "fma")))
+        y, z = O.ref_spm2v(p, c, v, x, "opt")
+        d[key("spm2v_opt_y")], d[key("spm2v_opt_z")] = digest(T.canon_nan(y)), digest(T.canon_nan(z))
     with open(os.path.join(OUT, "ref_digests.json"), "w") as f:
         json.dump(d, f, indent=0, sort_keys=True)
         f.write("\n")

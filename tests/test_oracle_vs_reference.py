@@ -39,6 +39,129 @@ def blas1_inputs():
         yield n, b, x1, B
 
 
+# ---- IEEE edge values (also applied to every product path on the GPU, tests/test_gpu_edges.py) ------------------------------
+# Each case takes a pattern (ptrow, indcol), its node block (4: FE node blocks, edits keep whole 4x4 blocks; 1: scalar rows) and a
+# generator, and returns (ptrow, indcol, coef, x, pins): pins name what the case asserts beyond equality with the oracle.
+
+DBL_MAX = np.finfo(np.float64).max
+
+
+def _drop(p, c, keep):
+    """CSR without the entries where keep is False."""
+    lens = np.bincount(_rows_of(p)[keep], minlength=len(p) - 1)
+    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), c[keep].astype(np.int32)
+
+
+def _rows_of(p):
+    return np.repeat(np.arange(len(p) - 1), np.diff(p))
+
+
+def _nodes(rng, count, nn, block):
+    """`count` distinct nodes of nn, as the (node-block) rows or columns they stand for."""
+    nodes = rng.choice(nn, size=min(count, nn), replace=False)
+    return (nodes[:, None] * block + np.arange(block)[None, :]).ravel()
+
+
+def case_referenced_nonfinite(p, c, block, rng):
+    n = len(p) - 1
+    v = rng.uniform(-1, 1, len(c))
+    x = rng.uniform(-1, 1, n)
+    cols = np.unique(c[rng.choice(len(c), 12, replace=False)])
+    x[cols[0::3]], x[cols[1::3]], x[cols[2::3]] = np.inf, -np.inf, np.nan
+    return p, c, v, x, {}
+
+
+def case_unreferenced_nonfinite(p, c, block, rng):
+    """NaN and Inf at every column no row names (column 0, the last, and a few hundred others next to named ones): y finite."""
+    n = len(p) - 1
+    nn = n // block
+    gone = np.union1d(np.arange(block), np.arange(n - block, n))
+    gone = np.union1d(gone, _nodes(rng, max(3, nn // 100), nn, block))
+    p, c = _drop(p, c, ~np.isin(c, gone))
+    named = np.zeros(n, bool)
+    named[c] = True
+    x = rng.uniform(-1, 1, n)
+    unnamed = np.nonzero(~named)[0]
+    x[unnamed] = np.resize([np.nan, np.inf, -np.inf, -np.nan], unnamed.size)
+    return p, c, rng.uniform(-1, 1, len(c)), x, {"finite": True}
+
+
+def case_stored_zero_inf(p, c, block, rng):
+    """Explicitly stored 0.0 coefficients against x = Inf: the chain multiplies them (NaN); treated as padding they would not be."""
+    n = len(p) - 1
+    v = rng.uniform(-1, 1, len(c))
+    x = rng.uniform(-1, 1, n)
+    cols = np.unique(c[rng.choice(len(c), 20, replace=False)])
+    x[cols] = np.inf
+    at = np.isin(c, cols)
+    v[at & (rng.random(len(c)) < 0.5)] = 0.0
+    return p, c, v, x, {}
+
+
+def case_signed_zeros(p, c, block, rng):
+    """Rows whose products are all -0.0, and empty rows: +0.0 (the chain starts at +0.0)."""
+    n = len(p) - 1
+    nn = n // block
+    empty = _nodes(rng, max(2, nn // 200), nn, block)
+    keep = ~np.isin(_rows_of(p), empty)
+    p, c = _drop(p, c, keep)
+    v = rng.uniform(-1, 1, len(c))
+    x = rng.uniform(0.25, 1, n) * rng.choice([-1.0, 1.0], n)
+    negz = rng.choice(n, max(4, n // 100), replace=False)
+    at = np.isin(_rows_of(p), negz)
+    v[at] = -np.copysign(0.0, x[c[at]])  # every product of these rows is -0.0
+    zero_rows = np.union1d(empty, negz)
+    return p, c, v, x, {"plus_zero": zero_rows}
+
+
+def case_subnormal(p, c, block, rng):
+    """Coefficients and x near 1e-160: the products and partial sums are subnormal (nothing may flush them)."""
+    n = len(p) - 1
+    v = rng.uniform(-1, 1, len(c)) * 1e-160
+    x = rng.uniform(-1, 1, n) * 1e-160
+    return p, c, v, x, {"subnormal": True}
+
+
+def case_overflow_order(p, c, block, rng):
+    """[DBL_MAX, DBL_MAX, -DBL_MAX] against x = 1 at several row lengths and positions: +Inf in CSR order."""
+    n = len(p) - 1
+    v = rng.uniform(-1, 1, len(c))
+    x = np.ones(n)
+    lens = np.diff(p)
+    rows = np.nonzero(lens >= 3)[0]
+    rows = rng.choice(rows, min(len(rows), max(8, n // 50)), replace=False)
+    for r in rows:
+        o = p[r] + int(rng.integers(0, lens[r] - 2))
+        v[o:o + 3] = [DBL_MAX, DBL_MAX, -DBL_MAX]
+    return p, c, v, x, {}
+
+
+IEEE_CASES = {
+    "referenced-nonfinite": case_referenced_nonfinite,
+    "unreferenced-nonfinite": case_unreferenced_nonfinite,
+    "stored-zero-inf": case_stored_zero_inf,
+    "signed-zeros": case_signed_zeros,
+    "subnormal": case_subnormal,
+    "overflow-order": case_overflow_order,
+}
+
+
+def ieee_inputs():
+    """(pattern, case, ptrow, indcol, coef, x, block, pins) of every IEEE case on a small FE matrix (node blocks: also BCSR) and on S15."""
+    for pat in ("fe3", "s15"):
+        p, c, _ = synth.fe_matrix(3) if pat == "fe3" else synth.rows("s15", 2000, w=100)
+        block = 4 if pat == "fe3" else 1
+        for ci, (name, make) in enumerate(IEEE_CASES.items()):
+            pp, cc, v, x, pins = make(p, c, block, np.random.default_rng(2000 + ci))
+            yield pat, name, pp, cc, v, x, block, pins
+
+
+def canon_nan(a):
+    """Every NaN as one bit pattern: which NaN an fma propagates depends on the operand order a compiler chose."""
+    a = np.asarray(a, dtype=np.float64)
+    return np.where(np.isnan(a), np.nan, a)
+
+
 def case_id(*parts):
     return "/".join(str(p) for p in parts)
 
@@ -104,3 +227,29 @@ def test_layer_tables_and_avx2_powers(ref, kind, n, w):
     assert case_id("layers", kind, n, w, "keys") in ref and sorted(a) == ref[case_id("layers", kind, n, w, "keys")]
     x = synth.x_sin(0, n)
     assert_ref(ref, O.spmkv_fused(4, p, c, v, x, "avx2row"), case_id("layers", kind, n, w, "spm4v_avx2"))
+
+
+IEEE_IDS = [f"{pat}-{name}" for pat, name, *_ in ieee_inputs()]
+
+
+@pytest.mark.parametrize("case", IEEE_IDS)
+def test_ieee_edge_values(ref, case):
+    """The judge on IEEE edge values: SpMV_CSR_OPT / _FMA, SpMV_BCSR_FMA and SpM2V_CSR_OPT of the reference's object code against the
+    oracle (NaNs canonicalised before digesting), and what each case pins by itself on the oracle's own output."""
+    pat, name, p, c, v, x, block, pins = next(t for t in ieee_inputs() if f"{t[0]}-{t[1]}" == case)
+    key = lambda what: case_id("ieee", pat, name, what)
+    y = O.spmv(p, c, v, x, "fma")
+    assert_ref(ref, canon_nan(y), key("spmv_opt"))
+    assert_ref(ref, canon_nan(y), key("spmv_fma"))
+    if block == 4:
+        bp, bc, bv = synth.csr_to_bcsr4(p, c, v)
+        assert_ref(ref, canon_nan(O.spmv_bcsr4(bp, bc, bv, x)), key("spmv_bcsr_fma"))
+    y2, z2 = O.spm2v_fused(p, c, v, x)
+    assert_ref(ref, canon_nan(y2), key("spm2v_opt_y"))
+    assert_ref(ref, canon_nan(z2), key("spm2v_opt_z"))
+    if pins.get("finite"):
+        assert np.isfinite(y).all()
+    if "plus_zero" in pins:
+        assert (y[pins["plus_zero"]].view(np.uint64) == 0).all()
+    if pins.get("subnormal"):
+        assert (np.abs(y[y != 0]) < np.finfo(np.float64).tiny).any()
