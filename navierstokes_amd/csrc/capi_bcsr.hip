@@ -6,6 +6,128 @@
 static int sell_fill(mi_bcsr4_t A, hipStream_t s);
 
 // ---------------------------------------------------------------- BCSR 4x4
+// The forms of a blocked handle timed against each other on a scratch pair (x = 0: timing does not depend on the values): two rounds
+// of 3 + 8 launches per form, select(c) putting form c in place; us[c] = the faster round, 0 where the measurement failed (it never
+// wins).  false: no room for the pair, nothing measured.
+template <class Select>
+static bool bcsr4_race(mi_bcsr4_t A, int ncand, Select select, double* us)
+{
+    LaunchTimer tm;
+    ScratchPair sp;
+    if (sp.alloc(4 * (size_t)std::max(A->nbcols, 1), 4 * (size_t)std::max(A->nbrows, 1)) != MI_OK || tm.init() != MI_OK) return false;
+    std::vector<char> failed((size_t)ncand, 0);
+    for (int round = 0; round < 2; round++)
+        for (int c = 0; c < ncand; c++) {
+            if (failed[c]) continue;
+            select(c);
+            double t = 0.0;
+            if (tm.time(3, 8, [&] { return launch_bcsr4(A, sp.x, sp.y, nullptr, false); }, &t) == MI_OK) us[c] = min_measured(us[c], t);
+            else failed[c] = 1;
+        }
+    for (int c = 0; c < ncand; c++)
+        if (failed[c]) us[c] = 0.0;
+    return true;
+}
+
+// The x tile per workgroup (spmv_bcsr4_tile): the distinct block columns of each group of 64 block rows, and every block's
+// position in its group's list.  Built when no group needs more than the tile holds; then both kernels are timed and the
+// faster is kept (MI355_BCSR_TILE=0 never builds it, =1 takes it unmeasured).
+static int build_bcsr4_tile(mi_bcsr4_t A, const int* ptrow, const int* indcol)
+{
+    const int nbrows = A->nbrows;
+    const long long nb = A->nblocks;
+    if (nb < 4096 || env_is("MI355_BCSR_TILE", "0")) return MI_OK;
+    const int per = kWG / 4, nwg = (nbrows + per - 1) / per;
+    std::vector<int> wg_ptr((size_t)nwg + 1, 0);
+    std::vector<unsigned> nodes;
+    std::vector<unsigned short> slots((size_t)nb + 1, 0);
+    std::vector<unsigned> u;
+    bool fits = true;
+    for (int w = 0; w < nwg && fits; w++) {
+        const int b0 = ptrow[(size_t)w * per], b1 = ptrow[std::min<long long>((long long)(w + 1) * per, nbrows)];
+        u.assign(indcol + b0, indcol + b1);
+        std::sort(u.begin(), u.end());
+        u.erase(std::unique(u.begin(), u.end()), u.end());
+        fits = (int)u.size() <= kBtileNodes;
+        for (int k = b0; k < b1 && fits; k++) slots[k] = (unsigned short)(std::lower_bound(u.begin(), u.end(), (unsigned)indcol[k]) - u.begin());
+        nodes.insert(nodes.end(), u.begin(), u.end());
+        wg_ptr[w + 1] = (int)nodes.size();
+    }
+    if (!fits) return MI_OK;
+    nodes.push_back(0);
+    hipError_t e;
+    if ((e = hipMalloc(&A->d_tl_ptr, sizeof(int) * wg_ptr.size())) != hipSuccess ||
+        (e = hipMalloc(&A->d_tl_nodes, sizeof(unsigned) * nodes.size())) != hipSuccess ||
+        (e = hipMalloc(&A->d_tl_slots, sizeof(unsigned short) * slots.size())) != hipSuccess ||
+        (e = hipMemcpy(A->d_tl_ptr, wg_ptr.data(), sizeof(int) * wg_ptr.size(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(A->d_tl_nodes, nodes.data(), sizeof(unsigned) * nodes.size(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(A->d_tl_slots, slots.data(), sizeof(unsigned short) * slots.size(), hipMemcpyHostToDevice)) != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string("bcsr4 tile upload: ") + hipGetErrorString(e));
+    if (env_is("MI355_BCSR_TILE", "1")) A->use_tile = true;
+    else if (!env_is("MI355_SPMV_AUTOTUNE", "0") && nb >= 100000) {
+        double us[2] = {0, 0};
+        if (bcsr4_race(A, 2, [&](int c) { A->use_tile = c == 1; }, us)) {
+            A->tune_us_plain = us[0];
+            A->tune_us_tile = us[1];
+            A->use_tile = us[1] > 0 && us[1] < us[0];
+        }
+    }
+    return MI_OK;
+}
+
+// The sliced copy (spmv_bcsr_sell.hpp): 16 block rows per slice, one contiguous stream per persistent wave.  MI_OK without it when
+// there is no room for a second copy of the block values: the row-per-quad kernels serve the handle, as build_sstream does for the
+// scalar format — a create that worked without the sliced copy must not fail because of it.
+static int build_bcsr4_sell(mi_bcsr4_t A, const int* ptrow, const int* indcol)
+{
+    SellPlanHost P, P2;
+    build_sell_plan(A->nbrows, ptrow, indcol, 1024, P);
+    build_sell_wave_ranges(P, 2048, P2.wrng, P2.nwaves);
+    const size_t vbytes = sizeof(double) * (size_t)(P.nsteps + kSellPadSteps) * kSellStepDoubles;
+    hipError_t e;
+    if ((e = hipMalloc(&A->d_sell_val, vbytes)) != hipSuccess || (e = hipMalloc(&A->d_sell_col, sizeof(unsigned) * P.col.size())) != hipSuccess ||
+        (e = hipMalloc(&A->d_sell_sptr, sizeof(int) * P.sptr.size())) != hipSuccess || (e = hipMalloc(&A->d_sell_wrng, sizeof(int) * P.wrng.size())) != hipSuccess ||
+        (e = hipMalloc(&A->d_sell_wrng2, sizeof(int) * P2.wrng.size())) != hipSuccess ||
+        (e = hipMemcpy(A->d_sell_wrng2, P2.wrng.data(), sizeof(int) * P2.wrng.size(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemset(A->d_sell_val + (size_t)P.nsteps * kSellStepDoubles, 0, sizeof(double) * (size_t)kSellPadSteps * kSellStepDoubles)) != hipSuccess ||
+        (e = hipMemcpy(A->d_sell_col, P.col.data(), sizeof(unsigned) * P.col.size(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(A->d_sell_sptr, P.sptr.data(), sizeof(int) * P.sptr.size(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(A->d_sell_wrng, P.wrng.data(), sizeof(int) * P.wrng.size(), hipMemcpyHostToDevice)) != hipSuccess) {
+        (void)hipGetLastError();
+        dfree(A->d_sell_val); dfree(A->d_sell_col); dfree(A->d_sell_sptr); dfree(A->d_sell_wrng); dfree(A->d_sell_wrng2);
+        A->d_sell_val = nullptr;
+        A->d_sell_col = nullptr;
+        A->d_sell_sptr = A->d_sell_wrng = A->d_sell_wrng2 = nullptr;
+        return e == hipErrorOutOfMemory ? MI_OK : fail(MI_ERR_HIP, std::string("bcsr4 sliced copy: ") + hipGetErrorString(e));
+    }
+    A->sell_nslices = P.nslices;
+    A->sell_nwaves = P.nwaves;
+    A->sell_nwaves2 = P2.nwaves;
+    A->sell_nsteps = P.nsteps;
+    // filled HERE and refilled where the block values change (mi_bcsr4_update_values*), on that call's stream — never lazily in
+    // front of a product: a product captured into a HIP graph holds only the product's node
+    return sell_fill(A, nullptr);
+}
+
+// which form mi_bcsr4_spmv* launches once the sliced copy is there: the fastest of the row-per-quad choice and the four sliced variants
+static void choose_bcsr4_sell_form(mi_bcsr4_t A, bool forced)
+{
+    if (const char* fe = getenv("MI355_BCSR_SELL_FORM")) A->sell_form = std::max(0, std::min(3, atoi(fe))); // tests: one variant, unmeasured
+    else if (forced) A->sell_form = 0;
+    else if (env_is("MI355_SPMV_AUTOTUNE", "0")) A->sell_form = 0; // no measurement: the sliced, non-temporal form for matrices of this size
+    else {
+        double us[5] = {0, 0, 0, 0, 0}; // [0] the row-per-quad choice made above, [1..4] the sliced variants
+        if (!bcsr4_race(A, 5, [&](int c) { A->sell_form = c - 1; }, us)) return;
+        int best = 0;
+        for (int c = 1; c < 5; c++) {
+            A->tune_us_sell[c - 1] = us[c];
+            if (better(us[c], us[best])) best = c;
+        }
+        if (A->tune_us_plain <= 0 && A->tune_us_tile <= 0) A->tune_us_plain = us[0];
+        A->sell_form = best - 1;
+    }
+}
+
 extern "C" int mi_bcsr4_create(int nbrows, int nbcols, const int* ptrow, const int* indcol, const double* coef,
                                mi_bcsr4_t* out)
 {
@@ -18,7 +140,9 @@ extern "C" int mi_bcsr4_create(int nbrows, int nbcols, const int* ptrow, const i
     for (long long k = 0; k < nb; k++) CHECK_ARG(indcol[k] >= 0 && indcol[k] < nbcols, "block column outside [0, nbcols)");
     int rc = need_device();
     if (rc) return rc;
-    mi_bcsr4_t A = new (std::nothrow) mi_bcsr4_s();
+    // destroyed on every early return below, released to the caller on success
+    std::unique_ptr<mi_bcsr4_s, int (*)(mi_bcsr4_t)> owner(new (std::nothrow) mi_bcsr4_s(), mi_bcsr4_destroy);
+    mi_bcsr4_t A = owner.get();
     if (!A) return fail(MI_ERR_ALLOC, "host allocation failed");
     A->nbrows = nbrows;
     A->nbcols = nbcols;
@@ -30,165 +154,22 @@ extern "C" int mi_bcsr4_create(int nbrows, int nbcols, const int* ptrow, const i
         (e = hipMalloc(&A->d_coef, sizeof(double) * 16 * ((size_t)nb + 1))) != hipSuccess ||
         (e = hipMemcpy(A->d_ptrow, ptrow, sizeof(int) * ((size_t)nbrows + 1), hipMemcpyHostToDevice)) != hipSuccess ||
         (nb && (e = hipMemcpy(A->d_indcol, indcol, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (nb && (e = hipMemcpy(A->d_coef, coef, sizeof(double) * 16 * (size_t)nb, hipMemcpyHostToDevice)) != hipSuccess)) {
-        mi_bcsr4_destroy(A);
+        (nb && (e = hipMemcpy(A->d_coef, coef, sizeof(double) * 16 * (size_t)nb, hipMemcpyHostToDevice)) != hipSuccess))
         return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string("bcsr4 upload: ") + hipGetErrorString(e));
-    }
     for (int s0 = 0; s0 < nbrows; s0 += kSellRows) // values of the longest slice of 16 block rows (bcsr4_refresh_kernel picks its LDS buffer by it)
         A->max_slice_vals = std::max(A->max_slice_vals, 16 * (ptrow[std::min(nbrows, s0 + kSellRows)] - ptrow[s0]));
-    // The x tile per workgroup (spmv_bcsr4_tile): the distinct block columns of each group of 64 block rows, and every block's
-    // position in its group's list.  Built when no group needs more than the tile holds; then both kernels are timed and the
-    // faster is kept (MI355_BCSR_TILE=0 never builds it, =1 takes it unmeasured).
-    const char* te = getenv("MI355_BCSR_TILE");
-    if (nb >= 4096 && !(te && !strcmp(te, "0"))) {
-        const int per = kWG / 4, nwg = (nbrows + per - 1) / per;
-        std::vector<int> wg_ptr((size_t)nwg + 1, 0);
-        std::vector<unsigned> nodes;
-        std::vector<unsigned short> slots((size_t)nb + 1, 0);
-        std::vector<unsigned> u;
-        bool fits = true;
-        for (int w = 0; w < nwg && fits; w++) {
-            const int b0 = ptrow[(size_t)w * per], b1 = ptrow[std::min<long long>((long long)(w + 1) * per, nbrows)];
-            u.assign(indcol + b0, indcol + b1);
-            std::sort(u.begin(), u.end());
-            u.erase(std::unique(u.begin(), u.end()), u.end());
-            fits = (int)u.size() <= kBtileNodes;
-            for (int k = b0; k < b1 && fits; k++) slots[k] = (unsigned short)(std::lower_bound(u.begin(), u.end(), (unsigned)indcol[k]) - u.begin());
-            nodes.insert(nodes.end(), u.begin(), u.end());
-            wg_ptr[w + 1] = (int)nodes.size();
-        }
-        if (fits) {
-            nodes.push_back(0);
-            if ((e = hipMalloc(&A->d_tl_ptr, sizeof(int) * wg_ptr.size())) != hipSuccess ||
-                (e = hipMalloc(&A->d_tl_nodes, sizeof(unsigned) * nodes.size())) != hipSuccess ||
-                (e = hipMalloc(&A->d_tl_slots, sizeof(unsigned short) * slots.size())) != hipSuccess ||
-                (e = hipMemcpy(A->d_tl_ptr, wg_ptr.data(), sizeof(int) * wg_ptr.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = hipMemcpy(A->d_tl_nodes, nodes.data(), sizeof(unsigned) * nodes.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = hipMemcpy(A->d_tl_slots, slots.data(), sizeof(unsigned short) * slots.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-                mi_bcsr4_destroy(A);
-                return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string("bcsr4 tile upload: ") + hipGetErrorString(e));
-            }
-            const char* at = getenv("MI355_SPMV_AUTOTUNE");
-            if (te && !strcmp(te, "1")) A->use_tile = true;
-            else if (!(at && !strcmp(at, "0")) && nb >= 100000) { // measure both (x = 0: timing does not depend on the values)
-                double *tx = nullptr, *ty = nullptr;
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                const size_t nx = 4 * (size_t)std::max(nbcols, 1), ny = 4 * (size_t)std::max(nbrows, 1);
-                if (hipMalloc(&tx, sizeof(double) * nx) == hipSuccess && hipMalloc(&ty, sizeof(double) * ny) == hipSuccess &&
-                    hipMemset(tx, 0, sizeof(double) * nx) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-                    double us[2] = {0, 0};
-                    for (int round = 0; round < 2; round++)
-                        for (int c = 0; c < 2; c++) {
-                            A->use_tile = c == 1;
-                            for (int w = 0; w < 3; w++) (void)launch_bcsr4(A, tx, ty, nullptr, false);
-                            (void)hipEventRecord(e0, nullptr);
-                            for (int w = 0; w < 8; w++) (void)launch_bcsr4(A, tx, ty, nullptr, false);
-                            (void)hipEventRecord(e1, nullptr);
-                            (void)hipEventSynchronize(e1);
-                            float ms = 0.f;
-                            (void)hipEventElapsedTime(&ms, e0, e1);
-                            const double t = ms * 1e3 / 8;
-                            us[c] = us[c] > 0 ? std::min(us[c], t) : t;
-                        }
-                    A->tune_us_plain = us[0];
-                    A->tune_us_tile = us[1];
-                    A->use_tile = us[1] > 0 && us[1] < us[0];
-                }
-                dfree(tx);
-                dfree(ty);
-                if (e0) (void)hipEventDestroy(e0);
-                if (e1) (void)hipEventDestroy(e1);
-            }
-        }
-    }
-    // The sliced copy (spmv_bcsr_sell.hpp): built for matrices large enough to stream (MI355_BCSR_SELL=0 never, =1 always and
-    // unmeasured with D = 4, non-temporal); its four variants are timed against the row-per-quad kernels above and the fastest of
-    // all is what mi_bcsr4_spmv* launches.  Costs a second copy of the block values on the device (+0.9 % padding on the FE matrix).
-    {
-        const char* se = getenv("MI355_BCSR_SELL");
-        const char* at = getenv("MI355_SPMV_AUTOTUNE");
-        const bool forced = se && !strcmp(se, "1");
-        if (!(se && !strcmp(se, "0")) && (forced || nb >= 100000) && nbcols < (1 << 30)) {
-            SellPlanHost P, P2;
-            build_sell_plan(nbrows, ptrow, indcol, 1024, P);
-            build_sell_wave_ranges(P, 2048, P2.wrng, P2.nwaves);
-            const size_t vbytes = sizeof(double) * (size_t)(P.nsteps + kSellPadSteps) * kSellStepDoubles;
-            if ((e = hipMalloc(&A->d_sell_val, vbytes)) != hipSuccess || (e = hipMalloc(&A->d_sell_col, sizeof(unsigned) * P.col.size())) != hipSuccess ||
-                (e = hipMalloc(&A->d_sell_sptr, sizeof(int) * P.sptr.size())) != hipSuccess || (e = hipMalloc(&A->d_sell_wrng, sizeof(int) * P.wrng.size())) != hipSuccess ||
-                (e = hipMalloc(&A->d_sell_wrng2, sizeof(int) * P2.wrng.size())) != hipSuccess ||
-                (e = hipMemcpy(A->d_sell_wrng2, P2.wrng.data(), sizeof(int) * P2.wrng.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = hipMemset(A->d_sell_val + (size_t)P.nsteps * kSellStepDoubles, 0, sizeof(double) * (size_t)kSellPadSteps * kSellStepDoubles)) != hipSuccess ||
-                (e = hipMemcpy(A->d_sell_col, P.col.data(), sizeof(unsigned) * P.col.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = hipMemcpy(A->d_sell_sptr, P.sptr.data(), sizeof(int) * P.sptr.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = hipMemcpy(A->d_sell_wrng, P.wrng.data(), sizeof(int) * P.wrng.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-                // no room for a second copy of the block values (or a failed upload): the row-per-quad kernels serve the handle, as
-                // build_sstream does for the scalar format — a create that worked without the sliced copy must not fail because of it
-                (void)hipGetLastError();
-                dfree(A->d_sell_val); dfree(A->d_sell_col); dfree(A->d_sell_sptr); dfree(A->d_sell_wrng); dfree(A->d_sell_wrng2);
-                A->d_sell_val = nullptr;
-                A->d_sell_col = nullptr;
-                A->d_sell_sptr = A->d_sell_wrng = A->d_sell_wrng2 = nullptr;
-                A->sell_form = -1;
-                if (e != hipErrorOutOfMemory) {
-                    mi_bcsr4_destroy(A);
-                    return fail(MI_ERR_HIP, std::string("bcsr4 sliced copy: ") + hipGetErrorString(e));
-                }
-            }
-            if (A->d_sell_val) {
-            A->sell_nslices = P.nslices;
-            A->sell_nwaves = P.nwaves;
-            A->sell_nwaves2 = P2.nwaves;
-            A->sell_nsteps = P.nsteps;
-            // filled HERE and refilled where the block values change (mi_bcsr4_update_values*), on that call's stream — never lazily in
-            // front of a product: a product captured into a HIP graph holds only the product's node
-            if ((rc = sell_fill(A, nullptr)) != MI_OK) {
-                mi_bcsr4_destroy(A);
-                return rc;
-            }
-            if (const char* fe = getenv("MI355_BCSR_SELL_FORM")) A->sell_form = std::max(0, std::min(3, atoi(fe))); // tests: one variant, unmeasured
-            else if (forced) A->sell_form = 0;
-            else if (!(at && !strcmp(at, "0"))) {
-                double *tx = nullptr, *ty = nullptr;
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                const size_t nx = 4 * (size_t)std::max(nbcols, 1), ny = 4 * (size_t)std::max(nbrows, 1);
-                if (hipMalloc(&tx, sizeof(double) * nx) == hipSuccess && hipMalloc(&ty, sizeof(double) * ny) == hipSuccess &&
-                    hipMemset(tx, 0, sizeof(double) * nx) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-                    double us[5] = {0, 0, 0, 0, 0}; // [0] the row-per-quad choice made above, [1..4] the sliced variants
-                    for (int round = 0; round < 2; round++)
-                        for (int c = 0; c < 5; c++) {
-                            A->sell_form = c - 1;
-                            for (int w = 0; w < 3; w++) (void)launch_bcsr4(A, tx, ty, nullptr, false);
-                            (void)hipEventRecord(e0, nullptr);
-                            for (int w = 0; w < 8; w++) (void)launch_bcsr4(A, tx, ty, nullptr, false);
-                            (void)hipEventRecord(e1, nullptr);
-                            (void)hipEventSynchronize(e1);
-                            float ms = 0.f;
-                            (void)hipEventElapsedTime(&ms, e0, e1);
-                            const double t = ms * 1e3 / 8;
-                            us[c] = us[c] > 0 ? std::min(us[c], t) : t;
-                        }
-                    int best = 0;
-                    for (int c = 1; c < 5; c++) {
-                        A->tune_us_sell[c - 1] = us[c];
-                        if (us[c] > 0 && us[c] < us[best]) best = c;
-                    }
-                    if (A->tune_us_plain <= 0 && A->tune_us_tile <= 0) A->tune_us_plain = us[0];
-                    A->sell_form = best - 1;
-                }
-                dfree(tx);
-                dfree(ty);
-                if (e0) (void)hipEventDestroy(e0);
-                if (e1) (void)hipEventDestroy(e1);
-            } else A->sell_form = 0; // no measurement: the sliced, non-temporal form for matrices of this size
-            }
-        }
+    if ((rc = build_bcsr4_tile(A, ptrow, indcol))) return rc;
+    // The sliced copy: built for matrices large enough to stream (MI355_BCSR_SELL=0 never, =1 always and unmeasured with D = 4,
+    // non-temporal); its four variants are timed against the row-per-quad kernels above and the fastest of all is what
+    // mi_bcsr4_spmv* launches.  Costs a second copy of the block values on the device (+0.9 % padding on the FE matrix).
+    const bool forced = env_is("MI355_BCSR_SELL", "1");
+    if (!env_is("MI355_BCSR_SELL", "0") && (forced || nb >= 100000) && nbcols < (1 << 30)) {
+        if ((rc = build_bcsr4_sell(A, ptrow, indcol))) return rc;
+        if (A->d_sell_val) choose_bcsr4_sell_form(A, forced);
     }
     // the handle is complete on return (the sliced values are filled on the null stream, which a non-blocking stream does not wait for)
-    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) {
-        mi_bcsr4_destroy(A);
-        return fail(MI_ERR_HIP, std::string("mi_bcsr4_create: ") + hipGetErrorString(e));
-    }
-    *out = A;
+    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return fail(MI_ERR_HIP, std::string("mi_bcsr4_create: ") + hipGetErrorString(e));
+    *out = owner.release();
     return MI_OK;
 }
 
@@ -488,7 +469,7 @@ static void launch_spmm_s(const Bcsr4View& V, int arith, const double* X, long l
     const bool xcd = xcd_env >= 0 ? xcd_env != 0 : S > 4;
     const dim3 grid((unsigned)(xcd ? kNXCD * ((nwg + kNXCD - 1) / kNXCD) : nwg)), block(kWG);
     constexpr bool PF = S <= 4; // beyond four columns the prefetch stage costs more occupancy than it hides latency
-    static const bool quad = !(getenv("MI355_SPMM_QUAD") && !strcmp(getenv("MI355_SPMM_QUAD"), "0"));
+    static const bool quad = !env_is("MI355_SPMM_QUAD", "0");
     if (S % 4 == 0 && quad) { // the quad of a block row shares its x blocks through DPP (spmv_kernels.hpp: spmm_bcsr4_quad)
         constexpr int SQ = S % 4 == 0 ? S : 4;
         static const int depth_env = getenv("MI355_SPMM_DEPTH") ? atoi(getenv("MI355_SPMM_DEPTH")) : 0;
@@ -599,7 +580,7 @@ static int build_spmm_tile_plan(mi_bcsr4_t A, int per, int ucap, const std::vect
         // (round 5) the tile's rows in ASCENDING order, not in the order the cluster grew: neighbouring lane groups then stream
         // neighbouring rows' blocks (one run of the coefficient array per run of consecutive rows) and store neighbouring pieces of Y.
         // MI355_SPMM_TILE_SORT=0: growth order (A/B).
-        static const bool sort_rows = !(getenv("MI355_SPMM_TILE_SORT") && !strcmp(getenv("MI355_SPMM_TILE_SORT"), "0"));
+        static const bool sort_rows = !env_is("MI355_SPMM_TILE_SORT", "0");
         if (sort_rows) std::sort(order.begin() + w.first, order.begin() + w.second);
         for (int i = 0; i < per; i++) rows.push_back(w.first + i < w.second ? order[w.first + i] : -1 - order[w.first]);
     }
@@ -634,8 +615,7 @@ static int build_spmm_tile(mi_bcsr4_t A)
 {
     if (A->st_state) return A->st_state;
     A->st_state = -1;
-    const char* e = getenv("MI355_SPMM_TILE");
-    if ((e && !strcmp(e, "0")) || A->nblocks < 4096) return -1;
+    if (env_is("MI355_SPMM_TILE", "0") || A->nblocks < 4096) return -1;
     std::vector<int> ptrow((size_t)A->nbrows + 1), indcol((size_t)A->nblocks);
     if (hipMemcpy(ptrow.data(), A->d_ptrow, sizeof(int) * ptrow.size(), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(indcol.data(), A->d_indcol, sizeof(int) * indcol.size(), hipMemcpyDeviceToHost) != hipSuccess) {
@@ -729,23 +709,17 @@ static int launch_spmm(mi_bcsr4_t A, int s, int arith, const double* X, long lon
             if (forced >= 0 && forced < kSpmmForms) form = possible(forced) ? forced : kSpmmGather;
             else {
                 if (A->spmm_choice[m] == 0) {
-                    hipEvent_t e0 = nullptr, e1 = nullptr;
                     int best = kSpmmGather;
-                    if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
+                    LaunchTimer tm(st);
+                    if (tm.init() == MI_OK) {
                         double us[kSpmmForms] = {0, 0, 0, 0, 0};
                         bool ok = true;
                         for (int round = 0; round < 2 && ok; round++)
                             for (int f = 0; f < kSpmmForms && ok; f++) {
                                 if (!possible(f)) continue;
-                                for (int i = 0; i < 2 && ok; i++) ok = run(f) == hipSuccess;
-                                (void)hipEventRecord(e0, st);
-                                for (int i = 0; i < 5 && ok; i++) ok = run(f) == hipSuccess;
-                                (void)hipEventRecord(e1, st);
-                                (void)hipEventSynchronize(e1);
-                                float ms = 0.f;
-                                (void)hipEventElapsedTime(&ms, e0, e1);
-                                const double t = ms * 1e3 / 5;
-                                us[f] = us[f] > 0 ? std::min(us[f], t) : t;
+                                double t = 0.0;
+                                ok = tm.time(2, 5, [&] { return run(f) == hipSuccess ? MI_OK : MI_ERR_HIP; }, &t) == MI_OK;
+                                if (ok) us[f] = min_measured(us[f], t);
                             }
                         for (int f = 0; f < kSpmmForms; f++) {
                             A->spmm_us[m][f] = us[f];
@@ -753,8 +727,6 @@ static int launch_spmm(mi_bcsr4_t A, int s, int arith, const double* X, long lon
                         }
                         if (!ok) { (void)hipGetLastError(); best = kSpmmGather; }
                     }
-                    if (e0) (void)hipEventDestroy(e0);
-                    if (e1) (void)hipEventDestroy(e1);
                     A->spmm_choice[m] = 1 + best;
                 }
                 form = A->spmm_choice[m] - 1;

@@ -52,6 +52,9 @@ static void free_sstream(mi_csr_t A)
     A->ss = SstreamTable();
 }
 
+// the matrix stream (bytes_per_nnz per nonzero) and two vectors no longer fit the 256 MB Infinity Cache with room to spare: stream past it
+static inline bool beyond_infinity_cache(double bytes_per_nnz, long long nnz, int n) { return bytes_per_nnz * (double)nnz + 16.0 * (double)n > 0.75 * 256e6; }
+
 constexpr double kSsMaxPadding = 0.12; // padded places per nonzero from which the sliced copy is not worth its bytes
 // MI355_SSTREAM_MAX_PADDING=<places per nonzero> (tests: the reference-made goldens — a few hundred ragged rows — through the sliced kernels)
 static double ss_max_padding()
@@ -68,6 +71,7 @@ static int build_sstream(mi_csr_t A, const int* ptrow, const int* indcol, int gh
 {
     if (A->ss.dev.val) return MI_OK;
     SsPlanHost P;
+    SsMwPlanHost M;
     const int shift = (A->y_offset & 1) && !A->d_rowmap ? 1 : 0;
     build_sstream_plan(A->n, A->ncols, ptrow, indcol, ss_max_padding(), P, true, shift, ghost_lo, ghost_hi);
     SstreamTable& T = A->ss;
@@ -75,25 +79,24 @@ static int build_sstream(mi_csr_t A, const int* ptrow, const int* indcol, int gh
     if (!P.eligible) {
         // rows that name several column neighbourhoods (3-D mesh operators in natural order): the cut-ring form (spmv_sstream_mw.hpp).
         // Not for a combined piece with ghost columns (the fused step has no such form).  MI355_SSTREAM_MW=0: never.
-        if (ghost_lo < ghost_hi || (getenv("MI355_SSTREAM_MW") && !strcmp(getenv("MI355_SSTREAM_MW"), "0"))) return MI_OK;
-        SsMwPlanHost M;
+        if (ghost_lo < ghost_hi || env_is("MI355_SSTREAM_MW", "0")) return MI_OK;
         build_sstream_mw_plan(A->n, A->ncols, ptrow, indcol, ss_max_padding(), M, shift);
         if (!M.eligible) return MI_OK;
         e = ss_mw_upload(M, T.dev);
         T.mw = e == hipSuccess;
-        P = M; // (the tables both forms share: rounds, steps, slices)
     } else e = ss_upload(P, T.dev, ghost_lo < ghost_hi);
+    const SsPlanHost& Q = P.eligible ? P : M; // (the tables both forms share: rounds, steps, slices)
     if (e != hipSuccess) {
         free_sstream(A);
         if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return MI_OK; } // no room for a second copy of the matrix: the other kernels serve it
         return fail(MI_ERR_HIP, std::string("sliced copy: ") + hipGetErrorString(e));
     }
-    T.nwg = P.nwg;
-    T.rounds = P.rounds;
-    T.shift = P.shift;
-    T.steps = P.steps;
-    T.padding = (double)P.pad_places / (double)A->nnz;
-    T.max_slice_nnz = P.max_slice_nnz;
+    T.nwg = Q.nwg;
+    T.rounds = Q.rounds;
+    T.shift = Q.shift;
+    T.steps = Q.steps;
+    T.padding = (double)Q.pad_places / (double)A->nnz;
+    T.max_slice_nnz = Q.max_slice_nnz;
     if (ghost_lo < ghost_hi) {
         T.h_wg_halo = P.wg_halo;
         T.h_wg = P.wg;
@@ -106,7 +109,7 @@ static int build_sstream(mi_csr_t A, const int* ptrow, const int* indcol, int gh
         free_sstream(A);
         return fail(MI_ERR_HIP, std::string("sliced copy fill: ") + hipGetErrorString(e));
     }
-    T.nt = 10.0 * (double)A->nnz + 16.0 * (double)A->n > 0.75 * 256e6; // beyond the Infinity Cache: stream past it
+    T.nt = beyond_infinity_cache(10.0, A->nnz, A->n);
     T.deep = T.nt;
     if (const char* fe = getenv("MI355_SSTREAM_FORM")) { // tests: one variant (0 D=8 nt, 1 D=8 temporal, 2 D=12 nt, 3 D=12 temporal)
         const int f = atoi(fe);
@@ -224,7 +227,7 @@ static int build_mring(mi_csr_t A, const int* indcol, int row_align = 0)
     M.ok_fraction = 1.0 - (double)P.bad_nnz / (double)A->nnz;
     M.depth = P.bpw >= 40 ? 4 : 2; // as for the single ring (tools/depth_ab.py)
     M.skew = ring_wants_skew(A->n, A->h_ptrow.data());
-    M.nt = 10.0 * (double)A->nnz + 16.0 * (double)A->n > 0.75 * 256e6;
+    M.nt = beyond_infinity_cache(10.0, A->nnz, A->n);
     return MI_OK;
 }
 
@@ -261,7 +264,7 @@ static int build_tile(mi_csr_t A, const int* indcol)
         mult8 += len > 0 && len % 8 == 0;
     }
     T.skew = 10 * mult8 > A->n;
-    T.nt = 10.0 * (double)A->nnz + 16.0 * (double)A->n > 0.75 * 256e6;
+    T.nt = beyond_infinity_cache(10.0, A->nnz, A->n);
     return MI_OK;
 }
 
@@ -295,7 +298,7 @@ static int fill_ring_table(RingTable& R, const RingPlanHost& best, int n, const 
     R.bpw = best.bpw;
     R.bad_runs = best.bad_runs;
     R.ok_fraction = nnz ? 1.0 - (double)best.bad_nnz / (double)nnz : 0.0;
-    R.lean = best.lean && best.cfg.id == 4 && !(getenv("MI355_RING_LEAN") && !strcmp(getenv("MI355_RING_LEAN"), "0"));
+    R.lean = best.lean && best.cfg.id == 4 && !env_is("MI355_RING_LEAN", "0");
     if (best.nblk <= 0) return MI_OK;
     hipError_t e;
 #define RING_TRY(expr)                                                                                                      \
@@ -334,7 +337,11 @@ static int fill_ring_table(RingTable& R, const RingPlanHost& best, int n, const 
     return MI_OK;
 }
 
-static int time_handle(mi_csr_t A, int warm, int timed, double* us);
+// mean launch time of A's current choice on the pair x / y, on the null stream
+static int time_on(LaunchTimer& tm, mi_csr_t A, const double* x, double* y, int warm, int timed, double* us)
+{
+    return tm.time(warm, timed, [&] { return launch_spmv(A, x, y, nullptr); }, us);
+}
 
 // Placement draws (round 3, profiles/NOTES.md §4.12; FROZEN in round 4: no further work goes into it).  WHERE the value array lies in device
 // memory moves a warm launch of the streaming kernels by up to 15 % on some boxes (tools/placement_lottery.py: 137-139 us against 158-166
@@ -362,45 +369,22 @@ static int placement_draws(mi_csr_t A, double* tx, double* ty, bool keep_pair)
     const bool blocked_choice = A->auto_kernel == MI_KERNEL_BCSR4 && A->blocked && A->blocked->d_coef && !(A->blocked->sell_form >= 0 && A->blocked->d_sell_val);
     const bool streams_coef = A->auto_kernel == MI_KERNEL_RING || A->auto_kernel == MI_KERNEL_MRING || A->auto_kernel == MI_KERNEL_STREAM || A->auto_kernel == MI_KERNEL_TILE || blocked_choice;
     if (!(draws > 0 && streams_coef && nnz >= kLargeNnz)) return MI_OK;
-    struct Own {
-        double *x = nullptr, *y = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Own()
-        {
-            dfree(x);
-            dfree(y);
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } own;
+    LaunchTimer tm;
+    ScratchPair own;
     if (!tx || !ty) {
         const size_t len = std::max(placed_vector_len(A->n, A->ncols), (size_t)(A->n_out > 0 ? A->n_out : 1));
-        HIP_TRY(hipMalloc(&own.x, sizeof(double) * len));
-        HIP_TRY(hipMalloc(&own.y, sizeof(double) * len));
-        HIP_TRY(hipMemset(own.x, 0, sizeof(double) * len));
+        if (int rc = own.alloc(len, len)) return rc;
         tx = own.x;
         ty = own.y;
     }
-    HIP_TRY(hipEventCreate(&own.e0));
-    HIP_TRY(hipEventCreate(&own.e1));
-    auto time_now = [&](int warm, int timed, double* us_out) -> int {
-        int rc2;
-        for (int w = 0; w < warm; w++)
-            if ((rc2 = launch_spmv(A, tx, ty, nullptr))) return rc2;
-        if (hipEventRecord(own.e0, nullptr) != hipSuccess) return MI_ERR_HIP;
-        for (int w = 0; w < timed; w++)
-            if ((rc2 = launch_spmv(A, tx, ty, nullptr))) return rc2;
-        float ms = 0.f;
-        if (hipEventRecord(own.e1, nullptr) != hipSuccess || hipEventSynchronize(own.e1) != hipSuccess || hipEventElapsedTime(&ms, own.e0, own.e1) != hipSuccess) return MI_ERR_HIP;
-        *us_out = ms * 1e3 / timed;
-        return MI_OK;
-    };
+    if (int rc = tm.init()) return rc;
+    auto time_now = [&](double* us) { return time_on(tm, A, tx, ty, 3, 8, us); };
     // pad_bytes: the zeroed tail the array was ALLOCATED with behind its payload — the ring family's unclamped loads read up to
     // kRingPadNnz values past the last nonzero, the blocked kernel one block past the last block; a copy must carry it too
     // (round 3's draws copied the payload into an exactly-sized buffer: every product on a redrawn array then read past its end)
     auto redraw = [&](void** slot, size_t bytes, size_t pad_bytes, int ndraws) {
         double best = 0.0;
-        if (!*slot || bytes == 0 || time_now(3, 8, &best) != MI_OK) return;
+        if (!*slot || bytes == 0 || time_now(&best) != MI_OK) return;
         const double first = best;
         A->place_us.push_back(best);
         std::vector<void*> losers;
@@ -411,7 +395,7 @@ static int placement_draws(mi_csr_t A, double* tx, double* ty, bool keep_pair)
                 hipMemcpy(fresh, *slot, bytes, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipGetLastError(); dfree(fresh); break; }
             std::swap(*slot, fresh); // fresh = the previous holder from here
             double t = 0.0;
-            const int rct = time_now(3, 8, &t);
+            const int rct = time_now(&t);
             A->place_us.push_back(rct == MI_OK ? t : -1.0);
             if (rct == MI_OK && t < 0.96 * best) best = t; // the copy is clearly faster (two timings of ONE placement differ by 2-3 %): it holds the data from now on
             else std::swap(*slot, fresh);
@@ -432,8 +416,386 @@ static int placement_draws(mi_csr_t A, double* tx, double* ty, bool keep_pair)
     if (keep_pair && !A->kept_x) {
         A->kept_x = tx;
         A->kept_y = ty;
-        if (tx == own.x) own.x = own.y = nullptr;
+        if (tx == own.x) own.hand_over();
     }
+    return MI_OK;
+}
+
+// ---- csr_create_impl, one stage at a time
+// nonzeros from which a matrix is measured at create (and its optional plans built by default); below, a product costs a few us and
+// the stream kernel serves it
+constexpr long long kMeasureNnz = 200000;
+
+// what csr_create_impl was given, once checked, with the column range of every row (the ring planner's input)
+struct CsrInput {
+    int n, ncols;
+    const int* ptrow;
+    const int* indcol;
+    const double* coef;
+    const int* rowmap;
+    int ghost_lo, ghost_hi; // ghost_lo < ghost_hi: a partition's combined piece (columns outside the range are ghosts)
+    long long nnz = 0;
+    bool offset_only = false; // the row map is "row r -> y[r + rowmap[0]]"
+    std::vector<int> row_min, row_max;
+    bool ghosts() const { return ghost_lo < ghost_hi; }
+};
+
+static int check_input(CsrInput& in)
+{
+    const int n = in.n;
+    const int* ptrow = in.ptrow;
+    CHECK_ARG(n >= 0 && in.ncols >= 0, "negative dimension");
+    CHECK_ARG(ptrow, "ptrow is null");
+    CHECK_ARG(ptrow[0] == 0, "ptrow[0] must be 0");
+    for (int i = 0; i < n; i++) CHECK_ARG(ptrow[i] <= ptrow[i + 1], "ptrow must be non-decreasing");
+    in.nnz = ptrow[n];
+    CHECK_ARG(in.nnz == 0 || (in.indcol && in.coef), "indcol/coef is null");
+    // 32-bit element offsets inside the kernels, padding included (ring_plan.hpp)
+    CHECK_ARG(in.nnz <= 0x7fffffffLL - 2 * kRingPadNnz && n <= 0x7fffffff - 2 * kRingPadRows, "matrix too large for 32-bit offsets: partition it (mi_part_*)");
+    in.row_min.resize((size_t)n);
+    in.row_max.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        int lo = 0x7fffffff, hi = -1;
+        for (int k = ptrow[i]; k < ptrow[i + 1]; k++) {
+            const int c = in.indcol[k];
+            CHECK_ARG(c >= 0 && c < in.ncols, "column index outside [0, ncols)");
+            lo = c < lo ? c : lo;
+            hi = c > hi ? c : hi;
+        }
+        in.row_min[i] = lo;
+        in.row_max[i] = hi;
+    }
+    in.offset_only = in.rowmap != nullptr && n > 0; // e.g. the interior rows of a banded partition: one contiguous range
+    for (int i = 1; in.offset_only && i < n; i++) in.offset_only = in.rowmap[i] == in.rowmap[0] + i;
+    return MI_OK;
+}
+
+// the CSR arrays and the row map on the device, each with a zeroed tail: the kernels' unclamped / vector loads may touch it (ring_plan.hpp)
+static int upload(mi_csr_t A, const CsrInput& in)
+{
+    const int n = in.n;
+    const long long nnz = in.nnz;
+    const size_t pad = 8, padv = kRingPadNnz, padr = kRingPadRows;
+    HIP_TRY(hipGetDevice(&A->device));
+    HIP_TRY(hipMalloc(&A->d_ptrow, sizeof(int) * ((size_t)n + 1 + padr)));
+    HIP_TRY(hipMalloc(&A->d_indcol, sizeof(int) * ((size_t)nnz + pad)));
+    HIP_TRY(hipMalloc(&A->d_coef, sizeof(double) * ((size_t)nnz + padv)));
+    HIP_TRY(hipMemset(A->d_ptrow + n + 1, 0, sizeof(int) * padr));
+    HIP_TRY(hipMemset(A->d_indcol + nnz, 0, sizeof(int) * pad));
+    HIP_TRY(hipMemset(A->d_coef + nnz, 0, sizeof(double) * padv));
+    HIP_TRY(hipMemcpy(A->d_ptrow, in.ptrow, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice));
+    if (nnz) {
+        HIP_TRY(hipMemcpy(A->d_indcol, in.indcol, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(A->d_coef, in.coef, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
+    }
+    A->mapped = in.rowmap != nullptr;
+    if (in.offset_only) A->y_offset = in.rowmap[0];
+    if (in.rowmap && n > 0 && !in.offset_only) {
+        HIP_TRY(hipMalloc(&A->d_rowmap, sizeof(int) * ((size_t)n + padr)));
+        HIP_TRY(hipMemset(A->d_rowmap + n, 0, sizeof(int) * padr));
+        HIP_TRY(hipMemcpy(A->d_rowmap, in.rowmap, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    return MI_OK;
+}
+
+// window plan of the ring kernel: first configuration (in preference order) that
+// serves at least 90 % of the nonzeros; MI355_RING_CONFIG=1..4 forces one
+static int plan_ring(mi_csr_t A, const CsrInput& in)
+{
+    const int n = in.n;
+    const long long nnz = in.nnz;
+    if (n == 0 || nnz == 0) return MI_OK;
+    int forced = 0;
+    if (const char* e = getenv("MI355_RING_CONFIG")) forced = atoi(e);
+    RingPlanHost best;
+    bool have = false;
+    for (int t = 0; t < kNumRingConfigs && !have; t++) {
+        const int id = forced >= 1 && forced <= kNumRingConfigs ? forced : kRingConfigOrder[t];
+        RingPlanHost P;
+        build_ring_plan(kRingConfigs[id - 1], n, in.ptrow, in.row_min.data(), in.row_max.data(), P, in.ghost_lo, in.ghost_hi, large_row_align(nnz));
+        const double okf = 1.0 - (double)P.bad_nnz / (double)nnz;
+        if (forced || okf >= 0.90) {
+            best = std::move(P);
+            have = true;
+        } else if (t == 0) {
+            best = std::move(P); // remember the preferred one for explicit MI_KERNEL_RING requests
+        }
+        if (forced) break;
+    }
+    if (int rc = fill_ring_table(A->ring, best, n, in.ptrow, in.indcol, nnz, in.ghosts(), in.row_min.data(), in.row_max.data(), n == in.ncols))
+        return rc;
+    A->auto_kernel = (have && A->ring.ok_fraction >= 0.90) ? MI_KERNEL_RING : MI_KERNEL_STREAM;
+    return MI_OK;
+}
+
+// The optional plans share one rule: MI355_<switch>=0 never builds one; =1 or MI355_SPMV_KERNEL=<name> asks for it (built whatever the
+// size, and kept); otherwise it is built when `by_size` holds
+static bool plan_wanted(const char* sw, const char* name, bool by_size, bool* asked)
+{
+    *asked = env_is(sw, "1") || env_is("MI355_SPMV_KERNEL", name);
+    return !env_is(sw, "0") && (*asked || by_size);
+}
+
+static int plan_optional(mi_csr_t A, const CsrInput& in)
+{
+    if (in.n == 0 || in.nnz == 0) return MI_OK;
+    const bool measured = in.nnz >= kMeasureNnz;
+    bool asked;
+    int rc;
+    // wide-band matrices (the ring does not serve them): the tile kernel's plan, kept if neighbouring rows share
+    // enough columns for it to pay (tile_plan.hpp)
+    if (plan_wanted("MI355_TILE", "tile", measured && A->auto_kernel != MI_KERNEL_RING, &asked)) {
+        if ((rc = build_tile(A, in.indcol))) return rc;
+        if (!asked && A->tile.unique_per_nnz > 0.6) free_tile(A); // little sharing: nothing to gain over the stream kernel
+    }
+    // ... and the multi-window ring's (3-D mesh operators: a few narrow column clusters far apart), kept if it serves >= 90 %
+    if (plan_wanted("MI355_MRING", "mring", measured && A->auto_kernel != MI_KERNEL_RING, &asked)) {
+        if ((rc = build_mring(A, in.indcol, large_row_align(in.nnz)))) return rc;
+        if (!asked && A->mring.ok_fraction < 0.90) free_mring(A);
+    }
+    // ... and the sliced copy of the sliced-stream kernel (spmv_sstream.hpp): matrices whose rounds of 512 rows fit the LDS window and
+    // whose slices pad little.  (Row-mapped handles — partition pieces, the relabelled twin — included since the store goes through the
+    // map; since round 5 also the fused multi-GPU step's combined piece: spmv_sstream_fused reads its ghost columns from the receive window)
+    if (plan_wanted("MI355_SSTREAM", "sstream", measured, &asked)) {
+        if ((rc = build_sstream(A, in.ptrow, in.indcol, in.ghost_lo, in.ghost_hi))) return rc;
+        A->ss.asked = asked;
+    }
+    return MI_OK;
+}
+
+// FE matrices: a blocked copy for the BCSR 4x4 kernel (same bits, 8.25 instead of 12 B per nonzero)
+// (a row map that moves whole nodes — rowmap[4b + q] = rowmap[4b] + q, 4-aligned — becomes a block-row map)
+static int attach_blocked(mi_csr_t A, const CsrInput& in)
+{
+    const int n = in.n;
+    const int* rowmap = in.rowmap;
+    bool node_map = rowmap != nullptr && !in.offset_only && n % 4 == 0;
+    for (int b = 0; node_map && b < n / 4; b++)
+        node_map = rowmap[4 * b] % 4 == 0 && rowmap[4 * b + 1] == rowmap[4 * b] + 1 && rowmap[4 * b + 2] == rowmap[4 * b] + 2 &&
+                   rowmap[4 * b + 3] == rowmap[4 * b] + 3;
+    if (!(!rowmap || in.offset_only || node_map) || n < 4 || in.nnz < 16 || in.ncols % 4 != 0 || env_is("MI355_AUTO_BCSR", "0")) return MI_OK;
+    std::vector<int> bptr, bcol;
+    std::vector<double> bval;
+    if (!csr_to_bcsr4_exact(n, in.ptrow, in.indcol, in.coef, bptr, bcol, bval)) return MI_OK;
+    if (int rc = mi_bcsr4_create(n / 4, in.ncols / 4, bptr.data(), bcol.data(), bval.data(), &A->blocked)) return rc;
+    if (node_map) {
+        std::vector<int> bmap((size_t)n / 4);
+        for (int b = 0; b < n / 4; b++) bmap[b] = rowmap[4 * b] / 4;
+        HIP_TRY(hipMalloc(&A->blocked->d_browmap, sizeof(int) * bmap.size()));
+        HIP_TRY(hipMemcpy(A->blocked->d_browmap, bmap.data(), sizeof(int) * bmap.size(), hipMemcpyHostToDevice));
+    }
+    return MI_OK;
+}
+
+// what holds when nothing is measured: value loads non-temporal once the matrix stream (10 B per nonzero in the ring kernel, 12 in the
+// stream kernel) no longer fits the Infinity Cache (MI355_<kernel>_NT=0|1 forces), and the blocked copy where there is one
+static void load_defaults(mi_csr_t A, const CsrInput& in)
+{
+    A->ring.nt = A->ring.d_slots && beyond_infinity_cache(10.0, in.nnz, in.n);
+    if (const char* e = getenv("MI355_RING_NT")) A->ring.nt = A->ring.d_slots && atoi(e) != 0;
+    A->stream_nt = beyond_infinity_cache(12.0, in.nnz, in.n);
+    if (const char* e = getenv("MI355_STREAM_NT")) A->stream_nt = atoi(e) != 0;
+    if (const char* e = getenv("MI355_TILE_NT")) A->tile.nt = atoi(e) != 0;
+    if (const char* e = getenv("MI355_MRING_NT")) A->mring.nt = atoi(e) != 0;
+    if (A->blocked) A->auto_kernel = MI_KERNEL_BCSR4; // unless measured otherwise
+    A->n_out = in.n;
+    if (in.rowmap)
+        for (int i = 0; i < in.n; i++) A->n_out = in.rowmap[i] + 1 > A->n_out ? in.rowmap[i] + 1 : A->n_out;
+}
+
+// MI355_SPMV_KERNEL=<name>: that kernel, unmeasured, if the handle holds what it needs; true if it applied
+static bool apply_forced_kernel(mi_csr_t A)
+{
+    const char* e = getenv("MI355_SPMV_KERNEL");
+    if (!e) return false;
+    if (!strcmp(e, "stream")) A->auto_kernel = MI_KERNEL_STREAM;
+    else if (!strcmp(e, "ring") && A->ring.d_plan) A->auto_kernel = MI_KERNEL_RING;
+    else if (!strcmp(e, "rowpar")) A->auto_kernel = MI_KERNEL_ROWPAR;
+    else if (!strcmp(e, "bcsr4") && A->blocked) A->auto_kernel = MI_KERNEL_BCSR4;
+    else if (!strcmp(e, "tile") && A->tile.d_desc) A->auto_kernel = MI_KERNEL_TILE;
+    else if (!strcmp(e, "mring") && A->mring.d_plan) A->auto_kernel = MI_KERNEL_MRING;
+    else if (!strcmp(e, "sstream") && A->ss.dev.val) A->auto_kernel = MI_KERNEL_SSTREAM;
+    else return false;
+    return true;
+}
+
+// the load form (non-temporal or not) a CSR kernel's launches use
+static bool& nt_flag(mi_csr_t A, int k)
+{
+    switch (k) {
+    case MI_KERNEL_RING: return A->ring.nt;
+    case MI_KERNEL_TILE: return A->tile.nt;
+    case MI_KERNEL_MRING: return A->mring.nt;
+    default: return A->stream_nt;
+    }
+}
+
+// measured microseconds of kernel k in the form it holds (0: not measured).  A blocked matrix enters the race with the blocked copy as
+// its default (load_defaults), which stands on the stream kernel's time until the blocked copy itself has been timed.
+static double tuned_us(mi_csr_t A, int k)
+{
+    if (k == MI_KERNEL_BCSR4 && A->tune_us[k][0] > 0) return A->tune_us[k][0];
+    if (k != MI_KERNEL_RING && k != MI_KERNEL_TILE && k != MI_KERNEL_MRING) k = MI_KERNEL_STREAM;
+    return A->tune_us[k][nt_flag(A, k)];
+}
+
+// The race on this very matrix, on the scratch pair (x = 0: timing does not depend on the values).  Timed in this order: the CSR kernels
+// of kTuneKernels, each with temporal and then non-temporal matrix loads, in two interleaved rounds of which the faster counts (one round
+// is not enough to tell two candidates 5 % apart: clock ramps, what the previous candidate left in the caches); then the blocked copy,
+// one round; then the four forms of the sliced stream, two rounds.  A kernel takes over from the one in use only if strictly faster.
+// A candidate whose measurement fails counts as not measured (0 us): it never wins.
+static const struct {
+    int kernel;
+    const char* nt_env; // forces the load form: only that one is timed
+} kTuneKernels[4] = {{MI_KERNEL_RING, "MI355_RING_NT"}, {MI_KERNEL_STREAM, "MI355_STREAM_NT"}, {MI_KERNEL_TILE, "MI355_TILE_NT"}, {MI_KERNEL_MRING, "MI355_MRING_NT"}};
+
+static void tune(mi_csr_t A, LaunchTimer& tm, const ScratchPair& sp)
+{
+    // warm launches first: a temporal candidate is judged with the Infinity Cache holding
+    // what it can of the matrix, as it would between the iterations of a solver
+    const int timed = A->nnz < 40000000 ? 12 : 6;
+    auto measure = [&](int warm, int count, double& slot, bool& failed) {
+        double t = 0.0;
+        if (time_on(tm, A, sp.x, sp.y, warm, count, &t) == MI_OK) slot = min_measured(slot, t);
+        else failed = true;
+    };
+    const bool ring_ok = A->auto_kernel == MI_KERNEL_RING;
+    auto in_race = [&](int k) {
+        return k == MI_KERNEL_RING ? ring_ok : k == MI_KERNEL_TILE ? A->tile.d_desc != nullptr : k == MI_KERNEL_MRING ? A->mring.d_plan != nullptr : true;
+    };
+    bool nt0[4], failed[4][2] = {};
+    for (int i = 0; i < 4; i++) nt0[i] = nt_flag(A, kTuneKernels[i].kernel);
+    const double* ring_us = A->tune_us[MI_KERNEL_RING];
+    for (int round = 0; round < 2; round++)
+        for (int i = 0; i < 4; i++)
+            for (int nt = 0; nt < 2; nt++) {
+                const int k = kTuneKernels[i].kernel;
+                double& us = A->tune_us[k][nt];
+                if (!in_race(k) || failed[i][nt] || (getenv(kTuneKernels[i].nt_env) && nt != nt0[i])) continue;
+                if (k == MI_KERNEL_RING && nt && !A->ring.d_slots) continue;
+                if (k == MI_KERNEL_STREAM && round == 1 && ring_ok &&
+                    us > 1.25 * std::min(ring_us[0] > 0 ? ring_us[0] : ring_us[1], ring_us[1] > 0 ? ring_us[1] : ring_us[0]))
+                    continue; // stream is out of the race already
+                nt_flag(A, k) = nt;
+                A->kernel = k;
+                measure(3, timed, us, failed[i][nt]);
+            }
+    for (int i = 0; i < 4; i++) {
+        const int k = kTuneKernels[i].kernel;
+        for (int nt = 0; nt < 2; nt++)
+            if (failed[i][nt]) A->tune_us[k][nt] = 0.0;
+        nt_flag(A, k) = in_race(k) ? better(A->tune_us[k][1], A->tune_us[k][0]) : nt0[i];
+    }
+    for (int i = 0; i < 4; i++)
+        if (better(tuned_us(A, kTuneKernels[i].kernel), tuned_us(A, A->auto_kernel))) A->auto_kernel = kTuneKernels[i].kernel;
+    if (A->blocked) { // the blocked copy against the best CSR kernel
+        const double holder = tuned_us(A, A->auto_kernel);
+        bool bfailed = false;
+        A->kernel = MI_KERNEL_BCSR4;
+        measure(3, 6, A->tune_us[MI_KERNEL_BCSR4][0], bfailed);
+        if (better(A->tune_us[MI_KERNEL_BCSR4][0], holder)) A->auto_kernel = MI_KERNEL_BCSR4;
+    }
+    if (A->ss.dev.val && !getenv("MI355_SSTREAM_FORM")) { // the sliced stream against whatever won so far: 8 / 12 steps of prefetch x non-temporal / temporal value loads
+        const double holder = tuned_us(A, A->auto_kernel);
+        double* us = A->ss.tune_us;
+        bool sfailed[4] = {};
+        A->kernel = MI_KERNEL_SSTREAM;
+        for (int round = 0; round < 2; round++)
+            for (int f = 0; f < 4; f++) {
+                if (sfailed[f]) continue;
+                A->ss.nt = (f & 1) == 0;
+                A->ss.deep = f >= 2;
+                measure(3, timed, us[f], sfailed[f]);
+            }
+        int bf = -1;
+        for (int f = 0; f < 4; f++) {
+            if (sfailed[f]) us[f] = 0.0;
+            if (us[f] > 0 && (bf < 0 || us[f] < us[bf])) bf = f;
+        }
+        if (bf >= 0) {
+            A->ss.nt = (bf & 1) == 0;
+            A->ss.deep = bf >= 2;
+            if (better(us[bf], holder)) A->auto_kernel = MI_KERNEL_SSTREAM;
+        }
+        // A sliced copy that lost the measurement is released (+10 B per nonzero and its padding): mi_csr_set_kernel(MI_KERNEL_SSTREAM)
+        // rebuilds it on demand.  Kept: one the environment asked for, and a combined piece's (the fused multi-GPU step takes the
+        // sliced stream wherever EVERY rank can: its choice is collective, not this rank's measurement).
+        if (A->auto_kernel != MI_KERNEL_SSTREAM && !A->ss.asked && !(A->ghost_lo < A->ghost_hi)) {
+            double keep_us[4];
+            std::copy(us, us + 4, keep_us);
+            free_sstream(A);
+            std::copy(keep_us, keep_us + 4, A->ss.tune_us); // (what it measured stays readable: mi_csr_sstream_info)
+        }
+    }
+    A->kernel = MI_KERNEL_AUTO;
+}
+
+// Large ring-served matrices take UNALIGNED blocks (large_row_align()).  MI355_RING_SHAPE_COMPARE=1 also builds the plan of
+// whole-wave blocks and times both on the create-time scratch vectors (mi_csr_ring_shape_info; the shape in use stays unless
+// the other is 2 % faster) — a comparison that says little about the caller's vectors, which is why it is no longer the rule.
+// (a rank's combined piece of the fused multi-GPU step included: timed here without the exchange, as a plain product)
+static void compare_ring_shapes(mi_csr_t A, const CsrInput& in, LaunchTimer& tm, const ScratchPair& sp)
+{
+    const long long nnz = in.nnz;
+    if (!env_is("MI355_RING_SHAPE_COMPARE", "1") || getenv("MI355_RING_ROW_ALIGN") || nnz < kLargeNnz) return;
+    auto time_now = [&](double* us) { return time_on(tm, A, sp.x, sp.y, 3, 8, us); };
+    double us64 = 0.0, us1 = 0.0;
+    if (A->auto_kernel == MI_KERNEL_RING && A->ring.cfg.id == 4) {
+        RingPlanHost alt;
+        build_ring_plan(kRingConfigs[3], in.n, in.ptrow, in.row_min.data(), in.row_max.data(), alt, in.ghost_lo, in.ghost_hi, 64);
+        RingTable T2;
+        if (1.0 - (double)alt.bad_nnz / (double)nnz >= 0.90 &&
+            fill_ring_table(T2, alt, in.n, in.ptrow, in.indcol, nnz, in.ghosts(), in.row_min.data(), in.row_max.data(), in.n == in.ncols) == MI_OK) {
+            T2.nt = A->ring.nt;
+            A->kernel = MI_KERNEL_RING;
+            int rct = time_now(&us1);
+            std::swap(A->ring, T2);
+            if (rct == MI_OK) rct = time_now(&us64);
+            A->kernel = MI_KERNEL_AUTO;
+            A->tune_us_ring_aligned = us64;
+            A->tune_us_ring_unaligned = us1;
+            if (rct != MI_OK || !(us64 < 0.98 * us1)) std::swap(A->ring, T2); // keep the default unless the other is clearly faster
+            free_ring_table(T2);
+        }
+    } else if (A->auto_kernel == MI_KERNEL_MRING) { // the same for the multi-window ring
+        MringTable keep = A->mring;
+        A->mring = MringTable();
+        if (build_mring(A, in.indcol, 64) == MI_OK && A->mring.d_plan && A->mring.ok_fraction >= 0.90) {
+            A->mring.nt = keep.nt;
+            A->kernel = MI_KERNEL_MRING;
+            int rct = time_now(&us64);
+            std::swap(A->mring, keep);
+            if (rct == MI_OK) rct = time_now(&us1);
+            A->kernel = MI_KERNEL_AUTO;
+            A->tune_us_ring_aligned = us64;
+            A->tune_us_ring_unaligned = us1;
+            if (rct == MI_OK && us64 < 0.98 * us1) std::swap(A->mring, keep); // the whole-wave plan is clearly faster here
+        } else {
+            std::swap(A->mring, keep);
+        }
+        std::swap(A->mring, keep); // release the plan not kept
+        free_mring(A);
+        A->mring = keep;
+    }
+}
+
+// the measurements of create: the race, the optional shape comparison, and (unless the caller defers them) the placement draws, all on
+// one scratch pair — where a vector lies in device memory moves a launch by a few per cent
+static int measure_at_create(mi_csr_t A, const CsrInput& in, bool defer_placement)
+{
+    // (sized like the vectors mi_vec_alloc_placed hands out: for a large square matrix this very pair becomes its first candidate)
+    const size_t scratch_len = placed_vector_len(in.n, in.ncols);
+    LaunchTimer tm;
+    ScratchPair sp;
+    int rc = sp.alloc(std::max(scratch_len, (size_t)(in.ncols > 0 ? in.ncols : 1)), std::max(scratch_len, (size_t)(A->n_out > 0 ? A->n_out : 1)));
+    if (rc || (rc = tm.init())) return rc;
+    tune(A, tm, sp);
+    compare_ring_shapes(A, in, tm, sp);
+    // placement draws (placement_draws() above): deferred when the caller (mi_csr_create) may still replace this handle's arrays by a
+    // relabelled twin.  The handle keeps the pair when the draws were made (mi_vec_alloc_placed's first candidate).
+    if (!defer_placement && placement_draws(A, sp.x, sp.y, !in.rowmap && in.n == in.ncols && in.n == A->n_out && !in.ghosts()) == MI_OK &&
+        A->kept_x == sp.x)
+        sp.hand_over();
     return MI_OK;
 }
 
@@ -442,454 +804,42 @@ int csr_create_impl(int n, int ncols, const int* ptrow, const int* indcol, const
 {
     CHECK_ARG(out, "out is null");
     *out = nullptr;
-    CHECK_ARG(n >= 0 && ncols >= 0, "negative dimension");
-    CHECK_ARG(ptrow, "ptrow is null");
-    CHECK_ARG(ptrow[0] == 0, "ptrow[0] must be 0");
-    for (int i = 0; i < n; i++) CHECK_ARG(ptrow[i] <= ptrow[i + 1], "ptrow must be non-decreasing");
-    const long long nnz = ptrow[n];
-    CHECK_ARG(nnz == 0 || (indcol && coef), "indcol/coef is null");
-    // 32-bit element offsets inside the kernels, padding included (ring_plan.hpp)
-    CHECK_ARG(nnz <= 0x7fffffffLL - 2 * kRingPadNnz && n <= 0x7fffffff - 2 * kRingPadRows, "matrix too large for 32-bit offsets: partition it (mi_part_*)");
-    std::vector<int> row_min((size_t)n), row_max((size_t)n);
-    for (int i = 0; i < n; i++) {
-        int lo = 0x7fffffff, hi = -1;
-        for (int k = ptrow[i]; k < ptrow[i + 1]; k++) {
-            const int c = indcol[k];
-            CHECK_ARG(c >= 0 && c < ncols, "column index outside [0, ncols)");
-            lo = c < lo ? c : lo;
-            hi = c > hi ? c : hi;
-        }
-        row_min[i] = lo;
-        row_max[i] = hi;
-    }
-    int rc = need_device();
-    if (rc) return rc;
-
-    mi_csr_t A = new (std::nothrow) mi_csr_s();
+    CsrInput in{n, ncols, ptrow, indcol, coef, rowmap, ghost_lo, ghost_hi};
+    int rc = check_input(in);
+    if (rc || (rc = need_device())) return rc;
+    // destroyed on every early return below, released to the caller on success
+    std::unique_ptr<mi_csr_s, int (*)(mi_csr_t)> owner(new (std::nothrow) mi_csr_s(), mi_csr_destroy);
+    mi_csr_t A = owner.get();
     if (!A) return fail(MI_ERR_ALLOC, "host allocation failed");
     A->n = n;
     A->ncols = ncols;
-    A->nnz = nnz;
+    A->nnz = in.nnz;
+    A->ghost_lo = ghost_lo;
+    A->ghost_hi = ghost_hi;
     A->h_ptrow.assign(ptrow, ptrow + n + 1);
-    hipError_t e = hipGetDevice(&A->device);
-    // zero padding behind the arrays: the kernels' unclamped / vector loads may touch it (ring_plan.hpp)
-    const size_t pad = 8, padv = kRingPadNnz, padr = kRingPadRows;
-    auto cleanup = [&]() { mi_csr_destroy(A); };
-#define TRY_OR_CLEAN(expr)                                                          \
-    do {                                                                            \
-        hipError_t e2_ = (expr);                                                    \
-        if (e2_ != hipSuccess) {                                                    \
-            cleanup();                                                              \
-            return fail(e2_ == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP,     \
-                        std::string(#expr) + ": " + hipGetErrorString(e2_));        \
-        }                                                                           \
-    } while (0)
-    TRY_OR_CLEAN(e);
-    TRY_OR_CLEAN(hipMalloc(&A->d_ptrow, sizeof(int) * ((size_t)n + 1 + padr)));
-    TRY_OR_CLEAN(hipMalloc(&A->d_indcol, sizeof(int) * ((size_t)nnz + pad)));
-    TRY_OR_CLEAN(hipMalloc(&A->d_coef, sizeof(double) * ((size_t)nnz + padv)));
-    TRY_OR_CLEAN(hipMemset(A->d_ptrow + n + 1, 0, sizeof(int) * padr));
-    TRY_OR_CLEAN(hipMemset(A->d_indcol + nnz, 0, sizeof(int) * pad));
-    TRY_OR_CLEAN(hipMemset(A->d_coef + nnz, 0, sizeof(double) * padv));
-    TRY_OR_CLEAN(hipMemcpy(A->d_ptrow, ptrow, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice));
-    if (nnz) {
-        TRY_OR_CLEAN(hipMemcpy(A->d_indcol, indcol, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
-        TRY_OR_CLEAN(hipMemcpy(A->d_coef, coef, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    }
-    A->mapped = rowmap != nullptr;
-    bool offset_only = rowmap != nullptr && n > 0;
-    for (int i = 1; offset_only && i < n; i++) offset_only = rowmap[i] == rowmap[0] + i;
-    if (offset_only) A->y_offset = rowmap[0]; // e.g. the interior rows of a banded partition: one contiguous range
-    if (rowmap && n > 0 && !offset_only) {
-        TRY_OR_CLEAN(hipMalloc(&A->d_rowmap, sizeof(int) * ((size_t)n + padr)));
-        TRY_OR_CLEAN(hipMemset(A->d_rowmap + n, 0, sizeof(int) * padr));
-        TRY_OR_CLEAN(hipMemcpy(A->d_rowmap, rowmap, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    }
-    // window plan of the ring kernel: first configuration (in preference order) that
-    // serves at least 90 % of the nonzeros; MI355_RING_CONFIG=1..4 forces one
-    if (n > 0 && nnz > 0) {
-        const int* order = kRingConfigOrder;
-        int forced = 0;
-        if (const char* e = getenv("MI355_RING_CONFIG")) forced = atoi(e);
-        RingPlanHost best;
-        bool have = false;
-        for (int t = 0; t < kNumRingConfigs && !have; t++) {
-            const int id = forced >= 1 && forced <= kNumRingConfigs ? forced : order[t];
-            RingPlanHost P;
-            build_ring_plan(kRingConfigs[id - 1], n, ptrow, row_min.data(), row_max.data(), P, ghost_lo, ghost_hi, large_row_align(nnz));
-            const double okf = 1.0 - (double)P.bad_nnz / (double)nnz;
-            if (forced || okf >= 0.90) {
-                best = std::move(P);
-                have = true;
-            } else if (t == 0) {
-                best = std::move(P); // remember the preferred one for explicit MI_KERNEL_RING requests
-            }
-            if (forced) break;
-        }
-        {
-            const int rcr = fill_ring_table(A->ring, best, n, ptrow, indcol, nnz, ghost_lo < ghost_hi, row_min.data(), row_max.data(), n == ncols);
-            if (rcr != MI_OK) {
-                mi_csr_destroy(A);
-                return rcr;
-            }
-        }
-        A->auto_kernel = (have && A->ring.ok_fraction >= 0.90) ? MI_KERNEL_RING : MI_KERNEL_STREAM;
-    }
-    // wide-band matrices (the ring does not serve them): the tile kernel's plan, kept if neighbouring rows share
-    // enough columns for it to pay (tile_plan.hpp); MI355_TILE=0 never, =1 always
-    {
-        const char* te = getenv("MI355_TILE");
-        const char* ke = getenv("MI355_SPMV_KERNEL");
-        const bool asked = (te && !strcmp(te, "1")) || (ke && !strcmp(ke, "tile"));
-        if (n > 0 && nnz > 0 && !(te && !strcmp(te, "0")) && (asked || (A->auto_kernel != MI_KERNEL_RING && nnz >= 200000))) {
-            const int rct = build_tile(A, indcol);
-            if (rct != MI_OK) {
-                mi_csr_destroy(A);
-                return rct;
-            }
-            if (!asked && A->tile.unique_per_nnz > 0.6) free_tile(A); // little sharing: nothing to gain over the stream kernel
-        }
-    }
-    // ... and the multi-window ring's (3-D mesh operators: a few narrow column clusters far apart), kept if it serves >= 90 %
-    {
-        const char* me = getenv("MI355_MRING");
-        const char* ke = getenv("MI355_SPMV_KERNEL");
-        const bool asked = (me && !strcmp(me, "1")) || (ke && !strcmp(ke, "mring"));
-        if (n > 0 && nnz > 0 && !(me && !strcmp(me, "0")) && (asked || (A->auto_kernel != MI_KERNEL_RING && nnz >= 200000))) {
-            const int rcm = build_mring(A, indcol, large_row_align(nnz));
-            if (rcm != MI_OK) {
-                mi_csr_destroy(A);
-                return rcm;
-            }
-            if (!asked && A->mring.ok_fraction < 0.90) free_mring(A);
-        }
-    }
-    // ... and the sliced copy of the sliced-stream kernel (spmv_sstream.hpp): unmapped matrices whose rounds of 512 rows fit the LDS
-    // window and whose slices pad little; MI355_SSTREAM=0 never, =1 whatever the size
-    {
-        const char* se = getenv("MI355_SSTREAM");
-        const char* ke = getenv("MI355_SPMV_KERNEL");
-        const bool asked = (se && !strcmp(se, "1")) || (ke && !strcmp(ke, "sstream"));
-        // (row-mapped handles — partition pieces, the relabelled twin — included since the store goes through the map; since round 5 also
-        // the fused multi-GPU step's combined piece: spmv_sstream_fused reads its ghost columns from the receive window)
-        A->ghost_lo = ghost_lo;
-        A->ghost_hi = ghost_hi;
-        if (n > 0 && nnz > 0 && !(se && !strcmp(se, "0")) && (asked || nnz >= 200000)) {
-            const int rcs = build_sstream(A, ptrow, indcol, ghost_lo, ghost_hi);
-            if (rcs != MI_OK) {
-                mi_csr_destroy(A);
-                return rcs;
-            }
-            A->ss.asked = asked;
-        }
-    }
-    // FE matrices: a blocked copy for the BCSR 4x4 kernel (same bits, 8.25 instead of 12 B per nonzero)
-    // (a row map that moves whole nodes — rowmap[4b + q] = rowmap[4b] + q, 4-aligned — becomes a block-row map)
-    bool node_map = rowmap != nullptr && !offset_only && n % 4 == 0;
-    for (int b = 0; node_map && b < n / 4; b++)
-        node_map = rowmap[4 * b] % 4 == 0 && rowmap[4 * b + 1] == rowmap[4 * b] + 1 && rowmap[4 * b + 2] == rowmap[4 * b] + 2 &&
-                   rowmap[4 * b + 3] == rowmap[4 * b] + 3;
-    if ((!rowmap || offset_only || node_map) && n >= 4 && nnz >= 16 && ncols % 4 == 0 && !(getenv("MI355_AUTO_BCSR") && !strcmp(getenv("MI355_AUTO_BCSR"), "0"))) {
-        std::vector<int> bptr, bcol;
-        std::vector<double> bval;
-        if (csr_to_bcsr4_exact(n, ptrow, indcol, coef, bptr, bcol, bval)) {
-            const int rcb = mi_bcsr4_create(n / 4, ncols / 4, bptr.data(), bcol.data(), bval.data(), &A->blocked);
-            if (rcb != MI_OK) {
-                mi_csr_destroy(A);
-                return rcb;
-            }
-            if (node_map) {
-                std::vector<int> bmap((size_t)n / 4);
-                for (int b = 0; b < n / 4; b++) bmap[b] = rowmap[4 * b] / 4;
-                TRY_OR_CLEAN(hipMalloc(&A->blocked->d_browmap, sizeof(int) * bmap.size()));
-                TRY_OR_CLEAN(hipMemcpy(A->blocked->d_browmap, bmap.data(), sizeof(int) * bmap.size(), hipMemcpyHostToDevice));
-            }
-        }
-    }
-    // default for the value loads when nothing is measured: non-temporal once the matrix stream
-    // (10 B per nonzero) no longer fits the 256 MB Infinity Cache with room for the vectors
-    A->ring.nt = A->ring.d_slots && 10.0 * (double)nnz + 16.0 * (double)n > 0.75 * 256e6;
-    if (const char* e = getenv("MI355_RING_NT")) A->ring.nt = A->ring.d_slots && atoi(e) != 0;
-    A->stream_nt = 12.0 * (double)nnz + 16.0 * (double)n > 0.75 * 256e6;
-    if (const char* e = getenv("MI355_STREAM_NT")) A->stream_nt = atoi(e) != 0;
-    if (const char* e = getenv("MI355_TILE_NT")) A->tile.nt = atoi(e) != 0;
-    if (const char* e = getenv("MI355_MRING_NT")) A->mring.nt = atoi(e) != 0;
-    if (A->blocked) A->auto_kernel = MI_KERNEL_BCSR4; // unless measured otherwise below
-    A->n_out = n;
-    if (rowmap)
-        for (int i = 0; i < n; i++) A->n_out = rowmap[i] + 1 > A->n_out ? rowmap[i] + 1 : A->n_out;
-    bool forced_kernel = false;
-    if (const char* e = getenv("MI355_SPMV_KERNEL")) {
-        forced_kernel = true;
-        if (!strcmp(e, "stream")) A->auto_kernel = MI_KERNEL_STREAM;
-        else if (!strcmp(e, "ring") && A->ring.d_plan) A->auto_kernel = MI_KERNEL_RING;
-        else if (!strcmp(e, "rowpar")) A->auto_kernel = MI_KERNEL_ROWPAR;
-        else if (!strcmp(e, "bcsr4") && A->blocked) A->auto_kernel = MI_KERNEL_BCSR4;
-        else if (!strcmp(e, "tile") && A->tile.d_desc) A->auto_kernel = MI_KERNEL_TILE;
-        else if (!strcmp(e, "mring") && A->mring.d_plan) A->auto_kernel = MI_KERNEL_MRING;
-        else if (!strcmp(e, "sstream") && A->ss.dev.val) A->auto_kernel = MI_KERNEL_SSTREAM;
-        else forced_kernel = false;
-    }
-    const char* at = getenv("MI355_SPMV_AUTOTUNE");
+    if ((rc = upload(A, in)) || (rc = plan_ring(A, in)) || (rc = plan_optional(A, in)) || (rc = attach_blocked(A, in))) return rc;
+    load_defaults(A, in);
+    const bool forced_kernel = apply_forced_kernel(A);
     // Too small to be measured (< 200 000 nonzeros: a partition's boundary rows, a test matrix): the stream kernel — a launch of as
     // many workgroups as there are row blocks — not the ring kernel's persistent grid with its plan loads and window fill: a rank's
     // 2 000 boundary rows cost 11-17 us through the ring and 4.8 through the stream kernel (profiles/r05_sp2_trace_tail.txt).
-    if (!forced_kernel && nnz < 200000 && A->auto_kernel == MI_KERNEL_RING && !(ghost_lo < ghost_hi)) A->auto_kernel = MI_KERNEL_STREAM;
-    if (!forced_kernel && !(at && !strcmp(at, "0")) && nnz >= 200000) {
-        // measure the candidates on this very matrix (x = 0: timing does not depend on the values):
-        // ring (if it serves the matrix) and stream, each with temporal and non-temporal matrix loads
-        struct TuneScratch { // released on every exit path, the early error returns of TRY_OR_CLEAN included
-            double *tx = nullptr, *ty = nullptr;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            ~TuneScratch()
-            {
-                dfree(tx);
-                dfree(ty);
-                if (e0) (void)hipEventDestroy(e0);
-                if (e1) (void)hipEventDestroy(e1);
-            }
-        } ts;
-        double *&tx = ts.tx, *&ty = ts.ty;
-        hipEvent_t &e0 = ts.e0, &e1 = ts.e1;
-        // (sized like the vectors mi_vec_alloc_placed hands out: for a large square matrix this very pair becomes its first candidate)
-        const size_t scratch_len = placed_vector_len(n, ncols);
-        TRY_OR_CLEAN(hipMalloc(&tx, sizeof(double) * std::max(scratch_len, (size_t)(ncols > 0 ? ncols : 1))));
-        TRY_OR_CLEAN(hipMalloc(&ty, sizeof(double) * std::max(scratch_len, (size_t)(A->n_out > 0 ? A->n_out : 1))));
-        TRY_OR_CLEAN(hipMemset(tx, 0, sizeof(double) * std::max(scratch_len, (size_t)(ncols > 0 ? ncols : 1))));
-        TRY_OR_CLEAN(hipEventCreate(&e0));
-        TRY_OR_CLEAN(hipEventCreate(&e1));
-        const bool ring_ok = A->auto_kernel == MI_KERNEL_RING;
-        const bool ring_nt_forced = getenv("MI355_RING_NT") != nullptr, stream_nt_forced = getenv("MI355_STREAM_NT") != nullptr;
-        const bool ring_nt0 = A->ring.nt, stream_nt0 = A->stream_nt;
-        const bool tile_nt_forced = getenv("MI355_TILE_NT") != nullptr;
-        const bool tile_nt0 = A->tile.nt;
-        const bool mring_nt_forced = getenv("MI355_MRING_NT") != nullptr;
-        const bool mring_nt0 = A->mring.nt;
-        double us[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // ring, ring nt, stream, stream nt, tile, tile nt, mring, mring nt
-        // two interleaved rounds, the faster of the two counts: one round is not enough to tell two
-        // candidates 5 % apart from each other (clock ramps, what the previous candidate left in the caches)
-        for (int round = 0; round < 2; round++)
-            for (int c = 0; c < 8; c++) {
-                const bool nt = c & 1;
-                if (c >= 6) {
-                    if (!A->mring.d_plan || (mring_nt_forced && nt != mring_nt0)) continue;
-                    A->mring.nt = nt;
-                    A->kernel = MI_KERNEL_MRING;
-                } else if (c >= 4) {
-                    if (!A->tile.d_desc || (tile_nt_forced && nt != tile_nt0)) continue;
-                    A->tile.nt = nt;
-                    A->kernel = MI_KERNEL_TILE;
-                } else if (c < 2) {
-                    if (!ring_ok || (nt && !A->ring.d_slots) || (ring_nt_forced && nt != ring_nt0)) continue;
-                    A->ring.nt = nt;
-                    A->kernel = MI_KERNEL_RING;
-                } else {
-                    if (stream_nt_forced && nt != stream_nt0) continue;
-                    if (round == 1 && ring_ok && us[c] > 1.25 * std::min(us[0] > 0 ? us[0] : us[1], us[1] > 0 ? us[1] : us[0]))
-                        continue; // stream is out of the race already
-                    A->stream_nt = nt;
-                    A->kernel = MI_KERNEL_STREAM;
-                }
-                // warm launches first: a temporal candidate is judged with the Infinity Cache holding
-                // what it can of the matrix, as it would between the iterations of a solver
-                const int warm = 3, timed = nnz < 40000000 ? 12 : 6;
-                for (int w = 0; w < warm; w++)
-                    if (launch_spmv(A, tx, ty, nullptr) != MI_OK) break;
-                TRY_OR_CLEAN(hipEventRecord(e0, nullptr));
-                for (int w = 0; w < timed; w++)
-                    if (launch_spmv(A, tx, ty, nullptr) != MI_OK) break;
-                TRY_OR_CLEAN(hipEventRecord(e1, nullptr));
-                TRY_OR_CLEAN(hipEventSynchronize(e1));
-                float ms = 0.f;
-                TRY_OR_CLEAN(hipEventElapsedTime(&ms, e0, e1));
-                const double t = ms * 1e3 / timed;
-                us[c] = us[c] > 0 ? std::min(us[c], t) : t;
-            }
-        A->kernel = MI_KERNEL_AUTO;
-        A->tune_us_ring = us[0];
-        A->tune_us_ring_nt = us[1];
-        A->tune_us_stream = us[2];
-        A->tune_us_stream_nt = us[3];
-        auto better = [](double a, double b) { return a > 0 && (b <= 0 || a < b); }; // a measured and faster than b
-        A->ring.nt = ring_ok ? better(us[1], us[0]) : ring_nt0;
-        A->stream_nt = better(us[3], us[2]);
-        A->tune_us_tile = us[4];
-        A->tune_us_tile_nt = us[5];
-        A->tile.nt = A->tile.d_desc ? better(us[5], us[4]) : tile_nt0;
-        const double best_ring = A->ring.nt ? us[1] : us[0], best_stream = A->stream_nt ? us[3] : us[2];
-        const double best_tile = A->tile.nt ? us[5] : us[4];
-        if (ring_ok && better(best_stream, best_ring)) A->auto_kernel = MI_KERNEL_STREAM;
-        if (better(best_tile, A->auto_kernel == MI_KERNEL_RING ? best_ring : best_stream)) A->auto_kernel = MI_KERNEL_TILE;
-        A->tune_us_mring = us[6];
-        A->tune_us_mring_nt = us[7];
-        A->mring.nt = A->mring.d_plan ? better(us[7], us[6]) : mring_nt0;
-        const double best_mring = A->mring.nt ? us[7] : us[6];
-        if (better(best_mring, A->auto_kernel == MI_KERNEL_RING ? best_ring : (A->auto_kernel == MI_KERNEL_TILE ? best_tile : best_stream)))
-            A->auto_kernel = MI_KERNEL_MRING;
-        if (A->blocked) { // the blocked copy against the best CSR kernel
-            A->kernel = MI_KERNEL_BCSR4;
-            for (int w = 0; w < 3; w++)
-                if (launch_spmv(A, tx, ty, nullptr) != MI_OK) break;
-            TRY_OR_CLEAN(hipEventRecord(e0, nullptr));
-            for (int w = 0; w < 6; w++)
-                if (launch_spmv(A, tx, ty, nullptr) != MI_OK) break;
-            TRY_OR_CLEAN(hipEventRecord(e1, nullptr));
-            TRY_OR_CLEAN(hipEventSynchronize(e1));
-            float ms = 0.f;
-            TRY_OR_CLEAN(hipEventElapsedTime(&ms, e0, e1));
-            A->tune_us_bcsr = ms * 1e3 / 6;
-            A->kernel = MI_KERNEL_AUTO;
-            const double best_csr = A->auto_kernel == MI_KERNEL_RING ? best_ring : (A->auto_kernel == MI_KERNEL_TILE ? best_tile : (A->auto_kernel == MI_KERNEL_MRING ? best_mring : best_stream));
-            if (better(A->tune_us_bcsr, best_csr)) A->auto_kernel = MI_KERNEL_BCSR4;
-        }
-        if (A->ss.dev.val && !getenv("MI355_SSTREAM_FORM")) { // the sliced stream against whatever won so far: 8 / 12 steps of prefetch x non-temporal / temporal value loads
-            const double best_so_far = A->auto_kernel == MI_KERNEL_BCSR4 ? A->tune_us_bcsr
-                                       : A->auto_kernel == MI_KERNEL_RING ? best_ring : (A->auto_kernel == MI_KERNEL_TILE ? best_tile : (A->auto_kernel == MI_KERNEL_MRING ? best_mring : best_stream));
-            A->kernel = MI_KERNEL_SSTREAM;
-            double bs = 0.0;
-            int bf = -1;
-            for (int round = 0; round < 2; round++)
-                for (int f = 0; f < 4; f++) {
-                    A->ss.nt = (f & 1) == 0;
-                    A->ss.deep = f >= 2;
-                    for (int w = 0; w < 3; w++)
-                        if (launch_spmv(A, tx, ty, nullptr) != MI_OK) break;
-                    TRY_OR_CLEAN(hipEventRecord(e0, nullptr));
-                    const int timed = nnz < 40000000 ? 12 : 6;
-                    for (int w = 0; w < timed; w++)
-                        if (launch_spmv(A, tx, ty, nullptr) != MI_OK) break;
-                    TRY_OR_CLEAN(hipEventRecord(e1, nullptr));
-                    TRY_OR_CLEAN(hipEventSynchronize(e1));
-                    float ms = 0.f;
-                    TRY_OR_CLEAN(hipEventElapsedTime(&ms, e0, e1));
-                    const double t = ms * 1e3 / timed;
-                    A->ss.tune_us[f] = A->ss.tune_us[f] > 0 ? std::min(A->ss.tune_us[f], t) : t;
-                }
-            for (int f = 0; f < 4; f++)
-                if (A->ss.tune_us[f] > 0 && (bf < 0 || A->ss.tune_us[f] < bs)) { bs = A->ss.tune_us[f]; bf = f; }
-            A->kernel = MI_KERNEL_AUTO;
-            if (bf >= 0) {
-                A->ss.nt = (bf & 1) == 0;
-                A->ss.deep = bf >= 2;
-                if (better(bs, best_so_far)) A->auto_kernel = MI_KERNEL_SSTREAM;
-            }
-            // A sliced copy that lost the measurement is released (+10 B per nonzero and its padding): mi_csr_set_kernel(MI_KERNEL_SSTREAM)
-            // rebuilds it on demand.  Kept: one the environment asked for, and a combined piece's (the fused multi-GPU step takes the
-            // sliced stream wherever EVERY rank can: its choice is collective, not this rank's measurement).
-            if (A->auto_kernel != MI_KERNEL_SSTREAM && !A->ss.asked && !(ghost_lo < ghost_hi)) {
-                double keep_us[4];
-                for (int f = 0; f < 4; f++) keep_us[f] = A->ss.tune_us[f];
-                free_sstream(A);
-                for (int f = 0; f < 4; f++) A->ss.tune_us[f] = keep_us[f]; // (what it measured stays readable: mi_csr_sstream_info)
-            }
-        }
-        // every further comparison on the SAME x / y scratch: where a vector lies in device memory moves a launch by a few per cent
-        auto time_now = [&](int warm, int timed, double* us_out) -> int {
-            int rc2;
-            for (int w = 0; w < warm; w++)
-                if ((rc2 = launch_spmv(A, tx, ty, nullptr))) return rc2;
-            if (hipEventRecord(e0, nullptr) != hipSuccess) return MI_ERR_HIP;
-            for (int w = 0; w < timed; w++)
-                if ((rc2 = launch_spmv(A, tx, ty, nullptr))) return rc2;
-            float ms = 0.f;
-            if (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return MI_ERR_HIP;
-            *us_out = ms * 1e3 / timed;
-            return MI_OK;
-        };
-        // Large ring-served matrices take UNALIGNED blocks (large_row_align()).  MI355_RING_SHAPE_COMPARE=1 also builds the plan of
-        // whole-wave blocks and times both on the create-time scratch vectors (mi_csr_ring_shape_info; the shape in use stays unless
-        // the other is 2 % faster) — a comparison that says little about the caller's vectors, which is why it is no longer the rule.
-        // (a rank's combined piece of the fused multi-GPU step included: timed here without the exchange, as a plain product)
-        const bool shape_compare = getenv("MI355_RING_SHAPE_COMPARE") && !strcmp(getenv("MI355_RING_SHAPE_COMPARE"), "1") && !getenv("MI355_RING_ROW_ALIGN");
-        if (shape_compare && A->auto_kernel == MI_KERNEL_RING && A->ring.cfg.id == 4 && nnz >= kLargeNnz) {
-            RingPlanHost alt;
-            build_ring_plan(kRingConfigs[3], n, ptrow, row_min.data(), row_max.data(), alt, ghost_lo, ghost_hi, 64);
-            RingTable T2;
-            if (nnz > 0 && 1.0 - (double)alt.bad_nnz / (double)nnz >= 0.90 &&
-                fill_ring_table(T2, alt, n, ptrow, indcol, nnz, ghost_lo < ghost_hi, row_min.data(), row_max.data(), n == ncols) == MI_OK) {
-                T2.nt = A->ring.nt;
-                double us64 = 0.0, us1 = 0.0;
-                A->kernel = MI_KERNEL_RING;
-                int rct = time_now(3, 8, &us1);
-                std::swap(A->ring, T2);
-                if (rct == MI_OK) rct = time_now(3, 8, &us64);
-                A->kernel = MI_KERNEL_AUTO;
-                A->tune_us_ring_aligned = us64;
-                A->tune_us_ring_unaligned = us1;
-                if (rct != MI_OK || !(us64 < 0.98 * us1)) std::swap(A->ring, T2); // keep the default unless the other is clearly faster
-                free_ring_table(T2);
-            }
-        }
-        if (shape_compare && A->auto_kernel == MI_KERNEL_MRING && nnz >= kLargeNnz) { // the same for the multi-window ring
-            MringTable keep = A->mring;
-            A->mring = MringTable();
-            if (build_mring(A, indcol, 64) == MI_OK && A->mring.d_plan && A->mring.ok_fraction >= 0.90) {
-                A->mring.nt = keep.nt;
-                double us64 = 0.0, us1 = 0.0;
-                A->kernel = MI_KERNEL_MRING;
-                int rct = time_now(3, 8, &us64);
-                std::swap(A->mring, keep);
-                if (rct == MI_OK) rct = time_now(3, 8, &us1);
-                A->kernel = MI_KERNEL_AUTO;
-                A->tune_us_ring_aligned = us64;
-                A->tune_us_ring_unaligned = us1;
-                if (rct == MI_OK && us64 < 0.98 * us1) std::swap(A->mring, keep); // the whole-wave plan is clearly faster here
-            } else {
-                std::swap(A->mring, keep);
-            }
-            MringTable loser = keep; // release the plan not kept
-            keep = A->mring;
-            A->mring = loser;
-            free_mring(A);
-            A->mring = keep;
-        }
-        // placement draws (placement_draws() below): on the scratch pair the comparisons above ran on; deferred when the caller
-        // (mi_csr_create) may still replace this handle's arrays by a relabelled twin
-        if (!defer_placement) {
-            const int rcp = placement_draws(A, tx, ty, !rowmap && n == ncols && n == A->n_out && !(ghost_lo < ghost_hi));
-            if (rcp == MI_OK && A->kept_x == tx) tx = ty = nullptr; // the handle keeps the pair (mi_vec_alloc_placed's first candidate)
-        }
-    }
+    if (!forced_kernel && in.nnz < kMeasureNnz && A->auto_kernel == MI_KERNEL_RING && !in.ghosts()) A->auto_kernel = MI_KERNEL_STREAM;
+    if (!forced_kernel && !env_is("MI355_SPMV_AUTOTUNE", "0") && in.nnz >= kMeasureNnz && (rc = measure_at_create(A, in, defer_placement))) return rc;
     // the handle is complete on return: the fills, zeroed paddings and uploads queued on the null stream above are done, so the first
     // product may come on any stream (a non-blocking one is not ordered behind the null stream)
-    TRY_OR_CLEAN(hipStreamSynchronize(nullptr));
-#undef TRY_OR_CLEAN
-    *out = A;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    *out = owner.release();
     return MI_OK;
 }
 
 // mean launch time of A's current choice over `timed` launches after `warm` (x = 0: timing does not depend on values)
 static int time_handle(mi_csr_t A, int warm, int timed, double* us)
 {
-    struct Scratch2 {
-        double *tx = nullptr, *ty = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Scratch2()
-        {
-            dfree(tx);
-            dfree(ty);
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } t;
-    const size_t nx = (size_t)(A->ncols > 0 ? A->ncols : 1), ny = (size_t)(A->n_out > 0 ? A->n_out : 1);
-    HIP_TRY(hipMalloc(&t.tx, sizeof(double) * nx));
-    HIP_TRY(hipMalloc(&t.ty, sizeof(double) * ny));
-    HIP_TRY(hipMemset(t.tx, 0, sizeof(double) * nx));
-    HIP_TRY(hipEventCreate(&t.e0));
-    HIP_TRY(hipEventCreate(&t.e1));
-    int rc;
-    for (int w = 0; w < warm; w++)
-        if ((rc = launch_spmv(A, t.tx, t.ty, nullptr))) return rc;
-    HIP_TRY(hipEventRecord(t.e0, nullptr));
-    for (int w = 0; w < timed; w++)
-        if ((rc = launch_spmv(A, t.tx, t.ty, nullptr))) return rc;
-    HIP_TRY(hipEventRecord(t.e1, nullptr));
-    HIP_TRY(hipEventSynchronize(t.e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t.e0, t.e1));
-    *us = ms * 1e3 / timed;
-    return MI_OK;
+    LaunchTimer tm;
+    ScratchPair sp;
+    int rc = sp.alloc((size_t)(A->ncols > 0 ? A->ncols : 1), (size_t)(A->n_out > 0 ? A->n_out : 1));
+    if (rc || (rc = tm.init())) return rc;
+    return time_on(tm, A, sp.x, sp.y, warm, timed, us);
 }
 
 static void release_natural_arrays(mi_csr_t A)
@@ -901,12 +851,7 @@ static void release_natural_arrays(mi_csr_t A)
     A->d_coef = nullptr;
     for (auto& kv : A->tables) dfree(kv.second.d_blk);
     A->tables.clear();
-    dfree(A->ring.d_plan);
-    dfree(A->ring.d_ok);
-    dfree(A->ring.d_rng);
-    dfree(A->ring.d_run_halo);
-    dfree(A->ring.d_slots);
-    A->ring = RingTable();
+    free_ring_table(A->ring);
     free_tile(A);
     free_mring(A);
     free_sstream(A);
@@ -920,9 +865,8 @@ static void release_natural_arrays(mi_csr_t A)
 // MI355_REORDER=0 never, =1 always try and keep (tests), unset: as described.
 static int maybe_reorder(mi_csr_t A, const int* ptrow, const int* indcol, const double* coef)
 {
-    const char* env = getenv("MI355_REORDER");
-    const bool force = env && !strcmp(env, "1");
-    if (env && !strcmp(env, "0")) return MI_OK;
+    const bool force = env_is("MI355_REORDER", "1");
+    if (env_is("MI355_REORDER", "0")) return MI_OK;
     const int n = A->n;
     if (A->mapped || n != A->ncols || n < 8 || A->nnz == 0) return MI_OK;
     if (!force && (n < 100000 || resolve_kernel(A) == MI_KERNEL_RING || resolve_kernel(A) == MI_KERNEL_SSTREAM)) return MI_OK; // (a band served by its window: nothing to relabel)
@@ -952,9 +896,8 @@ static int maybe_reorder(mi_csr_t A, const int* ptrow, const int* indcol, const 
         (e = hipMemcpy(A->d_iperm, R.iperm.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipMemcpy(A->d_src_start, src_start.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string("reorder upload: ") + hipGetErrorString(e));
-    const char* at = getenv("MI355_SPMV_AUTOTUNE");
     bool keep = true;
-    if (!force && !(at && !strcmp(at, "0"))) { // measure: natural choice against the twin (gather included)
+    if (!force && !env_is("MI355_SPMV_AUTOTUNE", "0")) { // measure: natural choice against the twin (gather included)
         const int timed = A->nnz < 40000000 ? 12 : 6;
         A->inner = nullptr;
         rc = time_handle(A, 3, timed, &A->us_natural);
@@ -1105,11 +1048,7 @@ extern "C" int mi_csr_destroy(mi_csr_t A)
     for (auto& kv : A->tables) {
         dfree(kv.second.d_blk);
     }
-    dfree(A->ring.d_plan);
-    dfree(A->ring.d_ok);
-    dfree(A->ring.d_rng);
-    dfree(A->ring.d_run_halo);
-    dfree(A->ring.d_slots);
+    free_ring_table(A->ring);
     free_tile(A);
     free_mring(A);
     free_sstream(A);
@@ -1241,8 +1180,8 @@ extern "C" int mi_csr_tune_info(mi_csr_t A, double* us_ring, double* us_stream)
 {
     CHECK_ARG(A, "null handle");
     if (A->inner) A = A->inner;
-    if (us_ring) *us_ring = A->ring.nt ? A->tune_us_ring_nt : A->tune_us_ring;
-    if (us_stream) *us_stream = A->stream_nt ? A->tune_us_stream_nt : A->tune_us_stream;
+    if (us_ring) *us_ring = A->tune_us[MI_KERNEL_RING][A->ring.nt];
+    if (us_stream) *us_stream = A->tune_us[MI_KERNEL_STREAM][A->stream_nt];
     return MI_OK;
 }
 
@@ -1251,11 +1190,11 @@ extern "C" int mi_csr_tune_detail(mi_csr_t A, double us[5], int* ring_nt, int* s
     CHECK_ARG(A, "null handle");
     if (A->inner) A = A->inner;
     if (us) {
-        us[0] = A->tune_us_ring;
-        us[1] = A->tune_us_ring_nt;
-        us[2] = A->tune_us_stream;
-        us[3] = A->tune_us_stream_nt;
-        us[4] = A->tune_us_bcsr;
+        us[0] = A->tune_us[MI_KERNEL_RING][0];
+        us[1] = A->tune_us[MI_KERNEL_RING][1];
+        us[2] = A->tune_us[MI_KERNEL_STREAM][0];
+        us[3] = A->tune_us[MI_KERNEL_STREAM][1];
+        us[4] = A->tune_us[MI_KERNEL_BCSR4][0];
     }
     if (ring_nt) *ring_nt = A->ring.nt ? 1 : 0;
     if (stream_nt) *stream_nt = A->stream_nt ? 1 : 0;
@@ -1552,8 +1491,8 @@ extern "C" int mi_csr_tile_info(mi_csr_t A, int* built, int* nblk, double* uniqu
     if (nblk) *nblk = A->tile.nblk;
     if (unique_per_nnz) *unique_per_nnz = A->tile.unique_per_nnz;
     if (us) {
-        us[0] = A->tune_us_tile;
-        us[1] = A->tune_us_tile_nt;
+        us[0] = A->tune_us[MI_KERNEL_TILE][0];
+        us[1] = A->tune_us[MI_KERNEL_TILE][1];
     }
     if (nt) *nt = A->tile.nt;
     return MI_OK;
@@ -1607,20 +1546,14 @@ extern "C" int mi_vec_alloc_placed(mi_csr_t A, int nvec, int draws, double** d_v
     std::vector<int> order((size_t)cand);
     for (int c = 0; c < cand; c++) order[c] = c;
     if (timed) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
         std::vector<double> t((size_t)cand, 0.0);
-        bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-        for (int c = 0; c < cand && ok; c++) {
-            for (int w = 0; w < 4 && ok; w++) ok = mi_spmv_dev(A, xs[c], ys[c], nullptr) == MI_OK;
-            ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
-            for (int w = 0; w < 10 && ok; w++) ok = mi_spmv_dev(A, xs[c], ys[c], nullptr) == MI_OK;
-            float ms = 0.f;
-            ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-            t[c] = ms * 1e3 / 10;
+        int rct;
+        {
+            LaunchTimer tm;
+            rct = tm.init();
+            for (int c = 0; c < cand && !rct; c++) rct = tm.time(4, 10, [&] { return mi_spmv_dev(A, xs[c], ys[c], nullptr); }, &t[c]);
         }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (!ok) {
+        if (rct) {
             release();
             return fail(MI_ERR_HIP, "mi_vec_alloc_placed: timing a candidate pair failed");
         }
@@ -1655,8 +1588,8 @@ extern "C" int mi_csr_mring_info(mi_csr_t A, int* built, int* runs, int* runs_no
     if (runs_not_served) *runs_not_served = A->mring.bad_runs;
     if (nnz_fraction_served) *nnz_fraction_served = A->mring.ok_fraction;
     if (us) {
-        us[0] = A->tune_us_mring;
-        us[1] = A->tune_us_mring_nt;
+        us[0] = A->tune_us[MI_KERNEL_MRING][0];
+        us[1] = A->tune_us[MI_KERNEL_MRING][1];
     }
     if (nt) *nt = A->mring.nt;
     return MI_OK;
@@ -1740,7 +1673,7 @@ extern "C" int mi_csr_set_kernel(mi_csr_t A, int kernel_id)
     CHECK_ARG(A, "null handle");
     if (A->inner) A = A->inner;
     CHECK_ARG(kernel_id >= MI_KERNEL_AUTO && kernel_id <= MI_KERNEL_SSTREAM, "unknown kernel id");
-    if (kernel_id == MI_KERNEL_SSTREAM && !A->ss.dev.val && A->nnz > 0 && A->d_indcol && !(getenv("MI355_SSTREAM") && !strcmp(getenv("MI355_SSTREAM"), "0"))) {
+    if (kernel_id == MI_KERNEL_SSTREAM && !A->ss.dev.val && A->nnz > 0 && A->d_indcol && !env_is("MI355_SSTREAM", "0")) {
         // not built at create (a small matrix) or released after losing the create-time measurement: built on request
         int rc = need_device();
         if (rc) return rc;

@@ -15,6 +15,7 @@
 #include <chrono>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -61,6 +62,80 @@ static inline int fail(int code, const std::string& msg)
 
 
 int need_device(); // capi_lib.hip
+
+// the environment switch `name` is set to exactly `value`
+static inline bool env_is(const char* name, const char* value)
+{
+    const char* e = getenv(name);
+    return e && !strcmp(e, value);
+}
+
+// ---------------------------------------------------------------- measurement
+// Mean time of one launch of `launch` (a callable returning MI_OK or an error code) on stream s: `warm` launches, then `timed`
+// launches between two events.  Stops at the first launch that fails and returns its status; an event call that fails returns
+// MI_ERR_HIP.  What a failed measurement means is the caller's business.
+struct LaunchTimer {
+    hipStream_t s;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit LaunchTimer(hipStream_t st = nullptr) : s(st) {}
+    LaunchTimer(const LaunchTimer&) = delete;
+    LaunchTimer& operator=(const LaunchTimer&) = delete;
+    ~LaunchTimer()
+    {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    int init()
+    {
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        return MI_OK;
+    }
+    template <class F>
+    int time(int warm, int timed, F&& launch, double* us)
+    {
+        int rc;
+        for (int w = 0; w < warm; w++)
+            if ((rc = launch())) return rc;
+        HIP_TRY(hipEventRecord(e0, s));
+        for (int w = 0; w < timed; w++)
+            if ((rc = launch())) return rc;
+        HIP_TRY(hipEventRecord(e1, s));
+        HIP_TRY(hipEventSynchronize(e1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        *us = ms * 1e3 / timed;
+        return MI_OK;
+    }
+};
+
+// the x / y pair a measurement launches on (x zeroed: timing does not depend on the values); freed on scope exit unless handed over.
+// Declare it AFTER the LaunchTimer that times on it: the pair is then freed before the events go, the order the library has always
+// released them in — where later allocations land moves launch times by several per cent (profiles/NOTES.md §4.12)
+struct ScratchPair {
+    double *x = nullptr, *y = nullptr;
+    ScratchPair() = default;
+    ScratchPair(const ScratchPair&) = delete;
+    ScratchPair& operator=(const ScratchPair&) = delete;
+    ~ScratchPair()
+    {
+        dfree(x);
+        dfree(y);
+    }
+    int alloc(size_t nx, size_t ny)
+    {
+        HIP_TRY(hipMalloc(&x, sizeof(double) * nx));
+        HIP_TRY(hipMalloc(&y, sizeof(double) * ny));
+        HIP_TRY(hipMemset(x, 0, sizeof(double) * nx));
+        return MI_OK;
+    }
+    void hand_over() { x = y = nullptr; } // the new owner frees them
+};
+
+// the lower of two measurements; 0 = not measured
+static inline double min_measured(double a, double b) { return a > 0 ? std::min(a, b) : b; }
+// a measured and faster than b (strictly)
+static inline bool better(double a, double b) { return a > 0 && (b <= 0 || a < b); }
 
 // true while stream s is being captured into a HIP graph.  Entry points whose kernels take a per-call counter as an ARGUMENT (the
 // one-launch powers step's epoch, the push step's step number) or that measure on first use must not do either under capture:
@@ -157,20 +232,17 @@ struct mi_csr_s {
     std::map<int, BlockTable> tables;
     RingTable ring;           // valid iff ring.d_plan != nullptr
     TileTable tile;           // valid iff tile.d_desc != nullptr
-    double tune_us_tile = 0.0, tune_us_tile_nt = 0.0;
     SstreamTable ss;          // valid iff ss.dev.val != nullptr
     MringTable mring;         // valid iff mring.d_plan != nullptr
-    double tune_us_mring = 0.0, tune_us_mring_nt = 0.0;
     int kernel = MI_KERNEL_AUTO;
     int auto_kernel = MI_KERNEL_STREAM;
     std::vector<double> place_us; // placement draws at create (capi_csr.hip): microseconds per launch, value array first ([0] = as first allocated) ...
     int place_draws_coef = 0;     // ... place_us[0 .. place_draws_coef) belong to the value array, the rest to the 16-bit column stream
     double *kept_x = nullptr, *kept_y = nullptr; // the scratch pair the placement draws were timed on, kept for mi_vec_alloc_placed (its first candidate)
-    double tune_us_ring = 0.0, tune_us_ring_nt = 0.0, tune_us_stream = 0.0, tune_us_stream_nt = 0.0;
+    double tune_us[MI_KERNEL_SSTREAM + 1][2] = {}; // create-time measurement per kernel id, [temporal, non-temporal] loads (the blocked copy: [BCSR4][0]); 0 = not measured
     double tune_us_ring_aligned = 0.0, tune_us_ring_unaligned = 0.0; // large matrices: the two block shapes (0 = not compared)
     bool stream_nt = false; // non-temporal matrix loads in the stream kernel
     mi_bcsr4_t blocked = nullptr; // BCSR 4x4 copy (exact 4x4 node-block structure only), else null
-    double tune_us_bcsr = 0.0;
     int n_out = 0; // length of the y a launch may write (n, or max rowmap + 1)
     // Locality reordering (reorder.hpp): when `inner` is set, this handle is a front for A' = P A P^T, a row-mapped
     // handle in the new numbering; products gather x into d_xp (new numbering) and inner writes y through its row

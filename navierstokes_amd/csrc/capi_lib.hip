@@ -98,8 +98,7 @@ static int flush_cache_on(hipStream_t st, bool sync)
     // for (measured: a cold C4 product 210 us behind the fill alone); behind the read sweep the caches hold clean lines of
     // a buffer nobody uses, i.e. "nothing of the caller's data is cached" and nothing else.
     HIP_TRY(hipMemsetAsync(buf, 1, bytes, st));
-    const char* only_fill = getenv("MI355_FLUSH_FILL_ONLY");
-    if (!(only_fill && !strcmp(only_fill, "1")))
+    if (!env_is("MI355_FLUSH_FILL_ONLY", "1"))
         hipLaunchKernelGGL(flush_read_kernel, dim3(4096), dim3(256), 0, st, reinterpret_cast<const double2*>((char*)buf + bytes), bytes / 16,
                            reinterpret_cast<double*>((char*)buf + 2 * bytes));
     HIP_TRY(hipGetLastError());
@@ -129,31 +128,18 @@ extern "C" int mi_stream_read_probe(long long bytes, int launches, double* us_pe
     CHECK_ARG(bytes >= (1 << 20) && launches >= 1 && us_per_launch, "bad argument");
     int rc = need_device();
     if (rc) return rc;
-    struct ProbeScratch {
-        void* buf = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~ProbeScratch()
-        {
-            dfree(buf);
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } t;
-    HIP_TRY(hipMalloc(&t.buf, (size_t)bytes + 256));
-    HIP_TRY(hipMemset(t.buf, 1, (size_t)bytes + 256));
-    HIP_TRY(hipEventCreate(&t.e0));
-    HIP_TRY(hipEventCreate(&t.e1));
-    double* sink = reinterpret_cast<double*>((char*)t.buf + ((size_t)bytes / 16) * 16);
+    LaunchTimer tm;
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { dfree(p); }
+    } buf;
+    HIP_TRY(hipMalloc(&buf.p, (size_t)bytes + 256));
+    HIP_TRY(hipMemset(buf.p, 1, (size_t)bytes + 256));
+    if ((rc = tm.init())) return rc;
+    double* sink = reinterpret_cast<double*>((char*)buf.p + ((size_t)bytes / 16) * 16);
     auto launch = [&]() {
-        hipLaunchKernelGGL(stream_read_kernel<true>, dim3(2048), dim3(256), 0, nullptr, (const double2*)t.buf, (size_t)bytes / 16, sink);
+        hipLaunchKernelGGL(stream_read_kernel<true>, dim3(2048), dim3(256), 0, nullptr, (const double2*)buf.p, (size_t)bytes / 16, sink);
+        return MI_OK;
     };
-    for (int i = 0; i < 3; i++) launch();
-    HIP_TRY(hipEventRecord(t.e0, nullptr));
-    for (int i = 0; i < launches; i++) launch();
-    HIP_TRY(hipEventRecord(t.e1, nullptr));
-    HIP_TRY(hipEventSynchronize(t.e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t.e0, t.e1));
-    *us_per_launch = ms * 1e3 / launches;
-    return MI_OK;
+    return tm.time(3, launches, launch, us_per_launch);
 }

@@ -558,7 +558,7 @@ extern "C" int mi_part_push_connect(mi_part_t P, const void* handles, const long
     const int R = pl.nranks, me = pl.rank;
     // MI355_PUSH_LOOPBACK=1 (tools/sim_rank.py only): a handle may map windows of its own process — one rank's step timed on
     // one GPU with its pushes looped back and every flag preset, so that nothing ever waits
-    const bool loopback = getenv("MI355_PUSH_LOOPBACK") && !strcmp(getenv("MI355_PUSH_LOOPBACK"), "1");
+    const bool loopback = env_is("MI355_PUSH_LOOPBACK", "1");
     std::vector<void*> bases((size_t)R, nullptr);
     for (int p = 0; p < R; p++) {
         if (p == me || (pl.send_counts[p] == 0 && pl.recv_counts[p] == 0)) continue; // not a neighbour
@@ -655,13 +655,13 @@ int part_push_connect_bases(mi_part_s* P, void* const* bases, const long long* l
     P->push_ready = true;
     // The one-launch step needs all local rows as ONE piece that the ring kernel serves (the push duty and the ghost
     // reads live in that kernel).  MI355_PUSH_FUSED=0 keeps the four-launch form.
-    const char* fe = getenv("MI355_PUSH_FUSED");
+    const bool fused_off = env_is("MI355_PUSH_FUSED", "0");
     // Ranks whose rows have the 4x4 node structure (FE): the piece numbered as x_ext is, the exchange in front of the grid, the ghosts
     // staged once per step (spmv_bcsr4_ext.hpp).  MI355_PUSH_FUSED_EXT=0 keeps the four-launch form for them.  (Up to round 5 halos of
     // <= 16 384 ghosts took a form that read every ghost use from the uncached window, spmv_bcsr4_fused: 14.5 against 7.8 us per step for
     // a 41^3-node box at N = 4, 8.5 against 6.8 for a 31^3-node one — removed.)
-    const char* fx = getenv("MI355_PUSH_FUSED_EXT");
-    if (!(fe && !strcmp(fe, "0")) && !(fx && !strcmp(fx, "0")) && P->kernel == MI_KERNEL_AUTO && pl.n_local > 0 && pl.n_local % 4 == 0 && pl.n_halo % 4 == 0 &&
+    const bool ext_off = env_is("MI355_PUSH_FUSED_EXT", "0");
+    if (!fused_off && !ext_off && P->kernel == MI_KERNEL_AUTO && pl.n_local > 0 && pl.n_local % 4 == 0 && pl.n_halo % 4 == 0 &&
         P->n_links > 0) {
         P->plan.build_all_ext();
         const LocalPiece& L = P->plan.all_ext;
@@ -721,8 +721,7 @@ int part_push_connect_bases(mi_part_s* P, void* const* bases, const long long* l
         }
     }
     // (MI355_PUSH_FUSED_KERNEL=csr_ext: none of the two forms below — the staged scalar step further down instead: tests, A/B)
-    const char* fk0 = getenv("MI355_PUSH_FUSED_KERNEL");
-    if (!P->fused && !(fe && !strcmp(fe, "0")) && !(fk0 && !strcmp(fk0, "csr_ext")) && pl.n_local > 0) {
+    if (!P->fused && !fused_off && !env_is("MI355_PUSH_FUSED_KERNEL", "csr_ext") && pl.n_local > 0) {
         P->plan.build_combined();
         const LocalPiece& L = P->plan.all;
         rc = csr_create_impl(pl.n_local, pl.n_local + pl.n_halo, L.ptrow.data(), L.indcol.data(), L.coef.data(), nullptr, &P->piece_all,
@@ -734,9 +733,8 @@ int part_push_connect_bases(mi_part_s* P, void* const* bases, const long long* l
         // the two is taken even if a kernel WITHOUT a fused form measured a hair faster on this rank: the one-launch step saves three
         // launches, and it only happens if EVERY rank has it (mi_part_push_unfuse) — a rank whose create-time measurement tipped the other
         // way by noise would cost all of them the fused step.  MI355_PUSH_FUSED_KERNEL=ring|sstream forces (A/B).
-        const char* fk = getenv("MI355_PUSH_FUSED_KERNEL");
-        const bool ss_ok = A->ss.dev.val && A->ss.fusable && !A->ss.h_wg_halo.empty() && !A->blocked && !(fk && !strcmp(fk, "ring"));
-        const bool ring_ok = A->ring.d_plan && A->ring.d_run_halo && A->ring.ok_fraction >= 0.90 && !A->blocked && !(fk && !strcmp(fk, "sstream"));
+        const bool ss_ok = A->ss.dev.val && A->ss.fusable && !A->ss.h_wg_halo.empty() && !A->blocked && !env_is("MI355_PUSH_FUSED_KERNEL", "ring");
+        const bool ring_ok = A->ring.d_plan && A->ring.d_run_halo && A->ring.ok_fraction >= 0.90 && !A->blocked && !env_is("MI355_PUSH_FUSED_KERNEL", "sstream");
         // (both are one-launch forms and may be mixed across ranks, so between the two this rank's own create-time measurement decides:
         // at N = 2 — 37 M nonzeros per rank, beyond the Infinity Cache — the ring form measured 66 us against 70 on one box, at N = 8 the
         // sliced stream 20.3 against 21.9)
@@ -774,8 +772,7 @@ int part_push_connect_bases(mi_part_s* P, void* const* bases, const long long* l
     // ... and for SCALAR rows that got no one-launch form above (no 4x4 structure; a halo too wide for the sliced stream's and the ring's fused
     // forms — a 3-D mesh operator over ranks: a plane of ghosts each side): the staged step on the stream kernel's row blocks
     // (spmv_csr_fused_ext, spmv_bcsr4_ext.hpp).  MI355_PUSH_FUSED_CSR_EXT=0 keeps the four launches.
-    const char* fc = getenv("MI355_PUSH_FUSED_CSR_EXT");
-    if (!P->fused && !(fe && !strcmp(fe, "0")) && !(fx && !strcmp(fx, "0")) && !(fc && !strcmp(fc, "0")) && P->kernel == MI_KERNEL_AUTO && pl.n_local > 0 &&
+    if (!P->fused && !fused_off && !ext_off && !env_is("MI355_PUSH_FUSED_CSR_EXT", "0") && P->kernel == MI_KERNEL_AUTO && pl.n_local > 0 &&
         P->n_links > 0) {
         P->plan.build_all_ext();
         const LocalPiece& L = P->plan.all_ext;

@@ -32,7 +32,7 @@ bool ring_dot_eligible(const mi_csr_s* A)
     int depth = R.cfg.depth;
     if (const char* e = getenv("MI355_RING_DEPTH")) depth = atoi(e);
     return R.cfg.id == 4 && R.lean && depth != 3 && R.all_in_loop && R.wgs >= 1 && R.wgs <= 1024 /* kMaxPartials */ &&
-           !(getenv("MI355_SPMV_DOT_EPILOGUE") && !strcmp(getenv("MI355_SPMV_DOT_EPILOGUE"), "0"));
+           !env_is("MI355_SPMV_DOT_EPILOGUE", "0");
 }
 
 int launch_spmv(mi_csr_t A, const double* d_x, double* d_y, hipStream_t s, bool use_map, const RingComm* comm, const RingDot* dot)

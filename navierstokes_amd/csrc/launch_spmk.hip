@@ -3,12 +3,6 @@
 #include "capi_internal.hpp"
 #include "spmk_ring.hpp"
 
-static bool env_is(const char* name, const char* v)
-{
-    const char* e = getenv(name);
-    return e && !strcmp(e, v);
-}
-
 template <int D, bool NT, bool SKEW>
 static hipError_t launch_fused_t(const mi_csr_s* H, const CsrView& V, const SpmkArgs& K, hipStream_t s, bool query, int* max_blocks)
 {
@@ -150,9 +144,8 @@ int spmk_unmapped(mi_csr_t H, int k, const double* d_x, double* const* d_y, hipS
     if (H->kstep_choice[k] == 0) {
         // first k-step of this handle at this k: both forms are the same bits, so run each a few times on the caller's own
         // vectors (outputs are fully overwritten either way) and keep the faster — the choice depends on matrix size and box
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-            if (e0) (void)hipEventDestroy(e0);
+        LaunchTimer tm(s);
+        if (tm.init() != MI_OK) {
             (void)hipGetLastError();
             return spmk_chain(H, k, d_x, d_y, s);
         }
@@ -160,22 +153,13 @@ int spmk_unmapped(mi_csr_t H, int k, const double* d_x, double* const* d_y, hipS
         int rc = MI_OK;
         for (int round = 0; round < 2 && !rc; round++)
             for (int form = 0; form < 2 && !rc; form++) {
-                const int warm = 2, timed = 5;
-                for (int i = 0; i < warm && !rc; i++) rc = form ? spmk_fused(H, k, d_x, d_y, s) : spmk_chain(H, k, d_x, d_y, s);
-                (void)hipEventRecord(e0, s);
-                for (int i = 0; i < timed && !rc; i++) rc = form ? spmk_fused(H, k, d_x, d_y, s) : spmk_chain(H, k, d_x, d_y, s);
-                (void)hipEventRecord(e1, s);
-                (void)hipEventSynchronize(e1);
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, e0, e1);
-                const double t = ms * 1e3 / timed;
-                us[form] = us[form] > 0 ? std::min(us[form], t) : t;
+                double t = 0.0;
+                rc = tm.time(2, 5, [&] { return form ? spmk_fused(H, k, d_x, d_y, s) : spmk_chain(H, k, d_x, d_y, s); }, &t);
+                if (!rc) us[form] = min_measured(us[form], t);
                 // a wait of the one-launch form gave up (the grid is not all resident: somebody else's kernel holds CUs): every further
                 // launch of it would spin its whole budget again — the measurement ends here and the handle takes k launches
                 if (form == 1 && H->h_ktimeouts && __atomic_load_n(H->h_ktimeouts, __ATOMIC_ACQUIRE) != 0) round = 2;
             }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         if (rc) return rc;
         H->kstep_us[k][0] = us[0];
         H->kstep_us[k][1] = us[1];
