@@ -306,7 +306,12 @@ int mi_spmk_plan_probe(int n, const int* ptrow, const int* indcol, int* eligible
 
 /* ---- BLAS-1 between SpMVs ---------------------------------------------- */
 /* out = sum x_i y_i  (std::inner_product, mpk/SpMVmulti.cpp:147).  Fixed
- * two-stage reduction tree: deterministic run to run, not the CPU's order. */
+ * two-stage reduction tree (blas1_kernels.hpp), not the CPU's order: the bits
+ * of mi_dot, mi_norm2 and mi_rel_error (host and device forms) depend only on
+ * n and the data — not on the vectors' alignment, the stream, or whether the
+ * loads are non-temporal.  oracle/cpu_ref.c restates the tree bit for bit; its
+ * distance to the exact sum is at most gamma_h * sum |x_i y_i| with h the tree's
+ * depth (about 30 roundings at 1 M elements). */
 int mi_dot(int n, const double* x, const double* y, double* out);
 int mi_dot_dev(int n, const double* d_x, const double* d_y, double* d_out, mi_stream_t s);
 /* y += a x  (VecAXPY at src/solve_newton.c:1269; the AXPY half of orthogonalize) */
@@ -326,12 +331,22 @@ int mi_orthogonalize_dev(int n, const double* d_b, const double* d_x1, double* d
  *                              by a dot kernel of their own.  Handles whose launch cannot carry the epilogue (other kernels,
  *                              relabelled or blocked matrices) run product and dot as separate launches: same call, same bound.
  *   mi_spmv_orthogonalize_dev  x1 = A x; beta = b . x1 (epilogue); x3 = fma(-(alpha*beta), b, x1): two launches instead of three.
- * beta is a fixed-tree reduction like mi_dot's (deterministic run to run; its last bits differ from mi_dot's and from the CPU's
- * left-to-right sum: |beta - b.y| <= 1e-13 * sum |b_i y_i| is what the tests assert); every row of y / x1 and, given beta, every
- * element of x3 are the reference's bits.  Square or rectangular, unmapped matrices; device vectors. */
+ * beta is a fixed-tree reduction like mi_dot's, not the CPU's left-to-right sum; every row of y / x1 and, given beta, every
+ * element of x3 are the reference's bits.  Square or rectangular, unmapped matrices; device vectors.
+ * WHICH tree gives beta depends on whether the handle's launch carries the dot (mi_csr_dot_epilogue_info): with the epilogue it
+ * is the ring kernel's tree over its runs (mi_csr_dot_epilogue_layout), without it mi_dot_dev's tree over (b, y).  The kernel
+ * choice made at create decides that, so beta's last bits can differ between boxes for the same matrix and vectors.  A caller
+ * who needs the same beta everywhere pins the kernel (mi_csr_set_kernel). */
 int mi_spmv_dot_dev(mi_csr_t A, const double* d_x, double* d_y, const double* d_b, double* d_beta_out, mi_stream_t s);
 /* *in_epilogue = 1 if the next mi_spmv_dot_dev / mi_spmv_orthogonalize_dev on this handle carries the dot in the product's launch */
 int mi_csr_dot_epilogue_info(mi_csr_t A, int* in_epilogue);
+/* Read-only: the layout the ring kernel's dot epilogue walks, for a handle whose launch carries it (else MI_ERR_STATE).
+ * *threads = workgroup size T, *wgs = logical workgroups (= partials), *nblk = row blocks.  When any array is given:
+ * run_first_block[g] (wgs + 1 entries, cap_runs >= wgs + 1) = first block of workgroup g's run, which ends where run g + 1
+ * begins; block_row0[b], block_rows[b] (nblk entries, cap_blocks >= nblk) = first row and row count of block b.  Thread t of
+ * workgroup g adds b[r] * y[r] for row r = block_row0[blk] + t (t < block_rows[blk]) of each block of its run in order. */
+int mi_csr_dot_epilogue_layout(mi_csr_t A, int* threads, int* wgs, int* nblk, int* run_first_block, int* block_row0,
+                               int* block_rows, int cap_runs, int cap_blocks);
 int mi_spmv_orthogonalize_dev(mi_csr_t A, const double* d_x, double* d_x1, const double* d_b, double* d_x3, double alpha,
                               double* d_beta_out, mi_stream_t s);
 /* orthonormalize_against_basis(nrow, basis, y), mpk/2SpMV.cpp:13-28: for each of the m basis vectors IN TURN

@@ -4,8 +4,9 @@
 // pack gather.  All are HBM-bound streams: 16-byte loads per lane, fixed grids,
 // and a fixed two-stage reduction tree (lane chain -> wave shuffle -> LDS across
 // the 4 waves -> one partial per workgroup -> one finishing workgroup), so a
-// result depends only on (n, data), never on scheduling: deterministic run to
-// run, though not the CPU's left-to-right order.
+// result depends only on (n, data), never on scheduling, alignment, stream or
+// the non-temporal choice: deterministic run to run, though not the CPU's
+// left-to-right order.  oracle/cpu_ref.c models every tree bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -92,9 +93,23 @@ __global__ __launch_bounds__(kRedWG) void reduce_stage1(int n, int seg, const do
             if (MODE == 0) s = fma(av, bv, s);
             else { const double d = av - bv; s = fma(d, d, s); s2 = fma(av, av, s2); }
         }
-    } else {
-        for (long long i = lo + threadIdx.x; i < hi; i += kRedWG) {
-            const double av = a[i], bv = b[i];
+    } else { // 8-byte-aligned bases: the same pairs in the same order as above, through scalar loads (the same tree, the same bits)
+        for (long long i = lo + 2 * threadIdx.x; i + 1 < hi; i += 2 * kRedWG) {
+            const double a0 = ld1_stream<NT>(a + i), a1 = ld1_stream<NT>(a + i + 1);
+            const double b0 = ld1_stream<NT>(b + i), b1 = ld1_stream<NT>(b + i + 1);
+            if (MODE == 0) {
+                s = fma(a0, b0, s);
+                s = fma(a1, b1, s);
+            } else {
+                const double d0 = a0 - b0, d1 = a1 - b1;
+                s = fma(d0, d0, s);
+                s = fma(d1, d1, s);
+                s2 = fma(a0, a0, s2);
+                s2 = fma(a1, a1, s2);
+            }
+        }
+        if (((hi - lo) & 1) && threadIdx.x == 0) {
+            const double av = a[hi - 1], bv = b[hi - 1];
             if (MODE == 0) s = fma(av, bv, s);
             else { const double d = av - bv; s = fma(d, d, s); s2 = fma(av, av, s2); }
         }

@@ -156,6 +156,47 @@ extern "C" int mi_csr_dot_epilogue_info(mi_csr_t A, int* in_epilogue)
     return MI_OK;
 }
 
+// what the ring kernel's DOT instantiation walks (spmv_ring.hpp): workgroup size, the blocks of each logical workgroup's run
+// and the rows of each block — enough to restate its summation tree on the host
+extern "C" int mi_csr_dot_epilogue_layout(mi_csr_t A, int* threads, int* wgs, int* nblk, int* run_first_block, int* block_row0,
+                                          int* block_rows, int cap_runs, int cap_blocks)
+{
+    CHECK_ARG(A && threads && wgs && nblk, "null argument");
+    if (!ring_dot_eligible(A)) return fail(MI_ERR_STATE, "this handle's launch does not carry the dot epilogue");
+    const RingTable& R = A->ring;
+    *threads = R.cfg.threads;
+    *wgs = R.wgs;
+    *nblk = R.nblk;
+    if (!run_first_block && !block_row0 && !block_rows) return MI_OK;
+    CHECK_ARG(cap_runs >= R.wgs + 1 && cap_blocks >= R.nblk, "arrays too short: need wgs + 1 run entries and nblk block entries");
+    std::vector<int> rng((size_t)2 * R.wgs);
+    if (R.uniform) {
+        for (int g = 0; g < R.wgs; g++) {
+            rng[2 * g] = std::min(R.nblk, g * R.bpw);
+            rng[2 * g + 1] = std::min(R.nblk, (g + 1) * R.bpw);
+        }
+    } else {
+        HIP_TRY(hipMemcpy(rng.data(), R.d_rng, sizeof(int) * rng.size(), hipMemcpyDeviceToHost));
+    }
+    for (int g = 0; g < R.wgs; g++) // the runs tile the blocks in order: one start per run and the end of the last
+        if (rng[2 * g] != (g ? rng[2 * g - 1] : 0) || rng[2 * g + 1] < rng[2 * g])
+            return fail(MI_ERR_STATE, "ring runs are not consecutive");
+    if (R.wgs && rng[2 * R.wgs - 1] != R.nblk) return fail(MI_ERR_STATE, "ring runs do not cover every block");
+    if (run_first_block) {
+        for (int g = 0; g < R.wgs; g++) run_first_block[g] = rng[2 * g];
+        run_first_block[R.wgs] = R.nblk;
+    }
+    if (block_row0 || block_rows) {
+        std::vector<int> plan((size_t)8 * R.nblk);
+        if (R.nblk) HIP_TRY(hipMemcpy(plan.data(), R.d_plan, sizeof(int) * plan.size(), hipMemcpyDeviceToHost));
+        for (int b = 0; b < R.nblk; b++) {
+            if (block_row0) block_row0[b] = plan[(size_t)8 * b];
+            if (block_rows) block_rows[b] = plan[(size_t)8 * b + 2];
+        }
+    }
+    return MI_OK;
+}
+
 extern "C" int mi_spmv_dot_dev(mi_csr_t A, const double* d_x, double* d_y, const double* d_b, double* d_beta_out, mi_stream_t s_)
 {
     CHECK_ARG(A, "null handle");

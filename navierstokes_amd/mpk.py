@@ -137,6 +137,7 @@ def lib():
         "mi_orthogonalize_dev": [i, _vp, _vp, _vp, d, _vp, _vp],
         "mi_spmv_dot_dev": [_vp, _vp, _vp, _vp, _vp, _vp],
         "mi_csr_dot_epilogue_info": [_vp, P(i)],
+        "mi_csr_dot_epilogue_layout": [_vp, P(i), P(i), P(i), _vp, _vp, _vp, i, i],
         "mi_spmv_orthogonalize_dev": [_vp, _vp, _vp, _vp, _vp, d, _vp, _vp],
         "mi_norm2": [i, _vp, P(d)],
         "mi_norm2_dev": [i, _vp, _vp, _vp],
@@ -413,6 +414,18 @@ class csrmatrix:
         r = _c.c_int()
         check(lib().mi_csr_dot_epilogue_info(self.handle, _c.byref(r)))
         return bool(r.value)
+
+    def dot_epilogue_layout(self):
+        """What the dot epilogue walks (mi_csr_dot_epilogue_layout): dict(threads, run_first_block [wgs + 1], block_row0 [nblk],
+        block_rows [nblk]).  Raises MiError on a handle whose launch does not carry the dot."""
+        t, w, nb = _c.c_int(), _c.c_int(), _c.c_int()
+        check(lib().mi_csr_dot_epilogue_layout(self.handle, _c.byref(t), _c.byref(w), _c.byref(nb), None, None, None, 0, 0))
+        first = np.zeros(w.value + 1, np.int32)
+        row0 = np.zeros(max(nb.value, 1), np.int32)
+        rows = np.zeros(max(nb.value, 1), np.int32)
+        check(lib().mi_csr_dot_epilogue_layout(self.handle, _c.byref(t), _c.byref(w), _c.byref(nb), first.ctypes.data,
+                                               row0.ctypes.data, rows.ctypes.data, first.size, row0.size))
+        return dict(threads=t.value, run_first_block=first, block_row0=row0[: nb.value], block_rows=rows[: nb.value])
 
     # -- the library's numbering (mi_csr_perm ...): permute once per solve, not once per product --------------------
     def perm(self):

@@ -397,6 +397,215 @@ void orc_axpy(int n, double a, const double *x, double *y)
     for (int i = 0; i < n; i++) y[i] = fma(a, x[i], y[i]);
 }
 
+/* ============================================================================
+ * BITWISE MODELS OF THIS LIBRARY'S DEVICE REDUCTION TREES — not the reference.
+ *
+ * The functions below restate, on the host, the fixed summation trees of the
+ * HIP library's reductions, so that tests can hold a device result to the bit:
+ *   - orc_tree_geometry / orc_tree_stage1 / orc_tree_stage2:
+ *       red_geometry (capi_blas1.hip), reduce_stage1, finish_sum, reduce_stage2
+ *       (blas1_kernels.hpp): per-lane fma chain over the pairs (lo+2t, lo+2t+1)
+ *       stepping by 512, the odd tail on thread 0, wave_sum, block_sum, one
+ *       partial per workgroup, then 0.0 + p[t] + p[t+256] + ... and block_sum.
+ *   - orc_tree_ortho_update: ortho_update_kernel's fma(-(alpha*beta), b, x1).
+ *   - orc_tree_mgs_step: one mgs_step_kernel launch.
+ *   - orc_tree_ring_partials: the ring kernel's dot epilogue (spmv_ring.hpp).
+ *   - orc_tree_rank_sum: the rank-order sum of capi_dist.hip.
+ *   - orc_two_products: (p, e) with p + e = a*b exactly, for an exact reference.
+ * Compiled with -ffp-contract=off: every + and * below is one IEEE rounding.
+ * ========================================================================== */
+#define ORC_RED_WG 256
+#define ORC_MAX_PARTIALS 1024
+
+void orc_tree_geometry(int n, int *np, int *seg)
+{
+    long long s = ((long long)n + ORC_MAX_PARTIALS - 1) / ORC_MAX_PARTIALS;
+    const int q = 2 * ORC_RED_WG;
+    s = ((s + q - 1) / q) * q;
+    if (s < q) s = q;
+    *seg = (int)s;
+    *np = (int)(((long long)n + s - 1) / s);
+    if (*np < 1) *np = 1;
+}
+
+/* __shfl_down with offsets 32 .. 1, lane 0's value: a fixed pairwise tree over 64 lanes */
+static double tree_wave(const double *v)
+{
+    double w[64];
+    memcpy(w, v, sizeof(w));
+    for (int off = 32; off > 0; off >>= 1)
+        for (int l = 0; l < off; l++) w[l] = w[l] + w[l + off];
+    return w[0];
+}
+
+/* block_sum over 256 lanes: ((w0 + w1) + w2) + w3 */
+static double tree_block(const double *v)
+{
+    const double w0 = tree_wave(v), w1 = tree_wave(v + 64), w2 = tree_wave(v + 128), w3 = tree_wave(v + 192);
+    return ((w0 + w1) + w2) + w3;
+}
+
+/* reduce_stage1<MODE>: partial[g] (and partial2[g] for MODE 1) for every workgroup; returns np */
+int orc_tree_stage1(int mode, int n, const double *a, const double *b, double *partial, double *partial2)
+{
+    int np, seg;
+    orc_tree_geometry(n, &np, &seg);
+    double s[ORC_RED_WG], s2[ORC_RED_WG];
+    for (int g = 0; g < np; g++) {
+        const long long lo = (long long)g * seg;
+        const long long hi = (lo + seg < n) ? lo + seg : n;
+        for (int t = 0; t < ORC_RED_WG; t++) {
+            double acc = 0.0, acc2 = 0.0;
+            for (long long i = lo + 2 * t; i + 1 < hi; i += 2 * ORC_RED_WG) {
+                if (mode == 0) {
+                    acc = fma(a[i], b[i], acc);
+                    acc = fma(a[i + 1], b[i + 1], acc);
+                } else {
+                    const double d0 = a[i] - b[i], d1 = a[i + 1] - b[i + 1];
+                    acc = fma(d0, d0, acc);
+                    acc = fma(d1, d1, acc);
+                    acc2 = fma(a[i], a[i], acc2);
+                    acc2 = fma(a[i + 1], a[i + 1], acc2);
+                }
+            }
+            if (((hi - lo) & 1) && t == 0) {
+                if (mode == 0) acc = fma(a[hi - 1], b[hi - 1], acc);
+                else {
+                    const double d = a[hi - 1] - b[hi - 1];
+                    acc = fma(d, d, acc);
+                    acc2 = fma(a[hi - 1], a[hi - 1], acc2);
+                }
+            }
+            s[t] = acc;
+            s2[t] = acc2;
+        }
+        partial[g] = tree_block(s);
+        if (mode == 1) partial2[g] = tree_block(s2);
+    }
+    return np;
+}
+
+/* finish_sum: thread t adds 0.0 + p[t] + p[t+256] + ..., then block_sum */
+double orc_tree_finish(int np, const double *partial)
+{
+    double s[ORC_RED_WG];
+    for (int t = 0; t < ORC_RED_WG; t++) {
+        double acc = 0.0;
+        for (int i = t; i < np; i += ORC_RED_WG) acc = acc + partial[i];
+        s[t] = acc;
+    }
+    return tree_block(s);
+}
+
+/* reduce_stage2<FIN>: 0 the sum, 1 sqrt(sum), 2 sqrt(sum) / sqrt(sum2) */
+double orc_tree_stage2(int fin, int np, const double *partial, const double *partial2)
+{
+    const double t = orc_tree_finish(np, partial);
+    if (fin == 0) return t;
+    if (fin == 1) return sqrt(t);
+    return sqrt(t) / sqrt(orc_tree_finish(np, partial2));
+}
+
+/* stage 1 then stage 2: mi_dot (mode 0, fin 0), mi_norm2 (a = b, mode 0, fin 1), mi_rel_error (mode 1, fin 2) */
+double orc_tree_reduce(int mode, int fin, int n, const double *a, const double *b)
+{
+    double *p = (double *)malloc(sizeof(double) * 2 * ORC_MAX_PARTIALS);
+    const int np = orc_tree_stage1(mode, n, a, b, p, p + ORC_MAX_PARTIALS);
+    const double r = orc_tree_stage2(fin, np, p, p + ORC_MAX_PARTIALS);
+    free(p);
+    return r;
+}
+
+/* ortho_update_kernel given beta: out[i] = fma(-(alpha*beta), b[i], x1[i]) (out may alias x1) */
+void orc_tree_ortho_update(long long n, double alpha, double beta, const double *b, const double *x1, double *out)
+{
+    const double nab = -(alpha * beta);
+    for (long long i = 0; i < n; i++) out[i] = fma(nab, b[i], x1[i]);
+}
+
+/* one mgs_step_kernel launch: d = finish(partial_in); y <- fma(-d, v, y); if v_next, partial_out[g] = the
+ * stride-256 chain fma(y_new, v_next, s) over segment g, block_sum.  Returns d. */
+double orc_tree_mgs_step(int n, int np_in, const double *partial_in, const double *v, const double *v_next, double *y,
+                         double *partial_out)
+{
+    const double d = orc_tree_finish(np_in, partial_in), nd = -d;
+    int np, seg;
+    orc_tree_geometry(n, &np, &seg);
+    double s[ORC_RED_WG];
+    for (int g = 0; g < np; g++) {
+        const long long lo = (long long)g * seg;
+        const long long hi = (lo + seg < n) ? lo + seg : n;
+        for (int t = 0; t < ORC_RED_WG; t++) {
+            double acc = 0.0;
+            for (long long i = lo + t; i < hi; i += ORC_RED_WG) {
+                const double yn = fma(nd, v[i], y[i]);
+                y[i] = yn;
+                if (v_next) acc = fma(yn, v_next[i], acc);
+            }
+            s[t] = acc;
+        }
+        if (v_next) partial_out[g] = tree_block(s);
+    }
+    return d;
+}
+
+/* mi_orthonormalize_against_basis_dev: stage 1 of (y, v_0), then one mgs step per basis vector.
+ * basis = m contiguous vectors of n; dots receives the m coefficients. */
+void orc_tree_mgs(int n, int m, const double *basis, double *y, double *dots)
+{
+    if (m <= 0) return;
+    if (n == 0) {
+        for (int j = 0; j < m; j++) dots[j] = 0.0;
+        return;
+    }
+    double *p = (double *)malloc(sizeof(double) * 2 * ORC_MAX_PARTIALS);
+    double *part[2] = {p, p + ORC_MAX_PARTIALS};
+    const int np = orc_tree_stage1(0, n, y, basis, part[0], part[1]);
+    for (int j = 0; j < m; j++) {
+        const double *vn = j + 1 < m ? basis + (size_t)(j + 1) * n : NULL;
+        dots[j] = orc_tree_mgs_step(n, np, part[j & 1], basis + (size_t)j * n, vn, y, part[(j + 1) & 1]);
+    }
+    free(p);
+}
+
+/* The ring kernel's dot epilogue: workgroup g walks blocks [first[g], first[g+1]) in order; its thread t keeps
+ * dacc = fma(b[r], y[r], dacc) for row r = row0[blk] + t of each block with t < rows[blk]; then the wave tree of each
+ * 64 lanes and s_c[0] + s_c[1] + ... over the T / 64 waves.  partial[g] for g < wgs; stage 2 follows (orc_tree_finish). */
+void orc_tree_ring_partials(int threads, int wgs, const int *first, const int *row0, const int *rows, const double *b,
+                            const double *y, double *partial)
+{
+    double *dacc = (double *)malloc(sizeof(double) * (size_t)threads);
+    for (int g = 0; g < wgs; g++) {
+        for (int t = 0; t < threads; t++) dacc[t] = 0.0;
+        for (int blk = first[g]; blk < first[g + 1]; blk++)
+            for (int t = 0; t < rows[blk] && t < threads; t++) {
+                const long long r = (long long)row0[blk] + t;
+                dacc[t] = fma(b[r], y[r], dacc[t]);
+            }
+        double acc = tree_wave(dacc);
+        for (int w = 1; w < threads / 64; w++) acc = acc + tree_wave(dacc + 64 * w);
+        partial[g] = first[g + 1] > first[g] ? acc : 0.0;
+    }
+    free(dacc);
+}
+
+/* ((0.0 + p_0) + p_1) + ...: mi_dist_dot on the host and ortho_update_ranks_kernel on the device */
+double orc_tree_rank_sum(int nparts, const double *p)
+{
+    double s = 0.0;
+    for (int r = 0; r < nparts; r++) s = s + p[r];
+    return s;
+}
+
+/* TwoProduct: p = a*b rounded, e = fma(a, b, -p), so p + e = a*b exactly unless the product underflows */
+void orc_two_products(long long n, const double *a, const double *b, double *p, double *e)
+{
+    for (long long i = 0; i < n; i++) {
+        p[i] = a[i] * b[i];
+        e[i] = fma(a[i], b[i], -p[i]);
+    }
+}
+
 /* ------------------------------------------------------- format builders */
 
 typedef struct { int r, c, k; double v; } orc_ent;

@@ -78,6 +78,24 @@ def cpu():
         L.orc_spmv_csr_fma_omp.argtypes = [_c.c_int, _i32, _i32, _f64, _f64, _f64, _c.c_int]
         L.orc_time_spmv_omp.argtypes = [_c.c_int, _i32, _i32, _f64, _f64, _f64, _c.c_int, _c.c_int]
         L.orc_time_spmv_omp.restype = _c.c_double
+        _i32p, _f64p = _c.POINTER(_c.c_int), _c.c_void_p
+        L.orc_tree_geometry.argtypes = [_c.c_int, _i32p, _i32p]
+        L.orc_tree_stage1.argtypes = [_c.c_int, _c.c_int, _f64p, _f64p, _f64p, _f64p]
+        L.orc_tree_stage1.restype = _c.c_int
+        L.orc_tree_finish.argtypes = [_c.c_int, _f64p]
+        L.orc_tree_finish.restype = _c.c_double
+        L.orc_tree_stage2.argtypes = [_c.c_int, _c.c_int, _f64p, _f64p]
+        L.orc_tree_stage2.restype = _c.c_double
+        L.orc_tree_reduce.argtypes = [_c.c_int, _c.c_int, _c.c_int, _f64p, _f64p]
+        L.orc_tree_reduce.restype = _c.c_double
+        L.orc_tree_ortho_update.argtypes = [_c.c_longlong, _c.c_double, _c.c_double, _f64p, _f64p, _f64p]
+        L.orc_tree_mgs_step.argtypes = [_c.c_int, _c.c_int, _f64p, _f64p, _f64p, _f64p, _f64p]
+        L.orc_tree_mgs_step.restype = _c.c_double
+        L.orc_tree_mgs.argtypes = [_c.c_int, _c.c_int, _f64p, _f64p, _f64p]
+        L.orc_tree_ring_partials.argtypes = [_c.c_int, _c.c_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]
+        L.orc_tree_rank_sum.argtypes = [_c.c_int, _f64p]
+        L.orc_tree_rank_sum.restype = _c.c_double
+        L.orc_two_products.argtypes = [_c.c_longlong, _f64p, _f64p, _f64p, _f64p]
         _CPU = L
     return _CPU
 
@@ -300,6 +318,113 @@ def time_spmv_omp(ptrow, indcol, coef, x, nthreads, reps=5):
     y = np.empty(n, np.float64)
     return cpu().orc_time_spmv_omp(n, ptrow, indcol, coef, x, y, reps, int(nthreads)), y
 
+
+
+# ------------------------------------------- models of this library's device reduction trees (not the reference)
+# Bit for bit what the HIP library's reductions compute (cpu_ref.c, section "BITWISE MODELS"): mi_dot / mi_norm2 /
+# mi_rel_error, the orthogonalize update, the Gram-Schmidt sweep, the ring kernel's dot epilogue, the rank-order sum.
+
+def _ptr(a):
+    return a.ctypes.data
+
+
+def tree_geometry(n):
+    """(np, seg) as red_geometry (capi_blas1.hip) computes them."""
+    np_, seg = _c.c_int(), _c.c_int()
+    cpu().orc_tree_geometry(int(n), _c.byref(np_), _c.byref(seg))
+    return np_.value, seg.value
+
+
+def tree_partials(a, b, mode=0):
+    """reduce_stage1<mode>: (partial, partial2) per workgroup (partial2 is None for mode 0)."""
+    a, b = _as_f64(a), _as_f64(b)
+    assert a.shape == b.shape
+    p = np.zeros(2048)
+    np_ = cpu().orc_tree_stage1(int(mode), len(a), _ptr(a), _ptr(b), _ptr(p), _ptr(p[1024:]))
+    return p[:np_].copy(), (p[1024:1024 + np_].copy() if mode == 1 else None)
+
+
+def tree_finish(partial, partial2=None, fin=0):
+    """reduce_stage2<fin> over the partials: 0 the sum, 1 its sqrt, 2 sqrt(sum) / sqrt(sum2)."""
+    p = _as_f64(partial)
+    p2 = _as_f64(partial2 if partial2 is not None else partial)
+    return cpu().orc_tree_stage2(int(fin), len(p), _ptr(p), _ptr(p2))
+
+
+def tree_dot(a, b):
+    a, b = _as_f64(a), _as_f64(b)
+    assert a.shape == b.shape
+    return cpu().orc_tree_reduce(0, 0, len(a), _ptr(a), _ptr(b))
+
+
+def tree_norm2(x):
+    x = _as_f64(x)
+    return cpu().orc_tree_reduce(0, 1, len(x), _ptr(x), _ptr(x))
+
+
+def tree_rel_error(ref, test):
+    ref, test = _as_f64(ref), _as_f64(test)
+    assert ref.shape == test.shape
+    return cpu().orc_tree_reduce(1, 2, len(ref), _ptr(ref), _ptr(test))
+
+
+def tree_ortho_update(alpha, beta, b, x1):
+    """ortho_update_kernel given beta: fma(-(alpha*beta), b, x1) elementwise."""
+    b, x1 = _as_f64(b), _as_f64(x1)
+    out = np.empty_like(x1)
+    cpu().orc_tree_ortho_update(len(b), float(alpha), float(beta), _ptr(b), _ptr(x1), _ptr(out))
+    return out
+
+
+def tree_orthogonalize(b, x1, alpha=1e-8):
+    """mi_orthogonalize(_dev): (beta, x3) with beta the stage-1 tree of (b, x1)."""
+    beta = tree_dot(b, x1)
+    return beta, tree_ortho_update(alpha, beta, b, x1)
+
+
+def tree_mgs(basis, y):
+    """mi_orthonormalize_against_basis(_dev): (y', dots) for basis of shape (m, n)."""
+    basis = _as_f64(basis)
+    m, n = basis.shape
+    y = _as_f64(y).copy()
+    dots = np.zeros(max(m, 1))
+    cpu().orc_tree_mgs(n, m, _ptr(basis), _ptr(y), _ptr(dots))
+    return y, dots[:m]
+
+
+def tree_ring_partials(layout, b, y):
+    """The ring kernel's dot epilogue, one partial per logical workgroup, for layout = csrmatrix.dot_epilogue_layout()."""
+    b, y = _as_f64(b), _as_f64(y)
+    first = np.ascontiguousarray(layout["run_first_block"], dtype=np.int32)
+    row0 = np.ascontiguousarray(layout["block_row0"], dtype=np.int32)
+    rows = np.ascontiguousarray(layout["block_rows"], dtype=np.int32)
+    wgs = len(first) - 1
+    assert len(row0) == len(rows) and int(first[-1]) == len(rows)
+    if len(rows):
+        assert int((row0.astype(np.int64) + rows).max()) <= len(b) and len(b) == len(y)
+    part = np.zeros(max(wgs, 1))
+    cpu().orc_tree_ring_partials(int(layout["threads"]), wgs, _ptr(first), _ptr(row0), _ptr(rows), _ptr(b), _ptr(y), _ptr(part))
+    return part[:wgs]
+
+
+def tree_ring_dot(layout, b, y):
+    """beta of mi_spmv_dot_dev on a handle whose launch carries the dot: the epilogue's partials, then stage 2."""
+    return tree_finish(tree_ring_partials(layout, b, y))
+
+
+def tree_rank_sum(parts):
+    """((0.0 + p_0) + p_1) + ...: the rank-order sum of mi_dist_dot and mi_dist_orthogonalize."""
+    p = _as_f64(parts)
+    return cpu().orc_tree_rank_sum(len(p), _ptr(p))
+
+
+def two_products(a, b):
+    """(p, e) with p = a*b rounded and e = fma(a, b, -p): math.fsum of both is the exact dot, rounded once
+    (for products that do not underflow)."""
+    a, b = _as_f64(a), _as_f64(b)
+    p, e = np.empty_like(a), np.empty_like(a)
+    cpu().orc_two_products(len(a), _ptr(a), _ptr(b), _ptr(p), _ptr(e))
+    return p, e
 
 # ------------------------------------------------ the real reference (if built)
 
