@@ -356,6 +356,30 @@ int mi_spmv_orthogonalize_dev(mi_csr_t A, const double* d_x, double* d_x1, const
 int mi_orthonormalize_against_basis(int n, int m, const double* const* basis, double* y, double* dots_out /* [m] or NULL */);
 int mi_orthonormalize_against_basis_dev(int n, int m, const double* const* d_basis, double* d_y, double* d_dots /* [m] */,
                                         mi_stream_t s);
+/* VecMDot (src/solve_newton.c:1265, inside KSPSolve: the dots of one GMRES iteration): dots[j] = y . v_j, j < m <= 64, in
+ * ONE pass over y per tile of basis vectors (blas1_multi.hpp) and two launches.  Tree: every column is reduced by mi_dot's own
+ * fixed two-stage tree, so dots[j] has the bits of mi_dot_dev(n, y, v_j), whatever the tile, alignment or stream.
+ * basis: HOST array of m pointers (host resp. device vectors).  m == 0: nothing is done; n == 0: dots = 0.
+ * MI_ERR_ARG: m outside 0..64, a null vector, y pointer-equal to a basis vector. */
+int mi_mdot(int n, int m, const double* const* basis, const double* y, double* dots /* [m] */);
+int mi_mdot_dev(int n, int m, const double* const* d_basis /* HOST array of m device pointers */, const double* d_y,
+                double* d_dots /* device [m] */, mi_stream_t s);
+/* VecMAXPY (src/solve_newton.c:1265, inside KSPSolve: the update of one GMRES iteration), in place:
+ * y <- fma(a_{m-1}, v_{m-1}, ... fma(a_0, v_0, y)) per element, a_j = negate ? -coef[j] : coef[j] (an exact sign flip) — the
+ * bits of m successive mi_axpy_dev.  The device form reads the coefficients from DEVICE memory (no host round trip after the
+ * dots).  d_norm_out (NULL or device [1]): norm2 of the new y, accumulated while it is written.  Tree: mi_norm2's, so the value
+ * has the bits of mi_norm2_dev of the new y.  m == 0: y is left alone, d_norm_out still receives norm2(y).
+ * MI_ERR_ARG: as for mi_mdot. */
+int mi_maxpy(int n, int m, const double* coef /* [m] */, int negate, const double* const* basis, double* y);
+int mi_maxpy_dev(int n, int m, const double* d_coef /* device [m] */, int negate, const double* const* d_basis, double* d_y,
+                 double* d_norm_out, mi_stream_t s);
+/* Classical Gram-Schmidt of y against m vectors out of VecMDot / VecMAXPY (src/solve_newton.c:1265; KSPGMRES's
+ * orthogonalisation, with passes = 2 its -ksp_gmres_cgs_refinement_type refine_always).  Per pass: d = mi_mdot_dev(y) — every
+ * dot against the same y — then y <- mi_maxpy_dev(d, negate = 1).  h = d of pass 1 (+ d of pass 2, ONE rounded add per entry);
+ * *d_norm = norm2 of the final y, from the last update.  Tree: those of mi_dot and mi_norm2.  3 launches per pass.
+ * MI_ERR_ARG: as for mi_mdot, or passes outside {1, 2}. */
+int mi_cgs_dev(int n, int m, const double* const* d_basis, double* d_y, int passes, double* d_h /* device [m] */,
+               double* d_norm /* device [1] */, mi_stream_t s);
 /* sqrt(sum x^2) (norm2, mpk/utils.cpp:131-136) and ||ref-test||/||ref|| (rel_error, :138-143) */
 int mi_norm2(int n, const double* x, double* out);
 int mi_norm2_dev(int n, const double* d_x, double* d_out, mi_stream_t s);
@@ -441,6 +465,13 @@ int mi_spmm_dev(mi_csr_t A, int s, const double* d_X, long long ldx, double* d_Y
  * k with column j (j <= k), [k*(s+2) + k+1] = the norm, [s*(s+2)] = ||v0||. */
 int mi_krylov_basis_dev(mi_csr_t A, int s, const double* d_v0, double* d_V, long long ldv, int orth, double* d_coef,
                         mi_stream_t st);
+/* mi_krylov_basis_dev's orthonormal basis with mi_cgs_dev (VecMDot / VecMAXPY, src/solve_newton.c:1265) in place of the
+ * sequential sweep; passes = 1 | 2.  Same V and d_coef layout ([k*(s+2) + j] = h_j of step k, [k*(s+2) + k+1] = the norm,
+ * [s*(s+2)] = ||v0||).  Tree: the product's fma chain, mi_dot's and mi_norm2's trees, IEEE division.  Two passes keep
+ * max |V^T V - I| at a few ulps on matrices where the sweep of mi_krylov_basis_dev(orth = 1), which is unchanged, loses
+ * orthogonality. */
+int mi_krylov_basis_cgs_dev(mi_csr_t A, int s, const double* d_v0, double* d_V, long long ldv, int passes, double* d_coef,
+                            mi_stream_t st);
 
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r

@@ -878,3 +878,39 @@ extern "C" int mi_krylov_basis_dev(mi_csr_t A, int s, const double* d_v0, double
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
+
+// mi_krylov_basis_dev's orthonormal basis with classical Gram-Schmidt (mi_cgs_dev: VecMDot + VecMAXPY, src/solve_newton.c:1265)
+// in place of the sequential sweep: step k is one product, `passes` x (all k + 1 dots against the same vector, one update), the
+// norm out of the last update, one division — 3 * passes + 2 launches whatever k.  passes = 2 (CGS2) keeps V orthonormal to a
+// few ulps where the sweep and a single pass lose it.  The same V and d_coef layout as mi_krylov_basis_dev;
+// entry [k * (s + 2) + j] is the sum of the two passes' dots.
+extern "C" int mi_krylov_basis_cgs_dev(mi_csr_t A, int s, const double* d_v0, double* d_V, long long ldv, int passes, double* d_coef,
+                                       mi_stream_t st_)
+{
+    CHECK_ARG(A, "null handle");
+    CHECK_ARG(s >= 0 && s <= 64, "s must be in 0..64");
+    CHECK_ARG(passes == 1 || passes == 2, "passes must be 1 or 2");
+    CHECK_ARG(A->n == A->ncols && !A->mapped, "a Krylov basis needs a square, unmapped matrix");
+    if (A->n == 0) return MI_OK;
+    CHECK_ARG(d_v0 && d_V && d_coef && ldv >= A->n, "bad argument");
+    hipStream_t st = (hipStream_t)st_;
+    const int n = A->n;
+    int grid = (n + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    int rc;
+    if (d_V != d_v0) HIP_TRY(hipMemcpyAsync(d_V, d_v0, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    double* nrm0 = d_coef + (size_t)s * (s + 2);
+    if ((rc = mi_norm2_dev(n, d_V, nrm0, st))) return rc;
+    hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, n, nrm0, d_V);
+    std::vector<const double*> cols;
+    for (int k = 0; k < s; k++) {
+        double* next = d_V + (size_t)(k + 1) * ldv;
+        double* h = d_coef + (size_t)k * (s + 2);
+        if ((rc = launch_spmv(A, d_V + (size_t)k * ldv, next, st))) return rc;
+        cols.push_back(d_V + (size_t)k * ldv);
+        if ((rc = mi_cgs_dev(n, (int)cols.size(), cols.data(), next, passes, h, h + k + 1, st))) return rc;
+        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, n, h + k + 1, next);
+    }
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}

@@ -2,13 +2,19 @@
 // Built for gfx950 only; no CPU fallback anywhere: every compute entry point needs a HIP device.
 #include "capi_internal.hpp"
 #include "blas1_kernels.hpp"
+#include "blas1_multi.hpp"
 
 // Reduction workspace: partials of the two-stage reductions, one per (device, stream) so that
 // reductions enqueued on different streams (or by different rank threads of one process) never share
-// partials.  4 * kMaxPartials doubles: [0, 2K) the two partial arrays of a reduction (or the
-// ping-pong pair of the Gram-Schmidt sweep), the rest spare.  32 KB per stream that ever reduced; a
-// destroyed stream's slot is simply reused if the runtime hands the same handle out again.
+// partials.  In units of K = kMaxPartials doubles: [0, 2K) the two partial arrays of a reduction (or the
+// ping-pong pair of the Gram-Schmidt sweep, or the norm partials of mi_maxpy_dev), [2K, 4K) spare,
+// [4K, 68K) one partial array per column of mi_mdot_dev, then kMultiMax doubles for the second-pass
+// dots of mi_cgs_dev.  548 KB per stream that ever reduced; a destroyed stream's slot is simply reused
+// if the runtime hands the same handle out again.
 static std::map<std::pair<int, hipStream_t>, double*> g_ws;
+constexpr size_t kWsMdot = 4 * (size_t)kMaxPartials;                         // the columns' partials
+constexpr size_t kWsDots2 = kWsMdot + (size_t)kMultiMax * kMaxPartials;      // mi_cgs_dev: dots of the second pass
+constexpr size_t kWsDoubles = kWsDots2 + kMultiMax + 8;
 
 int get_ws(hipStream_t s, double** out)
 {
@@ -16,7 +22,7 @@ int get_ws(hipStream_t s, double** out)
     HIP_TRY(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(g_mu);
     double*& w = g_ws[std::make_pair(dev, s)];
-    if (!w) HIP_TRY(hipMalloc(&w, sizeof(double) * (4 * kMaxPartials + 8)));
+    if (!w) HIP_TRY(hipMalloc(&w, sizeof(double) * kWsDoubles));
     *out = w;
     return MI_OK;
 }
@@ -268,6 +274,152 @@ extern "C" int mi_orthonormalize_against_basis_dev(int n, int m, const double* c
     return MI_OK;
 }
 
+// ---------------------------------------------------------------- VecMDot / VecMAXPY / classical Gram-Schmidt (blas1_multi.hpp)
+// basis vectors per pass over y: a compile-time set {4, 8, 16}; the default is what tools/bench_orth.py measured fastest
+// (profiles/NOTES.md), MI355_MDOT_TILE=4|8|16 forces another compiled value (the bits do not depend on it; other values are ignored)
+#ifndef MI355_MDOT_TILE_DEFAULT
+#define MI355_MDOT_TILE_DEFAULT 8
+#endif
+static int mdot_tile()
+{
+    static const int t = [] {
+        const int e = getenv("MI355_MDOT_TILE") ? atoi(getenv("MI355_MDOT_TILE")) : 0;
+        return (e == 4 || e == 8 || e == 16) ? e : MI355_MDOT_TILE_DEFAULT;
+    }();
+    return t;
+}
+
+// the argument rules shared by mi_mdot_dev / mi_maxpy_dev / mi_cgs_dev; nothing here touches the device
+static int multi_check(int n, int m, const double* const* basis, const double* y)
+{
+    CHECK_ARG(n >= 0, "negative n");
+    CHECK_ARG(m >= 0 && m <= kMultiMax, "m must be in 0..64");
+    CHECK_ARG(m == 0 || basis, "null basis");
+    if (n == 0) return MI_OK;
+    CHECK_ARG(y, "null y");
+    for (int j = 0; j < m; j++) {
+        CHECK_ARG(basis[j], "null basis vector");
+        CHECK_ARG(basis[j] != y, "y is one of the basis vectors");
+    }
+    return MI_OK;
+}
+
+template <int TILE>
+static void mdot_launch(int n, int seg, int np, int m, const double* y, const MultiVec& B, double* part, bool nt, hipStream_t s)
+{
+    const dim3 grid(np, (m + TILE - 1) / TILE);
+    if (nt) hipLaunchKernelGGL((mdot_stage1<TILE, true>), grid, dim3(kRedWG), 0, s, n, seg, m, y, B, part);
+    else hipLaunchKernelGGL((mdot_stage1<TILE, false>), grid, dim3(kRedWG), 0, s, n, seg, m, y, B, part);
+}
+
+// dots[j] = y . v_j (and accum[j] += dots[j] when accum is given); n > 0, m > 0, arguments checked
+static int mdot_run(int n, int m, const MultiVec& B, const double* y, double* d_dots, double* d_accum, double* ws, hipStream_t s)
+{
+    int np, seg;
+    red_geometry(n, &np, &seg);
+    const bool nt = blas1_nt(n);
+    switch (mdot_tile()) {
+    case 4: mdot_launch<4>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
+    case 16: mdot_launch<16>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
+    default: mdot_launch<8>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
+    }
+    hipLaunchKernelGGL(mdot_stage2, dim3(m), dim3(kRedWG), 0, s, np, ws + kWsMdot, d_dots, d_accum);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+template <int TILE>
+static void maxpy_launch(int n, int seg, int np, int m, const double* coef, int negate, const MultiVec& B, double* y, double* part,
+                         bool norm, bool nt, hipStream_t s)
+{
+    for (int first = 0; first < m; first += TILE) { // one chunk per launch: each continues the chain from the stored y
+        const int cnt = std::min(TILE, m - first);
+        const bool last = norm && first + TILE >= m;
+        if (nt && last) hipLaunchKernelGGL((maxpy_kernel<TILE, true, true>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
+        else if (nt) hipLaunchKernelGGL((maxpy_kernel<TILE, true, false>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
+        else if (last) hipLaunchKernelGGL((maxpy_kernel<TILE, false, true>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
+        else hipLaunchKernelGGL((maxpy_kernel<TILE, false, false>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
+    }
+}
+
+// y <- y + sum a_j v_j and, when d_norm_out is given, the norm of the new y from the last chunk's partials; n > 0, m > 0
+static int maxpy_run(int n, int m, const double* d_coef, int negate, const MultiVec& B, double* y, double* d_norm_out, double* ws,
+                     hipStream_t s)
+{
+    int np, seg;
+    red_geometry(n, &np, &seg);
+    const bool nt = blas1_nt(n), norm = d_norm_out != nullptr;
+    switch (mdot_tile()) {
+    case 4: maxpy_launch<4>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
+    case 16: maxpy_launch<16>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
+    default: maxpy_launch<8>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
+    }
+    if (norm) hipLaunchKernelGGL((reduce_stage2<1>), dim3(1), dim3(kRedWG), 0, s, np, ws, ws + kMaxPartials, d_norm_out);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+static MultiVec multi_vec(int m, const double* const* basis)
+{
+    MultiVec B;
+    for (int j = 0; j < kMultiMax; j++) B.v[j] = j < m ? basis[j] : nullptr;
+    return B;
+}
+
+extern "C" int mi_mdot_dev(int n, int m, const double* const* d_basis, const double* d_y, double* d_dots, mi_stream_t s_)
+{
+    int rc = multi_check(n, m, d_basis, d_y);
+    if (rc) return rc;
+    if (m == 0) return MI_OK;
+    CHECK_ARG(d_dots, "null dots");
+    hipStream_t s = (hipStream_t)s_;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_dots, 0, sizeof(double) * (size_t)m, s));
+        return MI_OK;
+    }
+    double* ws = nullptr;
+    if ((rc = get_ws(s, &ws))) return rc;
+    return mdot_run(n, m, multi_vec(m, d_basis), d_y, d_dots, nullptr, ws, s);
+}
+
+extern "C" int mi_maxpy_dev(int n, int m, const double* d_coef, int negate, const double* const* d_basis, double* d_y,
+                            double* d_norm_out, mi_stream_t s_)
+{
+    int rc = multi_check(n, m, d_basis, d_y);
+    if (rc) return rc;
+    CHECK_ARG(m == 0 || d_coef, "null coefficients");
+    hipStream_t s = (hipStream_t)s_;
+    if (m == 0 || n == 0) // nothing to update; the norm of y as it stands (0 for an empty vector)
+        return d_norm_out ? mi_norm2_dev(n, d_y, d_norm_out, s_) : MI_OK;
+    double* ws = nullptr;
+    if ((rc = get_ws(s, &ws))) return rc;
+    return maxpy_run(n, m, d_coef, negate, multi_vec(m, d_basis), d_y, d_norm_out, ws, s);
+}
+
+extern "C" int mi_cgs_dev(int n, int m, const double* const* d_basis, double* d_y, int passes, double* d_h, double* d_norm,
+                          mi_stream_t s_)
+{
+    int rc = multi_check(n, m, d_basis, d_y);
+    if (rc) return rc;
+    CHECK_ARG(passes == 1 || passes == 2, "passes must be 1 or 2");
+    CHECK_ARG(d_norm && (m == 0 || d_h), "null h / norm");
+    hipStream_t s = (hipStream_t)s_;
+    if (n == 0 && m) HIP_TRY(hipMemsetAsync(d_h, 0, sizeof(double) * (size_t)m, s));
+    if (m == 0 || n == 0) return mi_norm2_dev(n, d_y, d_norm, s_);
+    double* ws = nullptr;
+    if ((rc = get_ws(s, &ws))) return rc;
+    const MultiVec B = multi_vec(m, d_basis);
+    // per pass: every dot against the SAME y, then one update with the negated dots; the norm rides on the last update
+    if ((rc = mdot_run(n, m, B, d_y, d_h, nullptr, ws, s))) return rc;
+    if ((rc = maxpy_run(n, m, d_h, 1, B, d_y, passes == 1 ? d_norm : nullptr, ws, s))) return rc;
+    if (passes == 2) {
+        double* d2 = ws + kWsDots2;
+        if ((rc = mdot_run(n, m, B, d_y, d2, d_h, ws, s))) return rc; // h_j = h_j + d2_j, one rounded add
+        if ((rc = maxpy_run(n, m, d2, 1, B, d_y, d_norm, ws, s))) return rc;
+    }
+    return MI_OK;
+}
+
 extern "C" int mi_gather_dev(int m, const int* d_idx, const double* d_src, double* d_dst, mi_stream_t s)
 {
     CHECK_ARG(m >= 0, "negative m");
@@ -369,6 +521,48 @@ extern "C" int mi_orthonormalize_against_basis(int n, int m, const double* const
     if (n) HIP_TRY(hipMemcpy(y, dy, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     if (dots_out) HIP_TRY(hipMemcpy(dots_out, dd, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
     else HIP_TRY(hipDeviceSynchronize());
+    return MI_OK;
+}
+
+extern "C" int mi_mdot(int n, int m, const double* const* basis, const double* y, double* dots)
+{
+    int rc = multi_check(n, m, basis, y);
+    if (rc) return rc;
+    CHECK_ARG(m == 0 || dots, "null dots");
+    if ((rc = need_device())) return rc;
+    if (m == 0) return MI_OK;
+    Scratch S;
+    std::vector<const double*> dv((size_t)m);
+    double *dy = nullptr, *dd = nullptr;
+    for (int j = 0; j < m; j++) {
+        double* p = nullptr;
+        if ((rc = S.up(n ? basis[j] : nullptr, n, &p))) return rc;
+        dv[j] = p;
+    }
+    if ((rc = S.up(y, n, &dy)) || (rc = S.up(nullptr, m, &dd))) return rc;
+    if ((rc = mi_mdot_dev(n, m, dv.data(), dy, dd, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(dots, dd, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+extern "C" int mi_maxpy(int n, int m, const double* coef, int negate, const double* const* basis, double* y)
+{
+    int rc = multi_check(n, m, basis, y);
+    if (rc) return rc;
+    CHECK_ARG(m == 0 || coef, "null coefficients");
+    if ((rc = need_device())) return rc;
+    if (m == 0 || n == 0) return MI_OK;
+    Scratch S;
+    std::vector<const double*> dv((size_t)m);
+    double *dy = nullptr, *dc = nullptr;
+    for (int j = 0; j < m; j++) {
+        double* p = nullptr;
+        if ((rc = S.up(basis[j], n, &p))) return rc;
+        dv[j] = p;
+    }
+    if ((rc = S.up(y, n, &dy)) || (rc = S.up(coef, m, &dc))) return rc;
+    if ((rc = mi_maxpy_dev(n, m, dc, negate, dv.data(), dy, nullptr, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(y, dy, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     return MI_OK;
 }
 

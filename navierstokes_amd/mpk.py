@@ -76,6 +76,11 @@ def lib():
         "mi_bcsr4_update_values_dev": [_vp, _vp, _vp],
         "mi_orthonormalize_against_basis": [i, i, _vp, _vp, _vp],
         "mi_orthonormalize_against_basis_dev": [i, i, _vp, _vp, _vp, _vp],
+        "mi_mdot": [i, i, _vp, _vp, _vp],
+        "mi_mdot_dev": [i, i, _vp, _vp, _vp, _vp],
+        "mi_maxpy": [i, i, _vp, i, _vp, _vp],
+        "mi_maxpy_dev": [i, i, _vp, i, _vp, _vp, _vp, _vp],
+        "mi_cgs_dev": [i, i, _vp, _vp, i, _vp, _vp, _vp],
         "mi_part_status": [_vp],
         "mi_part_push_export": [_vp, _vp, _vp],
         "mi_part_push_connect": [_vp, _vp, _vp],
@@ -90,6 +95,7 @@ def lib():
         "mi_bcsr4_spmm_dev": [_vp, i, _vp, ll, _vp, ll, i, _vp],
         "mi_spmm_dev": [_vp, i, _vp, ll, _vp, ll, _vp],
         "mi_krylov_basis_dev": [_vp, i, _vp, _vp, ll, i, _vp, _vp],
+        "mi_krylov_basis_cgs_dev": [_vp, i, _vp, _vp, ll, i, _vp, _vp],
         "mi_csr_reorder_info": [_vp, P(i), P(i), P(d), P(d), P(d), P(d)],
         "mi_reorder_probe": [i, _vp, _vp, P(i), _vp, P(d), P(d)],
         "mi_csr_perm": [_vp, P(i), _vp],
@@ -839,15 +845,23 @@ def MatMatMult_SeqBAIJ_4(A, X, Y, arith="chain"):
 
 def BuildKrylovBasis(A, v0, s, orth=False):
     """orth=False: V[0] = v0, V[k+1] = A V[k], k < s — BuildKrylovBasis_AVX2, src/kernels/spmm_avx2.c:112-168.
-    orth=True: the orthonormal (Arnoldi) basis of the same space (mi_krylov_basis_dev explains).  Returns (V, H, nrm0):
+    orth=True: the orthonormal (Arnoldi) basis of the same space (mi_krylov_basis_dev explains).
+    orth="cgs" / "cgs2": the same basis by classical Gram-Schmidt with one / two passes (mi_krylov_basis_cgs_dev); "cgs2"
+    stays orthonormal where the other two do not.  Returns (V, H, nrm0):
     V a CUDA tensor of shape (s+1, n) (row k = basis vector k); H (s, s+2) with H[k, :k+1] the dots of step k and
     H[k, k+1] the norm, nrm0 = ||v0|| (both None when orth is False)."""
     import torch
+    if isinstance(orth, str) and orth not in ("cgs", "cgs2"):
+        raise ValueError(f"orth: expected False, True, 'cgs' or 'cgs2', got {orth!r}")
     n = A.n
     V = torch.empty((s + 1, n), dtype=torch.float64, device="cuda")
     coef = torch.zeros(s * (s + 2) + 1, dtype=torch.float64, device="cuda") if orth else None
-    check(lib().mi_krylov_basis_dev(A.handle, s, _dev_ptr(v0, n), _dev_ptr(V), n, 1 if orth else 0,
-                                    _dev_ptr(coef) if orth else None, _stream_ptr()))
+    if isinstance(orth, str):
+        check(lib().mi_krylov_basis_cgs_dev(A.handle, s, _dev_ptr(v0, n), _dev_ptr(V), n, 2 if orth == "cgs2" else 1,
+                                            _dev_ptr(coef), _stream_ptr()))
+    else:
+        check(lib().mi_krylov_basis_dev(A.handle, s, _dev_ptr(v0, n), _dev_ptr(V), n, 1 if orth else 0,
+                                        _dev_ptr(coef) if orth else None, _stream_ptr()))
     if not orth:
         return V, None, None
     return V, coef[: s * (s + 2)].reshape(s, s + 2), coef[s * (s + 2)]
@@ -935,6 +949,80 @@ def orthonormalize_against_basis(basis, y):
     dots = np.zeros(m)
     check(lib().mi_orthonormalize_against_basis(n, m, ptrs, yy.ctypes.data, dots.ctypes.data if m else None))
     return dots
+
+
+def _dev_basis(basis, n):
+    return (_vp * max(len(basis), 1))(*[_dev_ptr(b, n, f"basis[{j}]").value for j, b in enumerate(basis)])
+
+
+def _host_basis(basis, n):
+    rows = [_host_f64(b, n, f"basis[{j}]") for j, b in enumerate(basis)]
+    return rows, (_vp * max(len(rows), 1))(*[r.ctypes.data for r in rows])  # rows: keeps converted copies alive
+
+
+def mdot(basis, y):
+    """VecMDot (src/solve_newton.c:1265): dots[j] = y . basis[j] in one pass over y per tile of vectors (mi_mdot*); every
+    entry has the bits of dot(y, basis[j]).  Returns the m dots (numpy array, or a device tensor for device inputs)."""
+    m = len(basis)
+    if _is_torch(y):
+        import torch
+        n = int(y.numel())
+        dots = torch.empty(max(m, 1), dtype=torch.float64, device=y.device)
+        check(lib().mi_mdot_dev(n, m, _dev_basis(basis, n), _dev_ptr(y), _dev_ptr(dots), _stream_ptr()))
+        return dots[:m]
+    yy = _host_f64(y)
+    n = yy.size
+    rows, ptrs = _host_basis(basis, n)
+    dots = np.zeros(m)
+    check(lib().mi_mdot(n, m, ptrs, yy.ctypes.data, dots.ctypes.data if m else None))
+    return dots
+
+
+def maxpy(coef, basis, y, negate=False, norm=False):
+    """VecMAXPY (src/solve_newton.c:1265): y += sum_j a_j basis[j] in place, a_j = -coef[j] when negate else coef[j], as the
+    per-element fma chain of m successive axpy (mi_maxpy*).  Device form: coef is a CUDA tensor (anything else is copied to
+    one).  Returns y, or (y, ||y_new||_2) with norm=True — on the device the norm is accumulated while y is written
+    (mi_maxpy_dev's d_norm_out) and has the bits of norm2(y)."""
+    m = len(basis)
+    if _is_torch(y):
+        import torch
+        n = int(y.numel())
+        if not _is_torch(coef):
+            coef = torch.as_tensor(np.asarray(coef, dtype=np.float64), device=y.device)
+        out = _scalar_dev() if norm else None
+        check(lib().mi_maxpy_dev(n, m, _dev_ptr(coef, m, "coef") if m else None, 1 if negate else 0, _dev_basis(basis, n), _dev_ptr(y),
+                                 _dev_ptr(out) if norm else None, _stream_ptr()))
+        return (y, out) if norm else y
+    yy = _host_f64(y, None, "y", writable=True)
+    n = yy.size
+    rows, ptrs = _host_basis(basis, n)
+    cc = _host_f64(coef, m, "coef")
+    check(lib().mi_maxpy(n, m, cc.ctypes.data if m else None, 1 if negate else 0, ptrs, yy.ctypes.data))
+    return (y, norm2(yy)) if norm else y
+
+
+def cgs(basis, y, passes=2):
+    """Classical Gram-Schmidt of y against basis, in place (mi_cgs_dev): per pass d = mdot(basis, y), y = maxpy(d, basis, y,
+    negate=True); passes=2 is CGS2, what keeps a Krylov basis orthonormal.  Returns (h, norm): h the
+    coefficients (pass 1, plus pass 2 with one rounded add) and norm = ||y_new||_2 — device tensors for device inputs,
+    else a numpy array and a float (the host form composes the host calls: the same bits)."""
+    m = len(basis)
+    if passes not in (1, 2):
+        raise ValueError(f"passes: expected 1 or 2, got {passes!r}")
+    if _is_torch(y):
+        import torch
+        n = int(y.numel())
+        h = torch.empty(max(m, 1), dtype=torch.float64, device=y.device)
+        nrm = _scalar_dev()
+        check(lib().mi_cgs_dev(n, m, _dev_basis(basis, n), _dev_ptr(y), passes, _dev_ptr(h), _dev_ptr(nrm), _stream_ptr()))
+        return h[:m], nrm
+    h = mdot(basis, y)
+    maxpy(h, basis, y, negate=True)
+    if passes == 2:
+        d2 = mdot(basis, y)
+        maxpy(d2, basis, y, negate=True)
+        h = h + d2
+    return h, norm2(y)
 
 
 def norm2(x):
