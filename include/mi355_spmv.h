@@ -473,6 +473,65 @@ int mi_krylov_basis_dev(mi_csr_t A, int s, const double* d_v0, double* d_V, long
 int mi_krylov_basis_cgs_dev(mi_csr_t A, int s, const double* d_v0, double* d_V, long long ldv, int passes, double* d_coef,
                             mi_stream_t st);
 
+/* ---- 4x4-block ILU(k): factored on the host, solved on the GPU level by level ----
+ * The preconditioner of the reference's Newton solve: PCILU with 4 levels of fill on the BAIJ-4 Jacobian under GMRES(30)
+ * (src/solve_newton.c:1156-1164), ILU(0) on the Stokes matrix (:1068-1074), with the hand-written kernels the reference installs
+ * through MatSetOperation(MATOP_SOLVE) (:1088, :1257): src/kernels/baij4_factor_avx2.c (numeric factorisation) and
+ * src/kernels/baij4_solve.c, baij4_solve_avx2.c (MatSolve_SeqBAIJ_4).  Natural ordering (PETSc's default for PCILU: the row and
+ * column permutations of the reference's solve are the identity); single GPU.
+ *
+ * Pattern: symbolic ILU(fill) on the block pattern.  An original block has level 0; block (i, j) reached through a pivot block
+ * (i, p), p < min(i, j), gets lev(i, p) + lev(p, j) + 1 — the minimum over the pivots that reach it — and is kept when that is
+ * <= fill.  Block columns ascending in every row.
+ * Values (baij4_factor_avx2.c:114-170, IKJ): row i of A is scattered into a work row; for each block (i, p) left of the diagonal in
+ * ascending p — skipped when all 16 entries are zero — M = W(i, p) . Dinv(p) replaces it and W(i, j) -= M . U(p, j) for every block
+ * (p, j), j > p, of row p whose column is in row i's pattern; then the diagonal block is inverted in place and the INVERSE is kept,
+ * as PETSc keeps it.
+ * ARITHMETIC (part of the interface): every entry of a 4x4 product is p = fma(a3,b3, fma(a2,b2, fma(a1,b1, a0*b0))) — the four
+ * products chained from a rounded product, as MI_ARITH_BLOCKACC chains them — and an update is ONE rounded w - p.  The 4x4
+ * inverse is Gauss-Jordan without pivoting: for k = 0..3: d = a[k][k]; piv = 1/d; a[k][k] = 1; a[k][j] *= piv (j = 0..3); then for
+ * each other row i ascending: f = a[i][k]; a[i][k] = 0; a[i][j] = a[i][j] - f*a[k][j] (a rounded product, then a rounded
+ * subtraction).  A pivot with |d| < 1e-12 (the reference's threshold) is refused: MI_ERR_ARG with the block row in
+ * mi_last_error(); nothing is regularised (the reference's "+1e-8 and carry on" is not reproduced).  The rows of one dependency
+ * level are factored by several host threads (MI355_BILU_THREADS, default min(cores, 16)); the bits do not depend on the count.
+ * Solve (baij4_solve.c:4-93), x = U^-1 L^-1 b: forward, per block row in level order, s = b_i; for each L block in ascending
+ * column order s_r <- s_r - p_r, p_r the chain above of block row r with t_j; t_i = s.  Backward: s = t_i, the same over the U
+ * blocks, then x_i = Dinv_i . s, each entry one chain.  Every row is therefore ONE fixed sequence of roundings, independent of the
+ * level schedule, the folding and the alignment of the vectors.
+ * Schedule: level of row i = 1 + max level of its L columns (forward; over its U columns backward).  The device copy is
+ * level-major (the rows of a level contiguous, ascending row number); one launch per level, except that a run of consecutive
+ * levels of fewer than 64 block rows is ONE launch of one workgroup stepping through them with workgroup barriers.
+ * The solve is enqueued on the caller's stream; nothing is allocated or synchronised per call; d_x == d_b is allowed.  d_x serves
+ * as the solve's work vector: its contents are undefined until the solve has finished.
+ * MI_ERR_ARG: a null argument, fill < 0, block columns outside [0, nbrows) (the matrix must be square), unsorted or duplicate block
+ * columns, a row without a diagonal block, an unknown layout, a refused pivot.  nbrows == 0: every call is a no-op.
+ * MI355_BILU_FORM: 0 = one launch per (folded) level, the only form built; 1 (a one-launch form with grid-wide barriers) is
+ * refused with MI_ERR_UNSUPPORTED. */
+typedef struct mi_bilu4_s* mi_bilu4_t;
+int mi_bilu4_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout /* MI_BLOCK_* */, int fill,
+                    mi_bilu4_t* out);
+/* the same without a device: pattern, schedule and host factor only (mi_bilu4_refactor, _info, _factor_host work; a solve returns
+ * MI_ERR_STATE) */
+int mi_bilu4_create_host(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, mi_bilu4_t* out);
+int mi_bilu4_destroy(mi_bilu4_t F);
+/* new values, same pattern (a Newton step: the Jacobian is re-assembled, src/solve_newton.c:1257 onwards); waits for the device,
+ * then replaces the factor.  After a refused pivot the handle must be refactored before it is used again. */
+int mi_bilu4_refactor(mi_bilu4_t F, const double* coef, int layout);
+int mi_bilu4_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s); /* MatSolve_SeqBAIJ_4, baij4_solve.c:4-93 */
+int mi_bilu4_solve(mi_bilu4_t F, const double* b, double* x);                         /* host vectors: copied in and out */
+/* *launches = launches per solve (both sweeps, after folding); *form = 0; us[0] = microseconds per solve measured at create
+ * (us[1] = 0: form 1 is not built); *factor_seconds = host time of the last numeric factorisation; *factor_bytes = blocks,
+ * block columns and the per-row tables of the device copy.  Any output may be NULL. */
+int mi_bilu4_info(mi_bilu4_t F, int* nbrows, long long* nblocks, int* fwd_levels, int* bwd_levels, int* launches, int* form,
+                  double us[2], double* factor_seconds, long long* factor_bytes);
+/* the host factor: ptr [nbrows + 1], col and val (16 per block, row-major; L multipliers, INVERTED diagonal block, U blocks) of
+ * nblocks entries, diag [nbrows] = position of every diagonal block.  Any array may be NULL; cap_blocks = entries col / val hold. */
+int mi_bilu4_factor_host(mi_bilu4_t F, int* ptr, int* col, int* diag, double* val, long long cap_blocks);
+/* host-only: pattern and schedule exactly as mi_bilu4_create builds them: factor blocks, levels of the two sweeps, launches
+ * after folding and (optional, cap_levels entries each) the block rows of every level. */
+int mi_bilu4_plan_probe(int nbrows, const int* ptrow, const int* indcol, int fill, long long* nblocks, int* fwd_levels,
+                        int* bwd_levels, int* fwd_launches, int* bwd_launches, int* fwd_sizes, int* bwd_sizes, int cap_levels);
+
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r
  * owns global rows [row_starts[r], row_starts[r+1]) and the matching slice of

@@ -1,0 +1,278 @@
+// bilu4_plan.hpp — host side of the 4x4-block ILU(k) preconditioner (mi_bilu4_*, include/mi355_spmv.h): symbolic
+// factorisation, numeric factorisation, dependency levels and the launch schedule of the level-scheduled solve.
+// Plain C++ (no HIP), like ring_plan.hpp / partition.hpp, so that it can be probed and tested without a GPU.
+//
+// What it stands for in the reference: PCILU on the BAIJ-4 Jacobian (src/solve_newton.c:1156-1164; 4 levels of fill, natural
+// ordering) with the hand-written numeric factorisation src/kernels/baij4_factor_avx2.c:114-170 — row by row, IKJ, the
+// INVERSE of every diagonal block kept.
+//
+// ARITHMETIC (part of the interface, restated by tests/bilu4_model.py):
+//   * a 4x4 product entry is ONE chain from a rounded product: p = fma(a3,b3, fma(a2,b2, fma(a1,b1, a0*b0))), a = a row of
+//     the left block, b = a column of the right block;
+//   * an update is one rounded subtraction w - p;
+//   * the diagonal block is inverted in place by Gauss-Jordan without pivoting, for k = 0..3: d = a[k][k], refused when
+//     |d| < 1e-12; piv = 1/d; a[k][k] = 1; row k is multiplied by piv (one rounded product per entry); then for every other
+//     row i in ascending order: f = a[i][k], a[i][k] = 0, a[i][j] = a[i][j] - f*a[k][j] for j = 0..3 (a rounded product, then a
+//     rounded subtraction: never an fma).
+// The functions below are compiled with floating-point contraction OFF (pragma here, -ffp-contract=off in the Makefile):
+// every fma is written out, nothing else may be fused or reassociated.
+#pragma once
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+
+namespace mi355 {
+
+constexpr int kBiluRowsPerWG = 64;      // block rows one workgroup of the solve kernels serves (four lanes per block row)
+constexpr double kBiluPivotMin = 1e-12; // the reference's zero-pivot threshold (baij4_factor_avx2.c)
+
+// the factor's block pattern: row i holds its L blocks (columns < i), the diagonal block, its U blocks, columns ascending
+struct Bilu4Pattern {
+    int nb = 0;
+    std::vector<int> ptr, col, diag; // diag[i]: position of block (i, i)
+    long long nblocks() const { return ptr.empty() ? 0 : ptr.back(); }
+};
+
+// one sweep's schedule: rows in level-major order (ascending row number inside a level) and the launches after folding
+struct Bilu4Sweep {
+    std::vector<int> perm;       // [nb] position -> block row
+    std::vector<int> lev_ptr;    // [nlev + 1] first position of each level
+    std::vector<int> launch_ptr; // [nlaunch + 1] first level of each launch; a launch of more than one level is a folded run
+    int nlev() const { return (int)lev_ptr.size() - 1; }
+    int nlaunch() const { return (int)launch_ptr.size() - 1; }
+};
+
+// MI_ERR_ARG conditions of a square block pattern; empty string = fine
+inline std::string bilu4_check_pattern(int nb, const int* ptrow, const int* indcol)
+{
+    if (ptrow[0] != 0) return "ptrow[0] must be 0";
+    for (int i = 0; i < nb; i++) {
+        if (ptrow[i + 1] < ptrow[i]) return "ptrow decreases at block row " + std::to_string(i);
+        bool diag = false;
+        for (int k = ptrow[i]; k < ptrow[i + 1]; k++) {
+            const int j = indcol[k];
+            if (j < 0 || j >= nb) return "block column out of range (the matrix must be square) in block row " + std::to_string(i);
+            if (k > ptrow[i] && j <= indcol[k - 1])
+                return std::string(j == indcol[k - 1] ? "duplicate" : "unsorted") + " block columns in block row " + std::to_string(i);
+            diag |= j == i;
+        }
+        if (!diag) return "missing diagonal block in block row " + std::to_string(i);
+    }
+    return std::string();
+}
+
+// Symbolic ILU(fill), natural ordering.  Level-of-fill rule: an original block has level 0; block (i, j) reached through pivot p
+// gets lev(i, p) + lev(p, j) + 1, the MINIMUM over all pivots that reach it, and is kept when that is <= fill.  The pivots of
+// row i are its blocks left of the diagonal in ascending column order, fill blocks included.
+inline void bilu4_symbolic(int nb, const int* ptrow, const int* indcol, int fill, Bilu4Pattern* P)
+{
+    P->nb = nb;
+    P->ptr.assign(1, 0);
+    P->col.clear();
+    P->diag.assign(nb, 0);
+    std::vector<int> lev; // level of every kept block, beside P->col
+    std::vector<int> rc, rl, mc, ml;
+    for (int i = 0; i < nb; i++) {
+        rc.assign(indcol + ptrow[i], indcol + ptrow[i + 1]);
+        rl.assign(rc.size(), 0);
+        if (fill > 0) {
+            for (size_t a = 0; a < rc.size() && rc[a] < i; a++) {
+                const int p = rc[a], lp = rl[a];
+                // merge the U part of row p (columns > p) into the rest of row i
+                mc.assign(rc.begin(), rc.begin() + a + 1);
+                ml.assign(rl.begin(), rl.begin() + a + 1);
+                size_t b = a + 1;
+                int k = P->diag[p] + 1;
+                const int ke = P->ptr[p + 1];
+                while (b < rc.size() || k < ke) {
+                    const int cb = b < rc.size() ? rc[b] : nb, ck = k < ke ? P->col[k] : nb;
+                    if (ck < cb) {
+                        const int nl = lp + lev[k] + 1;
+                        if (nl <= fill) {
+                            mc.push_back(ck);
+                            ml.push_back(nl);
+                        }
+                        k++;
+                    } else if (cb < ck) {
+                        mc.push_back(cb);
+                        ml.push_back(rl[b]);
+                        b++;
+                    } else {
+                        mc.push_back(cb);
+                        ml.push_back(std::min(rl[b], lp + lev[k] + 1));
+                        b++;
+                        k++;
+                    }
+                }
+                rc.swap(mc);
+                rl.swap(ml);
+            }
+        }
+        for (size_t a = 0; a < rc.size(); a++) {
+            if (rc[a] == i) P->diag[i] = (int)P->col.size();
+            P->col.push_back(rc[a]);
+            lev.push_back(rl[a]);
+        }
+        P->ptr.push_back((int)P->col.size());
+    }
+}
+
+// dependency levels: forward, level(i) = 1 + max level of the L columns of row i (0 without any); backward the same over the
+// U columns, rows taken from the last to the first
+inline void bilu4_levels(const Bilu4Pattern& P, bool backward, std::vector<int>* level, int* nlev)
+{
+    level->assign(P.nb, 0);
+    int top = 0;
+    for (int t = 0; t < P.nb; t++) {
+        const int i = backward ? P.nb - 1 - t : t;
+        const int k0 = backward ? P.diag[i] + 1 : P.ptr[i], k1 = backward ? P.ptr[i + 1] : P.diag[i];
+        int l = 0;
+        for (int k = k0; k < k1; k++) l = std::max(l, (*level)[P.col[k]] + 1);
+        (*level)[i] = l;
+        top = std::max(top, l + 1);
+    }
+    *nlev = P.nb ? top : 0;
+}
+
+// level-major order and launches: one launch per level, except that a run of consecutive NARROW levels (fewer block rows than
+// one workgroup serves) is one launch of one workgroup that steps through the run with workgroup barriers
+inline void bilu4_sweep(const Bilu4Pattern& P, bool backward, Bilu4Sweep* S)
+{
+    std::vector<int> level;
+    int nlev = 0;
+    bilu4_levels(P, backward, &level, &nlev);
+    S->lev_ptr.assign(nlev + 1, 0);
+    for (int i = 0; i < P.nb; i++) S->lev_ptr[level[i] + 1]++;
+    for (int l = 0; l < nlev; l++) S->lev_ptr[l + 1] += S->lev_ptr[l];
+    S->perm.assign(P.nb, 0);
+    std::vector<int> fill_at(S->lev_ptr.begin(), S->lev_ptr.end() - (nlev ? 1 : 0));
+    for (int i = 0; i < P.nb; i++) S->perm[fill_at[level[i]]++] = i; // ascending row number inside a level
+    S->launch_ptr.assign(1, 0);
+    for (int l = 0; l < nlev;) {
+        int e = l + 1;
+        if (S->lev_ptr[l + 1] - S->lev_ptr[l] < kBiluRowsPerWG)
+            while (e < nlev && S->lev_ptr[e + 1] - S->lev_ptr[e] < kBiluRowsPerWG) e++;
+        S->launch_ptr.push_back(e);
+        l = e;
+    }
+}
+
+// ---------------------------------------------------------------- numeric
+// c = a . b, every entry one chain from a rounded product
+static inline void bilu4_matmul(const double* a, const double* b, double* c)
+{
+    for (int r = 0; r < 4; r++)
+        for (int q = 0; q < 4; q++) {
+            double p = a[4 * r] * b[q];
+            p = std::fma(a[4 * r + 1], b[4 + q], p);
+            p = std::fma(a[4 * r + 2], b[8 + q], p);
+            p = std::fma(a[4 * r + 3], b[12 + q], p);
+            c[4 * r + q] = p;
+        }
+}
+
+// in-place Gauss-Jordan inverse without pivoting, the order fixed at the top of this file; false: a pivot below the threshold
+static inline bool bilu4_invert(double* a)
+{
+    for (int k = 0; k < 4; k++) {
+        const double d = a[5 * k];
+        if (std::fabs(d) < kBiluPivotMin) return false;
+        const double piv = 1.0 / d;
+        a[5 * k] = 1.0;
+        for (int j = 0; j < 4; j++) a[4 * k + j] = a[4 * k + j] * piv;
+        for (int i = 0; i < 4; i++) {
+            if (i == k) continue;
+            const double f = a[4 * i + k];
+            a[4 * i + k] = 0.0;
+            for (int j = 0; j < 4; j++) {
+                const double t = f * a[4 * k + j];
+                a[4 * i + j] = a[4 * i + j] - t;
+            }
+        }
+    }
+    return true;
+}
+
+// one row of the IKJ factorisation (baij4_factor_avx2.c:114-170) into val; pos: a per-thread map block column -> place in the
+// row, all -1 on entry and on return.  false: zero pivot in this row.
+static inline bool bilu4_factor_row(const Bilu4Pattern& P, int i, const int* ptrow, const int* indcol, const double* coef, bool colmajor,
+                                    double* val, int* pos)
+{
+    const int k0 = P.ptr[i], k1 = P.ptr[i + 1];
+    double* w = val + 16 * (size_t)k0;
+    std::memset(w, 0, sizeof(double) * 16 * (size_t)(k1 - k0));
+    for (int k = k0; k < k1; k++) pos[P.col[k]] = k - k0;
+    for (int k = ptrow[i]; k < ptrow[i + 1]; k++) {
+        double* dst = w + 16 * (size_t)pos[indcol[k]];
+        const double* src = coef + 16 * (size_t)k;
+        if (colmajor)
+            for (int r = 0; r < 4; r++)
+                for (int q = 0; q < 4; q++) dst[4 * r + q] = src[4 * q + r];
+        else
+            std::memcpy(dst, src, sizeof(double) * 16);
+    }
+    double m[16], pr[16];
+    for (int k = k0; k < P.diag[i]; k++) {
+        double* wk = w + 16 * (size_t)(k - k0);
+        bool zero = true;
+        for (int e = 0; e < 16; e++) zero &= wk[e] == 0.0;
+        if (zero) continue;
+        const int p = P.col[k];
+        bilu4_matmul(wk, val + 16 * (size_t)P.diag[p], m);
+        std::memcpy(wk, m, sizeof(m));
+        for (int kk = P.diag[p] + 1; kk < P.ptr[p + 1]; kk++) {
+            const int at = pos[P.col[kk]];
+            if (at < 0) continue;
+            bilu4_matmul(m, val + 16 * (size_t)kk, pr);
+            double* wj = w + 16 * (size_t)at;
+            for (int e = 0; e < 16; e++) wj[e] = wj[e] - pr[e];
+        }
+    }
+    for (int k = k0; k < k1; k++) pos[P.col[k]] = -1;
+    return bilu4_invert(val + 16 * (size_t)P.diag[i]);
+}
+
+// The numeric factorisation over the forward schedule F: the rows of a level are independent, so wide levels are dealt to
+// `threads` threads (contiguous shares); every row is computed by one thread in one fixed order, so the bits do not depend on
+// the thread count.  Returns -1, or the lowest block row whose pivot was refused (rows behind it are then not meaningful).
+inline int bilu4_factor(const Bilu4Pattern& P, const Bilu4Sweep& F, const int* ptrow, const int* indcol, const double* coef, bool colmajor,
+                        int threads, double* val)
+{
+    const int nb = P.nb;
+    threads = std::max(1, std::min(threads, 64));
+    std::vector<std::vector<int>> pos(threads, std::vector<int>(nb, -1));
+    std::atomic<int> bad(nb);
+    auto note = [&](int i) {
+        int cur = bad.load();
+        while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
+    };
+    for (int l = 0; l < F.nlev(); l++) {
+        const int p0 = F.lev_ptr[l], p1 = F.lev_ptr[l + 1];
+        const int T = (p1 - p0 >= kBiluRowsPerWG) ? threads : 1; // a row costs ~10 us, a thread ~20 us to start
+        auto share = [&](int t) {
+            const int a = p0 + (int)((long long)(p1 - p0) * t / T), b = p0 + (int)((long long)(p1 - p0) * (t + 1) / T);
+            for (int q = a; q < b; q++)
+                if (!bilu4_factor_row(P, F.perm[q], ptrow, indcol, coef, colmajor, val, pos[t].data())) note(F.perm[q]);
+        };
+        if (T == 1) {
+            share(0);
+        } else {
+            std::vector<std::thread> th;
+            for (int t = 1; t < T; t++) th.emplace_back(share, t);
+            share(0);
+            for (auto& x : th) x.join();
+        }
+        if (bad.load() < nb) break; // later rows would divide by what was refused
+    }
+    return bad.load() < nb ? bad.load() : -1;
+}
+
+} // namespace mi355

@@ -1,0 +1,113 @@
+// bilu4_solve.hpp — the level-scheduled triangular solves of the 4x4-block ILU preconditioner, x = U^-1 L^-1 b: what
+// MatSolve_SeqBAIJ_4 computes (src/kernels/baij4_solve.c:4-93; natural ordering, the diagonal blocks stored INVERTED).
+//
+// The factor lies level-major on the device (bilu4_plan.hpp): for each sweep the rows of a dependency level are contiguous, so a
+// level is one contiguous stream of blocks; `perm` maps a position back to its block row.  Lane layout of spmv_bcsr4: four lanes
+// per block row, lane q owns row 4*i + q and reads its four coefficients of a block as two 16-byte loads (the quad reads the
+// block's 128 bytes contiguously); the t / x block of the block column is gathered through L2.  One block of look-ahead:
+// a level is a few MB at most, so a lane lives for (blocks per row) x (L2 latency) and the loop is written to keep the next
+// block's loads in flight while the current chain runs.
+//
+// Arithmetic (fixed, include/mi355_spmv.h): per block p = fma(a3,t3, fma(a2,t2, fma(a1,t1, a0*t0))), then ONE rounded s - p,
+// blocks in ascending column order; the backward sweep ends with x = Dinv . s, one chain from a rounded product per entry.
+// A row's result is one fixed sequence of roundings whatever the schedule, the folding or the alignment of the vectors.
+//
+// The vector x carries t between the sweeps and between the levels.  It is read with plain vector loads and is deliberately
+// NOT const __restrict__: inside the folded kernel other waves of the workgroup write it between two barriers.
+#pragma once
+#include "spmv_kernels.hpp"
+
+namespace mi355 {
+
+struct Bilu4SweepView {
+    const int* perm;    // [nb] position -> block row
+    const int* ptr;     // [nb + 1] by position: first off-diagonal block of the row in this sweep
+    const int* col;     // block columns, ascending per row
+    const double* val;  // 16 per block, row-major
+    const double* dinv; // backward sweep: [16 * nb] by position, the inverted diagonal blocks; forward: null
+    const int* lev_ptr; // [nlev + 1] first position of each level
+};
+
+// the four entries of block j of v; AL: v is 16-byte aligned
+template <bool AL>
+__device__ __forceinline__ void bilu4_load4(const double* v, unsigned j, double (&t)[4])
+{
+    if (AL) {
+        const double2* p = reinterpret_cast<const double2*>(v + 4 * (size_t)j);
+        const double2 a = p[0], b = p[1];
+        t[0] = a.x, t[1] = a.y, t[2] = b.x, t[3] = b.y;
+    } else {
+        const double* p = v + 4 * (size_t)j;
+        t[0] = p[0], t[1] = p[1], t[2] = p[2], t[3] = p[3];
+    }
+}
+
+__device__ __forceinline__ double bilu4_chain(double2 c01, double2 c23, const double (&t)[4])
+{
+    double p = __dmul_rn(c01.x, t[0]);
+    p = fma(c01.y, t[1], p);
+    p = fma(c23.x, t[2], p);
+    return fma(c23.y, t[3], p);
+}
+
+// one block row of one sweep, by the quad's lane q; pos < number of rows.  BWD: src == x (t lies there), else src == b.
+template <bool BWD, bool AL>
+__device__ __forceinline__ void bilu4_row(const Bilu4SweepView& V, int pos, int q, const double* src, double* x)
+{
+    const int row = V.perm[pos];
+    const int ia0 = V.ptr[pos], ia1 = V.ptr[pos + 1];
+    double s = src[4 * (size_t)row + q];
+    if (ia0 < ia1) {
+        const int last = ia1 - 1;
+        const double* cq = V.val + 4 * q;
+        const double2* r0 = reinterpret_cast<const double2*>(cq + 16 * (size_t)ia0);
+        double2 a01 = r0[0], a23 = r0[1];
+        double t[4];
+        bilu4_load4<AL>(x, (unsigned)V.col[ia0], t);
+        unsigned cn = (unsigned)V.col[min(ia0 + 1, last)];
+        for (int ia = ia0; ia < ia1; ia++) {
+            const double2 c01 = a01, c23 = a23;
+            const double u[4] = {t[0], t[1], t[2], t[3]};
+            // the next block (clamped to the row's last: loads are unconditional) while this one's chain runs
+            const int nb = min(ia + 1, last);
+            const double2* nr = reinterpret_cast<const double2*>(cq + 16 * (size_t)nb);
+            a01 = nr[0];
+            a23 = nr[1];
+            bilu4_load4<AL>(x, cn, t);
+            cn = (unsigned)V.col[min(ia + 2, last)];
+            s = __dsub_rn(s, bilu4_chain(c01, c23, u));
+        }
+    }
+    if (BWD) {
+        const double sv[4] = {quad_bcast<0>(s), quad_bcast<1>(s), quad_bcast<2>(s), quad_bcast<3>(s)};
+        const double2* d = reinterpret_cast<const double2*>(V.dinv + 16 * (size_t)pos + 4 * q);
+        s = bilu4_chain(d[0], d[1], sv);
+    }
+    x[4 * (size_t)row + q] = s;
+}
+
+// one level: positions [p0, p1), 64 block rows per workgroup
+template <bool BWD, bool AL>
+__global__ __launch_bounds__(kWG) void bilu4_level(Bilu4SweepView V, int p0, int p1, const double* src, double* x)
+{
+    const int g = blockIdx.x * kWG + threadIdx.x;
+    const int pos = p0 + (g >> 2);
+    if (pos >= p1) return; // whole quads leave together
+    bilu4_row<BWD, AL>(V, pos, g & 3, src, x);
+}
+
+// a run of narrow levels [l0, l1) (each fewer than 64 block rows) in ONE workgroup: a workgroup barrier between levels.  The
+// barrier orders the quads' stores to x before the next level's loads of it (same CU, same L1, write-through).
+template <bool BWD, bool AL>
+__global__ __launch_bounds__(kWG) void bilu4_folded(Bilu4SweepView V, int l0, int l1, const double* src, double* x)
+{
+    const int slot = threadIdx.x >> 2, q = threadIdx.x & 3;
+    for (int l = l0; l < l1; l++) {
+        const int pos = V.lev_ptr[l] + slot;
+        if (pos < V.lev_ptr[l + 1]) bilu4_row<BWD, AL>(V, pos, q, src, x);
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+} // namespace mi355

@@ -1,0 +1,315 @@
+// capi_ilu.hip: the 4x4-block ILU(k) preconditioner, mi_bilu4_* — part of libmi355spmv.so (see capi_internal.hpp for the layout of
+// the library).  Factored on the host (bilu4_plan.hpp), solved on the GPU by one launch per (folded) dependency level
+// (bilu4_solve.hpp).  No CPU fallback: the solve needs a HIP device; the planning and factorisation entry points need none.
+#include "capi_internal.hpp"
+#include "bilu4_plan.hpp"
+#include "bilu4_solve.hpp"
+
+struct Bilu4DevSweep {
+    int* perm = nullptr;
+    int* ptr = nullptr;
+    int* col = nullptr;
+    double* val = nullptr;
+    double* dinv = nullptr;
+    int* lev_ptr = nullptr;
+    std::vector<long long> src; // per device block: its place in the host factor (refactor re-gathers through it)
+    void release()
+    {
+        dfree(perm), dfree(ptr), dfree(col), dfree(val), dfree(dinv), dfree(lev_ptr);
+        perm = ptr = col = lev_ptr = nullptr;
+        val = dinv = nullptr;
+    }
+    Bilu4SweepView view() const { return Bilu4SweepView{perm, ptr, col, val, dinv, lev_ptr}; }
+};
+
+struct mi_bilu4_s {
+    int device = -1; // -1: host-only handle (mi_bilu4_create_host)
+    int fill = 0;
+    std::vector<int> a_ptr, a_col; // the matrix's pattern (refactor scatters new values through it)
+    Bilu4Pattern pat;
+    std::vector<double> val;       // host factor, row order, row-major blocks
+    Bilu4Sweep fwd, bwd;
+    Bilu4DevSweep dfwd, dbwd;
+    double factor_seconds = 0.0;
+    double us_form[2] = {0.0, 0.0}; // measured at create: [0] one launch per level; [1] not built
+    double* d_b = nullptr;          // scratch of the host-pointer solve
+    double* d_x = nullptr;
+};
+
+static int bilu_threads()
+{
+    const char* e = getenv("MI355_BILU_THREADS");
+    if (e && atoi(e) > 0) return atoi(e);
+    const unsigned hw = std::thread::hardware_concurrency();
+    return (int)std::max(1u, std::min(hw, 16u));
+}
+
+static int bilu_check_args(int nbrows, const int* ptrow, const int* indcol, int fill)
+{
+    CHECK_ARG(nbrows >= 0, "negative nbrows");
+    CHECK_ARG(fill >= 0, "fill must be >= 0");
+    if (nbrows == 0) return MI_OK;
+    CHECK_ARG(ptrow, "null ptrow");
+    CHECK_ARG(ptrow[nbrows] <= 0 || indcol, "null indcol");
+    const std::string why = bilu4_check_pattern(nbrows, ptrow, indcol);
+    if (!why.empty()) return fail(MI_ERR_ARG, "mi_bilu4: " + why);
+    return MI_OK;
+}
+
+static int bilu_factor(mi_bilu4_s* F, const double* coef, int layout)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const int bad = bilu4_factor(F->pat, F->fwd, F->a_ptr.data(), F->a_col.data(), coef, layout == MI_BLOCK_COLMAJOR, bilu_threads(), F->val.data());
+    F->factor_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (bad >= 0) return fail(MI_ERR_ARG, "mi_bilu4: zero pivot (|d| < 1e-12) in the diagonal block of block row " + std::to_string(bad));
+    return MI_OK;
+}
+
+// the level-major copy of one sweep
+static int bilu_upload_pattern(const mi_bilu4_s* F, bool backward, Bilu4DevSweep* D)
+{
+    const Bilu4Pattern& P = F->pat;
+    const Bilu4Sweep& S = backward ? F->bwd : F->fwd;
+    const int nb = P.nb;
+    std::vector<int> ptr(nb + 1, 0), col;
+    D->src.clear();
+    for (int q = 0; q < nb; q++) {
+        const int i = S.perm[q];
+        const int k0 = backward ? P.diag[i] + 1 : P.ptr[i], k1 = backward ? P.ptr[i + 1] : P.diag[i];
+        for (int k = k0; k < k1; k++) {
+            col.push_back(P.col[k]);
+            D->src.push_back(k);
+        }
+        ptr[q + 1] = (int)col.size();
+    }
+    const size_t nblk = col.size();
+    HIP_TRY(hipMalloc(&D->perm, sizeof(int) * nb));
+    HIP_TRY(hipMalloc(&D->ptr, sizeof(int) * (nb + 1)));
+    HIP_TRY(hipMalloc(&D->col, sizeof(int) * std::max<size_t>(nblk, 1)));
+    HIP_TRY(hipMalloc(&D->val, sizeof(double) * 16 * std::max<size_t>(nblk, 1)));
+    HIP_TRY(hipMalloc(&D->lev_ptr, sizeof(int) * S.lev_ptr.size()));
+    if (backward) HIP_TRY(hipMalloc(&D->dinv, sizeof(double) * 16 * nb));
+    HIP_TRY(hipMemcpy(D->perm, S.perm.data(), sizeof(int) * nb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(D->ptr, ptr.data(), sizeof(int) * (nb + 1), hipMemcpyHostToDevice));
+    if (nblk) HIP_TRY(hipMemcpy(D->col, col.data(), sizeof(int) * nblk, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(D->lev_ptr, S.lev_ptr.data(), sizeof(int) * S.lev_ptr.size(), hipMemcpyHostToDevice));
+    return MI_OK;
+}
+
+static int bilu_upload_values(const mi_bilu4_s* F, bool backward, Bilu4DevSweep* D)
+{
+    const int nb = F->pat.nb;
+    std::vector<double> v(16 * std::max<size_t>(D->src.size(), 1));
+    for (size_t b = 0; b < D->src.size(); b++) memcpy(&v[16 * b], &F->val[16 * (size_t)D->src[b]], sizeof(double) * 16);
+    if (!D->src.empty()) HIP_TRY(hipMemcpy(D->val, v.data(), sizeof(double) * 16 * D->src.size(), hipMemcpyHostToDevice));
+    if (backward) {
+        v.resize(16 * (size_t)nb);
+        for (int q = 0; q < nb; q++) memcpy(&v[16 * (size_t)q], &F->val[16 * (size_t)F->pat.diag[F->bwd.perm[q]]], sizeof(double) * 16);
+        HIP_TRY(hipMemcpy(D->dinv, v.data(), sizeof(double) * 16 * nb, hipMemcpyHostToDevice));
+    }
+    return MI_OK;
+}
+
+template <bool BWD, bool AL>
+static void bilu_sweep_launch(const Bilu4Sweep& S, const Bilu4SweepView& V, const double* src, double* x, hipStream_t s)
+{
+    for (int a = 0; a < S.nlaunch(); a++) {
+        const int l0 = S.launch_ptr[a], l1 = S.launch_ptr[a + 1];
+        const int p0 = S.lev_ptr[l0], p1 = S.lev_ptr[l1];
+        if (l1 - l0 > 1 || p1 - p0 < kBiluRowsPerWG) {
+            hipLaunchKernelGGL((bilu4_folded<BWD, AL>), dim3(1), dim3(kWG), 0, s, V, l0, l1, src, x);
+        } else {
+            const int grid = (p1 - p0 + kBiluRowsPerWG - 1) / kBiluRowsPerWG;
+            hipLaunchKernelGGL((bilu4_level<BWD, AL>), dim3(grid), dim3(kWG), 0, s, V, p0, p1, src, x);
+        }
+    }
+}
+
+// form A: one launch per (folded) level, forward then backward, on the caller's stream; nothing allocated or synchronised
+static int bilu_solve_launch(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
+{
+    const Bilu4SweepView vf = F->dfwd.view(), vb = F->dbwd.view();
+    if ((((uintptr_t)d_x) & 15) == 0) {
+        bilu_sweep_launch<false, true>(F->fwd, vf, d_b, d_x, s);
+        bilu_sweep_launch<true, true>(F->bwd, vb, d_x, d_x, s);
+    } else {
+        bilu_sweep_launch<false, false>(F->fwd, vf, d_b, d_x, s);
+        bilu_sweep_launch<true, false>(F->bwd, vb, d_x, d_x, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+static void bilu_free(mi_bilu4_s* F)
+{
+    if (!F) return;
+    F->dfwd.release();
+    F->dbwd.release();
+    dfree(F->d_b);
+    dfree(F->d_x);
+    delete F;
+}
+
+static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, bool device, mi_bilu4_t* out)
+{
+    CHECK_ARG(out, "null output handle");
+    *out = nullptr;
+    CHECK_ARG(layout == MI_BLOCK_ROWMAJOR || layout == MI_BLOCK_COLMAJOR, "unknown block layout");
+    int rc = bilu_check_args(nbrows, ptrow, indcol, fill);
+    if (rc) return rc;
+    CHECK_ARG(nbrows == 0 || coef, "null coef");
+    if (const char* e = getenv("MI355_BILU_FORM")) {
+        CHECK_ARG(!strcmp(e, "0") || !strcmp(e, "1"), "MI355_BILU_FORM must be 0 or 1");
+        if (!strcmp(e, "1"))
+            return fail(MI_ERR_UNSUPPORTED, "MI355_BILU_FORM=1: the one-launch form of the solve is not built in this version (form 0: one launch per level)");
+    }
+    if (device && (rc = need_device())) return rc;
+    mi_bilu4_s* F = new (std::nothrow) mi_bilu4_s;
+    if (!F) return fail(MI_ERR_ALLOC, "host allocation failed");
+    F->fill = fill;
+    if (nbrows > 0) {
+        F->a_ptr.assign(ptrow, ptrow + nbrows + 1);
+        F->a_col.assign(indcol, indcol + ptrow[nbrows]);
+    } else {
+        F->a_ptr.assign(1, 0);
+    }
+    bilu4_symbolic(nbrows, F->a_ptr.data(), F->a_col.data(), fill, &F->pat);
+    bilu4_sweep(F->pat, false, &F->fwd);
+    bilu4_sweep(F->pat, true, &F->bwd);
+    F->val.assign(16 * (size_t)F->pat.nblocks(), 0.0);
+    if ((rc = bilu_factor(F, coef, layout))) {
+        bilu_free(F);
+        return rc;
+    }
+    if (device && nbrows > 0) {
+        auto up = [&]() -> int {
+            HIP_TRY(hipGetDevice(&F->device));
+            int r;
+            if ((r = bilu_upload_pattern(F, false, &F->dfwd)) || (r = bilu_upload_pattern(F, true, &F->dbwd))) return r;
+            if ((r = bilu_upload_values(F, false, &F->dfwd)) || (r = bilu_upload_values(F, true, &F->dbwd))) return r;
+            HIP_TRY(hipMalloc(&F->d_b, sizeof(double) * 4 * nbrows));
+            HIP_TRY(hipMalloc(&F->d_x, sizeof(double) * 4 * nbrows));
+            HIP_TRY(hipMemset(F->d_b, 0, sizeof(double) * 4 * nbrows));
+            // the solve's time, through the library's one timing helper (zero right-hand side: the time does not depend on values)
+            LaunchTimer T(nullptr);
+            if ((r = T.init())) return r;
+            if ((r = T.time(2, 5, [&] { return bilu_solve_launch(F, F->d_b, F->d_x, nullptr); }, &F->us_form[0]))) return r;
+            return MI_OK;
+        };
+        if ((rc = up())) {
+            bilu_free(F);
+            return rc;
+        }
+    } else if (device) {
+        F->device = 0; // an empty matrix: every call on it is a no-op
+    }
+    *out = F;
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, mi_bilu4_t* out)
+{
+    return bilu_create(nbrows, ptrow, indcol, coef, layout, fill, true, out);
+}
+
+extern "C" int mi_bilu4_create_host(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, mi_bilu4_t* out)
+{
+    return bilu_create(nbrows, ptrow, indcol, coef, layout, fill, false, out);
+}
+
+extern "C" int mi_bilu4_destroy(mi_bilu4_t F)
+{
+    bilu_free(F);
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4_refactor(mi_bilu4_t F, const double* coef, int layout)
+{
+    CHECK_ARG(F, "null handle");
+    CHECK_ARG(layout == MI_BLOCK_ROWMAJOR || layout == MI_BLOCK_COLMAJOR, "unknown block layout");
+    if (F->pat.nb == 0) return MI_OK;
+    CHECK_ARG(coef, "null coef");
+    int rc = bilu_factor(F, coef, layout);
+    if (rc) return rc;
+    if (F->device < 0) return MI_OK;
+    // solves already enqueued read the old values: wait for them, then replace (a Newton step refactors between solves)
+    HIP_TRY(hipDeviceSynchronize());
+    if ((rc = bilu_upload_values(F, false, &F->dfwd)) || (rc = bilu_upload_values(F, true, &F->dbwd))) return rc;
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s)
+{
+    CHECK_ARG(F, "null handle");
+    if (F->pat.nb == 0) return MI_OK;
+    CHECK_ARG(d_b && d_x, "null vector");
+    if (F->device < 0) return fail(MI_ERR_STATE, "mi_bilu4_solve: a host-only handle (mi_bilu4_create_host) has no device factor");
+    return bilu_solve_launch(F, d_b, d_x, (hipStream_t)s);
+}
+
+extern "C" int mi_bilu4_solve(mi_bilu4_t F, const double* b, double* x)
+{
+    CHECK_ARG(F, "null handle");
+    if (F->pat.nb == 0) return MI_OK;
+    CHECK_ARG(b && x, "null vector");
+    if (F->device < 0) return fail(MI_ERR_STATE, "mi_bilu4_solve: a host-only handle (mi_bilu4_create_host) has no device factor");
+    const size_t bytes = sizeof(double) * 4 * (size_t)F->pat.nb;
+    HIP_TRY(hipMemcpy(F->d_b, b, bytes, hipMemcpyHostToDevice));
+    int rc = bilu_solve_launch(F, F->d_b, F->d_x, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(x, F->d_x, bytes, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4_info(mi_bilu4_t F, int* nbrows, long long* nblocks, int* fwd_levels, int* bwd_levels, int* launches, int* form,
+                             double us[2], double* factor_seconds, long long* factor_bytes)
+{
+    CHECK_ARG(F, "null handle");
+    if (nbrows) *nbrows = F->pat.nb;
+    if (nblocks) *nblocks = F->pat.nblocks();
+    if (fwd_levels) *fwd_levels = F->fwd.nlev();
+    if (bwd_levels) *bwd_levels = F->bwd.nlev();
+    if (launches) *launches = F->fwd.nlaunch() + F->bwd.nlaunch();
+    if (form) *form = 0;
+    if (us) us[0] = F->us_form[0], us[1] = F->us_form[1];
+    if (factor_seconds) *factor_seconds = F->factor_seconds;
+    if (factor_bytes) *factor_bytes = F->pat.nblocks() * (long long)(16 * sizeof(double) + sizeof(int)) + (long long)F->pat.nb * 4 * (long long)sizeof(int);
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4_factor_host(mi_bilu4_t F, int* ptr, int* col, int* diag, double* val, long long cap_blocks)
+{
+    CHECK_ARG(F, "null handle");
+    const long long nblk = F->pat.nblocks();
+    CHECK_ARG(cap_blocks >= nblk || (!col && !val), "arrays too short: need mi_bilu4_info's nblocks entries");
+    const int nb = F->pat.nb;
+    if (ptr && nb) memcpy(ptr, F->pat.ptr.data(), sizeof(int) * (nb + 1));
+    if (ptr && !nb) ptr[0] = 0;
+    if (col && nblk) memcpy(col, F->pat.col.data(), sizeof(int) * nblk);
+    if (diag && nb) memcpy(diag, F->pat.diag.data(), sizeof(int) * nb);
+    if (val && nblk) memcpy(val, F->val.data(), sizeof(double) * 16 * nblk);
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4_plan_probe(int nbrows, const int* ptrow, const int* indcol, int fill, long long* nblocks, int* fwd_levels,
+                                   int* bwd_levels, int* fwd_launches, int* bwd_launches, int* fwd_sizes, int* bwd_sizes, int cap_levels)
+{
+    int rc = bilu_check_args(nbrows, ptrow, indcol, fill);
+    if (rc) return rc;
+    Bilu4Pattern P;
+    Bilu4Sweep Fw, Bw;
+    bilu4_symbolic(nbrows, ptrow, indcol, fill, &P);
+    bilu4_sweep(P, false, &Fw);
+    bilu4_sweep(P, true, &Bw);
+    if (nblocks) *nblocks = P.nblocks();
+    if (fwd_levels) *fwd_levels = Fw.nlev();
+    if (bwd_levels) *bwd_levels = Bw.nlev();
+    if (fwd_launches) *fwd_launches = Fw.nlaunch();
+    if (bwd_launches) *bwd_launches = Bw.nlaunch();
+    CHECK_ARG((!fwd_sizes || cap_levels >= Fw.nlev()) && (!bwd_sizes || cap_levels >= Bw.nlev()), "level-size arrays too short");
+    if (fwd_sizes)
+        for (int l = 0; l < Fw.nlev(); l++) fwd_sizes[l] = Fw.lev_ptr[l + 1] - Fw.lev_ptr[l];
+    if (bwd_sizes)
+        for (int l = 0; l < Bw.nlev(); l++) bwd_sizes[l] = Bw.lev_ptr[l + 1] - Bw.lev_ptr[l];
+    return MI_OK;
+}

@@ -159,6 +159,15 @@ def lib():
         "mi_bcsr4_spmv_dev": [_vp, _vp, _vp, _vp],
         "mi_bcsr4_spmk": [_vp, i, _vp, _vp],
         "mi_bcsr4_spmk_dev": [_vp, i, _vp, _vp, _vp],
+        "mi_bilu4_create": [i, _vp, _vp, _vp, i, i, P(_vp)],
+        "mi_bilu4_create_host": [i, _vp, _vp, _vp, i, i, P(_vp)],
+        "mi_bilu4_destroy": [_vp],
+        "mi_bilu4_refactor": [_vp, _vp, i],
+        "mi_bilu4_solve_dev": [_vp, _vp, _vp, _vp],
+        "mi_bilu4_solve": [_vp, _vp, _vp],
+        "mi_bilu4_info": [_vp, P(i), P(ll), P(i), P(i), P(i), P(i), P(d), P(d), P(ll)],
+        "mi_bilu4_factor_host": [_vp, _vp, _vp, _vp, _vp, ll],
+        "mi_bilu4_plan_probe": [i, _vp, _vp, i, P(ll), P(i), P(i), P(i), P(i), _vp, _vp, i],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -526,6 +535,109 @@ class bcsr4x4_matrix:
             pass
 
 
+class bilu4:
+    """mi_bilu4_t: the incomplete LU factors of a square 4x4-block matrix — PCILU on the BAIJ-4 Jacobian,
+    src/solve_newton.c:1156-1164 — factored on the host at construction, solved on the GPU level by level.
+    bilu4(A, fill=0) takes a bcsr4x4_matrix's host arrays (and its block layout); bilu4(nbrows, ptrow, indcol, coef, fill=0,
+    layout="row") the arrays themselves.  host_only=True: no device copy (pattern, schedule and factor values only)."""
+
+    def __init__(self, A, ptrow=None, indcol=None, coef=None, fill=0, layout="row", host_only=False):
+        if isinstance(A, bcsr4x4_matrix):
+            nbrows, ptrow, indcol, coef, lay = A.nrows, A.ptrow, A.indcol, A.coef, A.layout
+        else:
+            nbrows, lay = int(A), {"row": 0, "col": 1}[layout]
+        self.nbrows = int(nbrows)
+        self.layout = lay
+        self.fill = int(fill)
+        ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+        indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+        coef = _host_f64(coef, None, "coef")
+        if len(ptrow) != self.nbrows + 1:
+            raise ValueError("ptrow must have nbrows+1 entries")
+        if coef.size < 16 * len(indcol):
+            raise ValueError("coef: 16 values per block")
+        self._nblocks_in = len(indcol)
+        self._h = None
+        h = _vp()
+        make = lib().mi_bilu4_create_host if host_only else lib().mi_bilu4_create
+        check(make(self.nbrows, ptrow.ctypes.data, indcol.ctypes.data, coef.ctypes.data, lay, self.fill, _c.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("bilu4: closed")
+        return self._h
+
+    def solve(self, x, b):
+        """x = U^-1 L^-1 b.  CUDA tensors: asynchronous on torch's current stream, x may be b; numpy arrays: copied in and out."""
+        n = 4 * self.nbrows
+        if _is_torch(b):
+            check(lib().mi_bilu4_solve_dev(self.handle, _dev_ptr(b, n, "b"), _dev_ptr(x, n, "x"), _stream_ptr()))
+        else:
+            xx = _host_f64(x, n, "x", writable=True)
+            check(lib().mi_bilu4_solve(self.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data))
+        return x
+
+    def refactor(self, coef):
+        """New block values for the same pattern (same layout as at construction)."""
+        coef = _host_f64(coef, 16 * self._nblocks_in, "coef")
+        check(lib().mi_bilu4_refactor(self.handle, coef.ctypes.data, self.layout))
+        return self
+
+    def info(self):
+        """dict(nbrows, nblocks, fwd_levels, bwd_levels, launches, form, us_per_level_launches, us_one_launch, factor_seconds,
+        factor_bytes) — mi_bilu4_info."""
+        nb, fl, bl, la, fo = (_c.c_int() for _ in range(5))
+        nblk, by = _c.c_longlong(), _c.c_longlong()
+        us = (_c.c_double * 2)()
+        fs = _c.c_double()
+        check(lib().mi_bilu4_info(self.handle, _c.byref(nb), _c.byref(nblk), _c.byref(fl), _c.byref(bl), _c.byref(la), _c.byref(fo), us,
+                                  _c.byref(fs), _c.byref(by)))
+        return dict(nbrows=nb.value, nblocks=nblk.value, fwd_levels=fl.value, bwd_levels=bl.value, launches=la.value, form=fo.value,
+                    us_per_level_launches=us[0], us_one_launch=us[1], factor_seconds=fs.value, factor_bytes=by.value)
+
+    def factor_host(self):
+        """(ptr, col, diag, val): the host factor — val (nblocks, 4, 4) row-major: L multipliers, INVERTED diagonal blocks, U."""
+        nblk = self.info()["nblocks"]
+        ptr = np.zeros(self.nbrows + 1, np.int32)
+        col = np.zeros(max(nblk, 1), np.int32)
+        diag = np.zeros(max(self.nbrows, 1), np.int32)
+        val = np.zeros((max(nblk, 1), 4, 4), np.float64)
+        check(lib().mi_bilu4_factor_host(self.handle, ptr.ctypes.data, col.ctypes.data, diag.ctypes.data, val.ctypes.data, max(nblk, 1)))
+        return ptr, col[:nblk], diag[: self.nbrows], val[:nblk]
+
+    def close(self):
+        if self._h is not None:
+            lib().mi_bilu4_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bilu4_plan_probe(nbrows, ptrow, indcol, fill=0):
+    """mi_bilu4_plan_probe (no GPU): dict(nblocks, fwd_levels, bwd_levels, fwd_launches, bwd_launches, fwd_sizes, bwd_sizes)."""
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    nblk = _c.c_longlong()
+    fl, bl, fa, ba = (_c.c_int() for _ in range(4))
+    cap = max(int(nbrows), 1)
+    fs, bs = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    check(lib().mi_bilu4_plan_probe(int(nbrows), ptrow.ctypes.data, indcol.ctypes.data, int(fill), _c.byref(nblk), _c.byref(fl), _c.byref(bl),
+                                    _c.byref(fa), _c.byref(ba), fs.ctypes.data, bs.ctypes.data, cap))
+    return dict(nblocks=nblk.value, fwd_levels=fl.value, bwd_levels=bl.value, fwd_launches=fa.value, bwd_launches=ba.value,
+                fwd_sizes=fs[: fl.value].copy(), bwd_sizes=bs[: bl.value].copy())
+
+
+def MatSolve_SeqBAIJ_4(F, b, x):
+    """x = U^-1 L^-1 b with the factors F (a bilu4) — MatSolve_SeqBAIJ_4(A, bb, xx), src/kernels/baij4_solve.c:4-93."""
+    return F.solve(x, b)
+
+
 class DistVector:
     """mi_dist_vec_t: a vector distributed like the rows of a DistMatrix (per rank [owned | halo] on the rank's device)."""
 
@@ -865,6 +977,77 @@ def BuildKrylovBasis(A, v0, s, orth=False):
     if not orth:
         return V, None, None
     return V, coef[: s * (s + 2)].reshape(s, s + 2), coef[s * (s + 2)]
+
+
+def GMRES(A, b, x, M=None, restart=30, rtol=1e-8, maxiter=300):
+    """Right-preconditioned restarted GMRES, KSPGMRES with restart 30 of src/solve_newton.c:1156-1164, assembled from the
+    library's pieces: the product (SpMV_BCSR / SpMV_CSR), classical Gram-Schmidt with two passes (cgs: VecMDot / VecMAXPY),
+    maxpy for the update and, with M (a bilu4), MatSolve_SeqBAIJ_4 as the preconditioner: A M^-1 u = b, x = x0 + M^-1 u.
+    b, x: CUDA tensors; x holds the initial guess and receives the solution.  The small Hessenberg least-squares problem is
+    solved on the host (Givens rotations), with one read-back of h per iteration.  Stops when the recurrence's relative
+    residual ||r|| / ||b|| <= rtol or after maxiter iterations.  Returns (iterations, history): history[0] the true relative
+    residual of the initial guess, then one entry per iteration (the recurrence's value; a restart recomputes the true one)."""
+    import torch
+    mult = SpMV_BCSR if isinstance(A, bcsr4x4_matrix) else SpMV_CSR
+    n = int(b.numel())
+    V = torch.empty((restart + 1, n), dtype=torch.float64, device=b.device)
+    w, z = torch.empty_like(b), torch.empty_like(b)
+    bnorm = float(norm2(b).item()) or 1.0
+    its, hist = 0, []
+    while True:
+        mult(w, x, A)
+        r = V[0]
+        r.copy_(b)
+        axpy(-1.0, w, r)
+        beta = float(norm2(r).item())
+        if not hist:
+            hist.append(beta / bnorm)
+        if beta / bnorm <= rtol or its >= maxiter or not np.isfinite(beta):
+            return its, hist
+        r.mul_(1.0 / beta)
+        H = np.zeros((restart + 1, restart))
+        cs, sn, g = np.zeros(restart), np.zeros(restart), np.zeros(restart + 1)
+        g[0] = beta
+        k = 0
+        while k < restart and its < maxiter:
+            if M is not None:
+                M.solve(z, V[k])
+                mult(w, z, A)
+            else:
+                mult(w, V[k], A)
+            h, nrm = cgs([V[j] for j in range(k + 1)], w, passes=2)
+            hk = torch.cat([h, nrm]).cpu().numpy()  # the iteration's one read-back
+            H[: k + 2, k] = hk
+            for j in range(k):
+                t = cs[j] * H[j, k] + sn[j] * H[j + 1, k]
+                H[j + 1, k] = -sn[j] * H[j, k] + cs[j] * H[j + 1, k]
+                H[j, k] = t
+            rho = float(np.hypot(H[k, k], H[k + 1, k]))
+            if rho == 0.0 or not np.isfinite(rho):
+                break
+            cs[k], sn[k] = H[k, k] / rho, H[k + 1, k] / rho
+            H[k, k], H[k + 1, k] = rho, 0.0
+            g[k + 1] = -sn[k] * g[k]
+            g[k] = cs[k] * g[k]
+            its += 1
+            k += 1
+            hist.append(abs(g[k]) / bnorm)
+            if hist[-1] <= rtol or hk[-1] == 0.0:
+                break
+            V[k].copy_(w)
+            V[k].mul_(1.0 / float(hk[-1]))
+        if k == 0:
+            return its, hist
+        y = np.linalg.solve(np.triu(H[:k, :k]), g[:k])
+        if M is not None:
+            w.zero_()
+            maxpy(y, [V[j] for j in range(k)], w)
+            M.solve(z, w)
+            axpy(1.0, z, x)
+        else:
+            maxpy(y, [V[j] for j in range(k)], x)
+        if hist[-1] <= rtol or its >= maxiter:
+            return its, hist
 
 
 # ------------------------------------------------------------------- BLAS-1
