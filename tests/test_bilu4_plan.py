@@ -1,6 +1,11 @@
 """mi_bilu4_plan_probe and the pattern of mi_bilu4_factor_host against the model (tests/bilu4_model.py), exactly: symbolic ILU(k),
 the dependency levels of the two sweeps, their sizes, the launches after folding.  No GPU.  Also: the model's vectorised fma is
-the C library's fma, and every refusal of the argument rules is reached."""
+the C library's fma, and every refusal of the argument rules is reached.
+
+The layered cases of tests/bilu4_cases.py prescribe their level widths; here it is asserted that they have them, in the model and
+in the library's plan, and that together they reach the limits of the schedule: levels of 1, 63, 64, 65, 128 and 129 rows in each
+sweep, a folded run of more than 100 levels that fills every slot a folded level can fill (63 of the workgroup's 64: a level of 64
+is no longer folded), and a sweep in which every launch boundary is a switch between the two kernels."""
 import ctypes
 
 import numpy as np
@@ -78,6 +83,52 @@ def test_fe_levels_are_the_mesh_planes(nx, levels):
     pr = mpk.bilu4_plan_probe(len(bp) - 1, bp, bc, 0)
     assert pr["fwd_levels"] == levels == 3 * nx + 1 and pr["bwd_levels"] == levels
     assert pr["fwd_sizes"].sum() == (nx + 1) ** 3 and pr["nblocks"] == len(bc)
+
+
+@pytest.mark.parametrize("case", C.LAYERED_CASES + C.WIDE_CASES, ids=C.case_id)
+def test_layered_cases_have_their_prescribed_levels_and_factor(case):
+    from navierstokes_amd import mpk
+    name, fill = case
+    assert fill == 0  # fill above 0 can change the levels
+    nb, bp, bc, _ = C.matrix(name)
+    ptr, col, diag = M.symbolic(nb, bp, bc, 0)
+    C.assert_layered_levels(name, M.schedule(nb, ptr, col, diag, False)["sizes"], M.schedule(nb, ptr, col, diag, True)["sizes"])
+    pr = mpk.bilu4_plan_probe(nb, bp, bc, 0)
+    C.assert_layered_levels(name, pr["fwd_sizes"], pr["bwd_sizes"])
+    # structurally symmetric, as the generator promises
+    pairs = set(zip(np.repeat(np.arange(nb), np.diff(bp)).tolist(), bc.tolist()))
+    assert all((j, i) in pairs for i, j in pairs)
+    # a zero pivot among the new cases is a failure, never a way round a GPU test
+    assert not isinstance(C.model_factor(name, 0), M.ZeroPivot) and not isinstance(C.model_factor(name, 0, 1), M.ZeroPivot)
+
+
+def test_layered_cases_reach_the_limits_of_the_schedule():
+    from navierstokes_amd import mpk
+    W = M.ROWS_PER_WG
+    seen = {False: set(), True: set()}
+    longest_full_fold, most_switches, longest_row = 0, 0, 0
+    for name, _ in C.LAYERED_CASES + C.WIDE_CASES:
+        nb, bp, bc, _ = C.matrix(name)
+        ptr, col, diag = M.symbolic(nb, bp, bc, 0)
+        pr = mpk.bilu4_plan_probe(nb, bp, bc, 0)
+        longest_row = max(longest_row, int(np.diff(bp).max()))
+        for backward in (False, True):
+            S = M.schedule(nb, ptr, col, diag, backward)
+            assert S["launches"] == pr["bwd_launches" if backward else "fwd_launches"]
+            seen[backward] |= set(int(s) for s in S["sizes"])
+            folded = []  # per launch: is it the folded kernel
+            for a in range(S["launches"]):
+                l0, l1 = S["launch_ptr"][a], S["launch_ptr"][a + 1]
+                sz = S["sizes"][l0:l1]
+                folded.append(bool(sz[0] < W))
+                assert (sz < W).all() if folded[-1] else (l1 - l0 == 1 and sz[0] >= W)
+                if folded[-1] and sz.max() == W - 1 and sz.min() == 1:
+                    longest_full_fold = max(longest_full_fold, l1 - l0)
+            most_switches = max(most_switches, sum(a != b for a, b in zip(folded, folded[1:])))
+    for backward in (False, True):
+        assert {1, W - 1, W, W + 1, 2 * W, 2 * W + 1} <= seen[backward], sorted(seen[backward])
+        assert set(range(1, W)) <= seen[backward]  # every slot count of a folded level
+    assert longest_full_fold > 100 and most_switches > 20 and longest_row > 200, (longest_full_fold, most_switches, longest_row)
 
 
 def _refused(status, word):
