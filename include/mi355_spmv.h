@@ -421,6 +421,15 @@ int mi_bcsr4_tile_info(mi_bcsr4_t A, int* built, int* in_use, double* us_plain, 
  * same with temporal loads; 2 two waves per SIMD (one workgroup of eight waves per CU), four steps, non-temporal; 3 as 0 with twelve steps;
  * *padding = padded places / blocks - 1; us[f] = microseconds per launch measured for variant f (0: not measured). */
 int mi_bcsr4_sell_info(mi_bcsr4_t A, int* built, int* form_in_use, long long* steps, double* padding, double us[4]);
+/* The plan of that sliced copy for a block pattern, built on the host as mi_bcsr4_create builds it (no device needed; nothing is kept):
+ * *nslices = ceil(nbrows / 16), *nsteps = the steps of all slices (a slice of empty rows takes one), *nwaves = the persistent waves for
+ * a cap of nwaves_max (the handle plans 1024 for variants 0, 1, 3 and the multi-vector product, 2048 for variant 2).  Copied out where
+ * the pointer is not null: sptr[nslices + 3] (first step of every slice, three terminators), wrng[nwaves + 1] (first slice of every
+ * wave), col[(nsteps + 48) * 16] (the column stream with its 48 tail steps: bit 31 a padding place, bit 30 a slice's first step).
+ * Call it once with null arrays for the sizes.  No slice table is made for a matrix without block columns: mi_bcsr4_create never
+ * builds the sliced copy there. */
+int mi_bcsr4_sell_plan_probe(int nbrows, const int* ptrow, const int* indcol, int nwaves_max, int* nslices, long long* nsteps, int* nwaves,
+                             int* sptr, int* wrng, unsigned* col);
 /* new block values (16 per block, row-major) for an unchanged block pattern; see mi_csr_update_values */
 int mi_bcsr4_update_values(mi_bcsr4_t A, const double* coef);
 int mi_bcsr4_update_values_dev(mi_bcsr4_t A, const double* d_coef, mi_stream_t s);

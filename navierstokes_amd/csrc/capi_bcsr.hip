@@ -162,8 +162,10 @@ extern "C" int mi_bcsr4_create(int nbrows, int nbcols, const int* ptrow, const i
     // The sliced copy: built for matrices large enough to stream (MI355_BCSR_SELL=0 never, =1 always and unmeasured with D = 4,
     // non-temporal); its four variants are timed against the row-per-quad kernels above and the fastest of all is what
     // mi_bcsr4_spmv* launches.  Costs a second copy of the block values on the device (+0.9 % padding on the FE matrix).
+    // Never for a matrix without block columns (forced only: it has no blocks): the sliced kernels read x at node 0 for every padding
+    // place, and every slice of such a matrix is one padding step — 32 bytes of an x that has no elements.
     const bool forced = env_is("MI355_BCSR_SELL", "1");
-    if (!env_is("MI355_BCSR_SELL", "0") && (forced || nb >= 100000) && nbcols < (1 << 30)) {
+    if (!env_is("MI355_BCSR_SELL", "0") && (forced || nb >= 100000) && nbcols > 0 && nbcols < (1 << 30)) {
         if ((rc = build_bcsr4_sell(A, ptrow, indcol))) return rc;
         if (A->d_sell_val) choose_bcsr4_sell_form(A, forced);
     }
@@ -235,6 +237,27 @@ extern "C" int mi_bcsr4_sell_info(mi_bcsr4_t A, int* built, int* form_in_use, lo
     if (padding) *padding = A->nblocks > 0 && A->d_sell_val ? (double)A->sell_nsteps * kSellRows / (double)A->nblocks - 1.0 : 0.0;
     if (us)
         for (int i = 0; i < 4; i++) us[i] = A->tune_us_sell[i];
+    return MI_OK;
+}
+
+// The plan of the sliced copy without a device: build_sell_plan as build_bcsr4_sell calls it (which asks for 1024 waves, then for the
+// ranges of 2048 through build_sell_wave_ranges — what build_sell_plan itself calls with nwaves_max), copied out.
+extern "C" int mi_bcsr4_sell_plan_probe(int nbrows, const int* ptrow, const int* indcol, int nwaves_max, int* nslices, long long* nsteps,
+                                        int* nwaves, int* sptr, int* wrng, unsigned* col)
+{
+    CHECK_ARG(nbrows >= 0 && ptrow && ptrow[0] == 0 && nwaves_max >= 1, "bad argument");
+    for (int i = 0; i < nbrows; i++) CHECK_ARG(ptrow[i] <= ptrow[i + 1], "ptrow must be non-decreasing");
+    const long long nb = ptrow[nbrows];
+    CHECK_ARG(nb == 0 || indcol, "indcol is null");
+    for (long long k = 0; k < nb; k++) CHECK_ARG(indcol[k] >= 0 && indcol[k] < (1 << 30), "block column outside [0, 2^30)");
+    SellPlanHost P;
+    build_sell_plan(nbrows, ptrow, indcol, nwaves_max, P);
+    if (nslices) *nslices = P.nslices;
+    if (nsteps) *nsteps = P.nsteps;
+    if (nwaves) *nwaves = P.nwaves;
+    if (sptr) std::copy(P.sptr.begin(), P.sptr.end(), sptr);
+    if (wrng) std::copy(P.wrng.begin(), P.wrng.end(), wrng);
+    if (col) std::copy(P.col.begin(), P.col.end(), col);
     return MI_OK;
 }
 

@@ -117,6 +117,7 @@ def lib():
         "mi_csr_tile_info": [_vp, P(i), P(i), P(d), P(d), P(i)],
         "mi_bcsr4_tile_info": [_vp, P(i), P(i), P(d), P(d)],
         "mi_bcsr4_sell_info": [_vp, P(i), P(i), P(ll), P(d), P(d)],
+        "mi_bcsr4_sell_plan_probe": [i, _vp, _vp, i, P(i), P(ll), P(i), _vp, _vp, _vp],
         "mi_csr_mring_info": [_vp, P(i), P(i), P(i), P(d), P(d), P(i)],
         "mi_csr_sstream_info": [_vp, P(i), P(i), P(ll), P(d), P(d), P(i)],
         "mi_sstream_plan_probe": [i, i, _vp, _vp, P(i), P(i), P(ll), P(d)],
@@ -631,6 +632,20 @@ def bilu4_plan_probe(nbrows, ptrow, indcol, fill=0):
                                     _c.byref(fa), _c.byref(ba), fs.ctypes.data, bs.ctypes.data, cap))
     return dict(nblocks=nblk.value, fwd_levels=fl.value, bwd_levels=bl.value, fwd_launches=fa.value, bwd_launches=ba.value,
                 fwd_sizes=fs[: fl.value].copy(), bwd_sizes=bs[: bl.value].copy())
+
+
+def bcsr4_sell_plan_probe(nbrows, ptrow, indcol, nwaves_max=1024):
+    """mi_bcsr4_sell_plan_probe (no GPU): dict(nslices, nsteps, nwaves, sptr, wrng, col) — the slice table of the blocked kernel's
+    sliced copy; sptr has nslices + 3 entries, wrng nwaves + 1, col (nsteps + 48, 16) as uint32."""
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    ns, nw, st = _c.c_int(), _c.c_int(), _c.c_longlong()
+    args = (int(nbrows), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, int(nwaves_max))
+    check(lib().mi_bcsr4_sell_plan_probe(*args, _c.byref(ns), _c.byref(st), _c.byref(nw), None, None, None))
+    sptr, wrng = np.zeros(ns.value + 3, np.int32), np.zeros(nw.value + 1, np.int32)
+    col = np.zeros((st.value + 48, 16), np.uint32)
+    check(lib().mi_bcsr4_sell_plan_probe(*args, _c.byref(ns), _c.byref(st), _c.byref(nw), sptr.ctypes.data, wrng.ctypes.data, col.ctypes.data))
+    return dict(nslices=ns.value, nsteps=st.value, nwaves=nw.value, sptr=sptr, wrng=wrng, col=col)
 
 
 def MatSolve_SeqBAIJ_4(F, b, x):
