@@ -37,7 +37,8 @@ extern "C" {
 
 #define MI355_SPMV_VERSION 501 /* 0.5.1: mi_bcsr4_spmm_info writes us[5] since 0.4 (it was us[4] in 0.3: a caller built against 0.3 must be rebuilt); 0.5 adds
                                 * mi_sstream_plan_probe_ex, mi_part_kernel_name, mi_part_sends_contiguous and refills sliced copies inside mi_*_update_values*;
-                                * 0.5.1 adds mi_sstream_mw_plan_probe (nothing changed for a caller built against 0.5.0) */
+                                * 0.5.1 adds mi_sstream_mw_plan_probe (nothing changed for a caller built against 0.5.0); mi_bilu4dev_* (the
+                                * device refactor of the block ILU) was added without a version change: nothing existing changed */
 
 enum {
     MI_OK = 0,
@@ -540,6 +541,47 @@ int mi_bilu4_factor_host(mi_bilu4_t F, int* ptr, int* col, int* diag, double* va
  * after folding and (optional, cap_levels entries each) the block rows of every level. */
 int mi_bilu4_plan_probe(int nbrows, const int* ptrow, const int* indcol, int fill, long long* nblocks, int* fwd_levels,
                         int* bwd_levels, int* fwd_launches, int* bwd_launches, int* fwd_sizes, int* bwd_sizes, int cap_levels);
+
+/* ---- 4x4-block ILU(k): the numeric REfactorisation on the GPU (mi_bilu4dev_*) ----
+ * A Newton step re-assembles the Jacobian and refactors before every linear solve (src/solve_newton.c:1257 onwards);
+ * mi_bilu4_refactor does that on host threads, waits for the device and uploads the factor.  mi_bilu4dev_refactor computes the
+ * same factor (baij4_factor_avx2.c:114-170, the ARITHMETIC above, operation for operation: the device factor is bit for bit what
+ * mi_bilu4_refactor would have uploaded for the same values) on the GPU, on the caller's stream, from block values that already
+ * lie on the device, in place into the device copies the solve reads; no second copy of the values is kept.
+ * Schedule: the forward sweep's levels and launches (a row needs the finished rows of its L columns), after ONE launch that
+ * clears the fill blocks, scatters the values and resets the refusal word: launches per refactor = forward launches + 1.
+ * Sixteen lanes per block row, one per entry of a block.
+ * ORDERING is the caller's business, as it is for the solve: a refactor on stream s is ordered with solves on s only.  A solve
+ * running on another stream during a refactor reads a half-written factor.
+ * Refused pivot: the refactor itself cannot report it (nothing is copied back); mi_bilu4dev_status does.  As on the host, the
+ * rows of later levels are then not factored and the handle must be refactored, by either path, before it is used.
+ * The host factor (mi_bilu4_factor_host) is NOT updated by a device refactor until mi_bilu4dev_fetch copies it back;
+ * mi_bilu4_refactor replaces host and device factor as before.  Creation still factors on the host.
+ * MI_ERR_ARG: a null handle, null d_coef, an unknown layout; MI_ERR_STATE: a host-only handle (_prepare, _refactor, _status,
+ * _fetch).  nbrows == 0: every call is a no-op. */
+/* host-only: the device refactor's plan for a pattern, exactly as mi_bilu4dev_prepare builds it: *update_pairs = the block
+ * updates W(i, j) -= M . U(p, j) of one factorisation (baij4_factor_avx2.c:114-170; once per Newton step, solve_newton.c:1257),
+ * *launches per refactor, *plan_bytes of its tables (below) */
+int mi_bilu4dev_plan_probe(int nbrows, const int* ptrow, const int* indcol, int fill, long long* update_pairs, int* launches,
+                           long long* plan_bytes);
+/* build and upload the pattern-only tables of the device refactor (idempotent; allocates, may synchronise): every block row's
+ * position in both sweeps, per factor block the block of the matrix that lands there, and per L block (i, p) the place in row i
+ * of every U block of row p (baij4_factor_avx2.c:114-170 keeps a dense column map per row instead).  Pattern-only: once per
+ * handle, not once per Newton step (solve_newton.c:1257) */
+int mi_bilu4dev_prepare(mi_bilu4_t F);
+/* new values, same pattern (src/solve_newton.c:1257 onwards; baij4_factor_avx2.c:114-170), d_coef on the device in the order of the
+ * arrays given at create (16 per block, `layout`); asynchronous on s: nothing allocated, copied to the host or synchronised once
+ * prepared (so it can be captured into a graph); calls mi_bilu4dev_prepare itself when needed (that first call is not capturable) */
+int mi_bilu4dev_refactor(mi_bilu4_t F, const double* d_coef, int layout, mi_stream_t s);
+/* waits for the device, hence for the last mi_bilu4dev_refactor; *bad_row = -1 and MI_OK, or the refused block row and MI_ERR_ARG
+ * with the same message mi_bilu4_refactor gives (the |d| < 1e-12 rule of baij4_factor_avx2.c:114-170; solve_newton.c:1257) */
+int mi_bilu4dev_status(mi_bilu4_t F, int* bad_row);
+/* waits, then copies the device factor back into the host factor, so that mi_bilu4_factor_host returns what the device holds
+ * (the factor of baij4_factor_avx2.c:114-170 after the refactor of solve_newton.c:1257) */
+int mi_bilu4dev_fetch(mi_bilu4_t F);
+/* *prepared, *launches per refactor, *plan_bytes of device tables beyond what mi_bilu4_info counts (0 until prepared); any output
+ * may be NULL (baij4_factor_avx2.c:114-170, solve_newton.c:1257: the cost of refactoring per Newton step) */
+int mi_bilu4dev_info(mi_bilu4_t F, int* prepared, int* launches, long long* plan_bytes);
 
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r

@@ -1,5 +1,6 @@
 // bilu4_plan.hpp — host side of the 4x4-block ILU(k) preconditioner (mi_bilu4_*, include/mi355_spmv.h): symbolic
-// factorisation, numeric factorisation, dependency levels and the launch schedule of the level-scheduled solve.
+// factorisation, numeric factorisation, dependency levels, the launch schedule of the level-scheduled solve, and the
+// pattern-only plan of the numeric factorisation on the device (Bilu4DevPlan, at the end; kernels in bilu4_factor.hpp).
 // Plain C++ (no HIP), like ring_plan.hpp / partition.hpp, so that it can be probed and tested without a GPU.
 //
 // What it stands for in the reference: PCILU on the BAIJ-4 Jacobian (src/solve_newton.c:1156-1164; 4 levels of fill, natural
@@ -273,6 +274,71 @@ inline int bilu4_factor(const Bilu4Pattern& P, const Bilu4Sweep& F, const int* p
         if (bad.load() < nb) break; // later rows would divide by what was refused
     }
     return bad.load() < nb ? bad.load() : -1;
+}
+
+// ---------------------------------------------------------------- the device refactor's plan (mi_bilu4dev_*)
+// Pattern-only tables of the numeric factorisation on the GPU (bilu4_factor.hpp), built once per handle.  The device factor is
+// three arrays: the L blocks in the forward sweep's order, the U blocks in the backward sweep's order, and the inverted diagonal
+// blocks by backward position.  A block of the factor is named by ONE index into their concatenation L | U | D ("home").
+constexpr int kBiluDevFixedLaunches = 1; // launches of a device refactor besides the forward sweep's: the one that clears and scatters
+
+struct Bilu4DevPlan {
+    long long nL = 0, nU = 0;       // blocks of the L and of the U array (the D array has nb)
+    std::vector<int> fpos, bpos;    // [nb] block row -> its position in the forward / backward order
+    std::vector<int> gather;        // [nL + nU + nb] by home: the block of the caller's matrix that lands there, or -1 (a fill
+                                    // block: it starts every refactor as zeros).  The scatter map, stored by destination, so that
+                                    // clearing and scattering are one launch that writes every block of the factor exactly once.
+    std::vector<long long> upd_ptr; // [nL + 1] by L block (i, p): its first entry in upd
+    std::vector<int> upd;           // per U block (p, j) of the pivot row, in row p's order: the home of block (i, j), or -1
+    long long update_pairs = 0;     // entries of upd that are not -1
+    long long bytes() const
+    {
+        return (long long)sizeof(int) * (long long)(fpos.size() + bpos.size() + gather.size() + upd.size() + 1) // + the refusal word
+               + (long long)sizeof(long long) * (long long)upd_ptr.size();
+    }
+};
+
+inline void bilu4dev_plan(const Bilu4Pattern& P, const Bilu4Sweep& F, const Bilu4Sweep& B, const int* ptrow, const int* indcol, Bilu4DevPlan* D)
+{
+    const int nb = P.nb;
+    D->fpos.assign(nb, 0);
+    D->bpos.assign(nb, 0);
+    for (int q = 0; q < nb; q++) D->fpos[F.perm[q]] = q, D->bpos[B.perm[q]] = q;
+    // home of every block of the pattern: the level-major copies list a row's blocks in the pattern's order
+    std::vector<int> home((size_t)P.nblocks());
+    long long n = 0;
+    for (int q = 0; q < nb; q++)
+        for (int k = P.ptr[F.perm[q]]; k < P.diag[F.perm[q]]; k++) home[k] = (int)n++;
+    D->nL = n;
+    for (int q = 0; q < nb; q++)
+        for (int k = P.diag[B.perm[q]] + 1; k < P.ptr[B.perm[q] + 1]; k++) home[k] = (int)n++;
+    D->nU = n - D->nL;
+    for (int i = 0; i < nb; i++) home[P.diag[i]] = (int)(n + D->bpos[i]);
+    D->gather.assign((size_t)P.nblocks(), -1);
+    for (int i = 0; i < nb; i++) {
+        int k = P.ptr[i]; // both column lists ascend, and the matrix's is a subset of the factor's
+        for (int a = ptrow[i]; a < ptrow[i + 1]; a++) {
+            while (P.col[k] != indcol[a]) k++;
+            D->gather[home[k]] = a;
+        }
+    }
+    D->upd_ptr.assign(1, 0);
+    D->upd.clear();
+    D->update_pairs = 0;
+    for (int q = 0; q < nb; q++) {
+        const int i = F.perm[q];
+        for (int k = P.ptr[i]; k < P.diag[i]; k++) {
+            const int p = P.col[k];
+            int at = k + 1; // row p's U columns are > p: merge them with the rest of row i
+            for (int kk = P.diag[p] + 1; kk < P.ptr[p + 1]; kk++) {
+                while (at < P.ptr[i + 1] && P.col[at] < P.col[kk]) at++;
+                const bool hit = at < P.ptr[i + 1] && P.col[at] == P.col[kk];
+                D->upd.push_back(hit ? home[at] : -1);
+                D->update_pairs += hit;
+            }
+            D->upd_ptr.push_back((long long)D->upd.size());
+        }
+    }
 }
 
 } // namespace mi355

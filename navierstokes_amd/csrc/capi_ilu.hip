@@ -1,9 +1,11 @@
 // capi_ilu.hip: the 4x4-block ILU(k) preconditioner, mi_bilu4_* — part of libmi355spmv.so (see capi_internal.hpp for the layout of
 // the library).  Factored on the host (bilu4_plan.hpp), solved on the GPU by one launch per (folded) dependency level
-// (bilu4_solve.hpp).  No CPU fallback: the solve needs a HIP device; the planning and factorisation entry points need none.
+// (bilu4_solve.hpp); mi_bilu4dev_* refactors on the GPU, into the same device copies, level by level (bilu4_factor.hpp).
+// No CPU fallback: the solve and the device refactor need a HIP device; the planning and host factorisation entry points need none.
 #include "capi_internal.hpp"
 #include "bilu4_plan.hpp"
 #include "bilu4_solve.hpp"
+#include "bilu4_factor.hpp"
 
 struct Bilu4DevSweep {
     int* perm = nullptr;
@@ -34,6 +36,15 @@ struct mi_bilu4_s {
     double us_form[2] = {0.0, 0.0}; // measured at create: [0] one launch per level; [1] not built
     double* d_b = nullptr;          // scratch of the host-pointer solve
     double* d_x = nullptr;
+    // the device refactor (mi_bilu4dev_prepare): pattern-only tables, see Bilu4DevPlan
+    bool dev_prepared = false;
+    long long dev_nL = 0, dev_nU = 0, dev_plan_bytes = 0;
+    int* d_fpos = nullptr;
+    int* d_bpos = nullptr;
+    int* d_gather = nullptr;
+    int* d_upd = nullptr;
+    long long* d_upd_ptr = nullptr;
+    int* d_bad = nullptr;
 };
 
 static int bilu_threads()
@@ -147,6 +158,7 @@ static void bilu_free(mi_bilu4_s* F)
     F->dbwd.release();
     dfree(F->d_b);
     dfree(F->d_x);
+    dfree(F->d_fpos), dfree(F->d_bpos), dfree(F->d_gather), dfree(F->d_upd), dfree(F->d_upd_ptr), dfree(F->d_bad);
     delete F;
 }
 
@@ -311,5 +323,137 @@ extern "C" int mi_bilu4_plan_probe(int nbrows, const int* ptrow, const int* indc
         for (int l = 0; l < Fw.nlev(); l++) fwd_sizes[l] = Fw.lev_ptr[l + 1] - Fw.lev_ptr[l];
     if (bwd_sizes)
         for (int l = 0; l < Bw.nlev(); l++) bwd_sizes[l] = Bw.lev_ptr[l + 1] - Bw.lev_ptr[l];
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------- mi_bilu4dev_*: the numeric factorisation on the GPU
+static const char* const kHostOnlyDev = ": a host-only handle (mi_bilu4_create_host) has no device factor";
+
+extern "C" int mi_bilu4dev_plan_probe(int nbrows, const int* ptrow, const int* indcol, int fill, long long* update_pairs, int* launches,
+                                      long long* plan_bytes)
+{
+    int rc = bilu_check_args(nbrows, ptrow, indcol, fill);
+    if (rc) return rc;
+    Bilu4Pattern P;
+    Bilu4Sweep Fw, Bw;
+    Bilu4DevPlan D;
+    bilu4_symbolic(nbrows, ptrow, indcol, fill, &P);
+    bilu4_sweep(P, false, &Fw);
+    bilu4_sweep(P, true, &Bw);
+    bilu4dev_plan(P, Fw, Bw, ptrow, indcol, &D);
+    if (update_pairs) *update_pairs = D.update_pairs;
+    if (launches) *launches = Fw.nlaunch() + kBiluDevFixedLaunches;
+    if (plan_bytes) *plan_bytes = D.bytes();
+    return MI_OK;
+}
+
+template <class T>
+static int bilu_dev_table(const std::vector<T>& h, T** d)
+{
+    HIP_TRY(hipMalloc(d, sizeof(T) * std::max<size_t>(h.size(), 1)));
+    if (!h.empty()) HIP_TRY(hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4dev_prepare(mi_bilu4_t F)
+{
+    CHECK_ARG(F, "null handle");
+    if (F->pat.nb == 0) return MI_OK;
+    if (F->device < 0) return fail(MI_ERR_STATE, std::string("mi_bilu4dev_prepare") + kHostOnlyDev);
+    if (F->dev_prepared) return MI_OK;
+    Bilu4DevPlan D;
+    bilu4dev_plan(F->pat, F->fwd, F->bwd, F->a_ptr.data(), F->a_col.data(), &D);
+    auto up = [&]() -> int {
+        int rc;
+        if ((rc = bilu_dev_table(D.fpos, &F->d_fpos)) || (rc = bilu_dev_table(D.bpos, &F->d_bpos)) || (rc = bilu_dev_table(D.gather, &F->d_gather)) ||
+            (rc = bilu_dev_table(D.upd, &F->d_upd)) || (rc = bilu_dev_table(D.upd_ptr, &F->d_upd_ptr)))
+            return rc;
+        if (!F->d_bad) HIP_TRY(hipMalloc(&F->d_bad, sizeof(int)));
+        const int none = kBiluBadNone;
+        HIP_TRY(hipMemcpy(F->d_bad, &none, sizeof(int), hipMemcpyHostToDevice));
+        return MI_OK;
+    };
+    if (int rc = up()) {
+        dfree(F->d_fpos), dfree(F->d_bpos), dfree(F->d_gather), dfree(F->d_upd), dfree(F->d_upd_ptr);
+        F->d_fpos = F->d_bpos = F->d_gather = F->d_upd = nullptr;
+        F->d_upd_ptr = nullptr;
+        return rc;
+    }
+    F->dev_nL = D.nL, F->dev_nU = D.nU, F->dev_plan_bytes = D.bytes();
+    F->dev_prepared = true;
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4dev_refactor(mi_bilu4_t F, const double* d_coef, int layout, mi_stream_t s)
+{
+    CHECK_ARG(F, "null handle");
+    CHECK_ARG(layout == MI_BLOCK_ROWMAJOR || layout == MI_BLOCK_COLMAJOR, "unknown block layout");
+    if (F->pat.nb == 0) return MI_OK;
+    CHECK_ARG(d_coef, "null coef");
+    if (F->device < 0) return fail(MI_ERR_STATE, std::string("mi_bilu4dev_refactor") + kHostOnlyDev);
+    int rc;
+    if (!F->dev_prepared && (rc = mi_bilu4dev_prepare(F))) return rc;
+    hipStream_t st = (hipStream_t)s;
+    const Bilu4FactorView V{F->dfwd.perm, F->dfwd.ptr, F->dfwd.col, F->dbwd.ptr, F->dfwd.lev_ptr, F->d_fpos, F->d_bpos, F->d_upd_ptr, F->d_upd,
+                            F->dfwd.val, F->dbwd.val, F->dbwd.dinv, (int)F->dev_nL, (int)F->dev_nU, F->d_bad};
+    const long long total = F->pat.nblocks();
+    hipLaunchKernelGGL(bilu4f_gather, dim3((unsigned)((total * 16 + kWG - 1) / kWG)), dim3(kWG), 0, st, V, F->d_gather, total, d_coef,
+                       (int)(layout == MI_BLOCK_COLMAJOR));
+    const Bilu4Sweep& S = F->fwd;
+    for (int a = 0; a < S.nlaunch(); a++) {
+        const int l0 = S.launch_ptr[a], l1 = S.launch_ptr[a + 1];
+        const int p0 = S.lev_ptr[l0], p1 = S.lev_ptr[l1];
+        if (l1 - l0 > 1 || p1 - p0 < kBiluRowsPerWG) {
+            hipLaunchKernelGGL(bilu4f_folded, dim3(1), dim3(kBiluFactorFoldedWG), 0, st, V, l0, l1);
+        } else {
+            const int grid = (int)(((long long)(p1 - p0) * 16 + kWG - 1) / kWG);
+            hipLaunchKernelGGL(bilu4f_level, dim3(grid), dim3(kWG), 0, st, V, p0, p1);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4dev_status(mi_bilu4_t F, int* bad_row)
+{
+    CHECK_ARG(F, "null handle");
+    if (bad_row) *bad_row = -1;
+    if (F->pat.nb == 0) return MI_OK;
+    if (F->device < 0) return fail(MI_ERR_STATE, std::string("mi_bilu4dev_status") + kHostOnlyDev);
+    if (!F->dev_prepared) return MI_OK; // no device refactor yet
+    HIP_TRY(hipDeviceSynchronize());
+    int bad = kBiluBadNone;
+    HIP_TRY(hipMemcpy(&bad, F->d_bad, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad == kBiluBadNone) return MI_OK;
+    if (bad_row) *bad_row = bad;
+    return fail(MI_ERR_ARG, "mi_bilu4: zero pivot (|d| < 1e-12) in the diagonal block of block row " + std::to_string(bad));
+}
+
+extern "C" int mi_bilu4dev_fetch(mi_bilu4_t F)
+{
+    CHECK_ARG(F, "null handle");
+    if (F->pat.nb == 0) return MI_OK;
+    if (F->device < 0) return fail(MI_ERR_STATE, std::string("mi_bilu4dev_fetch") + kHostOnlyDev);
+    HIP_TRY(hipDeviceSynchronize());
+    const int nb = F->pat.nb;
+    std::vector<double> v;
+    for (const Bilu4DevSweep* D : {&F->dfwd, &F->dbwd}) {
+        if (D->src.empty()) continue;
+        v.resize(16 * D->src.size());
+        HIP_TRY(hipMemcpy(v.data(), D->val, sizeof(double) * v.size(), hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < D->src.size(); b++) memcpy(&F->val[16 * (size_t)D->src[b]], &v[16 * b], sizeof(double) * 16);
+    }
+    v.resize(16 * (size_t)nb);
+    HIP_TRY(hipMemcpy(v.data(), F->dbwd.dinv, sizeof(double) * v.size(), hipMemcpyDeviceToHost));
+    for (int q = 0; q < nb; q++) memcpy(&F->val[16 * (size_t)F->pat.diag[F->bwd.perm[q]]], &v[16 * (size_t)q], sizeof(double) * 16);
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4dev_info(mi_bilu4_t F, int* prepared, int* launches, long long* plan_bytes)
+{
+    CHECK_ARG(F, "null handle");
+    if (prepared) *prepared = F->dev_prepared ? 1 : 0;
+    if (launches) *launches = F->fwd.nlaunch() + kBiluDevFixedLaunches;
+    if (plan_bytes) *plan_bytes = F->dev_plan_bytes;
     return MI_OK;
 }

@@ -169,6 +169,12 @@ def lib():
         "mi_bilu4_info": [_vp, P(i), P(ll), P(i), P(i), P(i), P(i), P(d), P(d), P(ll)],
         "mi_bilu4_factor_host": [_vp, _vp, _vp, _vp, _vp, ll],
         "mi_bilu4_plan_probe": [i, _vp, _vp, i, P(ll), P(i), P(i), P(i), P(i), _vp, _vp, i],
+        "mi_bilu4dev_plan_probe": [i, _vp, _vp, i, P(ll), P(i), P(ll)],
+        "mi_bilu4dev_prepare": [_vp],
+        "mi_bilu4dev_refactor": [_vp, _vp, i, _vp],
+        "mi_bilu4dev_status": [_vp, P(i)],
+        "mi_bilu4dev_fetch": [_vp],
+        "mi_bilu4dev_info": [_vp, P(i), P(i), P(ll)],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -586,6 +592,35 @@ class bilu4:
         check(lib().mi_bilu4_refactor(self.handle, coef.ctypes.data, self.layout))
         return self
 
+    def prepare_dev(self):
+        """Build and upload the pattern-only tables of the device refactor (mi_bilu4dev_prepare; idempotent)."""
+        check(lib().mi_bilu4dev_prepare(self.handle))
+        return self
+
+    def refactor_dev(self, coef):
+        """New block values for the same pattern from a CUDA tensor (the order and layout of the arrays at construction), factored
+        on the GPU into the device factor: asynchronous on torch's current stream (mi_bilu4dev_refactor).  A refused pivot shows
+        in factor_status(); the host factor follows only after fetch_factor()."""
+        check(lib().mi_bilu4dev_refactor(self.handle, _dev_ptr(coef, 16 * self._nblocks_in, "coef"), self.layout, _stream_ptr()))
+        return self
+
+    def factor_status(self):
+        """Wait for the last refactor_dev; MiError (MI_ERR_ARG, naming the block row) when it refused a pivot."""
+        bad = _c.c_int()
+        check(lib().mi_bilu4dev_status(self.handle, _c.byref(bad)))
+        return self
+
+    def fetch_factor(self):
+        """Copy the device factor back into the host factor, so that factor_host() returns what the device holds."""
+        check(lib().mi_bilu4dev_fetch(self.handle))
+        return self
+
+    def info_dev(self):
+        """dict(prepared, launches, plan_bytes) — mi_bilu4dev_info."""
+        pr, la, by = _c.c_int(), _c.c_int(), _c.c_longlong()
+        check(lib().mi_bilu4dev_info(self.handle, _c.byref(pr), _c.byref(la), _c.byref(by)))
+        return dict(prepared=bool(pr.value), launches=la.value, plan_bytes=by.value)
+
     def info(self):
         """dict(nbrows, nblocks, fwd_levels, bwd_levels, launches, form, us_per_level_launches, us_one_launch, factor_seconds,
         factor_bytes) — mi_bilu4_info."""
@@ -632,6 +667,15 @@ def bilu4_plan_probe(nbrows, ptrow, indcol, fill=0):
                                     _c.byref(fa), _c.byref(ba), fs.ctypes.data, bs.ctypes.data, cap))
     return dict(nblocks=nblk.value, fwd_levels=fl.value, bwd_levels=bl.value, fwd_launches=fa.value, bwd_launches=ba.value,
                 fwd_sizes=fs[: fl.value].copy(), bwd_sizes=bs[: bl.value].copy())
+
+
+def bilu4dev_plan_probe(nbrows, ptrow, indcol, fill=0):
+    """mi_bilu4dev_plan_probe (no GPU): dict(update_pairs, launches, plan_bytes) of the device refactor's plan."""
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    up, by, la = _c.c_longlong(), _c.c_longlong(), _c.c_int()
+    check(lib().mi_bilu4dev_plan_probe(int(nbrows), ptrow.ctypes.data, indcol.ctypes.data, int(fill), _c.byref(up), _c.byref(la), _c.byref(by)))
+    return dict(update_pairs=up.value, launches=la.value, plan_bytes=by.value)
 
 
 def bcsr4_sell_plan_probe(nbrows, ptrow, indcol, nwaves_max=1024):

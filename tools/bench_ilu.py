@@ -5,6 +5,13 @@ product's microseconds on a handle of the same matrix in the same process, and G
 with and without M.  Prints one JSON line and appends it to profiles/ilu_bench.jsonl.
 
     python3 tools/bench_ilu.py [--cells 68] [--fill 0] [--solves 200] [--maxiter 300] [--no-append]
+
+--refactor measures the two refactorisations instead, in one process, and appends one record (tool = "bench_ilu_refactor"): the
+wall time of the host path mi_bilu4_refactor (factor on host threads, wait for the device, upload; median of --host-reps calls),
+the time of mi_bilu4dev_refactor between device events (median of --reps single refactors after warm-ups), launches per refactor,
+the bytes of the device plan, and whether the fetched device factor equals the host factor bit for bit.
+
+    python3 tools/bench_ilu.py --refactor [--cells 68] [--fill 0] [--reps 30] [--host-reps 3] [--no-append]
 """
 import argparse
 import json
@@ -29,8 +36,58 @@ def timed_us(fn, warm, reps):
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
+def refactor_record(a):
+    import numpy as np
+    import torch
+    from navierstokes_amd import mpk, synth
+    bp, bc, bv = synth.csr_to_bcsr4(*synth.fe_matrix(a.cells))
+    nb = len(bp) - 1
+    F = mpk.bilu4(nb, bp, bc, bv, fill=a.fill)
+    info = F.info()
+    new = np.asarray(bv) * 1.25  # other values, the same pivots up to scale
+    host_s = []
+    for _ in range(a.host_reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        F.refactor(new)
+        host_s.append(time.perf_counter() - t0)
+    host_factor = F.factor_host()[3].copy()
+    host_only_s = F.info()["factor_seconds"]
+    t0 = time.perf_counter()
+    F.prepare_dev()
+    prepare_s = time.perf_counter() - t0
+    dcoef = torch.from_numpy(np.ascontiguousarray(new)).cuda()
+    for _ in range(3):
+        F.refactor_dev(dcoef)
+    F.factor_status()
+    dev_us = []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(a.reps):
+        e0.record()
+        F.refactor_dev(dcoef)
+        e1.record()
+        e1.synchronize()
+        dev_us.append(e0.elapsed_time(e1) * 1e3)
+    F.factor_status().fetch_factor()
+    same = bool(np.array_equal(F.factor_host()[3].view(np.uint64), host_factor.view(np.uint64)))
+    dinfo = F.info_dev()
+    probe = mpk.bilu4dev_plan_probe(nb, bp, bc, a.fill)
+    dev_med = float(np.median(dev_us))
+    out = dict(tool="bench_ilu_refactor", cells=a.cells, block_rows=nb, blocks=int(len(bc)), fill=a.fill, factor_blocks=info["nblocks"],
+               fwd_levels=info["fwd_levels"], host_refactor_seconds=round(float(np.median(host_s)), 4), host_refactor_calls=a.host_reps,
+               host_factor_only_seconds=round(host_only_s, 4), dev_refactor_us=round(dev_med, 1), dev_refactor_us_min=round(min(dev_us), 1),
+               dev_refactor_us_max=round(max(dev_us), 1), dev_refactor_reps=a.reps, launches_per_refactor=dinfo["launches"],
+               us_per_launch=round(dev_med / dinfo["launches"], 2), plan_bytes=dinfo["plan_bytes"], update_pairs=probe["update_pairs"],
+               prepare_seconds=round(prepare_s, 3), host_over_dev=round(float(np.median(host_s)) * 1e6 / dev_med, 1), device_factor_equals_host_bits=same)
+    F.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--refactor", action="store_true")
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--cells", type=int, default=68)
     ap.add_argument("--fill", type=int, default=0)
     ap.add_argument("--solves", type=int, default=200)
@@ -41,6 +98,13 @@ def main():
     import torch
     from navierstokes_amd import mpk, synth
     assert torch.cuda.is_available(), "bench_ilu.py needs a GPU"
+    if a.refactor:
+        line = json.dumps(refactor_record(a))
+        print(line)
+        if not a.no_append:
+            with open(os.path.join(ROOT, "profiles", "ilu_bench.jsonl"), "a") as f:
+                f.write(line + "\n")
+        return
     bp, bc, bv = synth.csr_to_bcsr4(*synth.fe_matrix(a.cells))
     nb = len(bp) - 1
     n = 4 * nb
