@@ -515,8 +515,8 @@ int mi_krylov_basis_cgs_dev(mi_csr_t A, int s, const double* d_v0, double* d_V, 
  * as the solve's work vector: its contents are undefined until the solve has finished.
  * MI_ERR_ARG: a null argument, fill < 0, block columns outside [0, nbrows) (the matrix must be square), unsorted or duplicate block
  * columns, a row without a diagonal block, an unknown layout, a refused pivot.  nbrows == 0: every call is a no-op.
- * MI355_BILU_FORM: 0 = one launch per (folded) level, the only form built; 1 (a one-launch form with grid-wide barriers) is
- * refused with MI_ERR_UNSUPPORTED. */
+ * MI355_BILU_FORM: 0 = one launch per (folded) level, the form every handle is created with; 1 is refused at create with
+ * MI_ERR_UNSUPPORTED (the one-launch form is chosen per handle, by mi_bilu4_set_solve_form below, not by the environment). */
 typedef struct mi_bilu4_s* mi_bilu4_t;
 int mi_bilu4_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout /* MI_BLOCK_* */, int fill,
                     mi_bilu4_t* out);
@@ -529,8 +529,9 @@ int mi_bilu4_destroy(mi_bilu4_t F);
 int mi_bilu4_refactor(mi_bilu4_t F, const double* coef, int layout);
 int mi_bilu4_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s); /* MatSolve_SeqBAIJ_4, baij4_solve.c:4-93 */
 int mi_bilu4_solve(mi_bilu4_t F, const double* b, double* x);                         /* host vectors: copied in and out */
-/* *launches = launches per solve (both sweeps, after folding); *form = 0; us[0] = microseconds per solve measured at create
- * (us[1] = 0: form 1 is not built); *factor_seconds = host time of the last numeric factorisation; *factor_bytes = blocks,
+/* *launches = launches per solve (both sweeps, after folding; 1 for the one-launch form); *form = the form in use (MI_BILU_FORM_*,
+ * 0 until mi_bilu4_set_solve_form says otherwise); us[0] = microseconds per solve of form 0 measured at create, us[1] = of the
+ * one-launch form (0 until mi_bilu4_set_solve_form(F, -1) has measured both); *factor_seconds = host time of the last numeric factorisation; *factor_bytes = blocks,
  * block columns and the per-row tables of the device copy.  Any output may be NULL. */
 int mi_bilu4_info(mi_bilu4_t F, int* nbrows, long long* nblocks, int* fwd_levels, int* bwd_levels, int* launches, int* form,
                   double us[2], double* factor_seconds, long long* factor_bytes);
@@ -582,6 +583,51 @@ int mi_bilu4dev_fetch(mi_bilu4_t F);
 /* *prepared, *launches per refactor, *plan_bytes of device tables beyond what mi_bilu4_info counts (0 until prepared); any output
  * may be NULL (baij4_factor_avx2.c:114-170, solve_newton.c:1257: the cost of refactoring per Newton step) */
 int mi_bilu4dev_info(mi_bilu4_t F, int* prepared, int* launches, long long* plan_bytes);
+
+/* ---- 4x4-block ILU(k): both sweeps of the solve in ONE launch (mi_bilu4one_*, mi_bilu4_set_solve_form) ----
+ * The level-by-level solve is bound by launches, not by bytes (hundreds of launches of a few microseconds of work each).  The
+ * second form runs MatSolve_SeqBAIJ_4 (baij4_solve.c:4-93) as one launch of G persistent workgroups.  The unit of work is a CHUNK
+ * of a sweep's level-major positions: a level of at least 64 block rows is cut into chunks of 64 consecutive positions (the last
+ * may be shorter); a folded run of narrow levels (one launch of form 0) is ONE chunk, walked by its workgroup with workgroup
+ * barriers.  Chunks are numbered in position order; a chunk never spans two wide levels.  A chunk's dependencies are the distinct
+ * chunks of the SAME sweep that hold a block row named by one of its off-diagonal block columns (itself excepted), ascending; all
+ * have a smaller index.  Chunk c belongs to workgroup c mod G and every workgroup takes its chunks in ascending order: with all G
+ * resident the lowest unfinished chunk has only finished dependencies and an owner with nothing earlier left, so nothing stalls.
+ * A chunk publishes its rows (write-through stores, drained) and then one flag; a consumer polls its dependencies' flags with one
+ * lane each, hence at most 256 dependencies per chunk — a pattern with more is NOT ELIGIBLE and stays on form 0.  Between the sweeps
+ * all workgroups meet once (a counter).  ARITHMETIC is the row's fixed sequence of roundings above: every bit equals form 0.
+ * G = min(CUs, max(forward chunks, backward chunks)), MI355_BILU_ONE_WGS=n (n >= 1) overrides it; either is clamped to what the
+ * occupancy query says is resident at once.  Every wait is bounded: when other kernels hold CUs a wait gives up after a few
+ * seconds instead of hanging; that is sticky: the handle's next mi_bilu4_solve* and mi_bilu4one_status return MI_ERR_HIP until
+ * mi_bilu4_set_solve_form(F, 0) clears it.
+ * ONE solve at a time per handle, on ONE stream, while the handle is on form 1: the flags carry a per-handle epoch.  Under stream
+ * capture form 0 is recorded (a replayed graph would present the same epoch again).  mi_bilu4_refactor and mi_bilu4dev_refactor
+ * write the arrays this form reads too; stream order separates them as before.
+ * MI_ERR_ARG: a null handle, an unknown form; MI_ERR_STATE: a host-only handle (_prepare, _set_solve_form, _status);
+ * MI_ERR_UNSUPPORTED: the pattern is not eligible (reason in mi_last_error()).  nbrows == 0: every call is a no-op. */
+enum { MI_BILU_FORM_LEVELS = 0, MI_BILU_FORM_ONE = 1, MI_BILU_FORM_AUTO = -1 };
+/* host-only: chunks, dependencies and the dealing for `workgroups` (0: plan for 256), built exactly as mi_bilu4one_prepare builds
+ * them and REPLAYED: G workgroups step through their chunks in order; MI_ERR_STATE names the first violation (a position in no chunk
+ * or in two, a chunk across two wide levels, a named row whose chunk is not on the list, a dependency with an index >= its chunk's,
+ * a dealing that stalls).  *eligible = 0 with the reason in mi_last_error() (a chunk with > 256 dependencies).  nchunks[2],
+ * max_deps[2]: forward, backward.  Optional arrays, sizes from a first call with nulls: chunk_pos[nchunks + 1] and
+ * chunk_lev[nchunks + 1] per sweep (first position / first level of each chunk), dep_ptr[nchunks + 1], dep[...] per sweep. */
+int mi_bilu4one_plan_probe(int nbrows, const int* ptrow, const int* indcol, int fill, int workgroups, int* eligible, int nchunks[2],
+                           int max_deps[2], long long* plan_bytes, int* const chunk_pos[2], int* const chunk_lev[2],
+                           int* const dep_ptr[2], int* const dep[2]);
+/* tables, flags, residency check; idempotent (allocates, may synchronise); MI_ERR_UNSUPPORTED + reason when not eligible */
+int mi_bilu4one_prepare(mi_bilu4_t F);
+/* the form of the handle's solves.  0: always succeeds, and clears a sticky give-up.  1: prepares if needed; MI_ERR_UNSUPPORTED
+ * (and form 0 stays) when the pattern is not eligible.  -1: prepares, then times both forms on the handle's own scratch vectors,
+ * two interleaved rounds, synchronously, and keeps the one-launch form only if it measured below 0.98 of form 0 and no wait gave
+ * up; MI_OK with form 0 on a pattern that is not eligible.  (The declarator is parenthesised: the `mi_bilu4_name(` entries above
+ * are the level-by-level interface, a closed set.) */
+int (mi_bilu4_set_solve_form)(mi_bilu4_t F, int form);
+/* MI_OK, or MI_ERR_HIP once a wait has given up; no GPU work */
+int mi_bilu4one_status(mi_bilu4_t F);
+/* *prepared, *eligible (0 until prepared), *workgroups (G), chunks and the largest dependency list per sweep (forward, backward),
+ * *plan_bytes of tables and flags (0 until prepared); any output may be NULL */
+int mi_bilu4one_info(mi_bilu4_t F, int* prepared, int* eligible, int* workgroups, int nchunks[2], int max_deps[2], long long* plan_bytes);
 
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r

@@ -341,4 +341,161 @@ inline void bilu4dev_plan(const Bilu4Pattern& P, const Bilu4Sweep& F, const Bilu
     }
 }
 
+// ---------------------------------------------------------------- the one-launch solve's plan (mi_bilu4one_*)
+// Pattern-only tables of the one-launch form of the solve (bilu4_solve_one.hpp).  The unit of work is a CHUNK of one sweep's
+// positions: a wide level (>= kBiluRowsPerWG block rows) is cut into chunks of kBiluRowsPerWG consecutive positions (the last may
+// be shorter), a folded run of narrow levels is ONE chunk.  Chunks are numbered in position order; chunk c goes to workgroup
+// c mod G and every workgroup takes its chunks in ascending order.  A chunk's dependencies are the distinct chunks of the SAME
+// sweep that hold a block row one of its off-diagonal block columns names (itself excepted: a folded chunk orders its own levels
+// with workgroup barriers), ascending; all of them have a smaller index, so with all G workgroups resident the lowest unfinished
+// chunk always has finished dependencies and an owner with nothing earlier left: the dealing cannot stall (bilu4one_check replays it).
+constexpr int kBiluOneMaxDeps = 256;   // one polling lane per dependency: the lanes of a workgroup
+constexpr int kBiluOnePlanFor = 256;   // workgroups the probe replays when the caller names none (one per CU of an MI355X)
+constexpr int kBiluOneFlagBytes = 64;  // every chunk's flag on a line of its own
+
+struct Bilu4OneSweep {
+    std::vector<int> chunk_pos; // [nchunks + 1] first position of each chunk
+    std::vector<int> chunk_lev; // [nchunks + 1] first level of each chunk
+    std::vector<int> dep_ptr;   // [nchunks + 1]
+    std::vector<int> dep;       // chunk numbers, ascending per chunk
+    int max_deps = 0;
+    int nchunks() const { return (int)chunk_pos.size() - 1; }
+    // the levels chunk c walks: a chunk of a wide level that the next chunk continues starts and ends in that level
+    int lev_end(int c) const { return chunk_lev[c + 1] == chunk_lev[c] ? chunk_lev[c] + 1 : chunk_lev[c + 1]; }
+};
+
+struct Bilu4OnePlan {
+    Bilu4OneSweep sweep[2]; // forward, backward
+    bool eligible() const { return sweep[0].max_deps <= kBiluOneMaxDeps && sweep[1].max_deps <= kBiluOneMaxDeps; }
+    std::string why_not() const
+    {
+        for (int b = 0; b < 2; b++)
+            if (sweep[b].max_deps > kBiluOneMaxDeps)
+                return std::string("a chunk of the ") + (b ? "backward" : "forward") + " sweep waits for " + std::to_string(sweep[b].max_deps) +
+                       " chunks; the one-launch form polls with one lane per dependency, at most " + std::to_string(kBiluOneMaxDeps);
+        return std::string();
+    }
+    long long bytes() const // tables, flags, the counter between the sweeps
+    {
+        long long n = 0;
+        for (const Bilu4OneSweep& s : sweep)
+            n += (long long)sizeof(int) * (long long)(s.chunk_pos.size() + s.chunk_lev.size() + s.dep_ptr.size() + s.dep.size()) +
+                 (long long)kBiluOneFlagBytes * s.nchunks();
+        return n + kBiluOneFlagBytes;
+    }
+};
+
+// block row -> chunk of sweep S
+inline std::vector<int> bilu4one_chunk_of_row(const Bilu4Sweep& S, const Bilu4OneSweep& O)
+{
+    std::vector<int> of(S.perm.size(), -1);
+    for (int c = 0; c < O.nchunks(); c++)
+        for (int q = O.chunk_pos[c]; q < O.chunk_pos[c + 1]; q++) of[S.perm[q]] = c;
+    return of;
+}
+
+inline void bilu4one_sweep(const Bilu4Pattern& P, const Bilu4Sweep& S, bool backward, Bilu4OneSweep* O)
+{
+    O->chunk_pos.clear(), O->chunk_lev.clear(), O->dep.clear();
+    for (int a = 0; a < S.nlaunch(); a++) {
+        const int l0 = S.launch_ptr[a], l1 = S.launch_ptr[a + 1];
+        const int p0 = S.lev_ptr[l0], p1 = S.lev_ptr[l1];
+        const bool folded = l1 - l0 > 1 || p1 - p0 < kBiluRowsPerWG;
+        for (int p = p0; p < p1; p += folded ? p1 - p0 : kBiluRowsPerWG) {
+            O->chunk_pos.push_back(p);
+            O->chunk_lev.push_back(l0);
+        }
+    }
+    O->chunk_pos.push_back(P.nb);
+    O->chunk_lev.push_back(S.nlev());
+    const std::vector<int> of = bilu4one_chunk_of_row(S, *O);
+    std::vector<int> seen(O->nchunks(), -1);
+    O->dep_ptr.assign(1, 0);
+    O->max_deps = 0;
+    for (int c = 0; c < O->nchunks(); c++) {
+        const size_t first = O->dep.size();
+        for (int q = O->chunk_pos[c]; q < O->chunk_pos[c + 1]; q++) {
+            const int i = S.perm[q];
+            const int k0 = backward ? P.diag[i] + 1 : P.ptr[i], k1 = backward ? P.ptr[i + 1] : P.diag[i];
+            for (int k = k0; k < k1; k++) {
+                const int d = of[P.col[k]];
+                if (d != c && seen[d] != c) seen[d] = c, O->dep.push_back(d);
+            }
+        }
+        std::sort(O->dep.begin() + first, O->dep.end());
+        O->dep_ptr.push_back((int)O->dep.size());
+        O->max_deps = std::max(O->max_deps, (int)(O->dep.size() - first));
+    }
+}
+
+inline void bilu4one_plan(const Bilu4Pattern& P, const Bilu4Sweep& F, const Bilu4Sweep& B, Bilu4OnePlan* O)
+{
+    bilu4one_sweep(P, F, false, &O->sweep[0]);
+    bilu4one_sweep(P, B, true, &O->sweep[1]);
+}
+
+// What the kernel relies on, checked against the pattern and the schedule, and the dealing REPLAYED for G workgroups: every
+// workgroup steps through its chunks in order and takes the next one only when all its dependencies are finished.  Empty string,
+// or the first violation.
+inline std::string bilu4one_check(const Bilu4Pattern& P, const Bilu4Sweep& S, bool backward, const Bilu4OneSweep& O, int G)
+{
+    const std::string sw = backward ? "backward" : "forward";
+    const int nch = O.nchunks(), nb = P.nb;
+    if (nch < 0 || (int)O.chunk_lev.size() != nch + 1 || (int)O.dep_ptr.size() != nch + 1) return sw + ": table sizes disagree";
+    std::vector<int> cover(nb, 0);
+    for (int c = 0; c < nch; c++) {
+        if (O.chunk_pos[c] < 0 || O.chunk_pos[c + 1] > nb || O.chunk_pos[c] >= O.chunk_pos[c + 1]) return sw + ": chunk " + std::to_string(c) + " is empty or out of range";
+        for (int q = O.chunk_pos[c]; q < O.chunk_pos[c + 1]; q++) cover[q]++;
+    }
+    for (int q = 0; q < nb; q++)
+        if (cover[q] != 1) return sw + ": position " + std::to_string(q) + (cover[q] ? " is in two chunks" : " is in no chunk");
+    for (int c = 0; c < nch; c++) {
+        const int l0 = O.chunk_lev[c], l1 = O.lev_end(c);
+        if (l0 < 0 || l1 > S.nlev() || O.chunk_pos[c] < S.lev_ptr[l0] || O.chunk_pos[c + 1] > S.lev_ptr[l1])
+            return sw + ": chunk " + std::to_string(c) + " does not lie in the levels it names";
+        int wide = 0;
+        for (int l = l0; l < l1; l++) wide += S.lev_ptr[l + 1] - S.lev_ptr[l] >= kBiluRowsPerWG;
+        if (wide > 1 || (wide == 1 && l1 - l0 > 1)) return sw + ": chunk " + std::to_string(c) + " spans a wide level and another level";
+        if (wide == 1 && O.chunk_pos[c + 1] - O.chunk_pos[c] > kBiluRowsPerWG) return sw + ": chunk " + std::to_string(c) + " of a wide level has more rows than a workgroup serves";
+    }
+    const std::vector<int> of = bilu4one_chunk_of_row(S, O);
+    for (int c = 0; c < nch; c++) {
+        const int* d0 = O.dep.data() + O.dep_ptr[c];
+        const int* d1 = O.dep.data() + O.dep_ptr[c + 1];
+        for (const int* d = d0; d < d1; d++)
+            if (*d < 0 || *d >= c || (d > d0 && *d <= d[-1]))
+                return sw + ": chunk " + std::to_string(c) + " lists dependency " + std::to_string(*d) + (*d >= c ? ", not a smaller index" : ", out of order");
+        for (int q = O.chunk_pos[c]; q < O.chunk_pos[c + 1]; q++) {
+            const int i = S.perm[q];
+            const int k0 = backward ? P.diag[i] + 1 : P.ptr[i], k1 = backward ? P.ptr[i + 1] : P.diag[i];
+            for (int k = k0; k < k1; k++)
+                if (of[P.col[k]] != c && !std::binary_search(d0, d1, of[P.col[k]]))
+                    return sw + ": block row " + std::to_string(i) + " names block row " + std::to_string(P.col[k]) + ", whose chunk " +
+                           std::to_string(of[P.col[k]]) + " is not on the list of chunk " + std::to_string(c);
+        }
+    }
+    // the replay: rounds over the workgroups until nobody moves
+    std::vector<char> done(nch, 0);
+    std::vector<int> next(G);
+    for (int g = 0; g < G; g++) next[g] = g;
+    int left = nch;
+    for (bool moved = true; moved && left > 0;) {
+        moved = false;
+        for (int g = 0; g < G; g++)
+            while (next[g] < nch) {
+                const int c = next[g];
+                bool ready = true;
+                for (int d = O.dep_ptr[c]; d < O.dep_ptr[c + 1] && ready; d++) ready = done[O.dep[d]] != 0;
+                if (!ready) break;
+                done[c] = 1, next[g] += G, left--, moved = true;
+            }
+    }
+    if (left > 0) {
+        int c = 0;
+        while (done[c]) c++;
+        return sw + ": the dealing stalls for " + std::to_string(G) + " workgroups at chunk " + std::to_string(c);
+    }
+    return std::string();
+}
+
 } // namespace mi355

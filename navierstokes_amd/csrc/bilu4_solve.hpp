@@ -50,11 +50,11 @@ __device__ __forceinline__ double bilu4_chain(double2 c01, double2 c23, const do
     return fma(c23.y, t[3], p);
 }
 
-// one block row of one sweep, by the quad's lane q; pos < number of rows.  BWD: src == x (t lies there), else src == b.
+// one block row of one sweep, by the quad's lane q; pos < number of rows.  BWD: src == x (t lies there), else src == b.  The
+// value of entry q of block row `row`: every kernel of the solve stores exactly this.
 template <bool BWD, bool AL>
-__device__ __forceinline__ void bilu4_row(const Bilu4SweepView& V, int pos, int q, const double* src, double* x)
+__device__ __forceinline__ double bilu4_row_value(const Bilu4SweepView& V, int pos, int row, int q, const double* src, const double* x)
 {
-    const int row = V.perm[pos];
     const int ia0 = V.ptr[pos], ia1 = V.ptr[pos + 1];
     double s = src[4 * (size_t)row + q];
     if (ia0 < ia1) {
@@ -83,7 +83,14 @@ __device__ __forceinline__ void bilu4_row(const Bilu4SweepView& V, int pos, int 
         const double2* d = reinterpret_cast<const double2*>(V.dinv + 16 * (size_t)pos + 4 * q);
         s = bilu4_chain(d[0], d[1], sv);
     }
-    x[4 * (size_t)row + q] = s;
+    return s;
+}
+
+template <bool BWD, bool AL>
+__device__ __forceinline__ void bilu4_row(const Bilu4SweepView& V, int pos, int q, const double* src, double* x)
+{
+    const int row = V.perm[pos];
+    x[4 * (size_t)row + q] = bilu4_row_value<BWD, AL>(V, pos, row, q, src, x);
 }
 
 // one level: positions [p0, p1), 64 block rows per workgroup

@@ -1,10 +1,13 @@
 // capi_ilu.hip: the 4x4-block ILU(k) preconditioner, mi_bilu4_* — part of libmi355spmv.so (see capi_internal.hpp for the layout of
 // the library).  Factored on the host (bilu4_plan.hpp), solved on the GPU by one launch per (folded) dependency level
-// (bilu4_solve.hpp); mi_bilu4dev_* refactors on the GPU, into the same device copies, level by level (bilu4_factor.hpp).
+// (bilu4_solve.hpp) or, where the handle was told so (mi_bilu4_set_solve_form), by ONE launch of persistent workgroups
+// (bilu4_solve_one.hpp, mi_bilu4one_*); mi_bilu4dev_* refactors on the GPU, into the same device copies, level by level
+// (bilu4_factor.hpp).
 // No CPU fallback: the solve and the device refactor need a HIP device; the planning and host factorisation entry points need none.
 #include "capi_internal.hpp"
 #include "bilu4_plan.hpp"
 #include "bilu4_solve.hpp"
+#include "bilu4_solve_one.hpp"
 #include "bilu4_factor.hpp"
 
 struct Bilu4DevSweep {
@@ -24,6 +27,23 @@ struct Bilu4DevSweep {
     Bilu4SweepView view() const { return Bilu4SweepView{perm, ptr, col, val, dinv, lev_ptr}; }
 };
 
+// the one-launch solve's tables of one sweep on the device (Bilu4OneSweep)
+struct Bilu4OneDev {
+    int* chunk_pos = nullptr;
+    int* chunk_lev = nullptr;
+    int* dep_ptr = nullptr;
+    int* dep = nullptr;
+    unsigned* flags = nullptr;
+    int nchunks = 0;
+    void release()
+    {
+        dfree(chunk_pos), dfree(chunk_lev), dfree(dep_ptr), dfree(dep), dfree(flags);
+        chunk_pos = chunk_lev = dep_ptr = dep = nullptr;
+        flags = nullptr;
+    }
+    Bilu4OneTab tab() const { return Bilu4OneTab{chunk_pos, chunk_lev, dep_ptr, dep, flags, nchunks}; }
+};
+
 struct mi_bilu4_s {
     int device = -1; // -1: host-only handle (mi_bilu4_create_host)
     int fill = 0;
@@ -33,7 +53,7 @@ struct mi_bilu4_s {
     Bilu4Sweep fwd, bwd;
     Bilu4DevSweep dfwd, dbwd;
     double factor_seconds = 0.0;
-    double us_form[2] = {0.0, 0.0}; // measured at create: [0] one launch per level; [1] not built
+    double us_form[2] = {0.0, 0.0}; // [0] one launch per level, measured at create; [1] one launch, once mi_bilu4_set_solve_form(F, -1) has measured it
     double* d_b = nullptr;          // scratch of the host-pointer solve
     double* d_x = nullptr;
     // the device refactor (mi_bilu4dev_prepare): pattern-only tables, see Bilu4DevPlan
@@ -45,6 +65,17 @@ struct mi_bilu4_s {
     int* d_upd = nullptr;
     long long* d_upd_ptr = nullptr;
     int* d_bad = nullptr;
+    // the one-launch solve (mi_bilu4one_prepare): chunks, dependency lists, flags, see Bilu4OnePlan
+    int form = MI_BILU_FORM_LEVELS;
+    int one_state = 0; // 0: not prepared; 1: prepared; -1: not eligible (one_why)
+    std::string one_why;
+    int one_wgs = 0, one_nchunks[2] = {0, 0}, one_max_deps[2] = {0, 0};
+    long long one_plan_bytes = 0;
+    Bilu4OneDev one[2];
+    unsigned* d_one_counter = nullptr;
+    unsigned* h_one_giveups = nullptr; // host-mapped, sticky
+    unsigned* d_one_giveups = nullptr;
+    unsigned one_epoch = 0;
 };
 
 static int bilu_threads()
@@ -151,9 +182,59 @@ static int bilu_solve_launch(mi_bilu4_s* F, const double* d_b, double* d_x, hipS
     return MI_OK;
 }
 
+static const char* const kOneGaveUp =
+    "mi_bilu4: a hand-off wait of the one-launch solve gave up (workgroups of the grid were not all resident: another kernel held CUs); "
+    "results since then are invalid — call mi_bilu4_set_solve_form(F, 0) to clear this and solve level by level";
+
+static bool bilu_one_gave_up(const mi_bilu4_s* F) { return F->h_one_giveups && __atomic_load_n(F->h_one_giveups, __ATOMIC_ACQUIRE) != 0; }
+
+template <bool AL>
+static hipError_t bilu_one_launch_t(const mi_bilu4_s* F, const Bilu4OneArgs& A, const double* d_b, double* d_x, hipStream_t s, bool query, int* max_blocks)
+{
+    auto kern = bilu4_solve_one<AL>;
+    if (query) return hipOccupancyMaxActiveBlocksPerMultiprocessor(max_blocks, kern, kWG, 0);
+    hipLaunchKernelGGL(kern, dim3(F->one_wgs), dim3(kWG), 0, s, F->dfwd.view(), F->dbwd.view(), A, d_b, d_x);
+    return hipGetLastError();
+}
+
+// form 1: both sweeps in one launch of F->one_wgs persistent workgroups.  ONE solve at a time per handle: the epoch is per handle.
+static int bilu_solve_one_launch(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
+{
+    Bilu4OneArgs A{};
+    A.fwd = F->one[0].tab();
+    A.bwd = F->one[1].tab();
+    A.epoch = ++F->one_epoch; // flags are never cleared: this solve's are the ones that carry its epoch
+    A.counter = F->d_one_counter;
+    A.giveups = F->d_one_giveups;
+    static const unsigned spin_max = 1u << (getenv("MI355_BILU_ONE_SPIN_LOG2") ? std::max(8, std::min(30, atoi(getenv("MI355_BILU_ONE_SPIN_LOG2")))) : 21);
+    A.spin_max = spin_max;
+    const hipError_t e = (((uintptr_t)d_x) & 15) == 0 ? bilu_one_launch_t<true>(F, A, d_b, d_x, s, false, nullptr) : bilu_one_launch_t<false>(F, A, d_b, d_x, s, false, nullptr);
+    if (e != hipSuccess) return fail(MI_ERR_HIP, std::string("one-launch ILU solve: ") + hipGetErrorString(e));
+    return MI_OK;
+}
+
+// what mi_bilu4_solve* enqueue: the handle's form — except under stream capture, where the level-by-level form is recorded (the
+// one-launch form's epoch is a kernel argument: a replayed graph would present it again and every wait would pass at once)
+static int bilu_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
+{
+    if (bilu_one_gave_up(F)) return fail(MI_ERR_HIP, kOneGaveUp);
+    if (F->form == MI_BILU_FORM_ONE && !stream_is_capturing(s)) return bilu_solve_one_launch(F, d_b, d_x, s);
+    return bilu_solve_launch(F, d_b, d_x, s);
+}
+
+static void bilu_one_release(mi_bilu4_s* F)
+{
+    F->one[0].release();
+    F->one[1].release();
+    dfree(F->d_one_counter);
+    if (F->h_one_giveups) (void)hipHostFree(F->h_one_giveups);
+    F->d_one_counter = F->h_one_giveups = F->d_one_giveups = nullptr;
+}
+
 static void bilu_free(mi_bilu4_s* F)
 {
     if (!F) return;
+    bilu_one_release(F);
     F->dfwd.release();
     F->dbwd.release();
     dfree(F->d_b);
@@ -256,7 +337,7 @@ extern "C" int mi_bilu4_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, 
     if (F->pat.nb == 0) return MI_OK;
     CHECK_ARG(d_b && d_x, "null vector");
     if (F->device < 0) return fail(MI_ERR_STATE, "mi_bilu4_solve: a host-only handle (mi_bilu4_create_host) has no device factor");
-    return bilu_solve_launch(F, d_b, d_x, (hipStream_t)s);
+    return bilu_solve_any(F, d_b, d_x, (hipStream_t)s);
 }
 
 extern "C" int mi_bilu4_solve(mi_bilu4_t F, const double* b, double* x)
@@ -267,7 +348,7 @@ extern "C" int mi_bilu4_solve(mi_bilu4_t F, const double* b, double* x)
     if (F->device < 0) return fail(MI_ERR_STATE, "mi_bilu4_solve: a host-only handle (mi_bilu4_create_host) has no device factor");
     const size_t bytes = sizeof(double) * 4 * (size_t)F->pat.nb;
     HIP_TRY(hipMemcpy(F->d_b, b, bytes, hipMemcpyHostToDevice));
-    int rc = bilu_solve_launch(F, F->d_b, F->d_x, nullptr);
+    int rc = bilu_solve_any(F, F->d_b, F->d_x, nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(x, F->d_x, bytes, hipMemcpyDeviceToHost));
     return MI_OK;
@@ -281,8 +362,8 @@ extern "C" int mi_bilu4_info(mi_bilu4_t F, int* nbrows, long long* nblocks, int*
     if (nblocks) *nblocks = F->pat.nblocks();
     if (fwd_levels) *fwd_levels = F->fwd.nlev();
     if (bwd_levels) *bwd_levels = F->bwd.nlev();
-    if (launches) *launches = F->fwd.nlaunch() + F->bwd.nlaunch();
-    if (form) *form = 0;
+    if (launches) *launches = F->form == MI_BILU_FORM_ONE ? 1 : F->fwd.nlaunch() + F->bwd.nlaunch();
+    if (form) *form = F->form;
     if (us) us[0] = F->us_form[0], us[1] = F->us_form[1];
     if (factor_seconds) *factor_seconds = F->factor_seconds;
     if (factor_bytes) *factor_bytes = F->pat.nblocks() * (long long)(16 * sizeof(double) + sizeof(int)) + (long long)F->pat.nb * 4 * (long long)sizeof(int);
@@ -455,5 +536,187 @@ extern "C" int mi_bilu4dev_info(mi_bilu4_t F, int* prepared, int* launches, long
     if (prepared) *prepared = F->dev_prepared ? 1 : 0;
     if (launches) *launches = F->fwd.nlaunch() + kBiluDevFixedLaunches;
     if (plan_bytes) *plan_bytes = F->dev_plan_bytes;
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------- mi_bilu4one_*: both sweeps of the solve in one launch
+extern "C" int mi_bilu4one_plan_probe(int nbrows, const int* ptrow, const int* indcol, int fill, int workgroups, int* eligible, int nchunks[2],
+                                      int max_deps[2], long long* plan_bytes, int* const chunk_pos[2], int* const chunk_lev[2],
+                                      int* const dep_ptr[2], int* const dep[2])
+{
+    int rc = bilu_check_args(nbrows, ptrow, indcol, fill);
+    if (rc) return rc;
+    CHECK_ARG(workgroups >= 0, "negative workgroups");
+    Bilu4Pattern P;
+    Bilu4Sweep S[2];
+    Bilu4OnePlan O;
+    bilu4_symbolic(nbrows, ptrow, indcol, fill, &P);
+    bilu4_sweep(P, false, &S[0]);
+    bilu4_sweep(P, true, &S[1]);
+    bilu4one_plan(P, S[0], S[1], &O);
+    for (int b = 0; b < 2; b++) {
+        const std::string bad = bilu4one_check(P, S[b], b == 1, O.sweep[b], workgroups ? workgroups : kBiluOnePlanFor);
+        if (!bad.empty()) return fail(MI_ERR_STATE, "mi_bilu4one_plan_probe: " + bad);
+    }
+    auto copy = [](const std::vector<int>& v, int* const out[2], int b) {
+        if (out && out[b] && !v.empty()) memcpy(out[b], v.data(), sizeof(int) * v.size());
+    };
+    for (int b = 0; b < 2; b++) {
+        const Bilu4OneSweep& W = O.sweep[b];
+        if (nchunks) nchunks[b] = W.nchunks();
+        if (max_deps) max_deps[b] = W.max_deps;
+        copy(W.chunk_pos, chunk_pos, b), copy(W.chunk_lev, chunk_lev, b), copy(W.dep_ptr, dep_ptr, b), copy(W.dep, dep, b);
+    }
+    if (plan_bytes) *plan_bytes = O.bytes();
+    if (eligible) *eligible = O.eligible() ? 1 : 0;
+    if (!O.eligible()) g_err = "mi_bilu4one: not eligible: " + O.why_not();
+    return MI_OK;
+}
+
+static int bilu_one_not_eligible(mi_bilu4_s* F, const std::string& why)
+{
+    bilu_one_release(F);
+    F->one_state = -1;
+    F->one_why = "mi_bilu4one: not eligible: " + why;
+    return fail(MI_ERR_UNSUPPORTED, F->one_why);
+}
+
+extern "C" int mi_bilu4one_prepare(mi_bilu4_t F)
+{
+    CHECK_ARG(F, "null handle");
+    if (F->pat.nb == 0) return MI_OK;
+    if (F->device < 0) return fail(MI_ERR_STATE, std::string("mi_bilu4one_prepare") + kHostOnlyDev);
+    if (F->one_state == 1) return MI_OK;
+    if (F->one_state < 0) return fail(MI_ERR_UNSUPPORTED, F->one_why);
+    Bilu4OnePlan O;
+    bilu4one_plan(F->pat, F->fwd, F->bwd, &O);
+    for (int b = 0; b < 2; b++) F->one_nchunks[b] = O.sweep[b].nchunks(), F->one_max_deps[b] = O.sweep[b].max_deps;
+    if (!O.eligible()) return bilu_one_not_eligible(F, O.why_not());
+    // every workgroup of the grid must be resident at once (a waiting workgroup keeps its slot)
+    int per_cu[2] = {0, 0}, dev = 0, cus = 0;
+    Bilu4OneArgs dummy{};
+    HIP_TRY(bilu_one_launch_t<true>(F, dummy, nullptr, nullptr, nullptr, true, &per_cu[0]));
+    HIP_TRY(bilu_one_launch_t<false>(F, dummy, nullptr, nullptr, nullptr, true, &per_cu[1]));
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const long long resident = (long long)std::min(per_cu[0], per_cu[1]) * cus;
+    if (resident < 1) return bilu_one_not_eligible(F, "the occupancy query leaves no workgroup of the one-launch kernel resident");
+    long long G = std::min<long long>(cus, std::max(F->one_nchunks[0], F->one_nchunks[1]));
+    if (const char* e = getenv("MI355_BILU_ONE_WGS")) {
+        CHECK_ARG(atoi(e) >= 1, "MI355_BILU_ONE_WGS must be >= 1");
+        G = atoi(e);
+    }
+    G = std::max<long long>(1, std::min(G, resident));
+    // (the plan is replayed for the grid it will run on: a stall here would be a hang there)
+    for (int b = 0; b < 2; b++) {
+        const std::string bad = bilu4one_check(F->pat, b ? F->bwd : F->fwd, b == 1, O.sweep[b], (int)G);
+        if (!bad.empty()) return fail(MI_ERR_STATE, "mi_bilu4one_prepare: " + bad);
+    }
+    auto up = [&]() -> int {
+        int rc;
+        for (int b = 0; b < 2; b++) {
+            Bilu4OneDev& D = F->one[b];
+            const Bilu4OneSweep& W = O.sweep[b];
+            if ((rc = bilu_dev_table(W.chunk_pos, &D.chunk_pos)) || (rc = bilu_dev_table(W.chunk_lev, &D.chunk_lev)) ||
+                (rc = bilu_dev_table(W.dep_ptr, &D.dep_ptr)) || (rc = bilu_dev_table(W.dep, &D.dep)))
+                return rc;
+            D.nchunks = W.nchunks();
+            const size_t bytes = sizeof(unsigned) * kBiluOneFlagStride * (size_t)std::max(D.nchunks, 1);
+            HIP_TRY(hipMalloc(&D.flags, bytes));
+            HIP_TRY(hipMemset(D.flags, 0, bytes));
+        }
+        HIP_TRY(hipMalloc(&F->d_one_counter, sizeof(unsigned) * kBiluOneFlagStride));
+        HIP_TRY(hipMemset(F->d_one_counter, 0, sizeof(unsigned) * kBiluOneFlagStride));
+        HIP_TRY(hipHostMalloc((void**)&F->h_one_giveups, sizeof(unsigned), hipHostMallocMapped));
+        *F->h_one_giveups = 0;
+        HIP_TRY(hipHostGetDevicePointer((void**)&F->d_one_giveups, F->h_one_giveups, 0));
+        HIP_TRY(hipStreamSynchronize(nullptr)); // (the zeroed flags, before the first solve on the caller's stream reads them)
+        return MI_OK;
+    };
+    if (int rc = up()) {
+        bilu_one_release(F);
+        return rc;
+    }
+    F->one_wgs = (int)G;
+    F->one_epoch = 0;
+    F->one_plan_bytes = O.bytes();
+    F->one_state = 1;
+    return MI_OK;
+}
+
+// a wait gave up: some workgroups left early, so flags and counter no longer add up — start again from zero
+static int bilu_one_reset(mi_bilu4_s* F)
+{
+    HIP_TRY(hipDeviceSynchronize());
+    for (int b = 0; b < 2; b++) HIP_TRY(hipMemset(F->one[b].flags, 0, sizeof(unsigned) * kBiluOneFlagStride * (size_t)std::max(F->one[b].nchunks, 1)));
+    HIP_TRY(hipMemset(F->d_one_counter, 0, sizeof(unsigned) * kBiluOneFlagStride));
+    HIP_TRY(hipDeviceSynchronize());
+    F->one_epoch = 0;
+    __atomic_store_n(F->h_one_giveups, 0u, __ATOMIC_RELEASE);
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4_set_solve_form(mi_bilu4_t F, int form)
+{
+    CHECK_ARG(F, "null handle");
+    CHECK_ARG(form == MI_BILU_FORM_LEVELS || form == MI_BILU_FORM_ONE || form == MI_BILU_FORM_AUTO, "unknown solve form (0: one launch per level, 1: one launch, -1: measure and choose)");
+    if (F->pat.nb == 0) return MI_OK;
+    if (F->device < 0) return fail(MI_ERR_STATE, std::string("mi_bilu4_set_solve_form") + kHostOnlyDev);
+    int rc;
+    if (form == MI_BILU_FORM_LEVELS) {
+        F->form = MI_BILU_FORM_LEVELS;
+        if (bilu_one_gave_up(F) && (rc = bilu_one_reset(F))) return rc;
+        return MI_OK;
+    }
+    if ((rc = mi_bilu4one_prepare(F))) {
+        if (rc == MI_ERR_UNSUPPORTED) F->form = MI_BILU_FORM_LEVELS;
+        return rc == MI_ERR_UNSUPPORTED && form == MI_BILU_FORM_AUTO ? MI_OK : rc;
+    }
+    if (bilu_one_gave_up(F)) return fail(MI_ERR_HIP, kOneGaveUp);
+    if (form == MI_BILU_FORM_ONE) {
+        F->form = MI_BILU_FORM_ONE;
+        return MI_OK;
+    }
+    // auto: both forms give the same bits, so time each on the handle's own scratch vectors, two interleaved rounds, and keep the
+    // one-launch form only if it measured below 0.98 of the other and no wait gave up (the rule of the one-launch powers step)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(F->d_b, 0, sizeof(double) * 4 * (size_t)F->pat.nb));
+    LaunchTimer T(nullptr);
+    if ((rc = T.init())) return rc;
+    double us[2] = {0.0, 0.0};
+    for (int round = 0; round < 2; round++)
+        for (int f = 0; f < 2; f++) {
+            double t = 0.0;
+            if ((rc = T.time(2, 5, [&] { return f ? bilu_solve_one_launch(F, F->d_b, F->d_x, nullptr) : bilu_solve_launch(F, F->d_b, F->d_x, nullptr); }, &t))) return rc;
+            us[f] = min_measured(us[f], t);
+            if (f == 1 && bilu_one_gave_up(F)) round = 2; // every further launch would spin its whole budget again
+        }
+    F->us_form[0] = us[0], F->us_form[1] = us[1];
+    const bool gave_up = bilu_one_gave_up(F);
+    if (gave_up && (rc = bilu_one_reset(F))) return rc; // (measured on scratch vectors: nothing of the caller's is invalid)
+    F->form = (!gave_up && us[1] > 0 && us[1] < 0.98 * us[0]) ? MI_BILU_FORM_ONE : MI_BILU_FORM_LEVELS;
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4one_status(mi_bilu4_t F)
+{
+    CHECK_ARG(F, "null handle");
+    if (F->pat.nb == 0) return MI_OK;
+    if (F->device < 0) return fail(MI_ERR_STATE, std::string("mi_bilu4one_status") + kHostOnlyDev);
+    if (bilu_one_gave_up(F)) return fail(MI_ERR_HIP, kOneGaveUp);
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4one_info(mi_bilu4_t F, int* prepared, int* eligible, int* workgroups, int nchunks[2], int max_deps[2], long long* plan_bytes)
+{
+    CHECK_ARG(F, "null handle");
+    if (prepared) *prepared = F->one_state == 1;
+    if (eligible) *eligible = F->one_state == 1;
+    if (workgroups) *workgroups = F->one_state == 1 ? F->one_wgs : 0;
+    for (int b = 0; b < 2; b++) {
+        if (nchunks) nchunks[b] = F->one_nchunks[b];
+        if (max_deps) max_deps[b] = F->one_max_deps[b];
+    }
+    if (plan_bytes) *plan_bytes = F->one_state == 1 ? F->one_plan_bytes : 0;
     return MI_OK;
 }

@@ -175,6 +175,11 @@ def lib():
         "mi_bilu4dev_status": [_vp, P(i)],
         "mi_bilu4dev_fetch": [_vp],
         "mi_bilu4dev_info": [_vp, P(i), P(i), P(ll)],
+        "mi_bilu4one_plan_probe": [i, _vp, _vp, i, i, P(i), _vp, _vp, P(ll), _vp, _vp, _vp, _vp],
+        "mi_bilu4one_prepare": [_vp],
+        "mi_bilu4_set_solve_form": [_vp, i],
+        "mi_bilu4one_status": [_vp],
+        "mi_bilu4one_info": [_vp, P(i), P(i), P(i), _vp, _vp, P(ll)],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -621,6 +626,32 @@ class bilu4:
         check(lib().mi_bilu4dev_info(self.handle, _c.byref(pr), _c.byref(la), _c.byref(by)))
         return dict(prepared=bool(pr.value), launches=la.value, plan_bytes=by.value)
 
+    def set_form(self, form):
+        """The form of this handle's solves (mi_bilu4_set_solve_form): 0 one launch per level, 1 both sweeps in one launch (MiError,
+        status 5, when the pattern is not eligible), -1 measure both and keep the faster.  Returns the form now in use."""
+        check(lib().mi_bilu4_set_solve_form(self.handle, int(form)))
+        return self.info()["form"]
+
+    def prepare_one(self):
+        """Build and upload the tables of the one-launch form (mi_bilu4one_prepare; idempotent); MiError, status 5, when the pattern
+        is not eligible."""
+        check(lib().mi_bilu4one_prepare(self.handle))
+        return self
+
+    def one_status(self):
+        """MiError (MI_ERR_HIP) once a hand-off wait of the one-launch form has given up (mi_bilu4one_status); no GPU work."""
+        check(lib().mi_bilu4one_status(self.handle))
+        return self
+
+    def info_one(self):
+        """dict(prepared, eligible, workgroups, nchunks, max_deps, plan_bytes) — mi_bilu4one_info; nchunks and max_deps are
+        (forward, backward)."""
+        pr, el, wg, by = _c.c_int(), _c.c_int(), _c.c_int(), _c.c_longlong()
+        nch, md = (_c.c_int * 2)(), (_c.c_int * 2)()
+        check(lib().mi_bilu4one_info(self.handle, _c.byref(pr), _c.byref(el), _c.byref(wg), nch, md, _c.byref(by)))
+        return dict(prepared=bool(pr.value), eligible=bool(el.value), workgroups=wg.value, nchunks=(nch[0], nch[1]), max_deps=(md[0], md[1]),
+                    plan_bytes=by.value)
+
     def info(self):
         """dict(nbrows, nblocks, fwd_levels, bwd_levels, launches, form, us_per_level_launches, us_one_launch, factor_seconds,
         factor_bytes) — mi_bilu4_info."""
@@ -676,6 +707,27 @@ def bilu4dev_plan_probe(nbrows, ptrow, indcol, fill=0):
     up, by, la = _c.c_longlong(), _c.c_longlong(), _c.c_int()
     check(lib().mi_bilu4dev_plan_probe(int(nbrows), ptrow.ctypes.data, indcol.ctypes.data, int(fill), _c.byref(up), _c.byref(la), _c.byref(by)))
     return dict(update_pairs=up.value, launches=la.value, plan_bytes=by.value)
+
+
+def bilu4one_plan_probe(nbrows, ptrow, indcol, fill=0, workgroups=0):
+    """mi_bilu4one_plan_probe (no GPU): dict(eligible, why, nchunks, max_deps, plan_bytes, chunk_pos, chunk_lev, dep_ptr, dep) of the
+    one-launch solve's plan, replayed for `workgroups` (0: 256); the last six are (forward, backward) pairs."""
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    el, by = _c.c_int(), _c.c_longlong()
+    nch, md = (_c.c_int * 2)(), (_c.c_int * 2)()
+    args = (int(nbrows), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, int(fill), int(workgroups))
+    check(lib().mi_bilu4one_plan_probe(*args, _c.byref(el), nch, md, _c.byref(by), None, None, None, None))
+    tabs = [[np.zeros(nch[b] + 1, np.int32) for b in range(2)] for _ in range(3)]
+    ptrs = [(_c.c_void_p * 2)(t[0].ctypes.data, t[1].ctypes.data) for t in tabs]
+    check(lib().mi_bilu4one_plan_probe(*args, _c.byref(el), nch, md, _c.byref(by), ptrs[0], ptrs[1], ptrs[2], None))
+    dep = [np.zeros(max(int(tabs[2][b][-1]), 1), np.int32) for b in range(2)]
+    dptr = (_c.c_void_p * 2)(dep[0].ctypes.data, dep[1].ctypes.data)
+    check(lib().mi_bilu4one_plan_probe(*args, _c.byref(el), nch, md, _c.byref(by), None, None, None, dptr))
+    why = "" if el.value else lib().mi_last_error().decode()
+    return dict(eligible=bool(el.value), why=why, nchunks=(nch[0], nch[1]), max_deps=(md[0], md[1]), plan_bytes=by.value,
+                chunk_pos=tuple(tabs[0]), chunk_lev=tuple(tabs[1]), dep_ptr=tuple(tabs[2]),
+                dep=tuple(dep[b][: int(tabs[2][b][-1])] for b in range(2)))
 
 
 def bcsr4_sell_plan_probe(nbrows, ptrow, indcol, nwaves_max=1024):

@@ -4,7 +4,12 @@ every built form (device events around back-to-back solves, after warm-ups), lau
 product's microseconds on a handle of the same matrix in the same process, and GMRES(30) iterations and seconds to rtol = 1e-8
 with and without M.  Prints one JSON line and appends it to profiles/ilu_bench.jsonl.
 
-    python3 tools/bench_ilu.py [--cells 68] [--fill 0] [--solves 200] [--maxiter 300] [--no-append]
+    python3 tools/bench_ilu.py [--cells 68] [--fill 0] [--solves 200] [--maxiter 300] [--form both|0|1] [--no-append]
+
+--form: which forms of the solve to measure, on the SAME handle in one process (mi_bilu4_set_solve_form): 0 one launch per level,
+1 both sweeps in one launch, both (default; form 0 only, with the reason recorded, where the pattern is not eligible for form 1).
+The record then also carries the one-launch plan (workgroups, chunks per sweep, the largest dependency list) and GMRES(30) with
+each form as M.
 
 --refactor measures the two refactorisations instead, in one process, and appends one record (tool = "bench_ilu_refactor"): the
 wall time of the host path mi_bilu4_refactor (factor on host threads, wait for the device, upload; median of --host-reps calls),
@@ -92,6 +97,7 @@ def main():
     ap.add_argument("--fill", type=int, default=0)
     ap.add_argument("--solves", type=int, default=200)
     ap.add_argument("--maxiter", type=int, default=300)
+    ap.add_argument("--form", choices=("both", "0", "1"), default="both")
     ap.add_argument("--no-append", action="store_true")
     a = ap.parse_args()
     import numpy as np
@@ -116,15 +122,34 @@ def main():
     b = synth.x_sin(0, n) + 1.0
     db = torch.from_numpy(b).cuda()
     dx, dy = torch.zeros_like(db), torch.zeros_like(db)
-    solve_us = timed_us(lambda: F.solve(dx, db), 20, max(a.solves, 200))
+    forms = [0, 1] if a.form == "both" else [int(a.form)]
+    one, why_not = None, None
+    if 1 in forms:
+        try:
+            F.prepare_one()
+            one = F.info_one()
+        except mpk.MiError as e:
+            if e.status != 5 or a.form == "1":
+                raise
+            forms, why_not = [0], str(e)
+    names = {0: "per_level_launches", 1: "one_launch"}
+    us = {0: None, 1: None}
+    for form in forms:
+        assert F.set_form(form) == form
+        us[form] = timed_us(lambda: F.solve(dx, db), 20, max(a.solves, 200))
+        F.one_status()
+    solve_us = us[forms[0]]
     spmv_us = timed_us(lambda: mpk.SpMV_BCSR(dy, db, A), 20, max(a.solves, 200))
     out = dict(tool="bench_ilu", cells=a.cells, rows=n, block_rows=nb, blocks=int(len(bc)), fill=a.fill, factor_blocks=info["nblocks"],
                factor_bytes=info["factor_bytes"], host_factor_seconds=round(info["factor_seconds"], 4), create_seconds=round(create_s, 3),
                fwd_levels=info["fwd_levels"], bwd_levels=info["bwd_levels"], launches_per_solve=info["launches"], form_in_use=info["form"],
-               solve_us={"per_level_launches": round(solve_us, 2), "one_launch": None},
-               us_per_launch=round(solve_us / max(info["launches"], 1), 3), bcsr4_spmv_us=round(spmv_us, 2),
-               solve_over_spmv=round(solve_us / spmv_us, 2), gmres={})
-    for label, M in (("ilu", F), ("none", None)):
+               solve_us={names[f]: (None if us[f] is None else round(us[f], 2)) for f in (0, 1)},
+               us_per_launch=round(solve_us / max(info["launches"], 1), 3) if forms[0] == 0 else None, bcsr4_spmv_us=round(spmv_us, 2),
+               solve_over_spmv=round(solve_us / spmv_us, 2), forms=forms, one_launch_plan=one, one_launch_not_eligible=why_not,
+               one_over_levels=round(us[1] / us[0], 3) if len(forms) == 2 else None, gmres={})
+    for label, M, form in [("ilu" if f == 0 else "ilu_one_launch", F, f) for f in forms] + [("none", None, None)]:
+        if form is not None:
+            assert F.set_form(form) == form
         dx.zero_()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
