@@ -4,6 +4,10 @@ the chunked patterns of tests/bilu4one_cases.py, with 1, 2, 3 and the default nu
 sides, out of place and in place, vectors offset by 8 bytes, a non-default stream, three solves back to back, after both refactors;
 NaN and Inf; fe_matrix(10) and fe_matrix(16), whose middle planes are wider than a chunk (50 solves into poisoned vectors: rows of
 one 128-byte line of x lie in different levels there); switching forms; stream capture; the pattern that is not eligible.
+No chunk of these patterns waits for more than 44 others.  The limits of the hand-off itself — 63, 64, 65, 128, 129, 255 and 256
+dependencies (the polling lanes of one wave, of several, of the whole workgroup), a last-listed dependency that finishes last,
+more chunks than the default grid has workgroups, two handles on form 1 on two streams, the cap of 256 from both sides — are in
+tests/test_gpu_bilu4one_limits.py.
 No test makes a wait give up (none shortens the spin bound): that path is read against launch_spmk.hip, not provoked."""
 import os
 
