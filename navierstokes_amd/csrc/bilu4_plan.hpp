@@ -24,6 +24,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #ifdef __clang__
@@ -40,15 +41,36 @@ struct Bilu4Pattern {
     int nb = 0;
     std::vector<int> ptr, col, diag; // diag[i]: position of block (i, i)
     long long nblocks() const { return ptr.empty() ? 0 : ptr.back(); }
+    // [first, second): the off-diagonal blocks of row i that a sweep reads — its L blocks forward, its U blocks backward
+    std::pair<int, int> offdiag(int i, bool backward) const
+    {
+        return backward ? std::make_pair(diag[i] + 1, ptr[i + 1]) : std::make_pair(ptr[i], diag[i]);
+    }
+};
+
+// one launch of a sweep: the levels [l0, l1), which are the positions [p0, p1).  THE FOLDING RULE, stated here and nowhere else:
+// a launch is a folded run — one workgroup that steps through its levels with workgroup barriers — iff it has more than one
+// level or fewer block rows than one workgroup serves; any other launch is one wide level, kBiluRowsPerWG positions per workgroup.
+// The solve's kernels, the factor's kernels and the one-launch form's chunks all follow it.
+struct Bilu4Launch {
+    int l0, l1, p0, p1;
+    bool folded() const { return l1 - l0 > 1 || p1 - p0 < kBiluRowsPerWG; }
 };
 
 // one sweep's schedule: rows in level-major order (ascending row number inside a level) and the launches after folding
 struct Bilu4Sweep {
     std::vector<int> perm;       // [nb] position -> block row
     std::vector<int> lev_ptr;    // [nlev + 1] first position of each level
-    std::vector<int> launch_ptr; // [nlaunch + 1] first level of each launch; a launch of more than one level is a folded run
+    std::vector<int> launch_ptr; // [nlaunch + 1] first level of each launch
     int nlev() const { return (int)lev_ptr.size() - 1; }
     int nlaunch() const { return (int)launch_ptr.size() - 1; }
+    Bilu4Launch launch(int a) const { return Bilu4Launch{launch_ptr[a], launch_ptr[a + 1], lev_ptr[launch_ptr[a]], lev_ptr[launch_ptr[a + 1]]}; }
+};
+
+// what a pattern and a fill fix: the factor's pattern and both sweeps.  Index 0 is the forward sweep, 1 the backward one, everywhere.
+struct Bilu4Schedule {
+    Bilu4Pattern pat;
+    Bilu4Sweep sweep[2];
 };
 
 // MI_ERR_ARG conditions of a square block pattern; empty string = fine
@@ -134,7 +156,7 @@ inline void bilu4_levels(const Bilu4Pattern& P, bool backward, std::vector<int>*
     int top = 0;
     for (int t = 0; t < P.nb; t++) {
         const int i = backward ? P.nb - 1 - t : t;
-        const int k0 = backward ? P.diag[i] + 1 : P.ptr[i], k1 = backward ? P.ptr[i + 1] : P.diag[i];
+        const auto [k0, k1] = P.offdiag(i, backward);
         int l = 0;
         for (int k = k0; k < k1; k++) l = std::max(l, (*level)[P.col[k]] + 1);
         (*level)[i] = l;
@@ -164,6 +186,12 @@ inline void bilu4_sweep(const Bilu4Pattern& P, bool backward, Bilu4Sweep* S)
         S->launch_ptr.push_back(e);
         l = e;
     }
+}
+
+inline void bilu4_schedule(int nb, const int* ptrow, const int* indcol, int fill, Bilu4Schedule* S)
+{
+    bilu4_symbolic(nb, ptrow, indcol, fill, &S->pat);
+    for (int b = 0; b < 2; b++) bilu4_sweep(S->pat, b == 1, &S->sweep[b]);
 }
 
 // ---------------------------------------------------------------- numeric
@@ -298,21 +326,24 @@ struct Bilu4DevPlan {
     }
 };
 
-inline void bilu4dev_plan(const Bilu4Pattern& P, const Bilu4Sweep& F, const Bilu4Sweep& B, const int* ptrow, const int* indcol, Bilu4DevPlan* D)
+inline void bilu4dev_plan(const Bilu4Schedule& S, const int* ptrow, const int* indcol, Bilu4DevPlan* D)
 {
+    const Bilu4Pattern& P = S.pat;
+    const Bilu4Sweep& F = S.sweep[0];
     const int nb = P.nb;
     D->fpos.assign(nb, 0);
     D->bpos.assign(nb, 0);
-    for (int q = 0; q < nb; q++) D->fpos[F.perm[q]] = q, D->bpos[B.perm[q]] = q;
+    for (int q = 0; q < nb; q++) D->fpos[F.perm[q]] = q, D->bpos[S.sweep[1].perm[q]] = q;
     // home of every block of the pattern: the level-major copies list a row's blocks in the pattern's order
     std::vector<int> home((size_t)P.nblocks());
     long long n = 0;
-    for (int q = 0; q < nb; q++)
-        for (int k = P.ptr[F.perm[q]]; k < P.diag[F.perm[q]]; k++) home[k] = (int)n++;
-    D->nL = n;
-    for (int q = 0; q < nb; q++)
-        for (int k = P.diag[B.perm[q]] + 1; k < P.ptr[B.perm[q] + 1]; k++) home[k] = (int)n++;
-    D->nU = n - D->nL;
+    for (int b = 0; b < 2; b++) {
+        for (int q = 0; q < nb; q++) {
+            const auto [k0, k1] = P.offdiag(S.sweep[b].perm[q], b == 1);
+            for (int k = k0; k < k1; k++) home[k] = (int)n++;
+        }
+        (b ? D->nU : D->nL) = n - (b ? D->nL : 0);
+    }
     for (int i = 0; i < nb; i++) home[P.diag[i]] = (int)(n + D->bpos[i]);
     D->gather.assign((size_t)P.nblocks(), -1);
     for (int i = 0; i < nb; i++) {
@@ -394,16 +425,16 @@ inline std::vector<int> bilu4one_chunk_of_row(const Bilu4Sweep& S, const Bilu4On
     return of;
 }
 
-inline void bilu4one_sweep(const Bilu4Pattern& P, const Bilu4Sweep& S, bool backward, Bilu4OneSweep* O)
+inline void bilu4one_sweep(const Bilu4Schedule& Sch, int b, Bilu4OneSweep* O)
 {
+    const Bilu4Pattern& P = Sch.pat;
+    const Bilu4Sweep& S = Sch.sweep[b];
     O->chunk_pos.clear(), O->chunk_lev.clear(), O->dep.clear();
     for (int a = 0; a < S.nlaunch(); a++) {
-        const int l0 = S.launch_ptr[a], l1 = S.launch_ptr[a + 1];
-        const int p0 = S.lev_ptr[l0], p1 = S.lev_ptr[l1];
-        const bool folded = l1 - l0 > 1 || p1 - p0 < kBiluRowsPerWG;
-        for (int p = p0; p < p1; p += folded ? p1 - p0 : kBiluRowsPerWG) {
+        const Bilu4Launch L = S.launch(a);
+        for (int p = L.p0; p < L.p1; p += L.folded() ? L.p1 - L.p0 : kBiluRowsPerWG) {
             O->chunk_pos.push_back(p);
-            O->chunk_lev.push_back(l0);
+            O->chunk_lev.push_back(L.l0);
         }
     }
     O->chunk_pos.push_back(P.nb);
@@ -415,8 +446,7 @@ inline void bilu4one_sweep(const Bilu4Pattern& P, const Bilu4Sweep& S, bool back
     for (int c = 0; c < O->nchunks(); c++) {
         const size_t first = O->dep.size();
         for (int q = O->chunk_pos[c]; q < O->chunk_pos[c + 1]; q++) {
-            const int i = S.perm[q];
-            const int k0 = backward ? P.diag[i] + 1 : P.ptr[i], k1 = backward ? P.ptr[i + 1] : P.diag[i];
+            const auto [k0, k1] = P.offdiag(S.perm[q], b == 1);
             for (int k = k0; k < k1; k++) {
                 const int d = of[P.col[k]];
                 if (d != c && seen[d] != c) seen[d] = c, O->dep.push_back(d);
@@ -428,18 +458,19 @@ inline void bilu4one_sweep(const Bilu4Pattern& P, const Bilu4Sweep& S, bool back
     }
 }
 
-inline void bilu4one_plan(const Bilu4Pattern& P, const Bilu4Sweep& F, const Bilu4Sweep& B, Bilu4OnePlan* O)
+inline void bilu4one_plan(const Bilu4Schedule& S, Bilu4OnePlan* O)
 {
-    bilu4one_sweep(P, F, false, &O->sweep[0]);
-    bilu4one_sweep(P, B, true, &O->sweep[1]);
+    for (int b = 0; b < 2; b++) bilu4one_sweep(S, b, &O->sweep[b]);
 }
 
 // What the kernel relies on, checked against the pattern and the schedule, and the dealing REPLAYED for G workgroups: every
 // workgroup steps through its chunks in order and takes the next one only when all its dependencies are finished.  Empty string,
-// or the first violation.
-inline std::string bilu4one_check(const Bilu4Pattern& P, const Bilu4Sweep& S, bool backward, const Bilu4OneSweep& O, int G)
+// or the first violation (of sweep b's tables O).
+inline std::string bilu4one_check(const Bilu4Schedule& Sch, int b, const Bilu4OneSweep& O, int G)
 {
-    const std::string sw = backward ? "backward" : "forward";
+    const Bilu4Pattern& P = Sch.pat;
+    const Bilu4Sweep& S = Sch.sweep[b];
+    const std::string sw = b ? "backward" : "forward";
     const int nch = O.nchunks(), nb = P.nb;
     if (nch < 0 || (int)O.chunk_lev.size() != nch + 1 || (int)O.dep_ptr.size() != nch + 1) return sw + ": table sizes disagree";
     std::vector<int> cover(nb, 0);
@@ -467,7 +498,7 @@ inline std::string bilu4one_check(const Bilu4Pattern& P, const Bilu4Sweep& S, bo
                 return sw + ": chunk " + std::to_string(c) + " lists dependency " + std::to_string(*d) + (*d >= c ? ", not a smaller index" : ", out of order");
         for (int q = O.chunk_pos[c]; q < O.chunk_pos[c + 1]; q++) {
             const int i = S.perm[q];
-            const int k0 = backward ? P.diag[i] + 1 : P.ptr[i], k1 = backward ? P.ptr[i + 1] : P.diag[i];
+            const auto [k0, k1] = P.offdiag(i, b == 1);
             for (int k = k0; k < k1; k++)
                 if (of[P.col[k]] != c && !std::binary_search(d0, d1, of[P.col[k]]))
                     return sw + ": block row " + std::to_string(i) + " names block row " + std::to_string(P.col[k]) + ", whose chunk " +

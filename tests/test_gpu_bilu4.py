@@ -12,7 +12,7 @@ import bilu4_model as M
 from conftest import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
-FORMS = ("0", None)  # MI355_BILU_FORM: form 0 forced, and the default (the one-launch form is not built: asking for it is refused)
+FORMS = ("0", None)  # MI355_BILU_FORM: form 0 forced, and the default (the one-launch form is chosen per handle, with mi_bilu4_set_solve_form: asking for it through the environment is refused)
 
 
 def _rhs(nb):

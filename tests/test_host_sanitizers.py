@@ -1,5 +1,5 @@
 """Host-side planners under the address and undefined-behaviour sanitizers (CPU only: GPU sanitizers are not available on this pool, and
-nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp) and say what they check."""
+nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp, bilu_asan.cpp) and say what they check."""
 import os
 import shutil
 import subprocess
@@ -26,6 +26,17 @@ def test_partition_planner_under_host_sanitizers(tmp_path):
         pytest.skip("g++ not found")
     exe = str(tmp_path / "part_asan")
     out = _run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tools", "part_asan.cpp")], exe, tmp_path)
+    assert "bad 0" in out, out
+
+
+def test_block_ilu_planner_under_host_sanitizers(tmp_path):
+    """bilu4_plan.hpp: the schedule (off-diagonal ranges, launches and the folding rule), the host factorisation with 1 and 4 threads, the
+    device refactor's plan and the one-launch solve's plan replayed for 1, 2, 7 and 256 workgroups, every table checked by brute force on
+    the empty matrix, a diagonal one, a chain, random patterns at fill 0-3 and layered patterns with levels of 1, 63, 64, 65 and 129 rows."""
+    if not shutil.which("g++"):
+        pytest.skip("g++ not found")
+    exe = str(tmp_path / "bilu_asan")
+    out = _run(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tools", "bilu_asan.cpp")], exe, tmp_path)
     assert "bad 0" in out, out
 
 

@@ -1,0 +1,192 @@
+// tools/bilu_asan.cpp — dev tool: bilu4_plan.hpp (the schedule of the block ILU, its host factorisation, the device refactor's plan, the
+// one-launch solve's plan) under the host address and undefined-behaviour sanitizers, every table checked by brute force on the empty
+// matrix, a diagonal one, a chain, random banded and random unsymmetric patterns at fill 0 to 3, and layered patterns whose levels
+// have 1, 63, 64, 65 and 129 rows (either side of the folding rule):
+//   g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -Inavierstokes_amd/csrc -o /tmp/bilu_asan tools/bilu_asan.cpp && /tmp/bilu_asan
+#include "bilu4_plan.hpp"
+#include <cstdio>
+#include <random>
+using namespace mi355;
+
+static int bad = 0;
+#define EXPECT(cond, ...)                  \
+    do {                                   \
+        if (!(cond)) {                     \
+            printf("%s fill %d: ", name, fill); \
+            printf(__VA_ARGS__);           \
+            printf("\n");                  \
+            bad++;                         \
+            return;                        \
+        }                                  \
+    } while (0)
+
+using Rows = std::vector<std::vector<int>>;
+
+// the layered patterns of tests/bilu4_cases.py: layer l holds widths[l] consecutive rows, every row is linked (both ways) to one row
+// of the layer before and is named by one of the layer after, so at fill 0 the forward levels are the layers, the backward ones the layers reversed
+static Rows layered(const std::vector<int>& widths, int extra, std::mt19937& rng)
+{
+    std::vector<int> first(1, 0);
+    for (int w : widths) first.push_back(first.back() + w);
+    Rows rows(first.back());
+    auto link = [&](int i, int j) { rows[i].push_back(j), rows[j].push_back(i); };
+    for (size_t l = 0; l + 1 < widths.size(); l++) {
+        for (int r = 0; r < widths[l + 1]; r++) link(first[l + 1] + r, first[l] + r % widths[l]);
+        for (int r = 0; r < widths[l]; r++) link(first[l] + r, first[l + 1] + r % widths[l + 1]);
+    }
+    for (size_t l = 2; l < widths.size(); l++)
+        for (int r = 0; r < widths[l]; r++)
+            for (int e = 0; e < extra; e++) link(first[l] + r, (int)(rng() % first[l - 1]));
+    return rows;
+}
+
+// widths: the level sizes the pattern must have at fill 0 (forward; reversed backward), or empty
+static void check(const char* name, Rows rows, int fill, const std::vector<int>& widths = {})
+{
+    const int nb = (int)rows.size();
+    std::vector<int> ptr(1, 0), col;
+    for (int i = 0; i < nb; i++) {
+        rows[i].push_back(i);
+        std::sort(rows[i].begin(), rows[i].end());
+        rows[i].erase(std::unique(rows[i].begin(), rows[i].end()), rows[i].end());
+        col.insert(col.end(), rows[i].begin(), rows[i].end());
+        ptr.push_back((int)col.size());
+    }
+    EXPECT(bilu4_check_pattern(nb, ptr.data(), col.data()).empty(), "the harness made a bad pattern");
+    Bilu4Schedule S;
+    bilu4_schedule(nb, ptr.data(), col.data(), fill, &S);
+    const Bilu4Pattern& P = S.pat;
+
+    // the two off-diagonal ranges and the diagonal partition every row; where[i * nb + j]: the place of block (i, j), found by walking the row
+    std::vector<int> where((size_t)nb * nb, -1);
+    EXPECT(P.nb == nb && (int)P.ptr.size() == nb + 1 && P.nblocks() == (long long)P.col.size(), "pattern sizes");
+    for (int i = 0; i < nb; i++) {
+        const auto [l0, l1] = P.offdiag(i, false);
+        const auto [u0, u1] = P.offdiag(i, true);
+        EXPECT(l0 == P.ptr[i] && l0 <= l1 && l1 == P.diag[i] && u0 == l1 + 1 && u0 <= u1 && u1 == P.ptr[i + 1], "row %d is not L | diagonal | U", i);
+        for (int k = P.ptr[i]; k < P.ptr[i + 1]; k++) {
+            EXPECT(k < l1 ? P.col[k] < i : k == l1 ? P.col[k] == i : P.col[k] > i, "row %d: block %d on the wrong side of the diagonal", i, k);
+            where[(size_t)i * nb + P.col[k]] = k;
+        }
+    }
+
+    // the launches partition the levels, and a launch is folded exactly when the rule says so
+    for (int b = 0; b < 2; b++) {
+        const Bilu4Sweep& W = S.sweep[b];
+        std::vector<int> level(nb, -1);
+        for (int l = 0; l < W.nlev(); l++)
+            for (int q = W.lev_ptr[l]; q < W.lev_ptr[l + 1]; q++) level[W.perm[q]] = l;
+        for (int i = 0; i < nb; i++) {
+            EXPECT(level[i] >= 0, "sweep %d: row %d has no position", b, i);
+            const auto [k0, k1] = P.offdiag(i, b == 1);
+            for (int k = k0; k < k1; k++) EXPECT(level[P.col[k]] < level[i], "sweep %d: row %d is not above the level of row %d", b, i, P.col[k]);
+        }
+        if (!widths.empty() && fill == 0) {
+            EXPECT(W.nlev() == (int)widths.size(), "sweep %d: %d levels, %zu layers", b, W.nlev(), widths.size());
+            for (int l = 0; l < W.nlev(); l++)
+                EXPECT(W.lev_ptr[l + 1] - W.lev_ptr[l] == widths[b ? widths.size() - 1 - l : l], "sweep %d: level %d is not its layer", b, l);
+        }
+        int lev = 0, pos = 0;
+        bool last_folded = false;
+        for (int a = 0; a < W.nlaunch(); a++) {
+            const Bilu4Launch L = W.launch(a);
+            EXPECT(L.l0 == lev && L.l1 > L.l0 && L.l1 <= W.nlev() && L.p0 == pos && L.p0 == W.lev_ptr[L.l0] && L.p1 == W.lev_ptr[L.l1], "sweep %d: launch %d does not continue the one before", b, a);
+            int narrow = 0;
+            for (int l = L.l0; l < L.l1; l++) narrow += W.lev_ptr[l + 1] - W.lev_ptr[l] < 64;
+            const bool rule = L.l1 - L.l0 > 1 || L.p1 - L.p0 < 64; // more than one level, or fewer block rows than one workgroup serves
+            EXPECT(L.folded() == rule, "sweep %d: launch %d: folded() is %d, the rule says %d", b, a, (int)L.folded(), (int)rule);
+            EXPECT(rule ? narrow == L.l1 - L.l0 && !last_folded : narrow == 0, "sweep %d: launch %d mixes wide and narrow levels, or splits a run", b, a);
+            lev = L.l1, pos = L.p1, last_folded = rule;
+        }
+        EXPECT(lev == W.nlev() && pos == nb, "sweep %d: the launches end at level %d, position %d", b, lev, pos);
+    }
+
+    // the factorisation: the same bits with 1 and with 4 threads
+    std::mt19937 rng(7 + nb);
+    std::vector<double> coef(16 * col.size());
+    for (int i = 0; i < nb; i++)
+        for (int k = ptr[i]; k < ptr[i + 1]; k++)
+            for (int e = 0; e < 16; e++)
+                coef[16 * (size_t)k + e] = ((int)(rng() % 2001) - 1000) / (col[k] == i ? 20000.0 : 4000.0 * (ptr[i + 1] - ptr[i])) + (col[k] == i && e % 5 == 0 ? 4.0 : 0.0);
+    std::vector<double> v1(16 * (size_t)P.nblocks(), -1.0), v4(v1.size(), -2.0);
+    const int r1 = bilu4_factor(P, S.sweep[0], ptr.data(), col.data(), coef.data(), false, 1, v1.data());
+    const int r4 = bilu4_factor(P, S.sweep[0], ptr.data(), col.data(), coef.data(), false, 4, v4.data());
+    EXPECT(r1 == -1 && r4 == -1, "a pivot was refused (rows %d, %d)", r1, r4);
+    EXPECT(v1.empty() || !memcmp(v1.data(), v4.data(), sizeof(double) * v1.size()), "the factor differs between 1 and 4 threads");
+
+    // the device refactor's plan
+    Bilu4DevPlan D;
+    bilu4dev_plan(S, ptr.data(), col.data(), &D);
+    std::vector<long long> start[2] = {std::vector<long long>(nb + 1, 0), std::vector<long long>(nb + 1, 0)}; // by position: blocks of the rows before it
+    for (int b = 0; b < 2; b++)
+        for (int q = 0; q < nb; q++) {
+            EXPECT((b ? D.bpos : D.fpos)[S.sweep[b].perm[q]] == q, "sweep %d: the position table does not invert perm at %d", b, q);
+            const auto [k0, k1] = P.offdiag(S.sweep[b].perm[q], b == 1);
+            start[b][q + 1] = start[b][q] + (k1 - k0);
+        }
+    EXPECT(D.nL == start[0][nb] && D.nU == start[1][nb] && D.nL + D.nU + nb == P.nblocks() && (long long)D.gather.size() == P.nblocks(), "the plan's block counts");
+    auto home = [&](int i, int j) -> long long { // of block (i, j) in L | U | D, or -1
+        const int k = where[(size_t)i * nb + j];
+        if (k < 0) return -1;
+        if (k < P.diag[i]) return start[0][D.fpos[i]] + (k - P.ptr[i]);
+        return k == P.diag[i] ? D.nL + D.nU + D.bpos[i] : D.nL + start[1][D.bpos[i]] + (k - P.diag[i] - 1);
+    };
+    long long hits = 0;
+    for (int h : D.gather) hits += h >= 0;
+    EXPECT(hits == (long long)col.size(), "gather names %lld blocks of the matrix, which has %zu", hits, col.size());
+    for (int i = 0; i < nb; i++)
+        for (int k = ptr[i]; k < ptr[i + 1]; k++) EXPECT(home(i, col[k]) >= 0 && D.gather[home(i, col[k])] == k, "block %d of the matrix does not land on its home", k);
+    EXPECT((long long)D.upd_ptr.size() == D.nL + 1 && D.upd_ptr[0] == 0 && D.upd_ptr.back() == (long long)D.upd.size(), "upd_ptr");
+    long long e = 0, at = 0, pairs = 0;
+    for (int q = 0; q < nb; q++) {
+        const int i = S.sweep[0].perm[q];
+        for (int k = P.ptr[i]; k < P.diag[i]; k++, e++) {
+            const int p = P.col[k];
+            EXPECT(D.upd_ptr[e] == at && D.upd_ptr[e + 1] - at == P.ptr[p + 1] - P.diag[p] - 1, "upd_ptr of L block (%d, %d)", i, p);
+            for (int kk = P.diag[p] + 1; kk < P.ptr[p + 1]; kk++, at++) {
+                EXPECT(D.upd[at] == home(i, P.col[kk]), "upd of (%d, %d) x (%d, %d) is %d, the home of (%d, %d) is %lld", i, p, p, P.col[kk], D.upd[at], i, P.col[kk], home(i, P.col[kk]));
+                pairs += D.upd[at] >= 0;
+            }
+        }
+    }
+    EXPECT(pairs == D.update_pairs, "update_pairs");
+
+    // the one-launch solve's plan, replayed
+    Bilu4OnePlan O;
+    bilu4one_plan(S, &O);
+    for (int G : {1, 2, 7, 256})
+        for (int b = 0; b < 2; b++) {
+            const std::string why = bilu4one_check(S, b, O.sweep[b], G);
+            EXPECT(why.empty(), "G = %d: %s", G, why.c_str());
+        }
+}
+
+int main()
+{
+    std::mt19937 rng(23);
+    int patterns = 0;
+    for (int fill = 0; fill <= 3; fill++) {
+        check("empty", Rows(), fill);
+        check("diagonal", Rows(150), fill);
+        Rows chain(150);
+        for (int i = 1; i < 150; i++) chain[i].push_back(i - 1), chain[i - 1].push_back(i);
+        check("chain", chain, fill);
+        patterns += 3;
+        for (int it = 0; it < 12; it++, patterns++) {
+            const bool banded = it % 2 == 0;
+            const int nb = 1 + (int)(rng() % 300), band = 1 + (int)(rng() % 12), per_row = (int)(rng() % 4);
+            Rows rows(nb);
+            for (int i = 0; i < nb; i++)
+                for (int e = 0; e < per_row; e++) {
+                    const int j = banded ? i - band + (int)(rng() % (2 * band + 1)) : (int)(rng() % nb);
+                    if (j >= 0 && j < nb) rows[i].push_back(j);
+                }
+            check(banded ? "random banded" : "random unsymmetric", rows, fill);
+        }
+    }
+    const std::vector<std::vector<int>> layers = {{1}, {63}, {64}, {65}, {129}, {1, 63, 64, 65, 1, 1, 128, 129, 2, 63, 64, 200, 1}, {63, 64, 63, 64, 65, 63}, {129, 1, 129}};
+    for (const std::vector<int>& w : layers)
+        for (int extra : {0, 3}) check("layered", layered(w, extra, rng), 0, w), patterns++;
+    printf("block ILU plans: patterns %d bad %d\n", patterns, bad);
+    return bad != 0;
+}
