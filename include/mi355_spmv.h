@@ -629,6 +629,42 @@ int mi_bilu4one_status(mi_bilu4_t F);
  * *plan_bytes of tables and flags (0 until prepared); any output may be NULL */
 int mi_bilu4one_info(mi_bilu4_t F, int* prepared, int* eligible, int* workgroups, int nchunks[2], int max_deps[2], long long* plan_bytes);
 
+/* ---- 4x4-block ILU(k): the factor applied by a FIXED number of Jacobi sweeps per triangle (mi_bilu4sw_*) ----
+ * The exact solve (mi_bilu4_solve*, either form) is bound by the dependency chain of the levels, not by bytes.  The sweep solve
+ * applies the SAME device factor by the truncated Neumann series of each triangle (Anzt, Chow, Dongarra, Euro-Par 2015): every
+ * sweep computes all rows at once from the previous iterate, one launch shaped like the blocked product.  With fixed counts the
+ * operator is a fixed linear map, so plain right-preconditioned GMRES stays valid with it as M.
+ * DEFINITION (part of the interface), for sweep counts sf, sb >= 0, L the block rows left of the diagonal (unit diagonal), U the
+ * block rows right of it, Dinv the inverted diagonal blocks:
+ *   forward    t^0 = b;  for k < sf:  t^{k+1}_i = b_i - sum_{j<i} L_ij t^k_j
+ *   diagonal   x^0_i = Dinv_i . t^{sf}_i                                (the chain that ends the exact backward row)
+ *   backward   for k < sb:  x^{k+1}_i = Dinv_i . (t^{sf}_i - sum_{j>i} U_ij x^k_j)
+ *   result     x^{sb}
+ * ARITHMETIC of a row is exactly the exact solve's above: s = the source entry; per block in ascending column order the chain
+ * p = fma(a3,t3, fma(a2,t2, fma(a1,t1, a0*t0))) and ONE rounded s - p; the backward row ends with Dinv . s, one chain per entry.
+ * Every sweep reads only the previous iterate and writes another vector: nothing is updated in place, so the result does not
+ * depend on the schedule and is deterministic.  A row of dependency level l (counted from 0) holds the bits of the exact solve
+ * after l sweeps and keeps them: (fwd_levels - 1, bwd_levels - 1) sweeps return mi_bilu4_solve's result BIT FOR BIT, and more
+ * change nothing.  Counts above those are therefore CLAMPED to them (a huge count costs no more than the level count).
+ * Launches per solve: sf + 1 + sb after clamping, on the caller's stream.  Once prepared a solve allocates nothing, copies nothing
+ * to the host and synchronises nothing (it can be captured into a graph, together with mi_bilu4dev_refactor); an unprepared
+ * handle is prepared by its first solve, except under stream capture: MI_ERR_STATE.  Three work vectors of 4 nbrows doubles
+ * belong to the handle; the last launch alone writes d_x.  d_x == d_b is allowed; d_b is never written unless it is d_x.
+ * Vectors need 8-byte alignment only.  The values are those of the device factor: whatever mi_bilu4_refactor or
+ * mi_bilu4dev_refactor wrote last, with no extra step.  Independent of the handle's solve form.
+ * ONE sweep solve at a time per handle (the work vectors are shared); ordering between streams is the caller's, as for the
+ * device refactor.
+ * MI_ERR_ARG: a null handle or vector, a negative count — before the device is touched; MI_ERR_NODEVICE: a host-only handle
+ * (mi_bilu4_create_host), hence any box without a GPU: there is no CPU fallback.  nbrows == 0: every call is a no-op. */
+/* allocates the work vectors; idempotent */
+int mi_bilu4sw_prepare(mi_bilu4_t F);
+int mi_bilu4sw_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s);
+int mi_bilu4sw_solve(mi_bilu4_t F, const double* b, double* x, int sweeps_fwd, int sweeps_bwd); /* host vectors: copied in and out */
+/* *prepared; *max_fwd = fwd_levels - 1 and *max_bwd = bwd_levels - 1, the counts the clamp ends at; *launches_last = launches of
+ * the last sweep solve, after clamping (0 before the first); *work_bytes of the work vectors (0 until prepared).  Any output may
+ * be NULL. */
+int mi_bilu4sw_info(mi_bilu4_t F, int* prepared, int* max_fwd, int* max_bwd, int* launches_last, long long* work_bytes);
+
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r
  * owns global rows [row_starts[r], row_starts[r+1]) and the matching slice of

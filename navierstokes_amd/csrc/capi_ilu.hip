@@ -2,13 +2,15 @@
 // the library).  Factored on the host (bilu4_plan.hpp), solved on the GPU by one launch per (folded) dependency level
 // (bilu4_solve.hpp) or, where the handle was told so (mi_bilu4_set_solve_form), by ONE launch of persistent workgroups
 // (bilu4_solve_one.hpp, mi_bilu4one_*); mi_bilu4dev_* refactors on the GPU, into the same device copies, level by level
-// (bilu4_factor.hpp).
+// (bilu4_factor.hpp); mi_bilu4sw_* applies the same device factor by a fixed number of Jacobi sweeps per triangle, one launch per
+// sweep (bilu4_sweep.hpp).
 // No CPU fallback: the solve and the device refactor need a HIP device; the planning and host factorisation entry points need none.
 #include "capi_internal.hpp"
 #include "bilu4_plan.hpp"
 #include "bilu4_solve.hpp"
 #include "bilu4_solve_one.hpp"
 #include "bilu4_factor.hpp"
+#include "bilu4_sweep.hpp"
 
 // ---------------------------------------------------------------- ownership
 // A device array that goes with its owner: move-only, freed by its destructor — the ONLY release path of this file.  Assigning a
@@ -99,6 +101,14 @@ struct Bilu4OneTables {
     unsigned epoch = 0;
 };
 
+// the sweep solve (mi_bilu4sw_prepare): its three work vectors — the forward iterates alternate between w[0] and w[1], the one
+// that does not end up holding t and w[2] carry the backward iterates
+struct Bilu4SweepWork {
+    bool prepared = false;
+    int launches_last = 0;
+    DevArray<double> w[3];
+};
+
 struct mi_bilu4_s {
     int device = -1; // -1: host-only handle (mi_bilu4_create_host)
     int fill = 0;
@@ -112,7 +122,8 @@ struct mi_bilu4_s {
     DevArray<double> d_b, d_x;     // scratch of the host-pointer solve
     Bilu4DevTables dev;
     Bilu4OneTables one;
-    ~mi_bilu4_s() { one = {}, lev[0] = {}, lev[1] = {}, d_b = {}, d_x = {}, dev = {}; } // the order the handle has always been freed in
+    Bilu4SweepWork sw;
+    ~mi_bilu4_s() { sw = {}, one = {}, lev[0] = {}, lev[1] = {}, d_b = {}, d_x = {}, dev = {}; } // the order the handle has always been freed in (sw: newest first)
     const Bilu4Pattern& pat() const { return sched.pat; }
     Bilu4FactorView factor_view() const
     {
@@ -679,5 +690,113 @@ extern "C" int mi_bilu4one_info(mi_bilu4_t F, int* prepared, int* eligible, int*
         if (max_deps) max_deps[b] = T.max_deps[b];
     }
     if (plan_bytes) *plan_bytes = T.state == 1 ? T.plan_bytes : 0;
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------- mi_bilu4sw_*: the factor applied by fixed Jacobi sweeps
+static const char* const kHostOnlySweep = ": a host-only handle (mi_bilu4_create_host) has no device factor, and the sweep solve has no CPU fallback";
+
+// What the sweep entry points begin with, in the order of bilu_dev_guard — except that a host-only handle is MI_ERR_NODEVICE here
+static int bilu_sw_guard(const mi_bilu4_s* F, const char* name, const char* bad_arg = nullptr, const char* bad_data = nullptr)
+{
+    CHECK_ARG(F, "null handle");
+    CHECK_ARG(!bad_arg, bad_arg);
+    if (F->pat().nb == 0) return MI_OK;
+    CHECK_ARG(!bad_data, bad_data);
+    if (F->device < 0) return fail(MI_ERR_NODEVICE, std::string(name) + kHostOnlySweep);
+    return kBiluGo;
+}
+
+static const char* bilu_sw_bad_counts(int sf, int sb) { return sf < 0 || sb < 0 ? "negative sweep count" : nullptr; }
+
+// levels - 1 of sweep b: the count at which the sweeps have reached the exact solve's bits, where counts are clamped
+static int bilu_sw_max(const mi_bilu4_s* F, int b) { return std::max(F->sched.sweep[b].nlev() - 1, 0); }
+
+static dim3 bilu_sw_grid(int nb) { return dim3((unsigned)((nb + kBiluRowsPerWG - 1) / kBiluRowsPerWG)); }
+
+// one sweep; AL by the vector that is gathered (the work vectors are aligned, b need not be)
+template <bool BWD>
+static void bilu_sw_launch(const Bilu4SweepView& V, int nb, const double* src, const double* old, double* out, hipStream_t s)
+{
+    bilu_by_alignment(old, [&](auto al) {
+        hipLaunchKernelGGL((bilu4_sweep<BWD, decltype(al)::value, kBiluSweepDepth>), bilu_sw_grid(nb), dim3(kWG), 0, s, V, nb, src, old, out);
+        return 0;
+    });
+}
+
+// sf forward sweeps, the diagonal pass, sb backward sweeps, on the caller's stream: launches only.  d_b is read by every forward
+// sweep and never written unless it is d_x; d_x is written by the LAST launch only, when d_b is no longer needed.
+static int bilu_sw_solve_launch(mi_bilu4_s* F, const double* d_b, double* d_x, int sf, int sb, hipStream_t s)
+{
+    static_assert(kBiluRowsPerWG * 4 == kWG, "four lanes per block row");
+    const int nb = F->pat().nb;
+    sf = std::min(sf, bilu_sw_max(F, 0));
+    sb = std::min(sb, bilu_sw_max(F, 1));
+    double* const w[3] = {F->sw.w[0], F->sw.w[1], F->sw.w[2]};
+    const Bilu4SweepView L = F->lev[0].view(), U = F->lev[1].view();
+    const double* t = d_b; // t^0
+    for (int k = 0; k < sf; k++) {
+        bilu_sw_launch<false>(L, nb, d_b, t, w[k & 1], s);
+        t = w[k & 1];
+    }
+    double* const pong[2] = {t == w[0] ? w[1] : w[0], w[2]}; // free of t, whichever vector holds it
+    double* x = sb == 0 ? d_x : pong[0];
+    hipLaunchKernelGGL(bilu4_sweep_diag, bilu_sw_grid(nb), dim3(kWG), 0, s, U, nb, t, x);
+    for (int k = 0; k < sb; k++) {
+        double* const out = k == sb - 1 ? d_x : pong[(k + 1) & 1];
+        bilu_sw_launch<true>(U, nb, t, x, out, s);
+        x = out;
+    }
+    HIP_TRY(hipGetLastError());
+    F->sw.launches_last = sf + 1 + sb;
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4sw_prepare(mi_bilu4_t F)
+{
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4sw_prepare"); rc != kBiluGo) return rc;
+    if (F->sw.prepared) return MI_OK;
+    Bilu4SweepWork W; // moves into the handle once it is complete; a failure on the way frees what there is
+    for (DevArray<double>& v : W.w) // (uninitialised: every sweep writes all rows of its output before anything reads them)
+        if (const int rc = v.alloc(4 * (size_t)F->pat().nb)) return rc;
+    W.prepared = true;
+    F->sw = std::move(W);
+    return MI_OK;
+}
+
+static int bilu_sw_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, int sf, int sb, hipStream_t s)
+{
+    if (!F->sw.prepared) {
+        if (stream_is_capturing(s))
+            return fail(MI_ERR_STATE, "mi_bilu4sw_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sw_prepare allocates: call it before the capture)");
+        if (const int rc = mi_bilu4sw_prepare(F)) return rc;
+    }
+    return bilu_sw_solve_launch(F, d_b, d_x, sf, sb, s);
+}
+
+extern "C" int mi_bilu4sw_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s)
+{
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4sw_solve_dev", bilu_sw_bad_counts(sweeps_fwd, sweeps_bwd), d_b && d_x ? nullptr : "null vector"); rc != kBiluGo) return rc;
+    return bilu_sw_solve_any(F, d_b, d_x, sweeps_fwd, sweeps_bwd, (hipStream_t)s);
+}
+
+extern "C" int mi_bilu4sw_solve(mi_bilu4_t F, const double* b, double* x, int sweeps_fwd, int sweeps_bwd)
+{
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4sw_solve", bilu_sw_bad_counts(sweeps_fwd, sweeps_bwd), b && x ? nullptr : "null vector"); rc != kBiluGo) return rc;
+    const size_t bytes = sizeof(double) * 4 * (size_t)F->pat().nb;
+    HIP_TRY(hipMemcpy(F->d_b, b, bytes, hipMemcpyHostToDevice));
+    if (const int rc = bilu_sw_solve_any(F, F->d_b, F->d_x, sweeps_fwd, sweeps_bwd, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(x, F->d_x, bytes, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4sw_info(mi_bilu4_t F, int* prepared, int* max_fwd, int* max_bwd, int* launches_last, long long* work_bytes)
+{
+    CHECK_ARG(F, "null handle");
+    if (prepared) *prepared = F->sw.prepared ? 1 : 0;
+    if (max_fwd) *max_fwd = bilu_sw_max(F, 0);
+    if (max_bwd) *max_bwd = bilu_sw_max(F, 1);
+    if (launches_last) *launches_last = F->sw.launches_last;
+    if (work_bytes) *work_bytes = F->sw.prepared ? 3LL * 4 * F->pat().nb * (long long)sizeof(double) : 0;
     return MI_OK;
 }

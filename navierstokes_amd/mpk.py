@@ -180,6 +180,10 @@ def lib():
         "mi_bilu4_set_solve_form": [_vp, i],
         "mi_bilu4one_status": [_vp],
         "mi_bilu4one_info": [_vp, P(i), P(i), P(i), _vp, _vp, P(ll)],
+        "mi_bilu4sw_prepare": [_vp],
+        "mi_bilu4sw_solve_dev": [_vp, _vp, _vp, i, i, _vp],
+        "mi_bilu4sw_solve": [_vp, _vp, _vp, i, i],
+        "mi_bilu4sw_info": [_vp, P(i), P(i), P(i), P(i), P(ll)],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -652,6 +656,23 @@ class bilu4:
         return dict(prepared=bool(pr.value), eligible=bool(el.value), workgroups=wg.value, nchunks=(nch[0], nch[1]), max_deps=(md[0], md[1]),
                     plan_bytes=by.value)
 
+    def sweeps(self, fwd, bwd=None):
+        """The same factor applied by `fwd` Jacobi sweeps of the forward triangle and `bwd` (default: fwd) of the backward one
+        instead of the exact solve (mi_bilu4sw_*): a view with .solve(x, b), which is what GMRES takes as M.  Counts above
+        levels - 1 are clamped: there the result is the exact solve's, bit for bit."""
+        return bilu4_sweeps(self, fwd, fwd if bwd is None else bwd)
+
+    def prepare_sweeps(self):
+        """Allocate the work vectors of the sweep solve (mi_bilu4sw_prepare; idempotent): needed before a graph capture."""
+        check(lib().mi_bilu4sw_prepare(self.handle))
+        return self
+
+    def sweep_info(self):
+        """dict(prepared, max_fwd, max_bwd, launches_last, work_bytes) — mi_bilu4sw_info."""
+        pr, mf, mb, la, by = _c.c_int(), _c.c_int(), _c.c_int(), _c.c_int(), _c.c_longlong()
+        check(lib().mi_bilu4sw_info(self.handle, _c.byref(pr), _c.byref(mf), _c.byref(mb), _c.byref(la), _c.byref(by)))
+        return dict(prepared=bool(pr.value), max_fwd=mf.value, max_bwd=mb.value, launches_last=la.value, work_bytes=by.value)
+
     def info(self):
         """dict(nbrows, nblocks, fwd_levels, bwd_levels, launches, form, us_per_level_launches, us_one_launch, factor_seconds,
         factor_bytes) — mi_bilu4_info."""
@@ -684,6 +705,26 @@ class bilu4:
             self.close()
         except Exception:
             pass
+
+
+class bilu4_sweeps:
+    """bilu4.sweeps(fwd, bwd): the factors of F applied by fixed numbers of Jacobi sweeps.  It shares F's handle and owns nothing."""
+
+    def __init__(self, F, fwd, bwd):
+        self.F, self.fwd, self.bwd = F, int(fwd), int(bwd)
+        if self.fwd < 0 or self.bwd < 0:
+            raise ValueError("bilu4.sweeps: negative sweep count")
+
+    def solve(self, x, b):
+        """x = the sweep operator applied to b.  CUDA tensors: asynchronous on torch's current stream, x may be b; numpy arrays:
+        copied in and out."""
+        n = 4 * self.F.nbrows
+        if _is_torch(b):
+            check(lib().mi_bilu4sw_solve_dev(self.F.handle, _dev_ptr(b, n, "b"), _dev_ptr(x, n, "x"), self.fwd, self.bwd, _stream_ptr()))
+        else:
+            xx = _host_f64(x, n, "x", writable=True)
+            check(lib().mi_bilu4sw_solve(self.F.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data, self.fwd, self.bwd))
+        return x
 
 
 def bilu4_plan_probe(nbrows, ptrow, indcol, fill=0):

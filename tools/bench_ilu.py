@@ -11,6 +11,14 @@ with and without M.  Prints one JSON line and appends it to profiles/ilu_bench.j
 The record then also carries the one-launch plan (workgroups, chunks per sweep, the largest dependency list) and GMRES(30) with
 each form as M.
 
+--sweeps 1,2,3,4,6,8 adds the sweep solve (mi_bilu4sw_*, mpk.bilu4.sweeps) on the SAME handle in the same process: for each count s
+(per triangle) microseconds per application (back-to-back solves between device events, as for the forms), its launches, the bytes
+of the byte model s L + D + s (U + D) and the rate they amount to, and GMRES(30) iterations, seconds and true residual with
+M = F.sweeps(s), beside the exact solve's.  The record names the depth of the kernel's software pipeline the library was built
+with (pipeline_depth: kBiluSweepDepth of bilu4_sweep.hpp).
+
+    python3 tools/bench_ilu.py --sweeps 1,2,3,4,6,8 [--cells 68] [--fill 0]
+
 --refactor measures the two refactorisations instead, in one process, and appends one record (tool = "bench_ilu_refactor"): the
 wall time of the host path mi_bilu4_refactor (factor on host threads, wait for the device, upload; median of --host-reps calls),
 the time of mi_bilu4dev_refactor between device events (median of --reps single refactors after warm-ups), launches per refactor,
@@ -88,6 +96,45 @@ def refactor_record(a):
     return out
 
 
+def sweeps_record(a, F, A, b, db, dx, dy):
+    """The sweep solve on the handle the forms were measured on (in whatever form it was left: the sweeps do not depend on it)."""
+    import re
+    import numpy as np
+    import torch
+    from navierstokes_amd import mpk
+    F.prepare_sweeps()
+    depth = int(re.search(r"kBiluSweepDepth = (\d+);", open(os.path.join(ROOT, "navierstokes_amd", "csrc", "bilu4_sweep.hpp")).read()).group(1))
+    ptr, col, diag, _ = F.factor_host()
+    nb = len(ptr) - 1
+    n_l = int(np.sum(diag - ptr[:-1]))
+    n_u = int(np.sum(ptr[1:] - diag - 1))
+    # values and block columns of a triangle, the inverted diagonal blocks; per launch the source read and the result written
+    # (the gathered iterate is left to the caches, as in the blocked product's byte model)
+    l_bytes, u_bytes, d_bytes, vec = n_l * 132, n_u * 132, nb * 128, 2 * 32 * nb
+    reps = max(a.solves, 200)
+    rec = dict(pipeline_depth=depth, max=[F.sweep_info()["max_fwd"], F.sweep_info()["max_bwd"]], work_bytes=F.sweep_info()["work_bytes"], l_bytes=l_bytes, u_bytes=u_bytes,
+               dinv_bytes=d_bytes, counts={})
+    for s in [int(c) for c in a.sweeps.split(",") if c]:
+        V = F.sweeps(s)
+        us = timed_us(lambda: V.solve(dx, db), 20, reps)
+        launches = F.sweep_info()["launches_last"]
+        sf, sb = min(s, rec["max"][0]), min(s, rec["max"][1])
+        model = sf * l_bytes + d_bytes + sb * (u_bytes + d_bytes) + launches * vec
+        dx.zero_()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        its, hist = mpk.GMRES(A, db, dx, M=V, restart=30, rtol=1e-8, maxiter=a.maxiter)
+        torch.cuda.synchronize()
+        sec = time.perf_counter() - t0
+        mpk.SpMV_BCSR(dy, dx, A)
+        true = float(np.linalg.norm(b - dy.cpu().numpy()) / np.linalg.norm(b))
+        rec["counts"][str(s)] = dict(us=round(us, 2), launches=launches, us_per_launch=round(us / launches, 2), model_bytes=model,
+                                     model_gb_per_s=round(model / us * 1e-3, 1),
+                                     gmres=dict(iterations=its, seconds=round(sec, 4), recurrence_residual=float(hist[-1]), true_residual=true,
+                                                converged=bool(hist[-1] <= 1e-8)))
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--refactor", action="store_true")
@@ -98,6 +145,7 @@ def main():
     ap.add_argument("--solves", type=int, default=200)
     ap.add_argument("--maxiter", type=int, default=300)
     ap.add_argument("--form", choices=("both", "0", "1"), default="both")
+    ap.add_argument("--sweeps", default="", help="comma-separated sweep counts per triangle")
     ap.add_argument("--no-append", action="store_true")
     a = ap.parse_args()
     import numpy as np
@@ -160,6 +208,8 @@ def main():
         true = float(np.linalg.norm(b - dy.cpu().numpy()) / np.linalg.norm(b))
         out["gmres"][label] = dict(iterations=its, seconds=round(sec, 4), recurrence_residual=float(hist[-1]), true_residual=true,
                                    converged=bool(hist[-1] <= 1e-8))
+    if a.sweeps:
+        out["sweeps"] = sweeps_record(a, F, A, b, db, dx, dy)
     line = json.dumps(out)
     print(line)
     if not a.no_append:
