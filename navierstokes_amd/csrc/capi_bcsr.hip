@@ -55,14 +55,14 @@ static int build_bcsr4_tile(mi_bcsr4_t A, const int* ptrow, const int* indcol)
     }
     if (!fits) return MI_OK;
     nodes.push_back(0);
-    hipError_t e;
-    if ((e = hipMalloc(&A->d_tl_ptr, sizeof(int) * wg_ptr.size())) != hipSuccess ||
-        (e = hipMalloc(&A->d_tl_nodes, sizeof(unsigned) * nodes.size())) != hipSuccess ||
-        (e = hipMalloc(&A->d_tl_slots, sizeof(unsigned short) * slots.size())) != hipSuccess ||
-        (e = hipMemcpy(A->d_tl_ptr, wg_ptr.data(), sizeof(int) * wg_ptr.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(A->d_tl_nodes, nodes.data(), sizeof(unsigned) * nodes.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(A->d_tl_slots, slots.data(), sizeof(unsigned short) * slots.size(), hipMemcpyHostToDevice)) != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string("bcsr4 tile upload: ") + hipGetErrorString(e));
+    Bcsr4TileLists T;
+    HIP_TRY(T.ptr.alloc(wg_ptr.size()));
+    HIP_TRY(T.nodes.alloc(nodes.size()));
+    HIP_TRY(T.slots.alloc(slots.size()));
+    HIP_TRY(T.ptr.fill(wg_ptr));
+    HIP_TRY(T.nodes.fill(nodes));
+    HIP_TRY(T.slots.fill(slots));
+    A->tl = std::move(T);
     if (env_is("MI355_BCSR_TILE", "1")) A->use_tile = true;
     else if (!env_is("MI355_SPMV_AUTOTUNE", "0") && nb >= 100000) {
         double us[2] = {0, 0};
@@ -83,23 +83,17 @@ static int build_bcsr4_sell(mi_bcsr4_t A, const int* ptrow, const int* indcol)
     SellPlanHost P, P2;
     build_sell_plan(A->nbrows, ptrow, indcol, 1024, P);
     build_sell_wave_ranges(P, 2048, P2.wrng, P2.nwaves);
-    const size_t vbytes = sizeof(double) * (size_t)(P.nsteps + kSellPadSteps) * kSellStepDoubles;
+    Bcsr4Sliced S;
     hipError_t e;
-    if ((e = hipMalloc(&A->d_sell_val, vbytes)) != hipSuccess || (e = hipMalloc(&A->d_sell_col, sizeof(unsigned) * P.col.size())) != hipSuccess ||
-        (e = hipMalloc(&A->d_sell_sptr, sizeof(int) * P.sptr.size())) != hipSuccess || (e = hipMalloc(&A->d_sell_wrng, sizeof(int) * P.wrng.size())) != hipSuccess ||
-        (e = hipMalloc(&A->d_sell_wrng2, sizeof(int) * P2.wrng.size())) != hipSuccess ||
-        (e = hipMemcpy(A->d_sell_wrng2, P2.wrng.data(), sizeof(int) * P2.wrng.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemset(A->d_sell_val + (size_t)P.nsteps * kSellStepDoubles, 0, sizeof(double) * (size_t)kSellPadSteps * kSellStepDoubles)) != hipSuccess ||
-        (e = hipMemcpy(A->d_sell_col, P.col.data(), sizeof(unsigned) * P.col.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(A->d_sell_sptr, P.sptr.data(), sizeof(int) * P.sptr.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(A->d_sell_wrng, P.wrng.data(), sizeof(int) * P.wrng.size(), hipMemcpyHostToDevice)) != hipSuccess) {
+    if ((e = S.val.alloc((size_t)(P.nsteps + kSellPadSteps) * kSellStepDoubles)) != hipSuccess || (e = S.col.alloc(P.col.size())) != hipSuccess ||
+        (e = S.sptr.alloc(P.sptr.size())) != hipSuccess || (e = S.wrng.alloc(P.wrng.size())) != hipSuccess || (e = S.wrng2.upload(P2.wrng)) != hipSuccess ||
+        (e = hipMemset(S.val + (size_t)P.nsteps * kSellStepDoubles, 0, sizeof(double) * (size_t)kSellPadSteps * kSellStepDoubles)) != hipSuccess ||
+        (e = S.col.fill(P.col)) != hipSuccess || (e = S.sptr.fill(P.sptr)) != hipSuccess || (e = S.wrng.fill(P.wrng)) != hipSuccess) {
         (void)hipGetLastError();
-        dfree(A->d_sell_val); dfree(A->d_sell_col); dfree(A->d_sell_sptr); dfree(A->d_sell_wrng); dfree(A->d_sell_wrng2);
-        A->d_sell_val = nullptr;
-        A->d_sell_col = nullptr;
-        A->d_sell_sptr = A->d_sell_wrng = A->d_sell_wrng2 = nullptr;
+        S = {};
         return e == hipErrorOutOfMemory ? MI_OK : fail(MI_ERR_HIP, std::string("bcsr4 sliced copy: ") + hipGetErrorString(e));
     }
+    A->sell = std::move(S);
     A->sell_nslices = P.nslices;
     A->sell_nwaves = P.nwaves;
     A->sell_nwaves2 = P2.nwaves;
@@ -141,21 +135,19 @@ extern "C" int mi_bcsr4_create(int nbrows, int nbcols, const int* ptrow, const i
     int rc = need_device();
     if (rc) return rc;
     // destroyed on every early return below, released to the caller on success
-    std::unique_ptr<mi_bcsr4_s, int (*)(mi_bcsr4_t)> owner(new (std::nothrow) mi_bcsr4_s(), mi_bcsr4_destroy);
+    std::unique_ptr<mi_bcsr4_s> owner(new (std::nothrow) mi_bcsr4_s());
     mi_bcsr4_t A = owner.get();
     if (!A) return fail(MI_ERR_ALLOC, "host allocation failed");
     A->nbrows = nbrows;
     A->nbcols = nbcols;
     A->nblocks = nb;
-    hipError_t e;
-    if ((e = hipGetDevice(&A->device)) != hipSuccess ||
-        (e = hipMalloc(&A->d_ptrow, sizeof(int) * ((size_t)nbrows + 1))) != hipSuccess ||
-        (e = hipMalloc(&A->d_indcol, sizeof(int) * ((size_t)nb + 1))) != hipSuccess ||
-        (e = hipMalloc(&A->d_coef, sizeof(double) * 16 * ((size_t)nb + 1))) != hipSuccess ||
-        (e = hipMemcpy(A->d_ptrow, ptrow, sizeof(int) * ((size_t)nbrows + 1), hipMemcpyHostToDevice)) != hipSuccess ||
-        (nb && (e = hipMemcpy(A->d_indcol, indcol, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (nb && (e = hipMemcpy(A->d_coef, coef, sizeof(double) * 16 * (size_t)nb, hipMemcpyHostToDevice)) != hipSuccess))
-        return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string("bcsr4 upload: ") + hipGetErrorString(e));
+    HIP_TRY(hipGetDevice(&A->device));
+    HIP_TRY(A->d_ptrow.alloc((size_t)nbrows + 1));
+    HIP_TRY(A->d_indcol.alloc((size_t)nb + 1));
+    HIP_TRY(A->d_coef.alloc(16 * ((size_t)nb + 1)));
+    HIP_TRY(A->d_ptrow.fill(ptrow, (size_t)nbrows + 1));
+    HIP_TRY(A->d_indcol.fill(indcol, (size_t)nb));
+    HIP_TRY(A->d_coef.fill(coef, 16 * (size_t)nb));
     for (int s0 = 0; s0 < nbrows; s0 += kSellRows) // values of the longest slice of 16 block rows (bcsr4_refresh_kernel picks its LDS buffer by it)
         A->max_slice_vals = std::max(A->max_slice_vals, 16 * (ptrow[std::min(nbrows, s0 + kSellRows)] - ptrow[s0]));
     if ((rc = build_bcsr4_tile(A, ptrow, indcol))) return rc;
@@ -167,10 +159,10 @@ extern "C" int mi_bcsr4_create(int nbrows, int nbcols, const int* ptrow, const i
     const bool forced = env_is("MI355_BCSR_SELL", "1");
     if (!env_is("MI355_BCSR_SELL", "0") && (forced || nb >= 100000) && nbcols > 0 && nbcols < (1 << 30)) {
         if ((rc = build_bcsr4_sell(A, ptrow, indcol))) return rc;
-        if (A->d_sell_val) choose_bcsr4_sell_form(A, forced);
+        if (A->sell.val) choose_bcsr4_sell_form(A, forced);
     }
     // the handle is complete on return (the sliced values are filled on the null stream, which a non-blocking stream does not wait for)
-    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return fail(MI_ERR_HIP, std::string("mi_bcsr4_create: ") + hipGetErrorString(e));
+    if (hipError_t e = hipStreamSynchronize(nullptr)) return fail(MI_ERR_HIP, std::string("mi_bcsr4_create: ") + hipGetErrorString(e));
     *out = owner.release();
     return MI_OK;
 }
@@ -179,7 +171,7 @@ extern "C" int mi_bcsr4_create(int nbrows, int nbcols, const int* ptrow, const i
 static int sell_fill(mi_bcsr4_t A, hipStream_t s)
 {
     const int grid = std::max(1, std::min(A->sell_nslices, 8192));
-    hipLaunchKernelGGL(bcsr4_to_sell_kernel, dim3((unsigned)grid), dim3(64), 0, s, A->sell_nslices, A->nbrows, A->d_ptrow, A->d_coef, A->d_sell_sptr, A->d_sell_val);
+    hipLaunchKernelGGL(bcsr4_to_sell_kernel, dim3((unsigned)grid), dim3(64), 0, s, A->sell_nslices, A->nbrows, A->d_ptrow, A->d_coef, A->sell.sptr, A->sell.val);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -191,8 +183,8 @@ int bcsr4_refresh_from_csr(mi_bcsr4_s* A, const int* d_csr_ptrow, const double* 
     if (!A || A->nbrows == 0) return MI_OK;
     const int nslices = (A->nbrows + kSellRows - 1) / kSellRows;
     const int grid = std::max(1, std::min(nslices, 2048));
-    const int* sptr = A->d_sell_val ? A->d_sell_sptr : nullptr;
-    double* sv = A->d_sell_val;
+    const int* sptr = A->sell.val ? A->sell.sptr : nullptr;
+    double* sv = A->sell.val;
     if (A->max_slice_vals <= 4096) // 32 KB of LDS: four workgroups per CU (the FE rows of 56-60: 3 584-3 840 values per slice)
         hipLaunchKernelGGL((bcsr4_refresh_kernel<4096>), dim3((unsigned)grid), dim3(256), 0, s, nslices, A->nbrows, d_csr_ptrow, d_src, d_csr_out, A->d_ptrow, A->d_coef, sptr, sv);
     else if (A->max_slice_vals <= 16384)
@@ -209,11 +201,11 @@ static int bcsr4_refresh_from_blocks(mi_bcsr4_s* A, const double* d_src, bool co
     if (!A || A->nbrows == 0 || A->nblocks == 0) return MI_OK;
     const int nslices = (A->nbrows + kSellRows - 1) / kSellRows;
     const int grid = std::max(1, std::min(nslices, 2048));
-    const int* sptr = A->d_sell_val ? A->d_sell_sptr : nullptr;
+    const int* sptr = A->sell.val ? A->sell.sptr : nullptr;
     double* out = d_src == A->d_coef ? nullptr : A->d_coef;
     if (colmajor && !out) return fail(MI_ERR_ARG, "column-major blocks cannot be transposed in place");
-    if (!out && !A->d_sell_val) return MI_OK;
-#define BR_LAUNCH(CAP_, CM_, G_) hipLaunchKernelGGL((bcsr4_blocks_refresh_kernel<CAP_, CM_>), dim3((unsigned)(G_)), dim3(256), 0, s, nslices, A->nbrows, A->d_ptrow, d_src, out, sptr, A->d_sell_val)
+    if (!out && !A->sell.val) return MI_OK;
+#define BR_LAUNCH(CAP_, CM_, G_) hipLaunchKernelGGL((bcsr4_blocks_refresh_kernel<CAP_, CM_>), dim3((unsigned)(G_)), dim3(256), 0, s, nslices, A->nbrows, A->d_ptrow, d_src, out, sptr, A->sell.val)
     if (A->max_slice_vals <= 4096) { if (colmajor) BR_LAUNCH(4096, true, grid); else BR_LAUNCH(4096, false, grid); }
     else if (A->max_slice_vals <= 16384) { if (colmajor) BR_LAUNCH(16384, true, std::min(grid, 256)); else BR_LAUNCH(16384, false, std::min(grid, 256)); }
     else { if (colmajor) BR_LAUNCH(0, true, grid); else BR_LAUNCH(0, false, grid); }
@@ -224,17 +216,17 @@ static int bcsr4_refresh_from_blocks(mi_bcsr4_s* A, const double* d_src, bool co
 
 int bcsr4_values_changed(mi_bcsr4_s* A, hipStream_t s)
 {
-    if (A && A->d_sell_val && A->nblocks > 0) return sell_fill(A, s);
+    if (A && A->sell.val && A->nblocks > 0) return sell_fill(A, s);
     return MI_OK;
 }
 
 extern "C" int mi_bcsr4_sell_info(mi_bcsr4_t A, int* built, int* form_in_use, long long* steps, double* padding, double us[4])
 {
     CHECK_ARG(A, "null handle");
-    if (built) *built = A->d_sell_val != nullptr;
-    if (form_in_use) *form_in_use = A->d_sell_val ? A->sell_form : -1;
+    if (built) *built = A->sell.val != nullptr;
+    if (form_in_use) *form_in_use = A->sell.val ? A->sell_form : -1;
     if (steps) *steps = A->sell_nsteps;
-    if (padding) *padding = A->nblocks > 0 && A->d_sell_val ? (double)A->sell_nsteps * kSellRows / (double)A->nblocks - 1.0 : 0.0;
+    if (padding) *padding = A->nblocks > 0 && A->sell.val ? (double)A->sell_nsteps * kSellRows / (double)A->nblocks - 1.0 : 0.0;
     if (us)
         for (int i = 0; i < 4; i++) us[i] = A->tune_us_sell[i];
     return MI_OK;
@@ -309,8 +301,8 @@ extern "C" int mi_bcsr4_update_values_layout_dev(mi_bcsr4_t A, const double* d_c
 extern "C" int mi_bcsr4_tile_info(mi_bcsr4_t A, int* built, int* in_use, double* us_plain, double* us_tile)
 {
     CHECK_ARG(A, "null handle");
-    if (built) *built = A->d_tl_ptr != nullptr;
-    if (in_use) *in_use = A->use_tile && A->d_tl_ptr;
+    if (built) *built = A->tl.ptr != nullptr;
+    if (in_use) *in_use = A->use_tile && A->tl.ptr;
     if (us_plain) *us_plain = A->tune_us_plain;
     if (us_tile) *us_tile = A->tune_us_tile;
     return MI_OK;
@@ -340,29 +332,6 @@ extern "C" int mi_bcsr4_update_values_dev(mi_bcsr4_t A, const double* d_coef, mi
 extern "C" int mi_bcsr4_destroy(mi_bcsr4_t A)
 {
     if (!A) return MI_OK;
-    dfree(A->d_ptrow);
-    dfree(A->d_indcol);
-    dfree(A->d_coef);
-    dfree(A->d_browmap);
-    dfree(A->d_tl_ptr);
-    dfree(A->d_tl_nodes);
-    dfree(A->d_tl_slots);
-    dfree(A->d_sell_val);
-    dfree(A->d_sell_col);
-    dfree(A->d_sell_sptr);
-    dfree(A->d_sell_wrng);
-    dfree(A->d_sell_wrng2);
-    dfree(A->st.d_ptr);
-    dfree(A->st.d_nodes);
-    dfree(A->st.d_slots);
-    dfree(A->st.d_rows);
-    dfree(A->st64.d_ptr);
-    dfree(A->st64.d_nodes);
-    dfree(A->st64.d_slots);
-    dfree(A->st64.d_rows);
-    dfree(A->d_x);
-    dfree(A->d_y);
-    for (double* p : A->d_pow) dfree(p);
     delete A;
     return MI_OK;
 }
@@ -379,11 +348,11 @@ int launch_bcsr4(mi_bcsr4_t A, const double* d_x, double* d_y, mi_stream_t s, bo
     static const int chunk = getenv("MI355_BCSR_XCD_CHUNK") ? atoi(getenv("MI355_BCSR_XCD_CHUNK")) : 0;
     const int grid = nwg;
     // the sliced form (a relabelled matrix's blocked copy stores through its block-row map)
-    if (A->sell_form >= 0 && A->d_sell_val) {
+    if (A->sell_form >= 0 && A->sell.val) {
         // forms (mi_bcsr4_sell_info): 0 / 1 / 3 one wave per SIMD — one workgroup of four waves per CU, 8 (12) steps of prefetch,
         // non-temporal / temporal / non-temporal; 2 one workgroup of eight waves per CU, 4 steps, non-temporal.  All park y in LDS.
         const bool two = A->sell_form == 2;
-        SellView S{A->d_sell_val, A->d_sell_col, A->d_sell_sptr, two ? A->d_sell_wrng2 : A->d_sell_wrng, A->sell_nslices, A->nbrows, V.browmap};
+        SellView S{A->sell.val, A->sell.col, A->sell.sptr, two ? A->sell.wrng2 : A->sell.wrng, A->sell_nslices, A->nbrows, V.browmap};
         const int swg = two ? A->sell_nwaves2 / 8 : A->sell_nwaves / 4;
         switch (A->sell_form) {
         case 0: hipLaunchKernelGGL((spmv_bcsr4_sell<8, true, 0, 2, 4>), dim3((unsigned)swg), dim3(256), 0, (hipStream_t)s, S, d_x, d_y, swg); break;
@@ -394,8 +363,8 @@ int launch_bcsr4(mi_bcsr4_t A, const double* d_x, double* d_y, mi_stream_t s, bo
         HIP_TRY(hipGetLastError());
         return MI_OK;
     }
-    if (A->use_tile && A->d_tl_ptr) {
-        Bcsr4Tile Tl{A->d_tl_ptr, A->d_tl_nodes, A->d_tl_slots};
+    if (A->use_tile && A->tl.ptr) {
+        Bcsr4Tile Tl{A->tl.ptr, A->tl.nodes, A->tl.slots};
         hipLaunchKernelGGL(spmv_bcsr4_tile<kBcsrDepth>, dim3((unsigned)grid), dim3(kWG), 0, (hipStream_t)s, V, Tl, d_x, d_y, nwg);
         HIP_TRY(hipGetLastError());
         return MI_OK;
@@ -407,16 +376,9 @@ int launch_bcsr4(mi_bcsr4_t A, const double* d_x, double* d_y, mi_stream_t s, bo
 
 void bcsr4_drop_sliced(mi_bcsr4_s* A)
 {
-    if (!A || !A->d_sell_val) return;
+    if (!A || !A->sell.val) return;
     (void)hipDeviceSynchronize();
-    dfree(A->d_sell_val);
-    dfree(A->d_sell_col);
-    dfree(A->d_sell_sptr);
-    dfree(A->d_sell_wrng);
-    dfree(A->d_sell_wrng2);
-    A->d_sell_val = nullptr;
-    A->d_sell_col = nullptr;
-    A->d_sell_sptr = A->d_sell_wrng = A->d_sell_wrng2 = nullptr;
+    A->sell = {};
     A->sell_form = -1;
 }
 
@@ -430,8 +392,8 @@ extern "C" int mi_bcsr4_spmv(mi_bcsr4_t A, const double* x, double* y)
     CHECK_ARG(A, "null handle");
     if (A->nbrows == 0) return MI_OK;
     CHECK_ARG(x && y, "null vector");
-    if (!A->d_x) HIP_TRY(hipMalloc(&A->d_x, sizeof(double) * 4 * (size_t)(A->nbcols > 0 ? A->nbcols : 1)));
-    if (!A->d_y) HIP_TRY(hipMalloc(&A->d_y, sizeof(double) * 4 * (size_t)A->nbrows));
+    if (!A->d_x) HIP_TRY(A->d_x.alloc(4 * (size_t)(A->nbcols > 0 ? A->nbcols : 1)));
+    if (!A->d_y) HIP_TRY(A->d_y.alloc(4 * (size_t)A->nbrows));
     HIP_TRY(hipMemcpy(A->d_x, x, sizeof(double) * 4 * (size_t)A->nbcols, hipMemcpyHostToDevice));
     int rc = mi_bcsr4_spmv_dev(A, A->d_x, A->d_y, nullptr);
     if (rc) return rc;
@@ -463,18 +425,14 @@ extern "C" int mi_bcsr4_spmk(mi_bcsr4_t A, int k, const double* x, double* const
     if (A->nbrows == 0) return MI_OK;
     CHECK_ARG(x && y_out, "null vector");
     const size_t n = 4 * (size_t)A->nbrows;
-    if (!A->d_x) HIP_TRY(hipMalloc(&A->d_x, sizeof(double) * n));
-    while ((int)A->d_pow.size() < k) {
-        double* p = nullptr;
-        HIP_TRY(hipMalloc(&p, sizeof(double) * n));
-        A->d_pow.push_back(p);
-    }
+    if (!A->d_x) HIP_TRY(A->d_x.alloc(n));
+    if (int rc = A->d_pow.grow(k, n)) return rc;
     HIP_TRY(hipMemcpy(A->d_x, x, sizeof(double) * n, hipMemcpyHostToDevice));
-    int rc = mi_bcsr4_spmk_dev(A, k, A->d_x, A->d_pow.data(), nullptr);
+    int rc = mi_bcsr4_spmk_dev(A, k, A->d_x, A->d_pow.ptr.data(), nullptr);
     if (rc) return rc;
     for (int p = 0; p < k; p++) {
         CHECK_ARG(y_out[p], "null output vector");
-        HIP_TRY(hipMemcpy(y_out[p], A->d_pow[p], sizeof(double) * n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(y_out[p], A->d_pow.ptr[p], sizeof(double) * n, hipMemcpyDeviceToHost));
     }
     return MI_OK;
 }
@@ -535,7 +493,7 @@ static void launch_spmm_s(const Bcsr4View& V, int arith, const double* X, long l
 // whose list would exceed `ucap` entries is cut in halves (in growth order) until it fits: the LDS footprint, hence the
 // workgroups per CU, is set by the LONGEST list.  rows[t * per + i] = block row of lane group i of tile t, or -1 - (a valid row of
 // the tile) for unused places (those lanes shadow that row and store nothing).
-static int build_spmm_tile_plan(mi_bcsr4_t A, int per, int ucap, const std::vector<int>& ptrow, const std::vector<int>& indcol, SpmmTilePlan& T)
+static int build_spmm_tile_plan(mi_bcsr4_t A, int per, int ucap, const std::vector<int>& ptrow, const std::vector<int>& indcol, SpmmTilePlan& out)
 {
     const int nbr = A->nbrows;
     std::vector<int> order;           // block rows in cluster growth order
@@ -610,27 +568,18 @@ static int build_spmm_tile_plan(mi_bcsr4_t A, int per, int ucap, const std::vect
     const int ntiles = (int)wg_ptr.size() - 1;
     if (umax < 1 || ntiles < 1) return -1;
     nodes.push_back(0);
-    hipError_t er;
-    if ((er = hipMalloc(&T.d_ptr, sizeof(int) * wg_ptr.size())) != hipSuccess ||
-        (er = hipMalloc(&T.d_nodes, sizeof(unsigned) * nodes.size())) != hipSuccess ||
-        (er = hipMalloc(&T.d_slots, sizeof(unsigned short) * slots.size())) != hipSuccess ||
-        (er = hipMalloc(&T.d_rows, sizeof(int) * rows.size())) != hipSuccess ||
-        (er = hipMemcpy(T.d_ptr, wg_ptr.data(), sizeof(int) * wg_ptr.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (er = hipMemcpy(T.d_nodes, nodes.data(), sizeof(unsigned) * nodes.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (er = hipMemcpy(T.d_slots, slots.data(), sizeof(unsigned short) * slots.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (er = hipMemcpy(T.d_rows, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice)) != hipSuccess) {
+    SpmmTilePlan T;
+    if (T.d_ptr.alloc(wg_ptr.size()) != hipSuccess || T.d_nodes.alloc(nodes.size()) != hipSuccess || T.d_slots.alloc(slots.size()) != hipSuccess ||
+        T.d_rows.alloc(rows.size()) != hipSuccess || T.d_ptr.fill(wg_ptr) != hipSuccess || T.d_nodes.fill(nodes) != hipSuccess ||
+        T.d_slots.fill(slots) != hipSuccess || T.d_rows.fill(rows) != hipSuccess) {
         (void)hipGetLastError();
-        dfree(T.d_ptr);
-        dfree(T.d_nodes);
-        dfree(T.d_slots);
-        dfree(T.d_rows);
-        T = SpmmTilePlan();
         return -1;
     }
     T.rows = per;
     T.umax = umax;
     T.ntiles = ntiles;
     T.mean_list = (double)(nodes.size() - 1) / ntiles;
+    out = std::move(T);
     return 1;
 }
 
@@ -670,7 +619,7 @@ static bool spmm_form_possible(const mi_bcsr4_s* A, int s, int form, bool mapped
 {
     if (form == kSpmmGather) return true;
     // the sliced stream (spmm_bcsr4_sell): four or eight columns, unmapped products of a handle that holds the sliced copy
-    if (form == kSpmmSell) return (s == 4 || s == 8) && A->d_sell_val; // (mapped products store through the block-row map)
+    if (form == kSpmmSell) return (s == 4 || s == 8) && A->sell.val; // (mapped products store through the block-row map)
     if (form == kSpmmTile) return spmm_plan_of(A, s) != nullptr;
     return s % 2 == 0 && A->st64.d_ptr && spmm_tile_lds(&A->st64, s) <= kLdsBytesPerCU;
 }
@@ -703,7 +652,7 @@ static int launch_spmm(mi_bcsr4_t A, int s, int arith, const double* X, long lon
         const bool mapped = V.browmap != nullptr;
         auto run = [&](int form) -> hipError_t {
             if (form == kSpmmSell) {
-                SellView Sv{A->d_sell_val, A->d_sell_col, A->d_sell_sptr, A->d_sell_wrng, A->sell_nslices, A->nbrows, V.browmap};
+                SellView Sv{A->sell.val, A->sell.col, A->sell.sptr, A->sell.wrng, A->sell_nslices, A->nbrows, V.browmap};
                 const int swg = A->sell_nwaves / 4;
                 if (m == 4) {
                     if (arith == MI_ARITH_CHAIN) hipLaunchKernelGGL((spmm_bcsr4_sell<4, 0, 6, true>), dim3((unsigned)swg), dim3(256), 0, st, Sv, Xj, ldx, Yj, ldy, swg);

@@ -8,8 +8,8 @@
 // ---------------------------------------------------------------- CSR create
 int get_table(mi_csr_t A, int nnzb, BlockTable** out)
 {
-    BlockTable& T = A->tables[nnzb];
-    if (!T.d_blk) {
+    auto it = A->tables.find(nnzb);
+    if (it == A->tables.end()) {
         std::vector<int> rows, ptrs;
         // whole waves of rows for the one-thread-per-row chain phase where that keeps 7/8 of the block (ring_plan.hpp) — for
         // matrices that live in the Infinity Cache: S15 1 M rows 61 -> 56 us, but the 5 M-row mesh 180 -> 193 us
@@ -17,39 +17,16 @@ int get_table(mi_csr_t A, int nnzb, BlockTable** out)
         int row_align = A->nnz < 20000000 ? 64 : 1;
         if (const char* e = getenv("MI355_STREAM_ROW_ALIGN")) row_align = std::max(1, atoi(e));
         build_row_blocks(A->n, A->h_ptrow.data(), nnzb, 4 * kWG, rows, ptrs, row_align, 7);
+        BlockTable T;
         T.nnzb = nnzb;
         T.nblk = (int)rows.size() - 1;
         std::vector<int2> h(rows.size());
         for (size_t i = 0; i < rows.size(); i++) h[i] = make_int2(rows[i], ptrs[i]);
-        HIP_TRY(hipMalloc(&T.d_blk, sizeof(int2) * h.size()));
-        HIP_TRY(hipMemcpy(T.d_blk, h.data(), sizeof(int2) * h.size(), hipMemcpyHostToDevice));
+        HIP_TRY(T.d_blk.upload(h));
+        it = A->tables.emplace(nnzb, std::move(T)).first; // (only a table that was filled: a failed upload leaves none behind)
     }
-    *out = &T;
+    *out = &it->second;
     return MI_OK;
-}
-
-static void free_tile(mi_csr_t A)
-{
-    dfree(A->tile.d_desc);
-    dfree(A->tile.d_ulist);
-    dfree(A->tile.d_slots);
-    A->tile = TileTable();
-}
-
-static void free_mring(mi_csr_t A)
-{
-    dfree(A->mring.d_plan);
-    dfree(A->mring.d_first);
-    dfree(A->mring.d_ok);
-    dfree(A->mring.d_rng);
-    dfree(A->mring.d_slots);
-    A->mring = MringTable();
-}
-
-static void free_sstream(mi_csr_t A)
-{
-    ss_free(A->ss.dev);
-    A->ss = SstreamTable();
 }
 
 // the matrix stream (bytes_per_nnz per nonzero) and two vectors no longer fit the 256 MB Infinity Cache with room to spare: stream past it
@@ -74,7 +51,7 @@ static int build_sstream(mi_csr_t A, const int* ptrow, const int* indcol, int gh
     SsMwPlanHost M;
     const int shift = (A->y_offset & 1) && !A->d_rowmap ? 1 : 0;
     build_sstream_plan(A->n, A->ncols, ptrow, indcol, ss_max_padding(), P, true, shift, ghost_lo, ghost_hi);
-    SstreamTable& T = A->ss;
+    SstreamCopy T;
     hipError_t e;
     if (!P.eligible) {
         // rows that name several column neighbourhoods (3-D mesh operators in natural order): the cut-ring form (spmv_sstream_mw.hpp).
@@ -87,7 +64,6 @@ static int build_sstream(mi_csr_t A, const int* ptrow, const int* indcol, int gh
     } else e = ss_upload(P, T.dev, ghost_lo < ghost_hi);
     const SsPlanHost& Q = P.eligible ? P : M; // (the tables both forms share: rounds, steps, slices)
     if (e != hipSuccess) {
-        free_sstream(A);
         if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return MI_OK; } // no room for a second copy of the matrix: the other kernels serve it
         return fail(MI_ERR_HIP, std::string("sliced copy: ") + hipGetErrorString(e));
     }
@@ -106,7 +82,7 @@ static int build_sstream(mi_csr_t A, const int* ptrow, const int* indcol, int gh
     // lazily in front of a product: a product captured into a HIP graph holds only the product's node and must find the values in place
     sstream_fill_values(T.rounds, A->n, T.shift, A->d_ptrow, A->d_coef, nullptr, T.dev.slice_step, T.dev.slice_len, T.dev.val, T.max_slice_nnz, nullptr, T.mw ? 1 : 0);
     if ((e = hipGetLastError()) != hipSuccess) {
-        free_sstream(A);
+        T = {};
         return fail(MI_ERR_HIP, std::string("sliced copy fill: ") + hipGetErrorString(e));
     }
     T.nt = beyond_infinity_cache(10.0, A->nnz, A->n);
@@ -116,6 +92,7 @@ static int build_sstream(mi_csr_t A, const int* ptrow, const int* indcol, int gh
         T.nt = (f & 1) == 0;
         T.deep = f >= 2;
     }
+    A->ss.copy() = std::move(T);
     return MI_OK;
 }
 
@@ -203,21 +180,16 @@ static int build_mring(mi_csr_t A, const int* indcol, int row_align = 0)
     }
     MringPlanHost P;
     build_mring_plan(A->n, A->h_ptrow.data(), indcol, P, row_align);
-    MringTable& M = A->mring;
-    hipError_t e;
-    if ((e = hipMalloc(&M.d_plan, sizeof(int) * P.plan.size())) != hipSuccess ||
-        (e = hipMalloc(&M.d_first, sizeof(int) * P.first.size())) != hipSuccess ||
-        (e = hipMemcpy(M.d_first, P.first.data(), sizeof(int) * P.first.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMalloc(&M.d_ok, sizeof(int) * P.run_ok.size())) != hipSuccess ||
-        (e = hipMalloc(&M.d_rng, sizeof(int) * P.run_rng.size())) != hipSuccess ||
-        (e = hipMalloc(&M.d_slots, sizeof(unsigned short) * P.slots.size())) != hipSuccess ||
-        (e = hipMemcpy(M.d_plan, P.plan.data(), sizeof(int) * P.plan.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(M.d_ok, P.run_ok.data(), sizeof(int) * P.run_ok.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(M.d_rng, P.run_rng.data(), sizeof(int) * P.run_rng.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(M.d_slots, P.slots.data(), sizeof(unsigned short) * P.slots.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-        free_mring(A);
-        return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string("mring plan upload: ") + hipGetErrorString(e));
-    }
+    MringTable M;
+    HIP_TRY(M.d_plan.alloc(P.plan.size()));
+    HIP_TRY(M.d_first.upload(P.first));
+    HIP_TRY(M.d_ok.alloc(P.run_ok.size()));
+    HIP_TRY(M.d_rng.alloc(P.run_rng.size()));
+    HIP_TRY(M.d_slots.alloc(P.slots.size()));
+    HIP_TRY(M.d_plan.fill(P.plan));
+    HIP_TRY(M.d_ok.fill(P.run_ok));
+    HIP_TRY(M.d_rng.fill(P.run_rng));
+    HIP_TRY(M.d_slots.fill(P.slots));
     M.nblk = P.nblk;
     M.wgs = P.wgs;
     M.nruns = P.nruns;
@@ -228,6 +200,7 @@ static int build_mring(mi_csr_t A, const int* indcol, int row_align = 0)
     M.depth = P.bpw >= 40 ? 4 : 2; // as for the single ring (tools/depth_ab.py)
     M.skew = ring_wants_skew(A->n, A->h_ptrow.data());
     M.nt = beyond_infinity_cache(10.0, A->nnz, A->n);
+    A->mring = std::move(M);
     return MI_OK;
 }
 
@@ -245,17 +218,13 @@ static int build_tile(mi_csr_t A, const int* indcol)
     }
     TilePlanHost P;
     build_tile_plan(A->n, A->h_ptrow.data(), indcol, P, kTileNnzb, 0, A->nnz < 20000000 ? 64 : 1);
-    TileTable& T = A->tile;
-    hipError_t e;
-    if ((e = hipMalloc(&T.d_desc, sizeof(int) * P.desc.size())) != hipSuccess ||
-        (e = hipMalloc(&T.d_ulist, sizeof(unsigned) * P.ulist.size())) != hipSuccess ||
-        (e = hipMalloc(&T.d_slots, sizeof(unsigned short) * P.slots.size())) != hipSuccess ||
-        (e = hipMemcpy(T.d_desc, P.desc.data(), sizeof(int) * P.desc.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(T.d_ulist, P.ulist.data(), sizeof(unsigned) * P.ulist.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(T.d_slots, P.slots.data(), sizeof(unsigned short) * P.slots.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-        free_tile(A);
-        return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string("tile plan upload: ") + hipGetErrorString(e));
-    }
+    TileTable T;
+    HIP_TRY(T.d_desc.alloc(P.desc.size()));
+    HIP_TRY(T.d_ulist.alloc(P.ulist.size()));
+    HIP_TRY(T.d_slots.alloc(P.slots.size()));
+    HIP_TRY(T.d_desc.fill(P.desc));
+    HIP_TRY(T.d_ulist.fill(P.ulist));
+    HIP_TRY(T.d_slots.fill(P.slots));
     T.nblk = P.nblk;
     T.unique_per_nnz = (double)(P.ulist.size() - kTileThreads) / (double)A->nnz;
     long long mult8 = 0;
@@ -265,21 +234,12 @@ static int build_tile(mi_csr_t A, const int* indcol)
     }
     T.skew = 10 * mult8 > A->n;
     T.nt = beyond_infinity_cache(10.0, A->nnz, A->n);
+    A->tile = std::move(T);
     return MI_OK;
 }
 
-
-static void free_ring_table(RingTable& R)
-{
-    dfree(R.d_plan);
-    dfree(R.d_ok);
-    dfree(R.d_rng);
-    dfree(R.d_run_halo);
-    dfree(R.d_slots);
-    R = RingTable();
-}
-
-// device copy of a ring plan (plan records, run tables, 16-bit column stream) and what the launch needs to know about it
+// device copy of a ring plan (plan records, run tables, 16-bit column stream) and what the launch needs to know about it, into R — a fresh
+// table of the caller's, moved to its place once this returns MI_OK
 static int fill_ring_table(RingTable& R, const RingPlanHost& best, int n, const int* ptrow, const int* indcol, long long nnz, bool ghosts,
                            const int* row_min = nullptr, const int* row_max = nullptr, bool square = false)
 {
@@ -300,16 +260,8 @@ static int fill_ring_table(RingTable& R, const RingPlanHost& best, int n, const 
     R.ok_fraction = nnz ? 1.0 - (double)best.bad_nnz / (double)nnz : 0.0;
     R.lean = best.lean && best.cfg.id == 4 && !env_is("MI355_RING_LEAN", "0");
     if (best.nblk <= 0) return MI_OK;
-    hipError_t e;
-#define RING_TRY(expr)                                                                                                      \
-    if ((e = (expr)) != hipSuccess) {                                                                                       \
-        free_ring_table(R);                                                                                                 \
-        return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); \
-    }
-    RING_TRY(hipMalloc(&R.d_plan, sizeof(int) * best.plan.size()));
-    RING_TRY(hipMemcpy(R.d_plan, best.plan.data(), sizeof(int) * best.plan.size(), hipMemcpyHostToDevice));
-    RING_TRY(hipMalloc(&R.d_ok, sizeof(int) * best.run_ok.size()));
-    RING_TRY(hipMemcpy(R.d_ok, best.run_ok.data(), sizeof(int) * best.run_ok.size(), hipMemcpyHostToDevice));
+    HIP_TRY(R.d_plan.upload(best.plan));
+    HIP_TRY(R.d_ok.upload(best.run_ok));
     R.all_in_loop = true;
     for (int g = 0; g < best.wgs; g++) R.all_in_loop = R.all_in_loop && best.run_ok[g] == 1;
     R.h_dep_ptr.clear();
@@ -318,20 +270,16 @@ static int fill_ring_table(RingTable& R, const RingPlanHost& best, int n, const 
     for (int g = 0; g < best.wgs; g++)
         R.uniform = R.uniform && best.run_rng[2 * g] == std::min(best.nblk, g * best.bpw) &&
                     best.run_rng[2 * g + 1] == std::min(best.nblk, (g + 1) * best.bpw);
-    RING_TRY(hipMalloc(&R.d_rng, sizeof(int) * best.run_rng.size()));
-    RING_TRY(hipMemcpy(R.d_rng, best.run_rng.data(), sizeof(int) * best.run_rng.size(), hipMemcpyHostToDevice));
+    HIP_TRY(R.d_rng.upload(best.run_rng));
     if (ghosts) {
         R.h_run_halo = best.run_halo;
-        RING_TRY(hipMalloc(&R.d_run_halo, sizeof(int) * best.run_halo.size()));
-        RING_TRY(hipMemcpy(R.d_run_halo, best.run_halo.data(), sizeof(int) * best.run_halo.size(), hipMemcpyHostToDevice));
+        HIP_TRY(R.d_run_halo.upload(best.run_halo));
     }
     {
         std::vector<unsigned short> slots;
         build_ring_slots(best, indcol, slots);
-        RING_TRY(hipMalloc(&R.d_slots, sizeof(unsigned short) * slots.size()));
-        RING_TRY(hipMemcpy(R.d_slots, slots.data(), sizeof(unsigned short) * slots.size(), hipMemcpyHostToDevice));
+        HIP_TRY(R.d_slots.upload(slots));
     }
-#undef RING_TRY
     R.skew = ring_wants_skew(n, ptrow);
     if (const char* e2 = getenv("MI355_RING_SKEW")) R.skew = atoi(e2) != 0;
     return MI_OK;
@@ -352,8 +300,8 @@ static int time_on(LaunchTimer& tm, mi_csr_t A, const double* x, double* y, int 
 // Default since round 4: at most 4 draws of the value array (2 of the column stream), and none after the first when the first copy
 // times within 2 % of the original (a box where placements are alike: nothing to find).  MI355_PLACEMENT_DRAWS=N (0..16) sets the
 // number and disables the early stop — the 12-draw / 7 GB form of round 3 is MI355_PLACEMENT_DRAWS=12; =0 turns the draws off.
-// tx / ty: the x / y pair to time on (null: a fresh pair is allocated; kept as A->kept_x/y when keep_pair and draws were made).
-static int placement_draws(mi_csr_t A, double* tx, double* ty, bool keep_pair)
+// given: the x / y pair to time on (null: a fresh pair is allocated); it moves into A->kept_x/y when keep_pair and draws were made.
+static int placement_draws(mi_csr_t A, ScratchPair* given, bool keep_pair)
 {
     const long long nnz = A->nnz;
     const char* pe = getenv("MI355_PLACEMENT_DRAWS");
@@ -365,59 +313,57 @@ static int placement_draws(mi_csr_t A, double* tx, double* ty, bool keep_pair)
             draws = (int)std::min<size_t>((size_t)draws, mem_free / 8 / (sizeof(double) * (size_t)nnz));
         else (void)hipGetLastError();
     }
-    // (a blocked copy served by its SLICED form streams d_sell_val, never d_coef: drawing d_coef there timed noise and could swap the array on it — ADVICE r4)
-    const bool blocked_choice = A->auto_kernel == MI_KERNEL_BCSR4 && A->blocked && A->blocked->d_coef && !(A->blocked->sell_form >= 0 && A->blocked->d_sell_val);
+    // (a blocked copy served by its SLICED form streams sell.val, never d_coef: drawing d_coef there timed noise and could swap the array on it — ADVICE r4)
+    const bool blocked_choice = A->auto_kernel == MI_KERNEL_BCSR4 && A->blocked && A->blocked->d_coef && !(A->blocked->sell_form >= 0 && A->blocked->sell.val);
     const bool streams_coef = A->auto_kernel == MI_KERNEL_RING || A->auto_kernel == MI_KERNEL_MRING || A->auto_kernel == MI_KERNEL_STREAM || A->auto_kernel == MI_KERNEL_TILE || blocked_choice;
     if (!(draws > 0 && streams_coef && nnz >= kLargeNnz)) return MI_OK;
     LaunchTimer tm;
     ScratchPair own;
-    if (!tx || !ty) {
+    ScratchPair& pair = given ? *given : own;
+    if (!given) {
         const size_t len = std::max(placed_vector_len(A->n, A->ncols), (size_t)(A->n_out > 0 ? A->n_out : 1));
         if (int rc = own.alloc(len, len)) return rc;
-        tx = own.x;
-        ty = own.y;
     }
+    double *const tx = pair.x, *const ty = pair.y;
     if (int rc = tm.init()) return rc;
     auto time_now = [&](double* us) { return time_on(tm, A, tx, ty, 3, 8, us); };
     // pad_bytes: the zeroed tail the array was ALLOCATED with behind its payload — the ring family's unclamped loads read up to
     // kRingPadNnz values past the last nonzero, the blocked kernel one block past the last block; a copy must carry it too
     // (round 3's draws copied the payload into an exactly-sized buffer: every product on a redrawn array then read past its end)
-    auto redraw = [&](void** slot, size_t bytes, size_t pad_bytes, int ndraws) {
+    // (entries, not bytes: slot is the owning member itself, and the copy that loses a draw stays with `losers` until the draws are over)
+    auto redraw = [&](auto& slot, size_t len, size_t pad, int ndraws) {
+        using Arr = std::remove_reference_t<decltype(slot)>;
         double best = 0.0;
-        if (!*slot || bytes == 0 || time_now(&best) != MI_OK) return;
+        if (!slot || len == 0 || time_now(&best) != MI_OK) return;
         const double first = best;
         A->place_us.push_back(best);
-        std::vector<void*> losers;
+        std::vector<Arr> losers;
         for (int d = 0; d < ndraws; d++) {
-            void* fresh = nullptr;
-            if (hipMalloc(&fresh, bytes + pad_bytes) != hipSuccess) { (void)hipGetLastError(); break; } // no room for a copy: keep what there is
-            if ((pad_bytes && hipMemset((char*)fresh + bytes, 0, pad_bytes) != hipSuccess) ||
-                hipMemcpy(fresh, *slot, bytes, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipGetLastError(); dfree(fresh); break; }
-            std::swap(*slot, fresh); // fresh = the previous holder from here
+            Arr fresh;
+            if (fresh.alloc(len + pad) != hipSuccess) { (void)hipGetLastError(); break; } // no room for a copy: keep what there is
+            if ((pad && hipMemset(fresh + len, 0, sizeof(*fresh.get()) * pad) != hipSuccess) ||
+                hipMemcpy(fresh, slot, sizeof(*fresh.get()) * len, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipGetLastError(); break; }
+            std::swap(slot, fresh); // fresh = the previous holder from here
             double t = 0.0;
             const int rct = time_now(&t);
             A->place_us.push_back(rct == MI_OK ? t : -1.0);
             if (rct == MI_OK && t < 0.96 * best) best = t; // the copy is clearly faster (two timings of ONE placement differ by 2-3 %): it holds the data from now on
-            else std::swap(*slot, fresh);
-            losers.push_back(fresh);
+            else std::swap(slot, fresh);
+            losers.push_back(std::move(fresh));
             if (early_stop && d == 0 && rct == MI_OK && std::fabs(t - first) <= 0.02 * first) break; // placements are alike on this box
         }
-        for (void* l : losers) dfree(l);
+        for (Arr& l : losers) l = {};
     };
     // (a matrix that runs the blocked kernel streams the BLOCKED copy's values: 16 doubles per block, zero fill included)
-    if (blocked_choice) redraw((void**)&A->blocked->d_coef, sizeof(double) * 16 * (size_t)A->blocked->nblocks, sizeof(double) * 16, draws); // capi_bcsr.hip: 16 * (nb + 1)
-    else redraw((void**)&A->d_coef, sizeof(double) * (size_t)nnz, sizeof(double) * (size_t)kRingPadNnz, draws);
+    if (blocked_choice) redraw(A->blocked->d_coef, 16 * (size_t)A->blocked->nblocks, 16, draws); // capi_bcsr.hip: 16 * (nb + 1)
+    else redraw(A->d_coef, (size_t)nnz, (size_t)kRingPadNnz, draws);
     A->place_draws_coef = (int)A->place_us.size();
     // (the slot streams are allocated at exactly nblk * nnzb entries: no tail to carry)
-    if (A->auto_kernel == MI_KERNEL_RING) redraw((void**)&A->ring.d_slots, sizeof(unsigned short) * (size_t)A->ring.nblk * A->ring.cfg.nnzb, 0, (draws + 1) / 2);
-    else if (A->auto_kernel == MI_KERNEL_MRING) redraw((void**)&A->mring.d_slots, sizeof(unsigned short) * (size_t)A->mring.nblk * kMringNnzb, 0, (draws + 1) / 2);
+    if (A->auto_kernel == MI_KERNEL_RING) redraw(A->ring.d_slots, (size_t)A->ring.nblk * A->ring.cfg.nnzb, 0, (draws + 1) / 2);
+    else if (A->auto_kernel == MI_KERNEL_MRING) redraw(A->mring.d_slots, (size_t)A->mring.nblk * kMringNnzb, 0, (draws + 1) / 2);
     // The draws chose copies that are fast WITH THIS x / y pair; a caller that asks the library for its vectors gets the pair
     // itself as the first candidate (user-facing square handles only: a partition's pieces and mapped views are not handed vectors)
-    if (keep_pair && !A->kept_x) {
-        A->kept_x = tx;
-        A->kept_y = ty;
-        if (tx == own.x) own.hand_over();
-    }
+    if (keep_pair && !A->kept_x) A->kept_x = std::move(pair.x), A->kept_y = std::move(pair.y);
     return MI_OK;
 }
 
@@ -477,23 +423,21 @@ static int upload(mi_csr_t A, const CsrInput& in)
     const long long nnz = in.nnz;
     const size_t pad = 8, padv = kRingPadNnz, padr = kRingPadRows;
     HIP_TRY(hipGetDevice(&A->device));
-    HIP_TRY(hipMalloc(&A->d_ptrow, sizeof(int) * ((size_t)n + 1 + padr)));
-    HIP_TRY(hipMalloc(&A->d_indcol, sizeof(int) * ((size_t)nnz + pad)));
-    HIP_TRY(hipMalloc(&A->d_coef, sizeof(double) * ((size_t)nnz + padv)));
+    HIP_TRY(A->d_ptrow.alloc((size_t)n + 1 + padr));
+    HIP_TRY(A->d_indcol.alloc((size_t)nnz + pad));
+    HIP_TRY(A->d_coef.alloc((size_t)nnz + padv));
     HIP_TRY(hipMemset(A->d_ptrow + n + 1, 0, sizeof(int) * padr));
     HIP_TRY(hipMemset(A->d_indcol + nnz, 0, sizeof(int) * pad));
     HIP_TRY(hipMemset(A->d_coef + nnz, 0, sizeof(double) * padv));
-    HIP_TRY(hipMemcpy(A->d_ptrow, in.ptrow, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice));
-    if (nnz) {
-        HIP_TRY(hipMemcpy(A->d_indcol, in.indcol, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(A->d_coef, in.coef, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    }
+    HIP_TRY(A->d_ptrow.fill(in.ptrow, (size_t)n + 1));
+    HIP_TRY(A->d_indcol.fill(in.indcol, (size_t)nnz));
+    HIP_TRY(A->d_coef.fill(in.coef, (size_t)nnz));
     A->mapped = in.rowmap != nullptr;
     if (in.offset_only) A->y_offset = in.rowmap[0];
     if (in.rowmap && n > 0 && !in.offset_only) {
-        HIP_TRY(hipMalloc(&A->d_rowmap, sizeof(int) * ((size_t)n + padr)));
+        HIP_TRY(A->d_rowmap.alloc((size_t)n + padr));
         HIP_TRY(hipMemset(A->d_rowmap + n, 0, sizeof(int) * padr));
-        HIP_TRY(hipMemcpy(A->d_rowmap, in.rowmap, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+        HIP_TRY(A->d_rowmap.fill(in.rowmap, (size_t)n));
     }
     return MI_OK;
 }
@@ -522,8 +466,9 @@ static int plan_ring(mi_csr_t A, const CsrInput& in)
         }
         if (forced) break;
     }
-    if (int rc = fill_ring_table(A->ring, best, n, in.ptrow, in.indcol, nnz, in.ghosts(), in.row_min.data(), in.row_max.data(), n == in.ncols))
-        return rc;
+    RingTable R;
+    if (int rc = fill_ring_table(R, best, n, in.ptrow, in.indcol, nnz, in.ghosts(), in.row_min.data(), in.row_max.data(), n == in.ncols)) return rc;
+    A->ring = std::move(R);
     A->auto_kernel = (have && A->ring.ok_fraction >= 0.90) ? MI_KERNEL_RING : MI_KERNEL_STREAM;
     return MI_OK;
 }
@@ -546,12 +491,12 @@ static int plan_optional(mi_csr_t A, const CsrInput& in)
     // enough columns for it to pay (tile_plan.hpp)
     if (plan_wanted("MI355_TILE", "tile", measured && A->auto_kernel != MI_KERNEL_RING, &asked)) {
         if ((rc = build_tile(A, in.indcol))) return rc;
-        if (!asked && A->tile.unique_per_nnz > 0.6) free_tile(A); // little sharing: nothing to gain over the stream kernel
+        if (!asked && A->tile.unique_per_nnz > 0.6) A->tile = {}; // little sharing: nothing to gain over the stream kernel
     }
     // ... and the multi-window ring's (3-D mesh operators: a few narrow column clusters far apart), kept if it serves >= 90 %
     if (plan_wanted("MI355_MRING", "mring", measured && A->auto_kernel != MI_KERNEL_RING, &asked)) {
         if ((rc = build_mring(A, in.indcol, large_row_align(in.nnz)))) return rc;
-        if (!asked && A->mring.ok_fraction < 0.90) free_mring(A);
+        if (!asked && A->mring.ok_fraction < 0.90) A->mring = {};
     }
     // ... and the sliced copy of the sliced-stream kernel (spmv_sstream.hpp): matrices whose rounds of 512 rows fit the LDS window and
     // whose slices pad little.  (Row-mapped handles — partition pieces, the relabelled twin — included since the store goes through the
@@ -577,12 +522,13 @@ static int attach_blocked(mi_csr_t A, const CsrInput& in)
     std::vector<int> bptr, bcol;
     std::vector<double> bval;
     if (!csr_to_bcsr4_exact(n, in.ptrow, in.indcol, in.coef, bptr, bcol, bval)) return MI_OK;
-    if (int rc = mi_bcsr4_create(n / 4, in.ncols / 4, bptr.data(), bcol.data(), bval.data(), &A->blocked)) return rc;
+    mi_bcsr4_t B = nullptr;
+    if (int rc = mi_bcsr4_create(n / 4, in.ncols / 4, bptr.data(), bcol.data(), bval.data(), &B)) return rc;
+    A->blocked.reset(B);
     if (node_map) {
         std::vector<int> bmap((size_t)n / 4);
         for (int b = 0; b < n / 4; b++) bmap[b] = rowmap[4 * b] / 4;
-        HIP_TRY(hipMalloc(&A->blocked->d_browmap, sizeof(int) * bmap.size()));
-        HIP_TRY(hipMemcpy(A->blocked->d_browmap, bmap.data(), sizeof(int) * bmap.size(), hipMemcpyHostToDevice));
+        HIP_TRY(B->d_browmap.upload(bmap));
     }
     return MI_OK;
 }
@@ -720,12 +666,7 @@ static void tune(mi_csr_t A, LaunchTimer& tm, const ScratchPair& sp)
         // A sliced copy that lost the measurement is released (+10 B per nonzero and its padding): mi_csr_set_kernel(MI_KERNEL_SSTREAM)
         // rebuilds it on demand.  Kept: one the environment asked for, and a combined piece's (the fused multi-GPU step takes the
         // sliced stream wherever EVERY rank can: its choice is collective, not this rank's measurement).
-        if (A->auto_kernel != MI_KERNEL_SSTREAM && !A->ss.asked && !(A->ghost_lo < A->ghost_hi)) {
-            double keep_us[4];
-            std::copy(us, us + 4, keep_us);
-            free_sstream(A);
-            std::copy(keep_us, keep_us + 4, A->ss.tune_us); // (what it measured stays readable: mi_csr_sstream_info)
-        }
+        if (A->auto_kernel != MI_KERNEL_SSTREAM && !A->ss.asked && !(A->ghost_lo < A->ghost_hi)) A->ss.copy() = {}; // (what it measured stays readable: mi_csr_sstream_info)
     }
     A->kernel = MI_KERNEL_AUTO;
 }
@@ -743,39 +684,38 @@ static void compare_ring_shapes(mi_csr_t A, const CsrInput& in, LaunchTimer& tm,
     if (A->auto_kernel == MI_KERNEL_RING && A->ring.cfg.id == 4) {
         RingPlanHost alt;
         build_ring_plan(kRingConfigs[3], in.n, in.ptrow, in.row_min.data(), in.row_max.data(), alt, in.ghost_lo, in.ghost_hi, 64);
-        RingTable T2;
+        RingTable aligned;
         if (1.0 - (double)alt.bad_nnz / (double)nnz >= 0.90 &&
-            fill_ring_table(T2, alt, in.n, in.ptrow, in.indcol, nnz, in.ghosts(), in.row_min.data(), in.row_max.data(), in.n == in.ncols) == MI_OK) {
-            T2.nt = A->ring.nt;
+            fill_ring_table(aligned, alt, in.n, in.ptrow, in.indcol, nnz, in.ghosts(), in.row_min.data(), in.row_max.data(), in.n == in.ncols) == MI_OK) {
+            aligned.nt = A->ring.nt;
             A->kernel = MI_KERNEL_RING;
             int rct = time_now(&us1);
-            std::swap(A->ring, T2);
+            RingTable unaligned = std::move(A->ring);
+            A->ring = std::move(aligned);
             if (rct == MI_OK) rct = time_now(&us64);
             A->kernel = MI_KERNEL_AUTO;
             A->tune_us_ring_aligned = us64;
             A->tune_us_ring_unaligned = us1;
-            if (rct != MI_OK || !(us64 < 0.98 * us1)) std::swap(A->ring, T2); // keep the default unless the other is clearly faster
-            free_ring_table(T2);
+            if (rct != MI_OK || !(us64 < 0.98 * us1)) A->ring = std::move(unaligned); // keep the default unless the other is clearly faster
+            else unaligned = {};
         }
     } else if (A->auto_kernel == MI_KERNEL_MRING) { // the same for the multi-window ring
-        MringTable keep = A->mring;
-        A->mring = MringTable();
+        MringTable unaligned = std::move(A->mring);
         if (build_mring(A, in.indcol, 64) == MI_OK && A->mring.d_plan && A->mring.ok_fraction >= 0.90) {
-            A->mring.nt = keep.nt;
+            A->mring.nt = unaligned.nt;
             A->kernel = MI_KERNEL_MRING;
             int rct = time_now(&us64);
-            std::swap(A->mring, keep);
+            MringTable aligned = std::move(A->mring);
+            A->mring = std::move(unaligned);
             if (rct == MI_OK) rct = time_now(&us1);
             A->kernel = MI_KERNEL_AUTO;
             A->tune_us_ring_aligned = us64;
             A->tune_us_ring_unaligned = us1;
-            if (rct == MI_OK && us64 < 0.98 * us1) std::swap(A->mring, keep); // the whole-wave plan is clearly faster here
+            if (rct == MI_OK && us64 < 0.98 * us1) A->mring = std::move(aligned); // the whole-wave plan is clearly faster here
+            else aligned = {};
         } else {
-            std::swap(A->mring, keep);
+            A->mring = std::move(unaligned); // (releases a whole-wave plan that serves too little)
         }
-        std::swap(A->mring, keep); // release the plan not kept
-        free_mring(A);
-        A->mring = keep;
     }
 }
 
@@ -793,9 +733,7 @@ static int measure_at_create(mi_csr_t A, const CsrInput& in, bool defer_placemen
     compare_ring_shapes(A, in, tm, sp);
     // placement draws (placement_draws() above): deferred when the caller (mi_csr_create) may still replace this handle's arrays by a
     // relabelled twin.  The handle keeps the pair when the draws were made (mi_vec_alloc_placed's first candidate).
-    if (!defer_placement && placement_draws(A, sp.x, sp.y, !in.rowmap && in.n == in.ncols && in.n == A->n_out && !in.ghosts()) == MI_OK &&
-        A->kept_x == sp.x)
-        sp.hand_over();
+    if (!defer_placement) (void)placement_draws(A, &sp, !in.rowmap && in.n == in.ncols && in.n == A->n_out && !in.ghosts());
     return MI_OK;
 }
 
@@ -808,7 +746,7 @@ int csr_create_impl(int n, int ncols, const int* ptrow, const int* indcol, const
     int rc = check_input(in);
     if (rc || (rc = need_device())) return rc;
     // destroyed on every early return below, released to the caller on success
-    std::unique_ptr<mi_csr_s, int (*)(mi_csr_t)> owner(new (std::nothrow) mi_csr_s(), mi_csr_destroy);
+    std::unique_ptr<mi_csr_s> owner(new (std::nothrow) mi_csr_s());
     mi_csr_t A = owner.get();
     if (!A) return fail(MI_ERR_ALLOC, "host allocation failed");
     A->n = n;
@@ -842,23 +780,6 @@ static int time_handle(mi_csr_t A, int warm, int timed, double* us)
     return time_on(tm, A, sp.x, sp.y, warm, timed, us);
 }
 
-static void release_natural_arrays(mi_csr_t A)
-{
-    dfree(A->d_ptrow);
-    dfree(A->d_indcol);
-    dfree(A->d_coef);
-    A->d_ptrow = A->d_indcol = nullptr;
-    A->d_coef = nullptr;
-    for (auto& kv : A->tables) dfree(kv.second.d_blk);
-    A->tables.clear();
-    free_ring_table(A->ring);
-    free_tile(A);
-    free_mring(A);
-    free_sstream(A);
-    mi_bcsr4_destroy(A->blocked);
-    A->blocked = nullptr;
-}
-
 // Locality reordering at create time (reorder.hpp).  Tried when the matrix is square, not row-mapped, large enough
 // to matter, NOT already served by the ring kernel, and its nonzeros lie far from the diagonal for its size (an
 // unstructured node numbering); kept when the reordered twin — x gather included — measures faster.
@@ -888,37 +809,32 @@ static int maybe_reorder(mi_csr_t A, const int* ptrow, const int* indcol, const 
     mi_csr_t inner = nullptr;
     int rc = csr_create_impl(n, n, p2.data(), c2.data(), v2.data(), R.iperm.data(), &inner);
     if (rc) return rc;
-    A->inner = inner; // from here on launch_spmv(A) goes through the twin; destroy releases it
-    hipError_t e;
-    if ((e = hipMalloc(&A->d_iperm, sizeof(int) * (size_t)n)) != hipSuccess ||
-        (e = hipMalloc(&A->d_src_start, sizeof(int) * (size_t)n)) != hipSuccess ||
-        (e = hipMalloc(&A->d_xp, sizeof(double) * (size_t)n)) != hipSuccess ||
-        (e = hipMemcpy(A->d_iperm, R.iperm.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(A->d_src_start, src_start.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP, std::string("reorder upload: ") + hipGetErrorString(e));
+    A->inner.reset(inner); // from here on launch_spmv(A) goes through the twin, which goes with A
+    HIP_TRY(A->d_iperm.alloc((size_t)n));
+    HIP_TRY(A->d_src_start.alloc((size_t)n));
+    HIP_TRY(A->d_xp.alloc((size_t)n));
+    HIP_TRY(A->d_iperm.fill(R.iperm));
+    HIP_TRY(A->d_src_start.fill(src_start));
     bool keep = true;
     if (!force && !env_is("MI355_SPMV_AUTOTUNE", "0")) { // measure: natural choice against the twin (gather included)
         const int timed = A->nnz < 40000000 ? 12 : 6;
-        A->inner = nullptr;
+        (void)A->inner.own.release(); // (the natural handle, for a moment)
         rc = time_handle(A, 3, timed, &A->us_natural);
-        A->inner = inner;
+        A->inner.reset(inner);
         if (rc) return rc;
         if ((rc = time_handle(A, 3, timed, &A->us_reordered))) return rc;
         keep = A->us_reordered < 0.97 * A->us_natural;
     }
     if (!keep) {
-        mi_csr_destroy(A->inner);
-        A->inner = nullptr;
-        dfree(A->d_iperm);
-        dfree(A->d_src_start);
-        dfree(A->d_xp);
-        A->d_iperm = A->d_src_start = nullptr;
-        A->d_xp = nullptr;
+        A->inner.reset(), A->d_iperm = {}, A->d_src_start = {}, A->d_xp = {};
         return MI_OK;
     }
     A->h_iperm = R.iperm; // host copy for mi_csr_perm (callers that keep their vectors in the library's numbering)
     A->xp_claimed = false; // (the measurement above ran on the default stream: the gather buffer goes to the caller's first stream)
-    release_natural_arrays(A);
+    // the natural-order arrays and everything planned on them go: the twin serves the handle
+    A->d_ptrow = {}, A->d_indcol = {}, A->d_coef = {};
+    A->drop_tables();
+    A->ring = {}, A->tile = {}, A->mring = {}, A->ss = {}, A->blocked.reset();
     return MI_OK;
 }
 
@@ -927,7 +843,7 @@ extern "C" int mi_csr_create(int n, int ncols, const int* ptrow, const int* indc
     // (placement draws deferred: a handle that maybe_reorder replaces by its relabelled twin would draw for arrays it is about to release)
     int rc = csr_create_impl(n, ncols, ptrow, indcol, coef, nullptr, out, 0, 0, true);
     if (rc) return rc;
-    if ((rc = maybe_reorder(*out, ptrow, indcol, coef)) || (!(*out)->inner && (rc = placement_draws(*out, nullptr, nullptr, n == ncols))) ||
+    if ((rc = maybe_reorder(*out, ptrow, indcol, coef)) || (!(*out)->inner && (rc = placement_draws(*out, nullptr, n == ncols))) ||
         (hipStreamSynchronize(nullptr) != hipSuccess && (rc = fail(MI_ERR_HIP, "mi_csr_create: synchronize")))) {
         mi_csr_destroy(*out);
         *out = nullptr;
@@ -1036,31 +952,6 @@ extern "C" int mi_csr_create_mapped(int n, int ncols, const int* ptrow, const in
 extern "C" int mi_csr_destroy(mi_csr_t A)
 {
     if (!A) return MI_OK;
-    dfree(A->d_ptrow);
-    dfree(A->d_indcol);
-    dfree(A->d_coef);
-    dfree(A->d_rowmap);
-    dfree(A->d_x);
-    dfree(A->d_y);
-    dfree(A->kept_x);
-    dfree(A->kept_y);
-    for (double* p : A->d_pow) dfree(p);
-    for (auto& kv : A->tables) {
-        dfree(kv.second.d_blk);
-    }
-    free_ring_table(A->ring);
-    free_tile(A);
-    free_mring(A);
-    free_sstream(A);
-    mi_bcsr4_destroy(A->blocked);
-    mi_csr_destroy(A->inner);
-    dfree(A->d_iperm);
-    dfree(A->d_src_start);
-    dfree(A->d_xp);
-    for (auto& kv : A->xp_more) dfree(kv.second);
-    dfree(A->d_vtmp);
-    for (double* p : A->d_pp) dfree(p);
-    spmk_release(A);
     delete A;
     return MI_OK;
 }
@@ -1142,7 +1033,7 @@ extern "C" int mi_csr_update_values(mi_csr_t A, const double* coef)
     if (A->nnz == 0) return MI_OK;
     CHECK_ARG(coef, "null coef");
     if (A->inner) {
-        if (!A->d_vtmp) HIP_TRY(hipMalloc(&A->d_vtmp, sizeof(double) * (size_t)A->nnz));
+        if (!A->d_vtmp) HIP_TRY(A->d_vtmp.alloc((size_t)A->nnz));
         HIP_TRY(hipMemcpy(A->d_vtmp, coef, sizeof(double) * (size_t)A->nnz, hipMemcpyHostToDevice));
         int rc = mi_csr_update_values_dev(A, A->d_vtmp, nullptr);
         if (rc) return rc;
@@ -1522,15 +1413,14 @@ extern "C" int mi_vec_alloc_placed(mi_csr_t A, int nvec, int draws, double** d_v
     const int cand = timed ? draws : npairs;
     std::vector<double*> xs((size_t)cand, nullptr), ys((size_t)cand, nullptr);
     auto release = [&]() {
-        for (double* q : xs) dfree(q);
-        for (double* q : ys) dfree(q);
+        for (double* q : xs) if (q) (void)hipFree(q);
+        for (double* q : ys) if (q) (void)hipFree(q);
     };
     for (int c = 0; c < cand; c++) { // pairs one after the other: the levels come in windows of consecutive allocations
         hipError_t e = hipSuccess;
         if (c == 0 && A->kept_x && A->kept_y) { // the pair the create-time placement draws were timed on (ownership leaves the handle)
-            xs[0] = A->kept_x;
-            ys[0] = A->kept_y;
-            A->kept_x = A->kept_y = nullptr;
+            xs[0] = A->kept_x.own.release();
+            ys[0] = A->kept_y.own.release();
         } else {
             e = hipMalloc(&xs[c], bytes);
             if (e == hipSuccess) e = hipMalloc(&ys[c], bytes);
@@ -1728,8 +1618,8 @@ extern "C" const char* mi_csr_kernel_name(mi_csr_t A)
     case MI_KERNEL_BCSR4: {
         const mi_bcsr4_s* B = A->blocked;
         static const char* const sell_names[4] = {"spmv_bcsr4_sell<8, true, 0, 2, 4>", "spmv_bcsr4_sell<8, false, 0, 2, 4>", "spmv_bcsr4_sell<4, true, 0, 2, 8>", "spmv_bcsr4_sell<12, true, 0, 2, 4>"};
-        if (B && B->sell_form >= 0 && B->d_sell_val) return sell_names[B->sell_form & 3];
-        return B && B->use_tile && B->d_tl_ptr ? "spmv_bcsr4_tile<2>" : "spmv_bcsr4<2>";
+        if (B && B->sell_form >= 0 && B->sell.val) return sell_names[B->sell_form & 3];
+        return B && B->use_tile && B->tl.ptr ? "spmv_bcsr4_tile<2>" : "spmv_bcsr4<2>";
     }
     case MI_KERNEL_MRING: {
         static thread_local char nm[96];
@@ -1764,8 +1654,8 @@ extern "C" int mi_spmv(mi_csr_t A, const double* x, double* y)
     CHECK_ARG(A->n == 0 || (x && y), "null vector");
     if (A->mapped) return fail(MI_ERR_UNSUPPORTED, "mapped matrices are device-only (use mi_spmv_dev)");
     if (A->n == 0) return MI_OK;
-    if (!A->d_x) HIP_TRY(hipMalloc(&A->d_x, sizeof(double) * (size_t)(A->ncols > 0 ? A->ncols : 1)));
-    if (!A->d_y) HIP_TRY(hipMalloc(&A->d_y, sizeof(double) * (size_t)A->n));
+    if (!A->d_x) HIP_TRY(A->d_x.alloc((size_t)(A->ncols > 0 ? A->ncols : 1)));
+    if (!A->d_y) HIP_TRY(A->d_y.alloc((size_t)A->n));
     HIP_TRY(hipMemcpy(A->d_x, x, sizeof(double) * (size_t)A->ncols, hipMemcpyHostToDevice));
     int rc = launch_spmv(A, A->d_x, A->d_y, nullptr);
     if (rc) return rc;
@@ -1786,18 +1676,14 @@ extern "C" int mi_spmk_dev(mi_csr_t A, int k, const double* d_x, double* const* 
     if (A->inner) {
         // the whole chain in the new numbering (each power feeds the next without leaving it), then every power scattered to
         // the caller's numbering
-        while ((int)A->d_pp.size() < k) {
-            double* p = nullptr;
-            HIP_TRY(hipMalloc(&p, sizeof(double) * (size_t)A->n));
-            A->d_pp.push_back(p);
-        }
-        double* xp = nullptr;
-        int rc = reorder_scratch(A, (hipStream_t)s, &xp);
+        int rc = A->d_pp.grow(k, (size_t)A->n);
         if (rc) return rc;
+        double* xp = nullptr;
+        if ((rc = reorder_scratch(A, (hipStream_t)s, &xp))) return rc;
         if ((rc = gather_perm(A, d_x, xp, (hipStream_t)s))) return rc;
-        if ((rc = spmk_unmapped(A->inner, k, xp, A->d_pp.data(), (hipStream_t)s))) return rc;
+        if ((rc = spmk_unmapped(A->inner, k, xp, A->d_pp.ptr.data(), (hipStream_t)s))) return rc;
         for (int p = 0; p < k; p++)
-            if ((rc = scatter_perm(A, A->d_pp[p], d_y_out[p], (hipStream_t)s))) return rc;
+            if ((rc = scatter_perm(A, A->d_pp.ptr[p], d_y_out[p], (hipStream_t)s))) return rc;
         return MI_OK;
     }
     return spmk_unmapped(A, k, d_x, d_y_out, (hipStream_t)s);
@@ -1810,18 +1696,14 @@ extern "C" int mi_spmk(mi_csr_t A, int k, const double* x, double* const* y_out)
     CHECK_ARG(A->n == A->ncols, "matrix powers need a square matrix");
     CHECK_ARG(A->n == 0 || (x && y_out), "null vector");
     if (A->n == 0) return MI_OK;
-    if (!A->d_x) HIP_TRY(hipMalloc(&A->d_x, sizeof(double) * (size_t)A->ncols));
-    while ((int)A->d_pow.size() < k) {
-        double* p = nullptr;
-        HIP_TRY(hipMalloc(&p, sizeof(double) * (size_t)A->n));
-        A->d_pow.push_back(p);
-    }
+    if (!A->d_x) HIP_TRY(A->d_x.alloc((size_t)A->ncols));
+    if (int rc = A->d_pow.grow(k, (size_t)A->n)) return rc;
     HIP_TRY(hipMemcpy(A->d_x, x, sizeof(double) * (size_t)A->ncols, hipMemcpyHostToDevice));
-    int rc = mi_spmk_dev(A, k, A->d_x, A->d_pow.data(), nullptr);
+    int rc = mi_spmk_dev(A, k, A->d_x, A->d_pow.ptr.data(), nullptr);
     if (rc) return rc;
     for (int p = 0; p < k; p++) {
         CHECK_ARG(y_out[p], "null output vector");
-        HIP_TRY(hipMemcpy(y_out[p], A->d_pow[p], sizeof(double) * (size_t)A->n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(y_out[p], A->d_pow.ptr[p], sizeof(double) * (size_t)A->n, hipMemcpyDeviceToHost));
     }
     return MI_OK;
 }

@@ -13,56 +13,9 @@
 #include "bilu4_sweep.hpp"
 
 // ---------------------------------------------------------------- ownership
-// A device array that goes with its owner: move-only, freed by its destructor — the ONLY release path of this file.  Assigning a
-// fresh object (x = {}) frees at once, member by member in the order of declaration, which is the order the tables are allocated
-// in.  Local to this file on purpose: where the other handles' allocations and frees land moves launch times (ScratchPair,
-// capi_internal.hpp), and they are not this file's business.
-template <hipError_t (*Free)(void*)>
-struct HipFree {
-    void operator()(void* p) const { (void)Free(p); }
-};
-
-template <class T>
-struct DevArray {
-    std::unique_ptr<T, HipFree<hipFree>> own;
-    operator T*() const { return own.get(); }
-    int alloc(size_t n) // n entries, uninitialised; never a zero-byte allocation
-    {
-        T* p = nullptr;
-        HIP_TRY(hipMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)));
-        own.reset(p);
-        return MI_OK;
-    }
-    int zeros(size_t n) // ... zero-filled, on the NULL stream
-    {
-        int rc = alloc(n);
-        if (rc) return rc;
-        HIP_TRY(hipMemset(own.get(), 0, sizeof(T) * std::max<size_t>(n, 1)));
-        return MI_OK;
-    }
-    int upload(const std::vector<T>& h)
-    {
-        int rc = alloc(h.size());
-        if (rc) return rc;
-        if (!h.empty()) HIP_TRY(hipMemcpy(own.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-        return MI_OK;
-    }
-};
-
-// the give-up word of the one-launch solve: host memory the kernel writes through dev (sticky; the host reads it at every entry point)
-struct MappedWord {
-    std::unique_ptr<unsigned, HipFree<hipHostFree>> host;
-    unsigned* dev = nullptr;
-    int alloc()
-    {
-        unsigned* p = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&p, sizeof(unsigned), hipHostMallocMapped));
-        host.reset(p);
-        *p = 0;
-        HIP_TRY(hipHostGetDevicePointer((void**)&dev, p, 0));
-        return MI_OK;
-    }
-};
+// Every device array of this file is a DevArray, the give-up word a MappedWord (dev_array.hpp, the types all handles of the library
+// own their device memory with): member destructors are the only release path.  This file floors every allocation at ONE entry
+// (an empty level or list still gets an address the kernels may be handed), which the shared type leaves to the caller: hence the 1s.
 
 // the level-major copy of one sweep (bilu4_solve.hpp)
 struct Bilu4DevSweep {
@@ -199,8 +152,8 @@ static int bilu_upload_pattern(const mi_bilu4_s* F, int b, Bilu4DevSweep* D)
         ptr[q + 1] = (int)col.size();
     }
     int rc;
-    if ((rc = D->perm.upload(S.perm)) || (rc = D->ptr.upload(ptr)) || (rc = D->col.upload(col)) || (rc = D->val.alloc(16 * std::max<size_t>(col.size(), 1))) ||
-        (rc = D->lev_ptr.upload(S.lev_ptr)) || (b == 1 && (rc = D->dinv.alloc(16 * (size_t)P.nb))))
+    if ((rc = dev_upload(D->perm, S.perm, 1)) || (rc = dev_upload(D->ptr, ptr, 1)) || (rc = dev_upload(D->col, col, 1)) || (rc = dev_alloc(D->val, 16 * std::max<size_t>(col.size(), 1))) ||
+        (rc = dev_upload(D->lev_ptr, S.lev_ptr, 1)) || (b == 1 && (rc = dev_alloc(D->dinv, 16 * (size_t)P.nb, 1))))
         return rc;
     return MI_OK;
 }
@@ -329,7 +282,7 @@ static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const do
     if (device && nbrows > 0) {
         HIP_TRY(hipGetDevice(&F->device));
         if ((rc = bilu_upload_pattern(F.get(), 0, &F->lev[0])) || (rc = bilu_upload_pattern(F.get(), 1, &F->lev[1])) || (rc = bilu_move_values(F.get(), true)) ||
-            (rc = F->d_b.alloc(4 * (size_t)nbrows)) || (rc = F->d_x.alloc(4 * (size_t)nbrows)))
+            (rc = dev_alloc(F->d_b, 4 * (size_t)nbrows, 1)) || (rc = dev_alloc(F->d_x, 4 * (size_t)nbrows, 1)))
             return rc;
         HIP_TRY(hipMemset(F->d_b, 0, sizeof(double) * 4 * nbrows));
         // the solve's time, through the library's one timing helper (zero right-hand side: the time does not depend on values)
@@ -467,8 +420,8 @@ extern "C" int mi_bilu4dev_prepare(mi_bilu4_t F)
     bilu4dev_plan(F->sched, F->a_ptr.data(), F->a_col.data(), &D);
     Bilu4DevTables T; // moves into the handle once it is complete; a failure on the way frees what there is
     int rc;
-    if ((rc = T.fpos.upload(D.fpos)) || (rc = T.bpos.upload(D.bpos)) || (rc = T.gather.upload(D.gather)) || (rc = T.upd.upload(D.upd)) ||
-        (rc = T.upd_ptr.upload(D.upd_ptr)) || (rc = T.bad.upload(std::vector<int>(1, kBiluBadNone))))
+    if ((rc = dev_upload(T.fpos, D.fpos, 1)) || (rc = dev_upload(T.bpos, D.bpos, 1)) || (rc = dev_upload(T.gather, D.gather, 1)) || (rc = dev_upload(T.upd, D.upd, 1)) ||
+        (rc = dev_upload(T.upd_ptr, D.upd_ptr, 1)) || (rc = dev_upload(T.bad, std::vector<int>(1, kBiluBadNone), 1)))
         return rc;
     T.nL = D.nL, T.nU = D.nU, T.plan_bytes = D.bytes();
     T.prepared = true;
@@ -605,11 +558,11 @@ extern "C" int mi_bilu4one_prepare(mi_bilu4_t F)
         Bilu4OneTables::Sweep& D = T.sweep[b];
         const Bilu4OneSweep& W = O.sweep[b];
         D.nchunks = W.nchunks();
-        if ((rc = D.chunk_pos.upload(W.chunk_pos)) || (rc = D.chunk_lev.upload(W.chunk_lev)) || (rc = D.dep_ptr.upload(W.dep_ptr)) ||
-            (rc = D.dep.upload(W.dep)) || (rc = D.flags.zeros(D.nflags())))
+        if ((rc = dev_upload(D.chunk_pos, W.chunk_pos, 1)) || (rc = dev_upload(D.chunk_lev, W.chunk_lev, 1)) || (rc = dev_upload(D.dep_ptr, W.dep_ptr, 1)) ||
+            (rc = dev_upload(D.dep, W.dep, 1)) || (rc = dev_zeros(D.flags, D.nflags())))
             return rc;
     }
-    if ((rc = T.counter.zeros(kBiluOneFlagStride)) || (rc = T.giveups.alloc())) return rc;
+    if ((rc = dev_zeros(T.counter, kBiluOneFlagStride)) || (rc = dev_alloc(T.giveups))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr)); // (the zeroed flags, before the first solve on the caller's stream reads them)
     T.wgs = (int)G;
     T.plan_bytes = O.bytes();
@@ -758,7 +711,7 @@ extern "C" int mi_bilu4sw_prepare(mi_bilu4_t F)
     if (F->sw.prepared) return MI_OK;
     Bilu4SweepWork W; // moves into the handle once it is complete; a failure on the way frees what there is
     for (DevArray<double>& v : W.w) // (uninitialised: every sweep writes all rows of its output before anything reads them)
-        if (const int rc = v.alloc(4 * (size_t)F->pat().nb)) return rc;
+        if (const int rc = dev_alloc(v, 4 * (size_t)F->pat().nb, 1)) return rc;
     W.prepared = true;
     F->sw = std::move(W);
     return MI_OK;

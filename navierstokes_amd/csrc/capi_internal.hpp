@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_array.hpp"
 #include "partition.hpp"
 #include "push_exchange.hpp"
 #include "ring_plan.hpp"
@@ -33,6 +34,7 @@ using namespace mi355;
 // ---------------------------------------------------------------- errors
 extern thread_local std::string g_err; // capi_lib.hip
 
+// (the partition, the distributed layer and the process-wide tables keep their own memory handling: raw pointers, freed by hand)
 static inline void dfree(void* p)
 {
     if (p) (void)hipFree(p);
@@ -60,6 +62,12 @@ static inline int fail(int code, const std::string& msg)
         if (!(cond)) return fail(MI_ERR_ARG, msg);  \
     } while (0)
 
+
+// the MI_* forms of the owning types' operations (dev_array.hpp), for `(rc = ...) ||` chains; at_least: a floor, in entries, where the site wants one
+template <class T> static inline int dev_alloc(DevArray<T>& a, size_t n, size_t at_least = 0) { HIP_TRY(a.alloc(std::max(n, at_least))); return MI_OK; }
+template <class T> static inline int dev_zeros(DevArray<T>& a, size_t n, size_t at_least = 0) { HIP_TRY(a.zeros(std::max(n, at_least))); return MI_OK; }
+template <class T> static inline int dev_upload(DevArray<T>& a, const std::vector<T>& h, size_t at_least = 0) { HIP_TRY(a.upload(h, at_least)); return MI_OK; }
+static inline int dev_alloc(MappedWord& w) { HIP_TRY(w.alloc()); return MI_OK; }
 
 int need_device(); // capi_lib.hip
 
@@ -109,27 +117,19 @@ struct LaunchTimer {
     }
 };
 
-// the x / y pair a measurement launches on (x zeroed: timing does not depend on the values); freed on scope exit unless handed over.
+// the x / y pair a measurement launches on (x zeroed: timing does not depend on the values); freed on scope exit, x first, unless moved out.
 // Declare it AFTER the LaunchTimer that times on it: the pair is then freed before the events go, the order the library has always
 // released them in — where later allocations land moves launch times by several per cent (profiles/NOTES.md §4.12)
 struct ScratchPair {
-    double *x = nullptr, *y = nullptr;
-    ScratchPair() = default;
-    ScratchPair(const ScratchPair&) = delete;
-    ScratchPair& operator=(const ScratchPair&) = delete;
-    ~ScratchPair()
-    {
-        dfree(x);
-        dfree(y);
-    }
+    DevArray<double> x, y;
+    ~ScratchPair() { x = {}, y = {}; }
     int alloc(size_t nx, size_t ny)
     {
-        HIP_TRY(hipMalloc(&x, sizeof(double) * nx));
-        HIP_TRY(hipMalloc(&y, sizeof(double) * ny));
+        HIP_TRY(x.alloc(nx));
+        HIP_TRY(y.alloc(ny));
         HIP_TRY(hipMemset(x, 0, sizeof(double) * nx));
         return MI_OK;
     }
-    void hand_over() { x = y = nullptr; } // the new owner frees them
 };
 
 // the lower of two measurements; 0 = not measured
@@ -151,28 +151,29 @@ static inline bool stream_is_capturing(hipStream_t s)
 }
 
 // ---------------------------------------------------------------- handles
+// Every device array below is owned by the member that names it (dev_array.hpp); a table's arrays are declared in the order they are freed in.
 struct BlockTable {
     int nnzb = 0;
     int nblk = 0;
-    int2* d_blk = nullptr;  // [nblk+1]
+    DevArray<int2> d_blk;  // [nblk+1]
 };
 
 struct RingTable {
     RingConfig cfg{};
     int nblk = 0, wgs = 0, bpw = 0, bad_runs = 0;
     double ok_fraction = 0.0; // share of the nonzeros in ring-served runs
-    int* d_plan = nullptr; // 8 ints per block, read as two int4
-    int* d_ok = nullptr;
-    int* d_rng = nullptr;      // {first block, end block} per run
-    int* d_run_halo = nullptr; // per run: touches a ghost column (fused multi-GPU step)
+    DevArray<int> d_plan; // 8 ints per block, read as two int4
+    DevArray<int> d_ok;
+    DevArray<int> d_rng;      // {first block, end block} per run
+    DevArray<int> d_run_halo; // per run: touches a ghost column (fused multi-GPU step)
     std::vector<int> h_run_halo;
     bool uniform = true;       // runs are consecutive ranges of bpw blocks (the kernel then computes them)
     bool lean = false;         // the plan allows the LEAN instantiation (spmv_ring.hpp)
     bool all_in_loop = false;  // every run is ring-served and holds no PLAIN block: every row is computed inside the counted loop
     std::vector<int> h_dep_ptr, h_dep_run; // one-launch powers step: per run the runs its columns name (ring_plan.hpp: build_run_deps); empty if not built
-    unsigned short* d_slots = nullptr; // 16-bit column stream (ring slots), nnzb per block
-    bool nt = false;                   // non-temporal loads of the values (chosen by measurement)
-    bool skew = false;                 // padded staging layout (many rows with a length that is a multiple of 8)
+    DevArray<unsigned short> d_slots; // 16-bit column stream (ring slots), nnzb per block
+    bool nt = false;                  // non-temporal loads of the values (chosen by measurement)
+    bool skew = false;                // padded staging layout (many rows with a length that is a multiple of 8)
 };
 
 // plan of the multi-window ring kernel (mring_plan.hpp); valid iff d_plan != nullptr
@@ -180,27 +181,27 @@ struct MringTable {
     int nblk = 0, wgs = 0, nruns = 0, bpw = 0, bad_runs = 0, depth = 2;
     double ok_fraction = 0.0;
     long long restarts = 0;
-    int* d_plan = nullptr;             // kMringRec ints per block, read as int4
-    int* d_first = nullptr;            // kMringFirst ints per run: the first block's windows
-    int* d_ok = nullptr;
-    int* d_rng = nullptr;
-    unsigned short* d_slots = nullptr;
+    DevArray<int> d_plan;              // kMringRec ints per block, read as int4
+    DevArray<int> d_first;             // kMringFirst ints per run: the first block's windows
+    DevArray<int> d_ok;
+    DevArray<int> d_rng;
+    DevArray<unsigned short> d_slots;
     bool nt = false, skew = false;
 };
 
 // plan of the tile kernel (tile_plan.hpp); valid iff d_desc != nullptr
 struct TileTable {
     int nblk = 0;
-    int* d_desc = nullptr;             // 4 ints per block, read as int4
-    unsigned* d_ulist = nullptr;       // distinct columns per block
-    unsigned short* d_slots = nullptr; // 16-bit column stream: position in the block's list
+    DevArray<int> d_desc;              // 4 ints per block, read as int4
+    DevArray<unsigned> d_ulist;        // distinct columns per block
+    DevArray<unsigned short> d_slots;  // 16-bit column stream: position in the block's list
     double unique_per_nnz = 0.0;       // distinct columns per nonzero, averaged over the matrix
     bool nt = false;                   // non-temporal loads of the values
     bool skew = false;                 // padded staging layout (see RingTable::skew)
 };
 
 // the sliced copy of the sliced-stream kernel (spmv_sstream.hpp); valid iff dev.val != nullptr
-struct SstreamTable {
+struct SstreamCopy {
     bool mw = false; // the cut-ring form (spmv_sstream_mw.hpp): several column neighbourhoods per row (3-D mesh operators)
     SsDevice dev;                 // values, slot stream, workgroup records, windows, slice tables (value refills), ghost marks
     int nwg = 0, rounds = 0;
@@ -214,97 +215,86 @@ struct SstreamTable {
     bool asked = false;           // built because the environment or the caller asked for it: never released for losing a measurement
     std::vector<int> h_wg_halo;   // a combined piece of the fused multi-GPU step: per workgroup, it reads ghost columns (empty otherwise)
     std::vector<SsWg> h_wg;       // ... and its workgroup records (capi_part.hip writes the push links into them at connect time)
+};
+// ... and what its four forms measured at create, which outlives a copy released for losing (copy() = {} leaves it; mi_csr_sstream_info)
+struct SstreamTable : SstreamCopy {
     double tune_us[4] = {0, 0, 0, 0}; // D = 8 nt, D = 8 temporal, D = 12 nt, D = 12 temporal
+    SstreamCopy& copy() { return *this; }
 };
 
-struct mi_csr_s {
-    int device = 0;
-    int n = 0, ncols = 0;
-    long long nnz = 0;
-    int* d_ptrow = nullptr;
-    int* d_indcol = nullptr;
-    double* d_coef = nullptr;
-    int* d_rowmap = nullptr;
-    bool mapped = false;  // created with a rowmap (device-only entry points, no powers)
-    int y_offset = 0;     // a rowmap that is just "row r -> y[r + offset]" is applied as a pointer offset, not as a gather
-    int ghost_lo = 0, ghost_hi = 0; // ghost_lo < ghost_hi: a partition's combined piece, columns outside [ghost_lo, ghost_hi) are ghosts
-    std::vector<int> h_ptrow; // kept to (re)build row-block tables
-    std::map<int, BlockTable> tables;
-    RingTable ring;           // valid iff ring.d_plan != nullptr
-    TileTable tile;           // valid iff tile.d_desc != nullptr
-    SstreamTable ss;          // valid iff ss.dev.val != nullptr
-    MringTable mring;         // valid iff mring.d_plan != nullptr
-    int kernel = MI_KERNEL_AUTO;
-    int auto_kernel = MI_KERNEL_STREAM;
-    std::vector<double> place_us; // placement draws at create (capi_csr.hip): microseconds per launch, value array first ([0] = as first allocated) ...
-    int place_draws_coef = 0;     // ... place_us[0 .. place_draws_coef) belong to the value array, the rest to the 16-bit column stream
-    double *kept_x = nullptr, *kept_y = nullptr; // the scratch pair the placement draws were timed on, kept for mi_vec_alloc_placed (its first candidate)
-    double tune_us[MI_KERNEL_SSTREAM + 1][2] = {}; // create-time measurement per kernel id, [temporal, non-temporal] loads (the blocked copy: [BCSR4][0]); 0 = not measured
-    double tune_us_ring_aligned = 0.0, tune_us_ring_unaligned = 0.0; // large matrices: the two block shapes (0 = not compared)
-    bool stream_nt = false; // non-temporal matrix loads in the stream kernel
-    mi_bcsr4_t blocked = nullptr; // BCSR 4x4 copy (exact 4x4 node-block structure only), else null
-    int n_out = 0; // length of the y a launch may write (n, or max rowmap + 1)
-    // Locality reordering (reorder.hpp): when `inner` is set, this handle is a front for A' = P A P^T, a row-mapped
-    // handle in the new numbering; products gather x into d_xp (new numbering) and inner writes y through its row
-    // map straight into the caller's numbering.  The natural-order device arrays are released then.
-    mi_csr_t inner = nullptr;
-    int* d_iperm = nullptr;     // [n] caller's index of new row / column
-    std::vector<int> h_iperm;   // the same on the host (mi_csr_perm)
-    int* d_src_start = nullptr; // [n] offset of new row r' in the caller's coef (values refresh)
-    double* d_xp = nullptr;     // x in the new numbering: the buffer of the FIRST stream that multiplies with this handle ...
-    hipStream_t xp_stream = nullptr;
-    bool xp_claimed = false;
-    std::map<hipStream_t, double*> xp_more; // ... products enqueued on other streams get a gather buffer of their own (reorder_scratch)
-    std::vector<double*> d_pp;  // powers in the new numbering (mi_spmk_dev: one k-step at a time per handle)
-    double* d_vtmp = nullptr;   // staging for mi_csr_update_values (host values)
-    double spread_before = 0.0, spread_after = 0.0, us_natural = 0.0, us_reordered = 0.0;
-    int reorder_block = 0;      // 0: no reordering attempted
-    // scratch for the host-pointer entry points
-    double* d_x = nullptr;
-    double* d_y = nullptr;
-    std::vector<double*> d_pow;
-    // the one-launch matrix-powers step (spmk_ring.hpp, launch_spmk.hip): run flags, dependency lists, the launch counter the
-    // flags count from, give-ups (host-visible, sticky), and per k the measured choice between one launch and k launches
-    unsigned* d_kflags = nullptr;
-    int* d_kdep_ptr = nullptr;
-    int* d_kdep_run = nullptr;
-    unsigned kstep_epoch = 0;
-    unsigned* h_ktimeouts = nullptr;
-    unsigned* d_ktimeouts = nullptr;
-    int kstep_setup = 0;                 // 0 not tried, 1 ready, -1 not eligible
-    int kstep_choice[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // per k <= 8: 0 not measured, 1 one launch, -1 k launches
-    double kstep_us[9][2] = {};          // measured microseconds per step: [k][0] k launches, [k][1] one launch
+// a handle that goes with another (the blocked copy, the relabelled twin): deleted with its owner, read like the plain pointer it replaces
+template <class H>
+struct OwnedHandle {
+    std::unique_ptr<H> own;
+    operator H*() const { return own.get(); }
+    H* operator->() const { return own.get(); }
+    void reset(H* p = nullptr) { own.reset(p); }
+};
+
+// vectors a handle allocates one by one as higher powers are asked for (the host-pointer and the relabelled k-step); freed first to last
+struct DevPowers {
+    std::vector<DevArray<double>> own;
+    std::vector<double*> ptr; // the same, as the kernels' argument
+    int grow(int k, size_t n) // at least k vectors of n doubles
+    {
+        while ((int)own.size() < k) {
+            DevArray<double> a;
+            HIP_TRY(a.alloc(n));
+            ptr.push_back(a);
+            own.push_back(std::move(a));
+        }
+        return MI_OK;
+    }
+    void release()
+    {
+        for (auto& a : own) a = {};
+        own.clear(), ptr.clear();
+    }
+};
+
+// the one-launch matrix-powers step's tables (launch_spmk.hip): run flags, dependency lists, give-ups (host-visible, sticky)
+struct SpmkTables {
+    DevArray<unsigned> flags;
+    DevArray<int> dep_ptr, dep_run;
+    MappedWord giveups;
 };
 
 struct SpmmTilePlan {
     int rows = 0, umax = 0, ntiles = 0; // block rows per tile (at most); longest list; tiles
     double mean_list = 0.0;
-    int* d_ptr = nullptr;
-    unsigned* d_nodes = nullptr;
-    unsigned short* d_slots = nullptr;
-    int* d_rows = nullptr;              // [ntiles * rows]: block row per lane group, -1 - r for unused places
+    DevArray<int> d_ptr;
+    DevArray<unsigned> d_nodes;
+    DevArray<unsigned short> d_slots;
+    DevArray<int> d_rows;               // [ntiles * rows]: block row per lane group, -1 - r for unused places
+};
+
+// x tile per workgroup (spmv_bcsr4_tile): lists of distinct block columns and 16-bit positions; built iff ptr != nullptr
+struct Bcsr4TileLists {
+    DevArray<int> ptr;
+    DevArray<unsigned> nodes;
+    DevArray<unsigned short> slots;
+};
+
+// the sliced copy (spmv_bcsr_sell.hpp): 16 block rows per slice, one contiguous stream per persistent wave; built iff val != nullptr
+struct Bcsr4Sliced {
+    DevArray<double> val;
+    DevArray<unsigned> col;
+    DevArray<int> sptr;
+    DevArray<int> wrng;  // slice ranges of the waves: [sell_nwaves + 1] for ONE wave per SIMD (1024 waves) ...
+    DevArray<int> wrng2; // ... and [sell_nwaves2 + 1] for two (2048)
 };
 
 struct mi_bcsr4_s {
     int device = 0;
     int nbrows = 0, nbcols = 0;
     long long nblocks = 0;
-    int* d_ptrow = nullptr;
-    int* d_indcol = nullptr;
-    double* d_coef = nullptr;
-    int* d_browmap = nullptr; // block-row map of a reordered matrix's blocked copy, else null
-    // x tile per workgroup (spmv_bcsr4_tile): lists of distinct block columns and 16-bit positions; null if not built
-    int* d_tl_ptr = nullptr;
-    unsigned* d_tl_nodes = nullptr;
-    unsigned short* d_tl_slots = nullptr;
+    DevArray<int> d_ptrow, d_indcol;
+    DevArray<double> d_coef;
+    DevArray<int> d_browmap;  // block-row map of a reordered matrix's blocked copy, else null
+    Bcsr4TileLists tl;
     bool use_tile = false;    // the measured choice between the two kernels (MI355_BCSR_TILE=0|1 forces)
     double tune_us_plain = 0.0, tune_us_tile = 0.0;
-    // the sliced copy (spmv_bcsr_sell.hpp): 16 block rows per slice, one contiguous stream per persistent wave; null if not built
-    double* d_sell_val = nullptr;
-    unsigned* d_sell_col = nullptr;
-    int* d_sell_sptr = nullptr;
-    int* d_sell_wrng = nullptr;  // slice ranges of the waves: [sell_nwaves + 1] for ONE wave per SIMD (1024 waves) ...
-    int* d_sell_wrng2 = nullptr; // ... and [sell_nwaves2 + 1] for two (2048)
+    Bcsr4Sliced sell;
     int sell_nslices = 0, sell_nwaves = 0, sell_nwaves2 = 0;
     long long sell_nsteps = 0;
     int max_slice_vals = 0;   // values of the longest slice of 16 block rows (the refresh kernel's LDS buffer)
@@ -318,9 +308,78 @@ struct mi_bcsr4_s {
     double spmm_us[9][5] = {};                         // [s][form] microseconds per launch: 0 gather kernels, 1 tile (four lanes per block row),
                                                        // 2 / 3 tile with eight lanes per block row, temporal / non-temporal coefficient loads,
                                                        // 4 the sliced stream (spmm_bcsr4_sell)
-    double* d_x = nullptr;
-    double* d_y = nullptr;
-    std::vector<double*> d_pow;
+    DevArray<double> d_x, d_y;
+    DevPowers d_pow;
+    // the order the handle has always been freed in
+    ~mi_bcsr4_s() { d_ptrow = {}, d_indcol = {}, d_coef = {}, d_browmap = {}, tl = {}, sell = {}, st = {}, st64 = {}, d_x = {}, d_y = {}, d_pow.release(); }
+};
+
+
+struct mi_csr_s {
+    int device = 0;
+    int n = 0, ncols = 0;
+    long long nnz = 0;
+    DevArray<int> d_ptrow, d_indcol;
+    DevArray<double> d_coef;
+    DevArray<int> d_rowmap;
+    bool mapped = false;  // created with a rowmap (device-only entry points, no powers)
+    int y_offset = 0;     // a rowmap that is just "row r -> y[r + offset]" is applied as a pointer offset, not as a gather
+    int ghost_lo = 0, ghost_hi = 0; // ghost_lo < ghost_hi: a partition's combined piece, columns outside [ghost_lo, ghost_hi) are ghosts
+    std::vector<int> h_ptrow; // kept to (re)build row-block tables
+    std::map<int, BlockTable> tables;
+    RingTable ring;           // valid iff ring.d_plan != nullptr
+    TileTable tile;           // valid iff tile.d_desc != nullptr
+    SstreamTable ss;          // valid iff ss.dev.val != nullptr
+    MringTable mring;         // valid iff mring.d_plan != nullptr
+    int kernel = MI_KERNEL_AUTO;
+    int auto_kernel = MI_KERNEL_STREAM;
+    std::vector<double> place_us; // placement draws at create (capi_csr.hip): microseconds per launch, value array first ([0] = as first allocated) ...
+    int place_draws_coef = 0;     // ... place_us[0 .. place_draws_coef) belong to the value array, the rest to the 16-bit column stream
+    DevArray<double> kept_x, kept_y; // the scratch pair the placement draws were timed on, kept for mi_vec_alloc_placed (its first candidate)
+    double tune_us[MI_KERNEL_SSTREAM + 1][2] = {}; // create-time measurement per kernel id, [temporal, non-temporal] loads (the blocked copy: [BCSR4][0]); 0 = not measured
+    double tune_us_ring_aligned = 0.0, tune_us_ring_unaligned = 0.0; // large matrices: the two block shapes (0 = not compared)
+    bool stream_nt = false; // non-temporal matrix loads in the stream kernel
+    OwnedHandle<mi_bcsr4_s> blocked; // BCSR 4x4 copy (exact 4x4 node-block structure only), else null
+    int n_out = 0; // length of the y a launch may write (n, or max rowmap + 1)
+    // Locality reordering (reorder.hpp): when `inner` is set, this handle is a front for A' = P A P^T, a row-mapped
+    // handle in the new numbering; products gather x into d_xp (new numbering) and inner writes y through its row
+    // map straight into the caller's numbering.  The natural-order device arrays are released then.
+    OwnedHandle<mi_csr_s> inner;
+    DevArray<int> d_iperm;      // [n] caller's index of new row / column
+    std::vector<int> h_iperm;   // the same on the host (mi_csr_perm)
+    DevArray<int> d_src_start;  // [n] offset of new row r' in the caller's coef (values refresh)
+    DevArray<double> d_xp;      // x in the new numbering: the buffer of the FIRST stream that multiplies with this handle ...
+    hipStream_t xp_stream = nullptr;
+    bool xp_claimed = false;
+    std::map<hipStream_t, DevArray<double>> xp_more; // ... products enqueued on other streams get a gather buffer of their own (reorder_scratch)
+    DevPowers d_pp;             // powers in the new numbering (mi_spmk_dev: one k-step at a time per handle)
+    DevArray<double> d_vtmp;    // staging for mi_csr_update_values (host values)
+    double spread_before = 0.0, spread_after = 0.0, us_natural = 0.0, us_reordered = 0.0;
+    int reorder_block = 0;      // 0: no reordering attempted
+    // scratch for the host-pointer entry points
+    DevArray<double> d_x, d_y;
+    DevPowers d_pow;
+    // the one-launch matrix-powers step (spmk_ring.hpp, launch_spmk.hip): run flags, dependency lists, the launch counter the
+    // flags count from, give-ups (host-visible, sticky), and per k the measured choice between one launch and k launches
+    SpmkTables kstep;
+    unsigned kstep_epoch = 0;
+    int kstep_setup = 0;                 // 0 not tried, 1 ready, -1 not eligible
+    int kstep_choice[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // per k <= 8: 0 not measured, 1 one launch, -1 k launches
+    double kstep_us[9][2] = {};          // measured microseconds per step: [k][0] k launches, [k][1] one launch
+    void drop_tables() // the row-block tables, lowest nnzb first
+    {
+        for (auto& kv : tables) kv.second = {};
+        tables.clear();
+    }
+    // the order the handle has always been freed in, written here and nowhere else
+    ~mi_csr_s()
+    {
+        d_ptrow = {}, d_indcol = {}, d_coef = {}, d_rowmap = {}, d_x = {}, d_y = {}, kept_x = {}, kept_y = {}, d_pow.release();
+        drop_tables();
+        ring = {}, tile = {}, mring = {}, ss = {}, blocked.reset(), inner.reset(), d_iperm = {}, d_src_start = {}, d_xp = {};
+        for (auto& kv : xp_more) kv.second = {};
+        d_vtmp = {}, d_pp.release(), kstep = {};
+    }
 };
 
 struct mi_part_s {
@@ -430,7 +489,6 @@ void launch_ring_cfg(const mi_csr_s* A, const CsrView& V, const double* d_x, dou
 // launch_spmk.hip: the k powers on an unmapped view of H (its row map, if any, is not applied): one launch where that is
 // eligible and measured faster, else k chained launches
 int spmk_unmapped(mi_csr_t H, int k, const double* d_x, double* const* d_y, hipStream_t s);
-void spmk_release(mi_csr_t H);
 // capi_blas1.hip
 int gather_perm(mi_csr_t A, const double* d_x, double* d_xp, hipStream_t s);
 int ortho_update_from_parts(int n, int nparts, const double* parts, double alpha, const double* d_b, const double* d_x1, double* d_x3, double* d_beta_out,

@@ -103,8 +103,8 @@ extern "C" int mi_debug_mring_trace(mi_csr_t A, const double* d_x, double* d_y, 
     HIP_TRY(hipMalloc(&d, sizeof(long long) * 4 * (size_t)M.wgs));
     HIP_TRY(hipMemset(d, 0, sizeof(long long) * 4 * (size_t)M.wgs));
     hipLaunchKernelGGL((spmv_csr_mring<kMringThreads, kMringNnzb, 4, kMringMaxB, false, true, false, true>), dim3(M.wgs), dim3(kMringThreads), 0, nullptr,
-                       V, reinterpret_cast<const int4*>(M.d_plan), reinterpret_cast<const int4*>(M.d_first), M.d_ok, M.d_slots, d_x, d_y,
-                       reinterpret_cast<const int2*>(M.d_rng), M.wgs, d);
+                       V, reinterpret_cast<const int4*>(M.d_plan.get()), reinterpret_cast<const int4*>(M.d_first.get()), M.d_ok, M.d_slots, d_x, d_y,
+                       reinterpret_cast<const int2*>(M.d_rng.get()), M.wgs, d);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(host_out, d, sizeof(long long) * 4 * (size_t)M.wgs, hipMemcpyDeviceToHost));
     dfree(d);
@@ -127,25 +127,27 @@ extern "C" int mi_debug_move_array(mi_csr_t A, int which, int how, unsigned long
     // the pad (below), the flag has not been tried again.
     CHECK_ARG(A && which >= 0 && which <= 3 && (how == 0 || how == 2 || how == 3), "bad argument (how = 1, hipDeviceMallocContiguous, is refused: see the comment in devtools.hip)");
     if (A->inner) A = A->inner;
-    void** slot = nullptr;
-    size_t bytes = 0, pad_bytes = 0;
-    if (which == 0) { slot = (void**)&A->d_coef; bytes = sizeof(double) * (size_t)A->nnz; pad_bytes = sizeof(double) * (size_t)kRingPadNnz; }
-    if (which == 1) { slot = (void**)&A->ring.d_slots; bytes = sizeof(unsigned short) * (size_t)A->ring.nblk * A->ring.cfg.nnzb; }
-    if (which == 2) { slot = (void**)&A->d_ptrow; bytes = sizeof(int) * ((size_t)A->n + 1); pad_bytes = sizeof(int) * (size_t)kRingPadRows; }
-    if (which == 3) { slot = (void**)&A->ring.d_plan; bytes = sizeof(int) * 8 * (size_t)A->ring.nblk; }
-    if (!*slot || bytes == 0) return fail(MI_ERR_STATE, "the handle has no such array");
-    void* fresh = nullptr;
-    if (how == 0) HIP_TRY(hipMalloc(&fresh, bytes + pad_bytes));
-    else HIP_TRY(hipExtMallocWithFlags(&fresh, bytes + pad_bytes, how == 2 ? hipDeviceMallocUncached : hipDeviceMallocFinegrained));
-    if (pad_bytes) HIP_TRY(hipMemset((char*)fresh + bytes, 0, pad_bytes)); // the zeroed tail the original allocation has (capi_csr.hip)
-    HIP_TRY(hipMemcpy(fresh, *slot, bytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-    if (old_ptr) *old_ptr = (unsigned long long)(uintptr_t)*slot;
-    if (new_ptr) *new_ptr = (unsigned long long)(uintptr_t)fresh;
-    void* old = *slot;
-    *slot = fresh;
-    HIP_TRY(hipFree(old));
-    return MI_OK;
+    // the array moves into a fresh allocation of `len` entries and a zeroed tail of `pad` (the tail the original has: capi_csr.hip)
+    auto move = [&](auto& arr, size_t len, size_t pad) -> int {
+        const size_t esz = sizeof(*arr.get()), bytes = esz * len, pad_bytes = esz * pad;
+        if (!arr || bytes == 0) return fail(MI_ERR_STATE, "the handle has no such array");
+        std::remove_reference_t<decltype(arr)> fresh;
+        void* p = nullptr;
+        if (how == 0) HIP_TRY(hipMalloc(&p, bytes + pad_bytes));
+        else HIP_TRY(hipExtMallocWithFlags(&p, bytes + pad_bytes, how == 2 ? hipDeviceMallocUncached : hipDeviceMallocFinegrained));
+        fresh.own.reset((decltype(arr.get()))p);
+        if (pad_bytes) HIP_TRY(hipMemset((char*)p + bytes, 0, pad_bytes));
+        HIP_TRY(hipMemcpy(fresh, arr, bytes, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipDeviceSynchronize());
+        if (old_ptr) *old_ptr = (unsigned long long)(uintptr_t)arr.get();
+        if (new_ptr) *new_ptr = (unsigned long long)(uintptr_t)fresh.get();
+        arr = std::move(fresh); // (frees the old one)
+        return MI_OK;
+    };
+    if (which == 0) return move(A->d_coef, (size_t)A->nnz, (size_t)kRingPadNnz);
+    if (which == 1) return move(A->ring.d_slots, (size_t)A->ring.nblk * A->ring.cfg.nnzb, 0);
+    if (which == 2) return move(A->d_ptrow, (size_t)A->n + 1, (size_t)kRingPadRows);
+    return move(A->ring.d_plan, 8 * (size_t)A->ring.nblk, 0);
 }
 
 // run-length experiments on ONE placement (tools/mring_skew_ab.py): rebuild the handle's multi-window ring plan with the given skew and
@@ -167,14 +169,13 @@ extern "C" int mi_debug_mring_replan(mi_csr_t A, int skew_pct, int* table_len, i
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(M.d_plan, P.plan.data(), sizeof(int) * P.plan.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(M.d_slots, P.slots.data(), sizeof(unsigned short) * P.slots.size(), hipMemcpyHostToDevice));
-    dfree(M.d_first); dfree(M.d_ok); dfree(M.d_rng);
-    M.d_first = M.d_ok = M.d_rng = nullptr;
-    HIP_TRY(hipMalloc(&M.d_first, sizeof(int) * P.first.size()));
-    HIP_TRY(hipMalloc(&M.d_ok, sizeof(int) * P.run_ok.size()));
-    HIP_TRY(hipMalloc(&M.d_rng, sizeof(int) * P.run_rng.size()));
-    HIP_TRY(hipMemcpy(M.d_first, P.first.data(), sizeof(int) * P.first.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(M.d_ok, P.run_ok.data(), sizeof(int) * P.run_ok.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(M.d_rng, P.run_rng.data(), sizeof(int) * P.run_rng.size(), hipMemcpyHostToDevice));
+    M.d_first = {}, M.d_ok = {}, M.d_rng = {};
+    HIP_TRY(M.d_first.alloc(P.first.size()));
+    HIP_TRY(M.d_ok.alloc(P.run_ok.size()));
+    HIP_TRY(M.d_rng.alloc(P.run_rng.size()));
+    HIP_TRY(M.d_first.fill(P.first));
+    HIP_TRY(M.d_ok.fill(P.run_ok));
+    HIP_TRY(M.d_rng.fill(P.run_rng));
     M.wgs = P.wgs;
     M.nruns = P.nruns;
     M.bpw = P.bpw;

@@ -15,10 +15,10 @@ int reorder_scratch(mi_csr_t A, hipStream_t s, double** buf)
         *buf = A->d_xp;
         return MI_OK;
     }
-    double*& b = A->xp_more[s];
+    DevArray<double>& b = A->xp_more[s];
     if (!b) {
         if (stream_is_capturing(s)) return fail(MI_ERR_STATE, "first product of a relabelled handle on this stream: run one outside stream capture first (it allocates a gather buffer)");
-        HIP_TRY(hipMalloc(&b, sizeof(double) * (size_t)A->n));
+        HIP_TRY(b.alloc((size_t)A->n));
     }
     *buf = b;
     return MI_OK;
@@ -90,9 +90,9 @@ int launch_spmv(mi_csr_t A, const double* d_x, double* d_y, hipStream_t s, bool 
     if (kid == MI_KERNEL_MRING) {
         const MringTable& M = A->mring;
         V.nblk = M.nblk;
-        const int4* plan = reinterpret_cast<const int4*>(M.d_plan);
-        const int2* rng = reinterpret_cast<const int2*>(M.d_rng);
-#define MRING_L(D_, MP_, NT_, SK_) hipLaunchKernelGGL((spmv_csr_mring<kMringThreads, kMringNnzb, D_, kMringMaxB, MP_, NT_, SK_>), dim3(M.wgs), dim3(kMringThreads), 0, s, V, plan, reinterpret_cast<const int4*>(M.d_first), M.d_ok, M.d_slots, d_x, d_y, rng, M.wgs)
+        const int4* plan = reinterpret_cast<const int4*>(M.d_plan.get());
+        const int2* rng = reinterpret_cast<const int2*>(M.d_rng.get());
+#define MRING_L(D_, MP_, NT_, SK_) hipLaunchKernelGGL((spmv_csr_mring<kMringThreads, kMringNnzb, D_, kMringMaxB, MP_, NT_, SK_>), dim3(M.wgs), dim3(kMringThreads), 0, s, V, plan, reinterpret_cast<const int4*>(M.d_first.get()), M.d_ok, M.d_slots, d_x, d_y, rng, M.wgs)
 #define MRING_L3(D_, MP_) do { if (M.nt) { if (M.skew) MRING_L(D_, MP_, true, true); else MRING_L(D_, MP_, true, false); } \
                                else { if (M.skew) MRING_L(D_, MP_, false, true); else MRING_L(D_, MP_, false, false); } } while (0)
 #define MRING_L2(D_) do { if (V.rowmap) MRING_L3(D_, true); else MRING_L3(D_, false); } while (0)
@@ -106,7 +106,7 @@ int launch_spmv(mi_csr_t A, const double* d_x, double* d_y, hipStream_t s, bool 
     } else if (kid == MI_KERNEL_TILE) {
         const TileTable& T = A->tile;
         const int grid = kNXCD * ((T.nblk + kNXCD - 1) / kNXCD);
-        const int4* desc = reinterpret_cast<const int4*>(T.d_desc);
+        const int4* desc = reinterpret_cast<const int4*>(T.d_desc.get());
 #define TILE_LAUNCH(NT_, SK_) hipLaunchKernelGGL((spmv_csr_tile<kTileNnzb, NT_, SK_>), dim3(grid), dim3(kTileThreads), 0, s, V, desc, T.nblk, T.d_ulist, T.d_slots, d_x, d_y)
         if (T.nt) { if (T.skew) TILE_LAUNCH(true, true); else TILE_LAUNCH(true, false); }
         else { if (T.skew) TILE_LAUNCH(false, true); else TILE_LAUNCH(false, false); }

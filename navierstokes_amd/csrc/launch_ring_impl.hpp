@@ -10,17 +10,17 @@ static void launch_ring3(const mi_csr_s* A, const CsrView& V, const double* d_x,
     if constexpr (LEAN && !MAPPED) {
         if (dot && !comm) { // the dot epilogue (spmv_ring.hpp: RingDot); the caller checked ring_dot_eligible()
             hipLaunchKernelGGL((spmv_csr_ring<T, NNZB, RING, D, kRingMaxB, false, NT, SKEW, false, true, true>), dim3(A->ring.wgs), dim3(T), 0, s, V,
-                               reinterpret_cast<const int4*>(A->ring.d_plan), A->ring.d_ok, A->ring.d_slots, d_x, d_y, reinterpret_cast<const int2*>(A->ring.d_rng), A->ring.uniform ? A->ring.bpw : 0, RingComm{}, *dot);
+                               reinterpret_cast<const int4*>(A->ring.d_plan.get()), A->ring.d_ok, A->ring.d_slots, d_x, d_y, reinterpret_cast<const int2*>(A->ring.d_rng.get()), A->ring.uniform ? A->ring.bpw : 0, RingComm{}, *dot);
             return;
         }
     }
     if (!MAPPED && comm) { // the fused multi-GPU step: push workgroups in front of the grid (spmv_ring.hpp)
         hipLaunchKernelGGL((spmv_csr_ring<T, NNZB, RING, D, kRingMaxB, MAPPED, NT, SKEW, true, LEAN>), dim3(A->ring.wgs + comm->push_wgs), dim3(T), 0, s,
-                           V, reinterpret_cast<const int4*>(A->ring.d_plan), A->ring.d_ok, A->ring.d_slots, d_x, d_y, reinterpret_cast<const int2*>(A->ring.d_rng), A->ring.uniform ? A->ring.bpw : 0, *comm);
+                           V, reinterpret_cast<const int4*>(A->ring.d_plan.get()), A->ring.d_ok, A->ring.d_slots, d_x, d_y, reinterpret_cast<const int2*>(A->ring.d_rng.get()), A->ring.uniform ? A->ring.bpw : 0, *comm);
         return;
     }
     hipLaunchKernelGGL((spmv_csr_ring<T, NNZB, RING, D, kRingMaxB, MAPPED, NT, SKEW, false, LEAN>), dim3(A->ring.wgs), dim3(T), 0, s, V,
-                       reinterpret_cast<const int4*>(A->ring.d_plan), A->ring.d_ok, A->ring.d_slots, d_x, d_y, reinterpret_cast<const int2*>(A->ring.d_rng), A->ring.uniform ? A->ring.bpw : 0, RingComm{});
+                       reinterpret_cast<const int4*>(A->ring.d_plan.get()), A->ring.d_ok, A->ring.d_slots, d_x, d_y, reinterpret_cast<const int2*>(A->ring.d_rng.get()), A->ring.uniform ? A->ring.bpw : 0, RingComm{});
 }
 
 template <int T, int NNZB, int RING, int D, bool MAPPED, bool NT, bool SKEW>

@@ -8,8 +8,8 @@ static hipError_t launch_fused_t(const mi_csr_s* H, const CsrView& V, const Spmk
 {
     auto kern = spmk_csr_ring<256, 2048, 5120, D, kRingMaxB, NT, SKEW>;
     if (query) return hipOccupancyMaxActiveBlocksPerMultiprocessor(max_blocks, kern, 256, 0);
-    hipLaunchKernelGGL(kern, dim3(H->ring.wgs), dim3(256), 0, s, V, reinterpret_cast<const int4*>(H->ring.d_plan), H->ring.d_slots,
-                       reinterpret_cast<const int2*>(H->ring.d_rng), H->ring.uniform ? H->ring.bpw : 0, K);
+    hipLaunchKernelGGL(kern, dim3(H->ring.wgs), dim3(256), 0, s, V, reinterpret_cast<const int4*>(H->ring.d_plan.get()), H->ring.d_slots,
+                       reinterpret_cast<const int2*>(H->ring.d_rng.get()), H->ring.uniform ? H->ring.bpw : 0, K);
     return hipGetLastError();
 }
 
@@ -24,17 +24,8 @@ static hipError_t launch_fused(const mi_csr_s* H, const CsrView& V, const SpmkAr
     return sk ? launch_fused_t<2, false, true>(H, V, K, s, query, max_blocks) : launch_fused_t<2, false, false>(H, V, K, s, query, max_blocks);
 }
 
-void spmk_release(mi_csr_t H)
-{
-    dfree(H->d_kflags);
-    dfree(H->d_kdep_ptr);
-    dfree(H->d_kdep_run);
-    if (H->h_ktimeouts) (void)hipHostFree(H->h_ktimeouts);
-    H->d_kflags = nullptr;
-    H->d_kdep_ptr = H->d_kdep_run = nullptr;
-    H->h_ktimeouts = H->d_ktimeouts = nullptr;
-    H->kstep_setup = 0;
-}
+// a wait of a one-launch step gave up since the word was last cleared
+static bool spmk_gave_up(const mi_csr_s* H) { return H->kstep.giveups.host && __atomic_load_n(H->kstep.giveups.host.get(), __ATOMIC_ACQUIRE) != 0; }
 
 static CsrView unmapped_view(const mi_csr_s* H)
 {
@@ -75,26 +66,15 @@ static int spmk_setup(mi_csr_t H)
         return -1;
     }
     if ((long long)per_cu * cus < R.wgs) return -1;
-    hipError_t e;
-    const size_t nflag = (size_t)R.wgs * kSpmkFlagStride;
-    if ((e = hipMalloc(&H->d_kflags, sizeof(unsigned) * nflag)) != hipSuccess || (e = hipMemset(H->d_kflags, 0, sizeof(unsigned) * nflag)) != hipSuccess ||
-        (e = hipStreamSynchronize(nullptr)) != hipSuccess || // (the zeroed flags, before the first step on the caller's stream reads them)
-        (e = hipMalloc(&H->d_kdep_ptr, sizeof(int) * R.h_dep_ptr.size())) != hipSuccess ||
-        (e = hipMalloc(&H->d_kdep_run, sizeof(int) * std::max<size_t>(1, R.h_dep_run.size()))) != hipSuccess ||
-        (e = hipMemcpy(H->d_kdep_ptr, R.h_dep_ptr.data(), sizeof(int) * R.h_dep_ptr.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (R.h_dep_run.size() && (e = hipMemcpy(H->d_kdep_run, R.h_dep_run.data(), sizeof(int) * R.h_dep_run.size(), hipMemcpyHostToDevice)) != hipSuccess) ||
-        (e = hipHostMalloc((void**)&H->h_ktimeouts, sizeof(unsigned), hipHostMallocMapped)) != hipSuccess) {
+    SpmkTables T;
+    if (T.flags.zeros((size_t)R.wgs * kSpmkFlagStride) != hipSuccess ||
+        hipStreamSynchronize(nullptr) != hipSuccess || // (the zeroed flags, before the first step on the caller's stream reads them)
+        T.dep_ptr.alloc(R.h_dep_ptr.size()) != hipSuccess || T.dep_run.alloc(std::max<size_t>(1, R.h_dep_run.size())) != hipSuccess ||
+        T.dep_ptr.fill(R.h_dep_ptr) != hipSuccess || T.dep_run.fill(R.h_dep_run) != hipSuccess || T.giveups.alloc() != hipSuccess) {
         (void)hipGetLastError();
-        spmk_release(H);
-        H->kstep_setup = -1;
         return -1;
     }
-    *H->h_ktimeouts = 0;
-    if (hipHostGetDevicePointer((void**)&H->d_ktimeouts, H->h_ktimeouts, 0) != hipSuccess) {
-        spmk_release(H);
-        H->kstep_setup = -1;
-        return -1;
-    }
+    H->kstep = std::move(T);
     H->kstep_epoch = 0;
     H->kstep_setup = 1;
     return 1;
@@ -120,10 +100,10 @@ static int spmk_fused(mi_csr_t H, int k, const double* d_x, double* const* d_y, 
     K.k = k;
     K.epoch = H->kstep_epoch;
     H->kstep_epoch += (unsigned)k; // the next launch's flags start above everything this one publishes
-    K.flags = H->d_kflags;
-    K.dep_ptr = H->d_kdep_ptr;
-    K.dep_run = H->d_kdep_run;
-    K.timeouts = H->d_ktimeouts;
+    K.flags = H->kstep.flags;
+    K.dep_ptr = H->kstep.dep_ptr;
+    K.dep_run = H->kstep.dep_run;
+    K.timeouts = H->kstep.giveups.dev;
     static const unsigned spin_max = 1u << (getenv("MI355_SPMK_SPIN_LOG2") ? std::max(8, std::min(30, atoi(getenv("MI355_SPMK_SPIN_LOG2")))) : 21);
     K.spin_max = spin_max;
     K.acquire = env_is("MI355_SPMK_ACQUIRE", "1") ? 1 : 0;
@@ -135,7 +115,7 @@ static int spmk_fused(mi_csr_t H, int k, const double* d_x, double* const* d_y, 
 int spmk_unmapped(mi_csr_t H, int k, const double* d_x, double* const* d_y, hipStream_t s)
 {
     // a wait of an earlier one-launch step gave up (CUs held by somebody else's kernel): everything since is invalid
-    if (H->h_ktimeouts && __atomic_load_n(H->h_ktimeouts, __ATOMIC_ACQUIRE) != 0)
+    if (spmk_gave_up(H))
         return fail(MI_ERR_HIP, "mi_spmk: a hand-off wait of the one-launch powers step gave up (workgroups of the grid were not all resident); "
                                 "results since then are invalid — set MI355_SPMK_FUSED=0 when other kernels share the GPU");
     // (under stream capture: k launches — the one-launch step's flag epoch is a kernel argument, a replayed graph would reuse it)
@@ -158,13 +138,13 @@ int spmk_unmapped(mi_csr_t H, int k, const double* d_x, double* const* d_y, hipS
                 if (!rc) us[form] = min_measured(us[form], t);
                 // a wait of the one-launch form gave up (the grid is not all resident: somebody else's kernel holds CUs): every further
                 // launch of it would spin its whole budget again — the measurement ends here and the handle takes k launches
-                if (form == 1 && H->h_ktimeouts && __atomic_load_n(H->h_ktimeouts, __ATOMIC_ACQUIRE) != 0) round = 2;
+                if (form == 1 && spmk_gave_up(H)) round = 2;
             }
         if (rc) return rc;
         H->kstep_us[k][0] = us[0];
         H->kstep_us[k][1] = us[1];
-        const bool gave_up = H->h_ktimeouts && __atomic_load_n(H->h_ktimeouts, __ATOMIC_ACQUIRE) != 0;
-        if (gave_up) *H->h_ktimeouts = 0; // (measured on scratch launches: the real product below is chained and valid)
+        const bool gave_up = spmk_gave_up(H);
+        if (gave_up) *H->kstep.giveups.host = 0; // (measured on scratch launches: the real product below is chained and valid)
         H->kstep_choice[k] = (!gave_up && us[1] > 0 && us[1] < 0.98 * us[0]) ? 1 : -1;
     }
     return H->kstep_choice[k] == 1 ? spmk_fused(H, k, d_x, d_y, s) : spmk_chain(H, k, d_x, d_y, s);

@@ -41,6 +41,7 @@
 #include <thread>
 #include <vector>
 
+#include "dev_array.hpp"
 #include "spmv_ring.hpp" // RingComm, ring_ldx, ring_push_link, ring_push_gate: the protocol pieces of the fused multi-GPU step
 
 namespace mi355 {
@@ -420,42 +421,31 @@ inline void sstream_fill_values(int rounds, int n, int shift, const int* d_ptrow
         hipLaunchKernelGGL((sstream_fill_kernel<0>), dim3((unsigned)std::min(nslices, 2048)), dim3(256), 0, s, nslices, n, shift, d_ptrow, d_src, d_csr_out, d_slice_step, d_slice_len, d_val, pair64);
 }
 
-// device copy of a plan (library and tools/ alike): allocate + upload; on failure everything is released and the error returned
+// device copy of a plan (library and tools/ alike), owned (dev_array.hpp): Dv = {} releases it, winK first
 struct SsDevice {
-    ss_v2d* val = nullptr;
-    unsigned* slot = nullptr;
-    SsWg* wg = nullptr;
-    int2* win = nullptr;
-    int* slice_step = nullptr;
-    int* slice_len = nullptr;
-    int* wg_halo = nullptr; // plans with ghost columns only
-    int2* winK = nullptr;   // the cut-ring form only (spmv_sstream_mw.hpp): [4 * rounds] intakes per sub-ring
+    DevArray<int2> winK;   // the cut-ring form only (spmv_sstream_mw.hpp): [4 * rounds] intakes per sub-ring
+    DevArray<ss_v2d> val;
+    DevArray<unsigned> slot;
+    DevArray<SsWg> wg;
+    DevArray<int2> win;
+    DevArray<int> slice_step, slice_len;
+    DevArray<int> wg_halo; // plans with ghost columns only
 };
-inline void ss_free(SsDevice& Dv)
-{
-    (void)hipFree(Dv.winK);
-    (void)hipFree(Dv.val); (void)hipFree(Dv.slot); (void)hipFree(Dv.wg); (void)hipFree(Dv.win); (void)hipFree(Dv.slice_step); (void)hipFree(Dv.slice_len); (void)hipFree(Dv.wg_halo);
-    Dv = SsDevice();
-}
+// allocate + upload into Dv (the caller's local: on failure the error is returned — hipErrorOutOfMemory as itself, a sliced copy that
+// does not fit is the caller's to judge — and Dv holds nothing)
 inline hipError_t ss_upload(const SsPlanHost& P, SsDevice& Dv, bool ghosts)
 {
     hipError_t e;
-    const size_t vbytes = sizeof(ss_v2d) * (size_t)(P.steps + kSsPadSteps) * 64;
-    if ((e = hipMalloc(&Dv.val, vbytes)) != hipSuccess || (e = hipMalloc(&Dv.slot, sizeof(unsigned) * P.slot.size())) != hipSuccess ||
-        (e = hipMalloc(&Dv.wg, sizeof(SsWg) * P.wg.size())) != hipSuccess || (e = hipMalloc(&Dv.win, sizeof(int2) * P.win.size())) != hipSuccess ||
-        (e = hipMalloc(&Dv.slice_step, sizeof(int) * P.slice_step.size())) != hipSuccess || (e = hipMalloc(&Dv.slice_len, sizeof(int) * P.slice_len.size())) != hipSuccess ||
-        (ghosts && (e = hipMalloc(&Dv.wg_halo, sizeof(int) * P.wg_halo.size())) != hipSuccess) ||
-        (e = hipMemset((char*)Dv.val + sizeof(ss_v2d) * (size_t)P.steps * 64, 0, sizeof(ss_v2d) * (size_t)kSsPadSteps * 64)) != hipSuccess ||
-        (e = hipMemcpy(Dv.slot, P.slot.data(), sizeof(unsigned) * P.slot.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(Dv.wg, P.wg.data(), sizeof(SsWg) * P.wg.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(Dv.win, P.win.data(), sizeof(int2) * P.win.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(Dv.slice_step, P.slice_step.data(), sizeof(int) * P.slice_step.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(Dv.slice_len, P.slice_len.data(), sizeof(int) * P.slice_len.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (ghosts && (e = hipMemcpy(Dv.wg_halo, P.wg_halo.data(), sizeof(int) * P.wg_halo.size(), hipMemcpyHostToDevice)) != hipSuccess)) {
-        ss_free(Dv);
-        return e;
-    }
-    return hipSuccess;
+    const size_t vsteps = (size_t)(P.steps + kSsPadSteps) * 64;
+    if ((e = Dv.val.alloc(vsteps)) != hipSuccess || (e = Dv.slot.alloc(P.slot.size())) != hipSuccess || (e = Dv.wg.alloc(P.wg.size())) != hipSuccess ||
+        (e = Dv.win.alloc(P.win.size())) != hipSuccess || (e = Dv.slice_step.alloc(P.slice_step.size())) != hipSuccess ||
+        (e = Dv.slice_len.alloc(P.slice_len.size())) != hipSuccess || (ghosts && (e = Dv.wg_halo.alloc(P.wg_halo.size())) != hipSuccess) ||
+        (e = hipMemset(Dv.val + (size_t)P.steps * 64, 0, sizeof(ss_v2d) * (size_t)kSsPadSteps * 64)) != hipSuccess ||
+        (e = Dv.slot.fill(P.slot)) != hipSuccess || (e = Dv.wg.fill(P.wg)) != hipSuccess || (e = Dv.win.fill(P.win)) != hipSuccess ||
+        (e = Dv.slice_step.fill(P.slice_step)) != hipSuccess || (e = Dv.slice_len.fill(P.slice_len)) != hipSuccess ||
+        (ghosts && (e = Dv.wg_halo.fill(P.wg_halo)) != hipSuccess))
+        Dv = {};
+    return e;
 }
 
 // D steps of the stream in flight per lane; ONE workgroup of four waves per CU.  Workgroup b is taken as logical workgroup

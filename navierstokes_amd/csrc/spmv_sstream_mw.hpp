@@ -314,13 +314,8 @@ inline const char* check_sstream_mw_plan(const SsMwPlanHost& P, int n, const int
 inline hipError_t ss_mw_upload(const SsMwPlanHost& P, SsDevice& Dv)
 {
     hipError_t e = ss_upload(P, Dv, false);
-    if (e != hipSuccess) return e;
-    if ((e = hipMalloc(&Dv.winK, sizeof(int2) * P.winK.size())) != hipSuccess ||
-        (e = hipMemcpy(Dv.winK, P.winK.data(), sizeof(int2) * P.winK.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-        ss_free(Dv);
-        return e;
-    }
-    return hipSuccess;
+    if (e == hipSuccess && (e = Dv.winK.upload(P.winK)) != hipSuccess) Dv = {};
+    return e;
 }
 
 // the four intakes of a round, wave-uniform
