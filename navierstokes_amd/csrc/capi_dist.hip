@@ -37,16 +37,25 @@ enum { kExEvent = 0, kExPush = 1, kExRccl = 2 };
 constexpr long long kDistAllGatherHalo = 16384; // ghosts of the widest rank from which the RCCL step all-gathers boundary slices
 const char* const kExNames[3] = {"event", "push", "rccl"};
 
-struct DistRank {
+struct PartDestroy { // (mi_part_destroy waits for the handle's queued steps before it deletes)
+    void operator()(mi_part_s* P) const { (void)mi_part_destroy(P); }
+};
+
+// what a rank owns beside its partition, declared in the order it is freed in; built and dropped on the rank's worker thread
+struct RankResources {
+    DevArray<double> d_sendbuf;  // event exchange: packed entries of non-contiguous send lists
+    DevArray<double> d_scal;     // BLAS-1: this rank's partial [0], the global value as its update kernel summed it [1]
+    DevArray<double> d_parts;    // RCCL exchange: every rank's partial, all-gathered (nranks doubles)
+    PinnedArray<double> h_scal;  // where d_scal lands on the host: [0] partial, [1] global
+    OwnedEvent ev_dot[2];        // my partial of an orthogonalize has landed in the shared table (two parities)
+    OwnedEvent ev_push, ev_done;
+    OwnedStream stream;
+};
+
+struct DistRank : RankResources {
     int device = 0;
-    mi_part_t part = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_push = nullptr, ev_done = nullptr;
-    double* d_sendbuf = nullptr; // event exchange: packed entries of non-contiguous send lists
-    double* d_scal = nullptr;    // BLAS-1: this rank's partial [0], the global value as its update kernel summed it [1]
-    double* h_scal = nullptr;    // ... and where they land on the host (pinned): [0] partial, [1] global
-    double* d_parts = nullptr;   // RCCL exchange: every rank's partial, all-gathered (nranks doubles)
-    hipEvent_t ev_dot[2] = {nullptr, nullptr}; // my partial of an orthogonalize has landed in the shared table (two parities)
+    OwnedHandle<mi_part_s, PartDestroy> part;
+    RankResources& resources() { return *this; }
     int n_local = 0, n_halo = 0;
     long long row0 = 0, nnz0 = 0, nnz_local = 0;
     std::vector<int> nb;         // neighbours: ranks I send to or receive from
@@ -159,7 +168,7 @@ struct Pool {
 
 struct mi_dist_vec_s {
     mi_dist_s* D = nullptr;
-    std::vector<double*> ext; // per rank: [owned | halo] on the rank's device
+    std::vector<DevArray<double>> ext; // per rank: [owned | halo] on the rank's device
 };
 
 struct mi_dist_s {
@@ -174,7 +183,7 @@ struct mi_dist_s {
     std::string note;         // how the exchange was chosen (what was tried, why it was dropped)
     Pool pool;
     std::mutex api_mu;        // one API call at a time per handle
-    double* h_parts = nullptr;  // orthogonalize without RCCL: the ranks' partials, 2 parities x nranks doubles of pinned memory every device reads
+    PinnedArray<double> h_parts; // orthogonalize without RCCL: the ranks' partials, 2 parities x nranks doubles of pinned memory every device reads
     unsigned ortho_calls = 0;
     std::vector<mi_dist_vec_t> live; // every vector handed out and not yet destroyed (mi_dist_destroy releases their device memory)
     mi_dist_vec_t vx = nullptr, vy = nullptr, vz = nullptr; // scratch of the host-pointer entry points
@@ -242,21 +251,24 @@ int vec_alloc(mi_dist_s* D, mi_dist_vec_t* out)
     mi_dist_vec_t v = new (std::nothrow) mi_dist_vec_s();
     if (!v) return fail(MI_ERR_ALLOC, "host allocation failed");
     v->D = D;
-    v->ext.assign((size_t)D->nranks, nullptr);
+    v->ext.resize((size_t)D->nranks);
     int rc = D->pool.run([&](int r) -> int {
         const DistRank& me = D->R[r];
         const size_t len = (size_t)me.n_local + (size_t)me.n_halo + 64; // (64 spare entries: 16-byte tails of the BLAS-1 kernels never straddle the end)
-        HIP_TRY(hipMalloc(&v->ext[r], sizeof(double) * len));
-        HIP_TRY(hipMemsetAsync(v->ext[r], 0, sizeof(double) * len, me.stream));
+        DevArray<double> a;
+        int c = dev_alloc(a, len);
+        if (c) return c;
+        HIP_TRY(hipMemsetAsync(a, 0, sizeof(double) * len, me.stream));
         // (create-time cost only) the zero fill is complete before anybody can use the vector: in the event exchange the PEERS write this
         // vector's halo part from their streams, ordered behind this rank's ev_done of the previous step only — a fill still queued here
         // could land on top of a neighbour's entries
         HIP_TRY(hipStreamSynchronize(me.stream));
+        v->ext[r] = std::move(a);
         return MI_OK;
     });
     if (rc) {
         const std::string keep = g_err;
-        D->pool.run([&](int r) -> int { dfree(v->ext[r]); return MI_OK; });
+        D->pool.run([&](int r) -> int { v->ext[r] = {}; return MI_OK; });
         delete v;
         return fail(rc, keep);
     }
@@ -271,7 +283,7 @@ void vec_free(mi_dist_s* D, mi_dist_vec_t v)
     D->live.erase(std::remove(D->live.begin(), D->live.end(), v), D->live.end());
     D->pool.run([&](int r) -> int {
         (void)hipStreamSynchronize(D->R[r].stream);
-        dfree(v->ext[r]);
+        v->ext[r] = {};
         return MI_OK;
     });
     delete v;
@@ -358,7 +370,7 @@ int dist_ortho(mi_dist_s* D, const mi_dist_vec_s* b, const mi_dist_vec_s* x1, mi
         else W_HIP(hipMemsetAsync(me.d_scal, 0, sizeof(double), me.stream));
         if (N == 1) parts = me.d_scal;
         else if (by_rccl) {
-            if (rc == MI_OK && rccl_state().AllGather(me.d_scal, me.d_parts, 1, kNcclDouble, me.part->comm, me.stream) != 0) rc = fail(MI_ERR_HIP, "ncclAllGather of the partial dots failed");
+            if (rc == MI_OK && rccl_state().AllGather(me.d_scal, me.d_parts, 1, kNcclDouble, me.part->rccl.comm.get(), me.stream) != 0) rc = fail(MI_ERR_HIP, "ncclAllGather of the partial dots failed");
             parts = me.d_parts;
         } else {
             double* slot = D->h_parts + (size_t)par * N;
@@ -395,8 +407,7 @@ void dist_release(mi_dist_s* D)
         for (mi_dist_vec_t v : orphans) {
             D->pool.run([&](int r) -> int {
                 (void)hipStreamSynchronize(D->R[r].stream);
-                dfree(v->ext[r]);
-                v->ext[r] = nullptr;
+                v->ext[r] = {};
                 return MI_OK;
             });
             v->D = nullptr;
@@ -405,22 +416,11 @@ void dist_release(mi_dist_s* D)
         D->pool.run([&](int r) -> int {
             DistRank& me = D->R[r];
             if (me.stream) (void)hipStreamSynchronize(me.stream);
-            (void)mi_part_destroy(me.part);
-            me.part = nullptr;
-            dfree(me.d_sendbuf);
-            dfree(me.d_scal);
-            dfree(me.d_parts);
-            if (me.h_scal) (void)hipHostFree(me.h_scal);
-            for (hipEvent_t& e : me.ev_dot)
-                if (e) (void)hipEventDestroy(e);
-            if (me.ev_push) (void)hipEventDestroy(me.ev_push);
-            if (me.ev_done) (void)hipEventDestroy(me.ev_done);
-            if (me.stream) (void)hipStreamDestroy(me.stream);
+            me.part.reset(), me.resources() = {};
             return MI_OK;
         });
         D->pool.shutdown();
     }
-    if (D->h_parts) (void)hipHostFree(D->h_parts);
     delete D;
 }
 
@@ -453,12 +453,12 @@ int try_push(mi_dist_s* D, bool* ok, std::string* why)
     });
     if (rc == MI_OK) {
         std::vector<void*> bases((size_t)N, nullptr);
-        for (int r = 0; r < N; r++) bases[r] = D->R[r].part->win;
+        for (int r = 0; r < N; r++) bases[r] = D->R[r].part->push.win.get();
         rc = D->pool.run([&](int r) -> int { return part_push_connect_bases(D->R[r].part, bases.data(), layouts.data()); });
     }
     if (rc == MI_OK) { // one form for everybody (mixed forms are legal; equal forms keep the step times balanced)
         bool all_fused = true;
-        for (int r = 0; r < N; r++) all_fused = all_fused && D->R[r].part->fused;
+        for (int r = 0; r < N; r++) all_fused = all_fused && D->R[r].part->one.fused;
         if (!all_fused) rc = D->pool.run([&](int r) -> int { return mi_part_push_unfuse(D->R[r].part); });
         D->fused = all_fused;
     }
@@ -620,7 +620,10 @@ extern "C" int mi_dist_create(int ndev, int n, const int* ptrow, const int* indc
         DistRank& me = D->R[r];
         me.ptrow.resize((size_t)me.n_local + 1);
         for (int i = 0; i <= me.n_local; i++) me.ptrow[i] = (int)(ptrow[me.row0 + i] - me.nnz0);
-        return mi_part_create(N, r, D->rs.data(), me.ptrow.data(), indcol ? indcol + me.nnz0 : nullptr, coef ? coef + me.nnz0 : nullptr, &me.part);
+        mi_part_t P = nullptr;
+        int c = mi_part_create(N, r, D->rs.data(), me.ptrow.data(), indcol ? indcol + me.nnz0 : nullptr, coef ? coef + me.nnz0 : nullptr, &P);
+        me.part.reset(P);
+        return c;
     });
     // what rank r wants from q is what q sends to r: read off the plans (one address space: no id exchange)
     if (rc == MI_OK)
@@ -642,20 +645,20 @@ extern "C" int mi_dist_create(int ndev, int n, const int* ptrow, const int* indc
             me.n_halo = pl.n_halo;
             for (int p = 0; p < N; p++)
                 if (p != r && (pl.send_counts[p] || pl.recv_counts[p])) me.nb.push_back(p);
-            HIP_TRY(hipStreamCreateWithFlags(&me.stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&me.ev_push, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&me.ev_done, hipEventDisableTiming));
-            HIP_TRY(hipMalloc(&me.d_sendbuf, sizeof(double) * std::max<size_t>(pl.send_idx.size(), 1)));
-            HIP_TRY(hipMalloc(&me.d_scal, 2 * sizeof(double)));
-            HIP_TRY(hipMalloc(&me.d_parts, sizeof(double) * (size_t)std::max(N, 1)));
-            HIP_TRY(hipHostMalloc((void**)&me.h_scal, 2 * sizeof(double), hipHostMallocDefault));
-            for (hipEvent_t& e : me.ev_dot) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            RankResources X;
+            int c;
+            (c = dev_create(X.stream, hipStreamNonBlocking)) || (c = dev_create(X.ev_push, hipEventDisableTiming)) || (c = dev_create(X.ev_done, hipEventDisableTiming)) ||
+                (c = dev_alloc(X.d_sendbuf, pl.send_idx.size(), 1)) || (c = dev_alloc(X.d_scal, 2)) || (c = dev_alloc(X.d_parts, (size_t)std::max(N, 1)));
+            if (c) return c;
+            HIP_TRY_AS("hipHostMalloc", X.h_scal.alloc(2));
+            (c = dev_create(X.ev_dot[0], hipEventDisableTiming)) || (c = dev_create(X.ev_dot[1], hipEventDisableTiming));
+            if (c) return c;
+            me.resources() = std::move(X);
             std::vector<int>().swap(me.ptrow);
             return MI_OK;
         });
-    if (rc == MI_OK && hipHostMalloc((void**)&D->h_parts, sizeof(double) * 2 * (size_t)std::max(N, 1), hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
+    if (rc == MI_OK && D->h_parts.alloc(2 * (size_t)std::max(N, 1), hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
         (void)hipGetLastError();
-        D->h_parts = nullptr;
         rc = fail(MI_ERR_ALLOC, "pinned table of the ranks' partial dots");
     }
     if (rc) {

@@ -34,28 +34,27 @@ using namespace mi355;
 // ---------------------------------------------------------------- errors
 extern thread_local std::string g_err; // capi_lib.hip
 
-// (the partition, the distributed layer and the process-wide tables keep their own memory handling: raw pointers, freed by hand)
-static inline void dfree(void* p)
-{
-    if (p) (void)hipFree(p);
-}
-
 static inline int fail(int code, const std::string& msg)
 {
     g_err = msg;
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            int code_ = (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorInsufficientDriver) \
-                            ? MI_ERR_NODEVICE                                                           \
-                            : (e_ == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP);                  \
-            return fail(code_, std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-        }                                                                                               \
+// `what`: the call that failed, as the error text names it
+static inline int hip_fail(hipError_t e, const char* what)
+{
+    const int code = (e == hipErrorNoDevice || e == hipErrorInvalidDevice || e == hipErrorInsufficientDriver) ? MI_ERR_NODEVICE
+                                                                                                               : (e == hipErrorOutOfMemory ? MI_ERR_ALLOC : MI_ERR_HIP);
+    return fail(code, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// HIP_TRY_AS: an operation of an owning type (dev_array.hpp), reported under the name of the HIP call it makes
+#define HIP_TRY_AS(what, expr)                            \
+    do {                                                  \
+        hipError_t e_ = (expr);                           \
+        if (e_ != hipSuccess) return hip_fail(e_, what);  \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(#expr, expr)
 
 #define CHECK_ARG(cond, msg)                        \
     do {                                            \
@@ -64,10 +63,12 @@ static inline int fail(int code, const std::string& msg)
 
 
 // the MI_* forms of the owning types' operations (dev_array.hpp), for `(rc = ...) ||` chains; at_least: a floor, in entries, where the site wants one
-template <class T> static inline int dev_alloc(DevArray<T>& a, size_t n, size_t at_least = 0) { HIP_TRY(a.alloc(std::max(n, at_least))); return MI_OK; }
-template <class T> static inline int dev_zeros(DevArray<T>& a, size_t n, size_t at_least = 0) { HIP_TRY(a.zeros(std::max(n, at_least))); return MI_OK; }
-template <class T> static inline int dev_upload(DevArray<T>& a, const std::vector<T>& h, size_t at_least = 0) { HIP_TRY(a.upload(h, at_least)); return MI_OK; }
-static inline int dev_alloc(MappedWord& w) { HIP_TRY(w.alloc()); return MI_OK; }
+template <class T> static inline int dev_alloc(DevArray<T>& a, size_t n, size_t at_least = 0) { HIP_TRY_AS("hipMalloc", a.alloc(std::max(n, at_least))); return MI_OK; }
+template <class T> static inline int dev_zeros(DevArray<T>& a, size_t n, size_t at_least = 0) { HIP_TRY_AS("hipMalloc + hipMemset", a.zeros(std::max(n, at_least))); return MI_OK; }
+template <class T> static inline int dev_upload(DevArray<T>& a, const std::vector<T>& h, size_t at_least = 0) { HIP_TRY_AS("hipMalloc + hipMemcpy", a.upload(h, at_least)); return MI_OK; }
+static inline int dev_alloc(MappedWord& w) { HIP_TRY_AS("hipHostMalloc (mapped)", w.alloc()); return MI_OK; }
+static inline int dev_create(OwnedStream& s, unsigned flags = hipStreamDefault) { HIP_TRY_AS("hipStreamCreate", s.create(flags)); return MI_OK; }
+static inline int dev_create(OwnedEvent& e, unsigned flags = hipEventDefault) { HIP_TRY_AS("hipEventCreate", e.create(flags)); return MI_OK; }
 
 int need_device(); // capi_lib.hip
 
@@ -84,20 +85,13 @@ static inline bool env_is(const char* name, const char* value)
 // MI_ERR_HIP.  What a failed measurement means is the caller's business.
 struct LaunchTimer {
     hipStream_t s;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    OwnedEvent e1, e0; // (destroyed e0 first)
     explicit LaunchTimer(hipStream_t st = nullptr) : s(st) {}
-    LaunchTimer(const LaunchTimer&) = delete;
-    LaunchTimer& operator=(const LaunchTimer&) = delete;
-    ~LaunchTimer()
-    {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
     int init()
     {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        return MI_OK;
+        int rc;
+        (rc = dev_create(e0)) || (rc = dev_create(e1));
+        return rc;
     }
     template <class F>
     int time(int warm, int timed, F&& launch, double* us)
@@ -223,9 +217,9 @@ struct SstreamTable : SstreamCopy {
 };
 
 // a handle that goes with another (the blocked copy, the relabelled twin): deleted with its owner, read like the plain pointer it replaces
-template <class H>
+template <class H, class Destroy = std::default_delete<H>>
 struct OwnedHandle {
-    std::unique_ptr<H> own;
+    std::unique_ptr<H, Destroy> own;
     operator H*() const { return own.get(); }
     H* operator->() const { return own.get(); }
     void reset(H* p = nullptr) { own.reset(p); }
@@ -382,71 +376,102 @@ struct mi_csr_s {
     }
 };
 
-struct mi_part_s {
-    PartPlan plan;
-    mi_csr_t piece[2] = {nullptr, nullptr};
-    int* d_send_idx = nullptr;
-    bool finalized = false;
-    int kernel = MI_KERNEL_AUTO;
-    // native exchange (mi_part_comm_init)
-    void* comm = nullptr; // ncclComm_t
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_pack = nullptr, ev_comm = nullptr;
-    double* d_sendbuf = nullptr;
-    unsigned* d_flags = nullptr; // [0] "x ready" (set on the caller's stream), [1] "halo rows done" (set on the comm stream)
-    unsigned* h_timeouts = nullptr; // pinned, device-mapped: hand-off waits that gave up (read by the host at every entry point)
-    unsigned* d_timeouts = nullptr; // the device address of h_timeouts
+// ---- what a partition owns besides its pieces: four tables, each declared in the order it is freed in, each dropped by assigning a fresh one.
+// The three deleters below are capi_part.hip's: they need RCCL's function table and the window registry.
+struct RcclCommDestroy { void operator()(void* comm) const; };                  // ncclCommDestroy
+struct IpcMappingClose { void operator()(void* base) const; };                  // hipIpcCloseMemHandle
+struct WinRegistryErase { void operator()(std::string* key) const; };           // erases the key (under g_mu), deletes the string
+using RcclComm = std::unique_ptr<void, RcclCommDestroy>;
+using IpcMappings = std::vector<std::unique_ptr<void, IpcMappingClose>>;
+using WinRegistryEntry = std::unique_ptr<std::string, WinRegistryErase>;        // the IPC handle bytes under which my window is registered
+
+// native exchange (mi_part_comm_init)
+struct PartRccl {
+    RcclComm comm; // ncclComm_t
+    OwnedStream comm_stream;
+    OwnedEvent ev_pack, ev_comm;
+    DevArray<double> d_sendbuf;
     unsigned step_no = 0;
     // Hand-offs between the two streams: HIP events by default.  Flag kernels (handoff_kernels.hpp) are ~8 us per
     // step cheaper in the one-GPU harness but have not run against real multi-GPU RCCL yet: opt in with
     // MI355_PART_HANDOFF=flags.
     bool flag_handoff = false;
-    // the all-gather form of the RCCL exchange (wide halos): every rank contributes the M-entry slice of ITS entries that anybody
-    // needs (the sorted union of its send lists, padded to the largest), one ncclAllGather, each ghost picked out of the N x M result
-    std::vector<int> ag_union;   // local ids, ascending
+};
+
+// the all-gather form of the RCCL exchange (wide halos): every rank contributes the M-entry slice of ITS entries that anybody
+// needs (the sorted union of its send lists, padded to the largest), one ncclAllGather, each ghost picked out of the N x M result.
+// Set up iff d_ag_idx != nullptr.
+struct PartAllGather {
+    DevArray<int> d_ag_idx;      // [M] my union, padded with entry 0
+    DevArray<int> d_ag_src;      // [n_halo] where ghost h lies in the gathered buffer
+    DevArray<double> d_ag_send;  // [M]
+    DevArray<double> d_ag_recv;  // [nranks * M]
     int ag_slice = 0;            // M
-    int* d_ag_idx = nullptr;     // [M] my union, padded with entry 0
-    int* d_ag_src = nullptr;     // [n_halo] where ghost h lies in the gathered buffer
-    double* d_ag_send = nullptr; // [M]
-    double* d_ag_recv = nullptr; // [nranks * M]
-    bool ag_ready = false, ag_use = false;
-    // peer-push exchange (push_exchange.hpp): my receive window, the peers' windows I write to
-    void* win = nullptr;          // [flags: nranks x 64 B][pad][data: 2 x n_halo doubles]
-    bool win_uncached = false, win_registered = false;
-    std::string win_key;          // the IPC handle bytes (key of the in-process registry)
-    unsigned* win_flags = nullptr;
+    bool ready() const { return d_ag_idx != nullptr; }
+};
+
+// peer-push exchange (push_exchange.hpp): my receive window, the peers' windows I write to
+struct PushWindow {
+    IpcMappings ipc_opened; // the peers' windows, mapped
+    WinRegistryEntry win_entry;
+    DevArray<char> win;            // [flags: nranks x 64 B][pad][data: 2 x n_halo doubles], uncached
+    unsigned* win_flags = nullptr; // views of win
     double* win_data = nullptr;
-    std::vector<void*> ipc_opened; // mappings to close
-    PushLink* d_links = nullptr;
-    int n_links = 0;
-    int2* d_push_work = nullptr;   // stand-alone push kernel: {link, chunk} per workgroup
-    int* d_link_chunks = nullptr;  // chunks per link
-    unsigned* d_tickets = nullptr; // per link: chunks out so far
-    int n_push_work = 0;
-    int* d_nb = nullptr;           // ranks whose flags I wait for
-    int n_nb = 0;
+    bool peer_on_my_device = false; // a neighbour's window lives on this rank's device: ranks share a card
+};
+struct PushTables { // what connecting builds
+    DevArray<PushLink> d_links;
+    DevArray<int2> d_push_work;    // stand-alone push kernel: {link, chunk} per workgroup
+    DevArray<int> d_link_chunks;   // chunks per link
+    DevArray<unsigned> d_tickets;  // per link: chunks out so far
+    DevArray<int> d_nb;            // ranks whose flags I wait for
+    int n_links = 0, n_push_work = 0, n_nb = 0;
+};
+struct PartPush : PushWindow, PushTables {
     unsigned push_step = 0;
     bool push_ready = false;
-    // the one-launch form of the push step (spmv_ring.hpp, FUSED): all local rows in one ring-served, row-mapped piece
-    mi_csr_t piece_all = nullptr;
-    int* d_run_link = nullptr; // per run of piece_all: first push link it serves, or -1
+    PushTables& tables() { return *this; }
+};
+
+// the one-launch form of the push step: all local rows in one piece.  Three forms: the ring kernel's or the sliced stream's FUSED
+// form (spmv_ring.hpp, spmv_sstream.hpp), and the staged step (spmv_bcsr4_ext.hpp: piece_all numbered [owned | halo], exchange
+// workgroups in front of the grid, ghosts staged) on blocked (FE) or on scalar rows
+struct PartOneLaunch {
+    DevArray<int> d_run_link;        // per run of piece_all: first push link it serves, or -1
+    DevArray<double> d_stage;        // [n_halo] cached copy of the window's current parity
+    DevArray<unsigned> d_ready;      // exchange workgroups done (up by ext_wgs per step)
+    DevArray<int2> d_ext_units;      // blocked rows, per workgroup behind the exchange: {first block row, mode}
+    DevArray<unsigned> d_ext_order;  // scalar rows, per workgroup behind the exchange: its row block of piece_all's 1024-nonzero table, bit 31: it waits
+    OwnedHandle<mi_csr_s> piece_all;
     const int* d_run_halo = nullptr; // per run (ring) / workgroup (sliced stream) of piece_all: it reads ghosts (owned by piece_all)
     int npush_runs = 0;
     bool fused = false;
     bool ghost_readers = true; // some run / workgroup of the fused launch waits for the neighbours (false: the pushers wait)
-    // the blocked (FE) form of it (spmv_bcsr4_ext.hpp): piece_all numbered [owned | halo], exchange workgroups in front of the grid, ghosts staged
-    bool fused_ext = false;
-    double* d_stage = nullptr;   // [n_halo] cached copy of the window's current parity
-    unsigned* d_ready = nullptr; // exchange workgroups done (up by ext_wgs per step)
+    bool fused_ext = false;    // the staged step ...
+    bool ext_csr = false;      // ... on SCALAR rows (spmv_csr_fused_ext): d_ext_order instead of d_ext_units
     int ext_wgs = 0;
-    int2* d_ext_units = nullptr; // per workgroup behind the exchange: {first block row, mode}
-    int n_ext_units = 0;         // plain units first, then the waiting ones
+    int n_ext_units = 0;       // plain units first, then the waiting ones
     int n_ext_plain = 0;
-    bool peer_on_my_device = false; // a neighbour's window lives on this rank's device: ranks share a card
-    bool ext_split = false;      // two launches (exchange + plain units, then the waiting units): no workgroup but the exchange's waits in-kernel
-    bool ext_csr = false;        // the staged step on SCALAR rows (spmv_csr_fused_ext): d_ext_order instead of d_ext_units
-    unsigned* d_ext_order = nullptr; // per workgroup behind the exchange: its row block of piece_all's 1024-nonzero table, bit 31: it waits
-    int ext_debug = 0; // devtools only (mi_debug_part_ext_mode): parts of the exchange left out, for timing
+    bool ext_split = false;    // two launches (exchange + plain units, then the waiting units): no workgroup but the exchange's waits in-kernel
+    int ext_debug = 0;         // devtools only (mi_debug_part_ext_mode): parts of the exchange left out, for timing
+};
+
+struct mi_part_s {
+    PartPlan plan;
+    OwnedHandle<mi_csr_s> piece[2];
+    DevArray<int> d_send_idx;
+    bool finalized = false;
+    int kernel = MI_KERNEL_AUTO;
+    PartRccl rccl;
+    std::vector<int> ag_union;   // local ids, ascending (mi_part_send_union)
+    PartAllGather ag;
+    bool ag_use = false;
+    DevArray<unsigned> d_flags; // the RCCL step's hand-off flags: [0] "x ready" (set on the caller's stream), [1] "halo rows done" (set on the comm stream)
+    MappedWord timeouts; // hand-off and push waits that gave up (read by the host at every entry point); allocated by whichever exchange comes up first
+    PartPush push;
+    PartOneLaunch one;
+    // the order the handle has always been freed in
+    ~mi_part_s() { piece[0].reset(), piece[1].reset(), d_send_idx = {}, rccl = {}, ag = {}, d_flags = {}, timeouts = {}, push = {}, one = {}; }
 };
 
 static inline size_t win_data_offset(int nranks) { return ((size_t)nranks * kWinFlagStride * sizeof(unsigned) + 255) / 256 * 256; }
@@ -457,16 +482,19 @@ int get_ws(hipStream_t s, double** out); // capi_blas1.hip: reduction workspace 
 
 // host-pointer helper: upload vectors, run on the device copies, download
 struct Scratch {
-    std::vector<double*> bufs;
+    std::vector<DevArray<double>> bufs;
     ~Scratch()
     {
-        for (double* p : bufs) dfree(p);
+        for (auto& a : bufs) a = {}; // first to last
     }
     int up(const double* h, size_t n, double** d)
     {
         *d = nullptr;
-        HIP_TRY(hipMalloc(d, sizeof(double) * (n ? n : 1)));
-        bufs.push_back(*d);
+        DevArray<double> a;
+        int rc = dev_alloc(a, n, 1);
+        if (rc) return rc;
+        *d = a;
+        bufs.push_back(std::move(a));
         if (h && n) HIP_TRY(hipMemcpy(*d, h, sizeof(double) * n, hipMemcpyHostToDevice));
         return MI_OK;
     }
@@ -504,7 +532,8 @@ hipError_t spmm_otile_launch(const mi_bcsr4_s* A, const SpmmTilePlan* Pl, const 
 // capi_part.hip: pieces of the peer-push set-up that capi_dist.hip (ranks of one process on different devices) uses directly
 int part_push_window(mi_part_s* P);
 void part_push_layout(const mi_part_s* P, long long* layout /* [2*nranks + 1] */);
-int part_push_connect_bases(mi_part_s* P, void* const* bases /* [nranks] */, const long long* layouts);
+int part_push_connect_bases(mi_part_s* P, void* const* bases /* [nranks] */, const long long* layouts,
+                            IpcMappings opened = {}, bool peer_on_my_device = false);
 // the staged one-launch step of a blocked rank (spmv_bcsr4_ext.hpp); trace: devtools only (3 stamps per workgroup of the grid)
 int part_ext_launch(mi_part_s* P, const double* d_x_ext, double* d_y_local, unsigned step, unsigned spin_max, hipStream_t s, unsigned long long* trace, int* grid_out);
 // capi_csr.hip: the sliced-stream kernel of a handle (spmv_sstream.hpp); d_y: where the handle's row 0 goes (unmapped) or the mapped vector's base;

@@ -129,16 +129,13 @@ extern "C" int mi_stream_read_probe(long long bytes, int launches, double* us_pe
     int rc = need_device();
     if (rc) return rc;
     LaunchTimer tm;
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { dfree(p); }
-    } buf;
-    HIP_TRY(hipMalloc(&buf.p, (size_t)bytes + 256));
-    HIP_TRY(hipMemset(buf.p, 1, (size_t)bytes + 256));
+    DevArray<char> buf;
+    HIP_TRY_AS("hipMalloc", buf.alloc((size_t)bytes + 256));
+    HIP_TRY(hipMemset(buf, 1, (size_t)bytes + 256));
     if ((rc = tm.init())) return rc;
-    double* sink = reinterpret_cast<double*>((char*)buf.p + ((size_t)bytes / 16) * 16);
+    double* sink = reinterpret_cast<double*>(buf + ((size_t)bytes / 16) * 16);
     auto launch = [&]() {
-        hipLaunchKernelGGL(stream_read_kernel<true>, dim3(2048), dim3(256), 0, nullptr, (const double2*)buf.p, (size_t)bytes / 16, sink);
+        hipLaunchKernelGGL(stream_read_kernel<true>, dim3(2048), dim3(256), 0, nullptr, (const double2*)buf.get(), (size_t)bytes / 16, sink);
         return MI_OK;
     };
     return tm.time(3, launches, launch, us_per_launch);

@@ -31,6 +31,13 @@ struct DevArray {
         if (e == hipSuccess) own.reset(p);
         return e;
     }
+    hipError_t alloc_uncached(size_t n) // ... of uncached memory (the push exchange's receive window); hipFree releases it like any other
+    {
+        void* p = nullptr;
+        const hipError_t e = hipExtMallocWithFlags(&p, sizeof(T) * n, hipDeviceMallocUncached);
+        if (e == hipSuccess) own.reset((T*)p);
+        return e;
+    }
     hipError_t zeros(size_t n) // ... zero-filled, on the NULL stream
     {
         const hipError_t e = alloc(n);
@@ -48,6 +55,20 @@ struct DevArray {
     }
 };
 
+// pinned host memory that goes with its owner
+template <class T>
+struct PinnedArray {
+    std::unique_ptr<T, HipFree<hipHostFree>> own;
+    operator T*() const { return own.get(); }
+    hipError_t alloc(size_t n, unsigned flags = hipHostMallocDefault)
+    {
+        T* p = nullptr;
+        const hipError_t e = hipHostMalloc((void**)&p, sizeof(T) * n, flags);
+        if (e == hipSuccess) own.reset(p);
+        return e;
+    }
+};
+
 // a word of host memory that kernels write through dev (the give-up counts of the in-kernel waits: sticky, read by the host at every entry point)
 struct MappedWord {
     std::unique_ptr<unsigned, HipFree<hipHostFree>> host;
@@ -60,5 +81,35 @@ struct MappedWord {
         host.reset(p);
         *p = 0;
         return hipHostGetDevicePointer((void**)&dev, p, 0);
+    }
+};
+
+// a stream / an event that goes with its owner; read like the plain handle it replaces
+template <class H, hipError_t (*Destroy)(H*)>
+struct HipDestroy {
+    void operator()(H* h) const { (void)Destroy(h); }
+};
+
+struct OwnedStream {
+    std::unique_ptr<ihipStream_t, HipDestroy<ihipStream_t, hipStreamDestroy>> own;
+    operator hipStream_t() const { return own.get(); }
+    hipError_t create(unsigned flags = hipStreamDefault)
+    {
+        hipStream_t s = nullptr;
+        const hipError_t e = flags == hipStreamDefault ? hipStreamCreate(&s) : hipStreamCreateWithFlags(&s, flags);
+        if (e == hipSuccess) own.reset(s);
+        return e;
+    }
+};
+
+struct OwnedEvent {
+    std::unique_ptr<ihipEvent_t, HipDestroy<ihipEvent_t, hipEventDestroy>> own;
+    operator hipEvent_t() const { return own.get(); }
+    hipError_t create(unsigned flags = hipEventDefault)
+    {
+        hipEvent_t ev = nullptr;
+        const hipError_t e = flags == hipEventDefault ? hipEventCreate(&ev) : hipEventCreateWithFlags(&ev, flags);
+        if (e == hipSuccess) own.reset(ev);
+        return e;
     }
 };

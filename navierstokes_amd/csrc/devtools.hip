@@ -16,11 +16,10 @@ extern "C" int mi_debug_xcc_map(int wgs, int* host_out)
     CHECK_ARG(wgs > 0 && host_out, "bad argument");
     int rc = need_device();
     if (rc) return rc;
-    int* d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(int) * wgs));
+    DevArray<int> d;
+    if ((rc = dev_alloc(d, (size_t)wgs))) return rc;
     hipLaunchKernelGGL(xcc_probe_kernel, dim3(wgs), dim3(256), 0, nullptr, d);
     HIP_TRY(hipMemcpy(host_out, d, sizeof(int) * wgs, hipMemcpyDeviceToHost));
-    dfree(d);
     return MI_OK;
 }
 // one 4-byte read every `stride` bytes of an array: brings its address translations (and 1 line per stride) back after
@@ -38,11 +37,11 @@ extern "C" int mi_debug_touch_pages(mi_csr_t A, int stride_bytes, const void* d_
 {
     CHECK_ARG(A && stride_bytes >= 64 && stride_bytes % 4 == 0, "bad argument");
     if (A->inner) A = A->inner;
-    int* sink = nullptr;
-    HIP_TRY(hipMalloc(&sink, 64));
+    DevArray<int> sink;
+    HIP_TRY_AS("hipMalloc", sink.alloc(16));
     auto touch = [&](const void* p, size_t bytes) {
         if (!p || bytes < 4) return;
-        hipLaunchKernelGGL(touch_pages_kernel, dim3(256), dim3(256), 0, nullptr, (const char*)p, bytes - 3, (size_t)stride_bytes, sink);
+        hipLaunchKernelGGL(touch_pages_kernel, dim3(256), dim3(256), 0, nullptr, (const char*)p, bytes - 3, (size_t)stride_bytes, sink.get());
     };
     const size_t nnz = (size_t)A->nnz, n = (size_t)A->n;
     touch(A->d_coef, 8 * nnz);
@@ -67,16 +66,15 @@ extern "C" int mi_debug_touch_pages(mi_csr_t A, int stride_bytes, const void* d_
     touch(d_extra1, (size_t)bytes1);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    dfree(sink);
     return MI_OK;
 }
 // development aid (tools/sim_rank.py): set every flag slot of MY window to `value`, so that one rank's step can be timed on
 // one GPU with its pushes looped back into its own window and its waits satisfied in advance
 extern "C" int mi_part_push_debug_preset(mi_part_t P, unsigned value)
 {
-    CHECK_ARG(P && P->win, "no window");
+    CHECK_ARG(P && P->push.win, "no window");
     std::vector<unsigned> f((size_t)P->plan.nranks * kWinFlagStride, value);
-    HIP_TRY(hipMemcpy(P->win_flags, f.data(), sizeof(unsigned) * f.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(P->push.win_flags, f.data(), sizeof(unsigned) * f.size(), hipMemcpyHostToDevice));
     return MI_OK;
 }
 
@@ -99,15 +97,13 @@ extern "C" int mi_debug_mring_trace(mi_csr_t A, const double* d_x, double* d_y, 
     V.coef = A->d_coef;
     V.rowmap = nullptr;
     V.nblk = M.nblk;
-    long long* d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(long long) * 4 * (size_t)M.wgs));
-    HIP_TRY(hipMemset(d, 0, sizeof(long long) * 4 * (size_t)M.wgs));
+    DevArray<long long> d;
+    if (int rc = dev_zeros(d, 4 * (size_t)M.wgs)) return rc;
     hipLaunchKernelGGL((spmv_csr_mring<kMringThreads, kMringNnzb, 4, kMringMaxB, false, true, false, true>), dim3(M.wgs), dim3(kMringThreads), 0, nullptr,
                        V, reinterpret_cast<const int4*>(M.d_plan.get()), reinterpret_cast<const int4*>(M.d_first.get()), M.d_ok, M.d_slots, d_x, d_y,
-                       reinterpret_cast<const int2*>(M.d_rng.get()), M.wgs, d);
+                       reinterpret_cast<const int2*>(M.d_rng.get()), M.wgs, d.get());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(host_out, d, sizeof(long long) * 4 * (size_t)M.wgs, hipMemcpyDeviceToHost));
-    dfree(d);
     *wgs_out = M.wgs;
     return MI_OK;
 }
@@ -192,34 +188,33 @@ extern "C" int mi_debug_mring_replan(mi_csr_t A, int skew_pct, int* table_len, i
 extern "C" int mi_debug_part_push_trace(mi_part_t P, double* d_x_ext, double* d_y_local, int max_wgs, long long* host_out, int* wgs_out, int* halo_out)
 {
     CHECK_ARG(P && d_x_ext && d_y_local && host_out && wgs_out, "null argument");
-    if (!P->push_ready || !P->fused || !P->piece_all || resolve_kernel(P->piece_all) != MI_KERNEL_SSTREAM || !P->piece_all->ss.fusable)
+    if (!P->push.push_ready || !P->one.fused || !P->one.piece_all || resolve_kernel(P->one.piece_all) != MI_KERNEL_SSTREAM || !P->one.piece_all->ss.fusable)
         return fail(MI_ERR_STATE, "the one-launch push step of this handle does not run the sliced stream");
-    mi_csr_t A = P->piece_all;
+    mi_csr_t A = P->one.piece_all;
     SstreamTable& T = A->ss;
     CHECK_ARG(T.nwg <= max_wgs, "host buffer too small");
     const PartPlan& pl = P->plan;
-    const unsigned step = ++P->push_step;
+    const unsigned step = ++P->push.push_step;
     RingComm C{};
-    C.links = P->d_links;
+    C.links = P->push.d_links;
     C.send_idx = P->d_send_idx;
-    C.flags = P->win_flags;
-    C.nb = P->d_nb;
-    C.halo = P->win_data + (size_t)(step & 1u) * (size_t)(pl.n_halo > 0 ? pl.n_halo : 1);
-    C.run_halo = P->d_run_halo;
-    C.timeouts = P->d_timeouts;
-    C.n_links = P->n_links;
-    C.n_nb = P->n_nb;
+    C.flags = P->push.win_flags;
+    C.nb = P->push.d_nb;
+    C.halo = P->push.win_data + (size_t)(step & 1u) * (size_t)(pl.n_halo > 0 ? pl.n_halo : 1);
+    C.run_halo = P->one.d_run_halo;
+    C.timeouts = P->timeouts.dev;
+    C.n_links = P->push.n_links;
+    C.n_nb = P->push.n_nb;
     C.n_local = pl.n_local;
     C.n_left = pl.n_left;
-    C.run_link = P->d_run_link;
-    C.npush_runs = P->npush_runs;
-    C.push_wgs = (P->npush_runs == 0 && P->n_links > 0) ? kNXCD : 0;
+    C.run_link = P->one.d_run_link;
+    C.npush_runs = P->one.npush_runs;
+    C.push_wgs = (P->one.npush_runs == 0 && P->push.n_links > 0) ? kNXCD : 0;
     C.step = step;
     C.spin_max = 1u << kPushSpinLog2Default;
-    C.gate_push = P->ghost_readers ? 0 : 1;
-    unsigned long long* d_tr = nullptr;
-    HIP_TRY(hipMalloc(&d_tr, sizeof(unsigned long long) * 4 * (size_t)T.nwg));
-    HIP_TRY(hipMemset(d_tr, 0, sizeof(unsigned long long) * 4 * (size_t)T.nwg));
+    C.gate_push = P->one.ghost_readers ? 0 : 1;
+    DevArray<unsigned long long> d_tr;
+    if (int rc = dev_zeros(d_tr, 4 * (size_t)T.nwg)) return rc;
     SsView S{T.dev.val, T.dev.slot, T.dev.wg, T.dev.win, T.nwg, A->n + T.shift, A->ncols, nullptr, T.shift};
     S.trace = d_tr;
     HIP_TRY(hipDeviceSynchronize());
@@ -227,7 +222,6 @@ extern "C" int mi_debug_part_push_trace(mi_part_t P, double* d_x_ext, double* d_
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(host_out, d_tr, sizeof(unsigned long long) * 4 * (size_t)T.nwg, hipMemcpyDeviceToHost));
-    dfree(d_tr);
     *wgs_out = T.nwg;
     if (halo_out)
         for (int g = 0; g < T.nwg; g++) halo_out[g] = T.h_wg_halo[g] + 2 * (T.h_wg[g].link >= 0 ? 1 : 0) + 4 * (T.h_wg[g].r_end - T.h_wg[g].r_begin);
@@ -239,19 +233,19 @@ extern "C" int mi_debug_part_push_trace(mi_part_t P, double* d_x_ext, double* d_
 extern "C" int mi_debug_part_ext_mode(mi_part_t P, int mode)
 {
     CHECK_ARG(P, "null handle");
-    if (!P->fused_ext) return fail(MI_ERR_STATE, "the handle does not run the staged one-launch step");
+    if (!P->one.fused_ext) return fail(MI_ERR_STATE, "the handle does not run the staged one-launch step");
     HIP_TRY(hipDeviceSynchronize());
-    P->ext_debug = mode;
-    if ((mode & 1) && P->ext_csr) {
-        std::vector<unsigned> o((size_t)P->n_ext_units);
-        HIP_TRY(hipMemcpy(o.data(), P->d_ext_order, sizeof(unsigned) * o.size(), hipMemcpyDeviceToHost));
+    P->one.ext_debug = mode;
+    if ((mode & 1) && P->one.ext_csr) {
+        std::vector<unsigned> o((size_t)P->one.n_ext_units);
+        HIP_TRY(hipMemcpy(o.data(), P->one.d_ext_order, sizeof(unsigned) * o.size(), hipMemcpyDeviceToHost));
         for (unsigned& e : o) e &= 0x7fffffffu;
-        HIP_TRY(hipMemcpy(P->d_ext_order, o.data(), sizeof(unsigned) * o.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(P->one.d_ext_order, o.data(), sizeof(unsigned) * o.size(), hipMemcpyHostToDevice));
     } else if (mode & 1) {
-        std::vector<int2> u((size_t)P->n_ext_units);
-        HIP_TRY(hipMemcpy(u.data(), P->d_ext_units, sizeof(int2) * u.size(), hipMemcpyDeviceToHost));
+        std::vector<int2> u((size_t)P->one.n_ext_units);
+        HIP_TRY(hipMemcpy(u.data(), P->one.d_ext_units, sizeof(int2) * u.size(), hipMemcpyDeviceToHost));
         for (int2& e : u) e.y &= ~1;
-        HIP_TRY(hipMemcpy(P->d_ext_units, u.data(), sizeof(int2) * u.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(P->one.d_ext_units, u.data(), sizeof(int2) * u.size(), hipMemcpyHostToDevice));
     }
     return MI_OK;
 }
@@ -261,28 +255,26 @@ extern "C" int mi_debug_part_ext_mode(mi_part_t P, int mode)
 extern "C" int mi_debug_part_ext_trace(mi_part_t P, double* d_x_ext, double* d_y_local, int max_wgs, long long* host_out, int* wgs_out, int* modes_out)
 {
     CHECK_ARG(P && d_x_ext && d_y_local && host_out && wgs_out, "null argument");
-    if (!P->fused_ext) return fail(MI_ERR_STATE, "the handle does not run the staged one-launch step");
-    const int grid = P->n_ext_units + P->n_push_work + P->ext_wgs;
+    if (!P->one.fused_ext) return fail(MI_ERR_STATE, "the handle does not run the staged one-launch step");
+    const int grid = P->one.n_ext_units + P->push.n_push_work + P->one.ext_wgs;
     CHECK_ARG(grid <= max_wgs, "host buffer too small");
-    unsigned long long* d_tr = nullptr;
-    HIP_TRY(hipMalloc(&d_tr, sizeof(unsigned long long) * 3 * (size_t)grid));
-    HIP_TRY(hipMemset(d_tr, 0, sizeof(unsigned long long) * 3 * (size_t)grid));
+    DevArray<unsigned long long> d_tr;
+    if (int rc = dev_zeros(d_tr, 3 * (size_t)grid)) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    const unsigned step = ++P->push_step;
+    const unsigned step = ++P->push.push_step;
     int rc = part_ext_launch(P, d_x_ext, d_y_local, step, 1u << kPushSpinLog2Default, nullptr, d_tr, nullptr);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(host_out, d_tr, sizeof(unsigned long long) * 3 * (size_t)grid, hipMemcpyDeviceToHost));
-    dfree(d_tr);
     *wgs_out = grid;
-    if (modes_out && P->ext_csr) {
-        std::vector<unsigned> o((size_t)P->n_ext_units);
-        HIP_TRY(hipMemcpy(o.data(), P->d_ext_order, sizeof(unsigned) * o.size(), hipMemcpyDeviceToHost));
-        for (int g = 0; g < grid; g++) modes_out[g] = g < P->n_push_work ? -2 : (g < P->n_push_work + P->ext_wgs ? -1 : (int)(o[g - P->n_push_work - P->ext_wgs] >> 31));
+    if (modes_out && P->one.ext_csr) {
+        std::vector<unsigned> o((size_t)P->one.n_ext_units);
+        HIP_TRY(hipMemcpy(o.data(), P->one.d_ext_order, sizeof(unsigned) * o.size(), hipMemcpyDeviceToHost));
+        for (int g = 0; g < grid; g++) modes_out[g] = g < P->push.n_push_work ? -2 : (g < P->push.n_push_work + P->one.ext_wgs ? -1 : (int)(o[g - P->push.n_push_work - P->one.ext_wgs] >> 31));
     } else if (modes_out) {
-        std::vector<int2> u((size_t)P->n_ext_units);
-        HIP_TRY(hipMemcpy(u.data(), P->d_ext_units, sizeof(int2) * u.size(), hipMemcpyDeviceToHost));
-        for (int g = 0; g < grid; g++) modes_out[g] = g < P->n_push_work ? -2 : (g < P->n_push_work + P->ext_wgs ? -1 : u[g - P->n_push_work - P->ext_wgs].y);
+        std::vector<int2> u((size_t)P->one.n_ext_units);
+        HIP_TRY(hipMemcpy(u.data(), P->one.d_ext_units, sizeof(int2) * u.size(), hipMemcpyDeviceToHost));
+        for (int g = 0; g < grid; g++) modes_out[g] = g < P->push.n_push_work ? -2 : (g < P->push.n_push_work + P->one.ext_wgs ? -1 : u[g - P->push.n_push_work - P->one.ext_wgs].y);
     }
     return MI_OK;
 }

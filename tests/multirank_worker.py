@@ -2,6 +2,7 @@
 environment (MI355_SPMV_LIBRARY, MI355_PUSH_LOOPBACK, MI355_RCCL_LIBRARY) once per process.
   push            the one-launch push steps: N mi_part handles in THIS process, pushes looped back into their windows
   dist <exchange> mi_dist end to end (event | sendrecv | allgather; the two RCCL forms over tests/fake_rccl)
+  lifecycle <cycles>  tests/test_gpu_part_lifecycle.py: every way a partition and an mi_dist handle come to own device memory, over and over
 Prints one line per case, FORM lines (push), and MULTIRANK_OK on success."""
 import ctypes
 import os
@@ -48,6 +49,11 @@ class PushRanks:
         self.plans = MC.make_plans(P, C, V, rs)
         for pl in self.plans:
             mpk.check(L.mi_part_finalize(pl._h))
+        self.connect()
+
+    def connect(self):
+        """export every window, connect every rank, read the forms the ranks took"""
+        L = mpk.lib()
         hb = [ctypes.create_string_buffer(64) for _ in range(self.N)]
         lays = np.zeros((self.N, 2 * self.N + 1), np.int64)
         for r, pl in enumerate(self.plans):
@@ -193,11 +199,134 @@ def dist(exchange):
                 Dm.close()
 
 
+# ---------------------------------------------------------------------------------------------------- lifecycle
+GRANULE = 2 << 20
+FE_CELLS = 13     # the smallest synth.fe_matrix whose two ranks each hold a value array above the granule (tests/test_gpu_part_lifecycle.py asserts it)
+S15_ROWS = 34954  # ... and the smallest even synth.rows("s15", n): 15 nonzeros per row, 17 477 rows per rank
+S15_WIDTH = 300
+SCALAR_FORMS = ("ring", "sstream", "csr_ext")
+DIST_LIVES = (("event", 0, 2), ("sendrecv", 2, 3), ("allgather", 3, 5))  # exchange, seed of the multirank_cases case, ranks (all on device 0)
+
+
+def lifecycle_matrices():
+    """(P, C, V, row_starts) of the two push lives: a blocked FE matrix and a scalar band, two ranks each"""
+    from navierstokes_amd import dist, synth
+    out = []
+    for (P, C, V), align in ((synth.fe_matrix(FE_CELLS), 4), (synth.rows("s15", S15_ROWS, w=S15_WIDTH), 1)):
+        out.append((P, C, V, dist.balanced_row_starts(len(P) - 1, 2, np.diff(P), align=align)))
+    return out
+
+
+def lifecycle_reference():
+    """Everything the lives compare against, computed once: x, the second set of values, the oracle's products."""
+    ref = {"push": [], "dist": []}
+    for i, (P, C, V, rs) in enumerate(lifecycle_matrices()):
+        x = np.random.default_rng(31 + i).uniform(-1, 1, len(P) - 1)
+        V2 = V * np.cos(np.arange(len(V)))
+        ref["push"].append(dict(P=P, C=C, V=V, rs=rs, x=x, V2=V2, y=O.spmv(P, C, V, x), y2=O.spmv(P, C, V2, x)))
+    for exchange, seed, ndev in DIST_LIVES:
+        P, C, V, _, label = MC.case(seed)
+        x = np.random.default_rng(41 + seed).uniform(-1, 1, len(P) - 1)
+        V2 = V * np.cos(np.arange(len(V)))
+        ref["dist"].append(dict(P=P, C=C, V=V, x=x, V2=V2, Y=O.spmk_chain(3, P, C, V, x), y2=O.spmv(P, C, V2, x), exchange=exchange, ndev=ndev, label=label))
+    return ref
+
+
+def push_life(R_, form, what, say=None):
+    """create -> send ids -> finalize -> export -> connect, a one-launch product, new values, the four launches, the exchange given
+    up, brought up again, destroy; every product bitwise.  say: told which kernels the pieces' create-time measurements chose"""
+    env, marker = PUSH_FORMS[form]
+    for k in FORM_VARS:
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    L = mpk.lib()
+    P, rs = R_["P"], R_["rs"]
+    R = PushRanks(P, R_["C"], R_["V"], rs)
+    if say:
+        say(f"{what}: " + " | ".join(L.mi_part_kernel_name(pl._h, w).decode() for pl in R.plans for w in (0, 1, 2)))
+
+    def check(want, step, one_launch):
+        assert all((marker in nm) if one_launch else nm == "" for nm in R.names), (what, step, R.names)
+        got = R.product(R_["x"], what, form)
+        for r in range(R.N):
+            assert_bit_equal(got[r], want[int(rs[r]):int(rs[r + 1])], f"{what}: {step}, rank {r} ({R.names[r] or 'four launches'})")
+
+    try:
+        check(R_["y"], "one launch", True)
+        for r, pl in enumerate(R.plans):
+            mpk.check(L.mi_part_update_values(pl._h, np.ascontiguousarray(R_["V2"][P[int(rs[r])]:P[int(rs[r + 1])]]).ctypes.data))
+        check(R_["y2"], "after mi_part_update_values", True)
+        for pl in R.plans:
+            mpk.check(L.mi_part_push_unfuse(pl._h))
+        R.names = [L.mi_part_kernel_name(pl._h, 2).decode() for pl in R.plans]
+        check(R_["y2"], "after mi_part_push_unfuse", False)
+        torch.cuda.synchronize()
+        for pl in R.plans:
+            mpk.check(L.mi_part_push_disable(pl._h))
+        R.connect()
+        check(R_["y2"], "connected again", True)
+        torch.cuda.synchronize()
+    finally:
+        R.close()
+        for k in FORM_VARS:  # (the lives that follow run under no forced form)
+            os.environ.pop(k, None)
+
+
+def dist_life(R_, what):
+    """an mi_dist handle: product, three powers, a device vector left to the handle's destroy, one closed, new values, destroy"""
+    ex = R_["exchange"]
+    os.environ["MI355_DIST_EXCHANGE"] = "event" if ex == "event" else "rccl"
+    os.environ["MI355_PART_EXCHANGE"] = ex
+    P, C, n = R_["P"], R_["C"], len(R_["P"]) - 1
+    Dm = mpk.DistMatrix(R_["ndev"], n, P, C, R_["V"])
+    try:
+        info = Dm.info()
+        assert info["exchange"] == {"event": "event", "sendrecv": "rccl", "allgather": "rccl-allgather"}[ex], (what, info["exchange"], info["note"])
+        assert_bit_equal(Dm.spmv(np.full(n, np.nan), R_["x"]), R_["Y"][0], f"{what}: product")
+        outs = Dm.spmk([np.full(n, np.nan) for _ in range(3)], R_["x"])
+        for q in range(3):
+            assert_bit_equal(outs[q], R_["Y"][q], f"{what}: power {q + 1}")
+        left, closed = Dm.vector(R_["x"]), Dm.vector()
+        Dm.spmv_dev(closed, left)
+        Dm.synchronize()
+        assert_bit_equal(closed.get(), R_["Y"][0], f"{what}: device-resident vectors")
+        closed.close()
+        Dm.update_values(R_["V2"])
+        assert_bit_equal(Dm.spmv(np.full(n, np.nan), R_["x"]), R_["y2"], f"{what}: after mi_dist_update_values")
+    finally:
+        Dm.close()
+    left.close()  # (its device memory went with the handle: this frees the host object)
+
+
+def lifecycle_cycle(ref, cycle, say=None):
+    """one cycle: a push life on the FE matrix (the blocked staged step), one on the scalar band (its form rotates), three mi_dist lives"""
+    push_life(ref["push"][0], "bcsr4_ext-l1-s0", f"cycle {cycle}, FE", say)
+    form = SCALAR_FORMS[cycle % 3]
+    push_life(ref["push"][1], form, f"cycle {cycle}, scalar {form}", say)
+    for R_ in ref["dist"]:
+        dist_life(R_, f"cycle {cycle}, mi_dist {R_['exchange']} {R_['label']} ndev={R_['ndev']}")
+
+
+def lifecycle(cycles):
+    import time
+    ref = lifecycle_reference()
+    free = {}
+    t0 = time.perf_counter()
+    for cycle in range(cycles):
+        lifecycle_cycle(ref, cycle)
+        torch.cuda.synchronize()
+        free[cycle] = torch.cuda.mem_get_info()[0]
+    print(f"LIFECYCLE cycles {cycles} free4 {free[4]} last {free[cycles - 1]} seconds {time.perf_counter() - t0:.1f}", flush=True)
+    assert free[cycles - 1] >= free[4], f"{free[4] - free[cycles - 1]} bytes of device memory went in {cycles - 5} cycles"
+
+
 if __name__ == "__main__":
     mode = sys.argv[1]
     torch.cuda.set_device(0)
     if mode == "push":
         push()
+    elif mode == "lifecycle":
+        lifecycle(int(sys.argv[2]))
     else:
         dist(sys.argv[2])
     print("MULTIRANK_OK", flush=True)
