@@ -665,6 +665,50 @@ int mi_bilu4sw_solve(mi_bilu4_t F, const double* b, double* x, int sweeps_fwd, i
  * be NULL. */
 int mi_bilu4sw_info(mi_bilu4_t F, int* prepared, int* max_fwd, int* max_bwd, int* launches_last, long long* work_bytes);
 
+/* ---- 4x4-block ILU(k): the sweeps over an opt-in SINGLE-PRECISION COPY of the factor's values (mi_bilu4sp_*) ----
+ * The sweep solve streams a whole triangle of the factor per sweep, 128 bytes of values per block.  The factor is a preconditioner:
+ * right-preconditioned GMRES converges to the same solution whatever fixed linear operator plays M, so its stored coefficients
+ * need not carry 53 bits.  mi_bilu4sp_prepare adds a second representation of the device factor: a copy of the level-major
+ * values (L blocks, U blocks, inverted diagonal blocks) as float, 64 bytes per block more device memory; the double factor stays
+ * (the refactorisations and the exact solves need it).  Nothing chooses the copy automatically: mi_bilu4_solve* (form 0 and form 1)
+ * and mi_bilu4sw_* never read it, and their results, their info and every default are unchanged by it.
+ * DEFINITION (part of the interface): for every factor value v
+ *   v32 = (double)(float)v      rounded to nearest, ties to EVEN (what numpy's astype(float32) does); float SUBNORMALS are kept, not
+ *                               flushed; a finite v beyond the float range becomes +-Inf; -0 stays -0
+ * and the sweep solve with the single-precision factor is the definition of mi_bilu4sw_* above with v32 in place of v — forward,
+ * diagonal and backward — with the same ARITHMETIC of a row in double: the fma chain per block, ONE rounded subtraction per block,
+ * Dinv . s to end a backward row.  Vectors and work vectors are double; the conversion to double happens in registers and is exact.
+ * Counts are CLAMPED as before; at the clamp the result is, BIT FOR BIT, the exact solve of the rounded factor.
+ * KEPT CURRENT: once the handle is prepared, every entry point that writes the factor ends with the conversion:
+ * mi_bilu4_refactor runs it before it returns; mi_bilu4dev_refactor enqueues it on the caller's stream behind the factorisation (two
+ * more launches; a captured graph that holds a device refactor carries the conversion with it).  mi_bilu4dev_fetch writes the
+ * host factor only and converts nothing.  The solves never convert and never check the host for staleness.
+ * OVERFLOW: the conversion counts the values that are finite as double and not as float and keeps the count and the smallest
+ * block row that holds one on the device.  An overflow does not block solves: they return what the definition says (Inf / NaN
+ * where it has them); mi_bilu4sp_status is how a caller finds out, as mi_bilu4dev_status is for a refused pivot.
+ * Launches per solve: sf + 1 + sb after clamping, on the caller's stream; once prepared a solve allocates nothing, copies nothing
+ * to the host and synchronises nothing (it can be captured); an unprepared handle is prepared by its first solve, except under
+ * stream capture: MI_ERR_STATE ("not prepared").  d_x == d_b is allowed; vectors need 8-byte alignment only.
+ * ONE sweep solve of EITHER precision at a time per handle: the three work vectors are those of mi_bilu4sw_prepare, shared.
+ * mi_bilu4sw_info keeps reporting the double sweeps only.  The copy lives until mi_bilu4_destroy.
+ * MI_ERR_ARG: a null handle or vector, a negative count — before the device is touched; MI_ERR_NODEVICE: a host-only handle
+ * (_prepare, _solve*, _status, _fetch): there is no CPU fallback.  nbrows == 0: every call is a no-op. */
+/* allocates the copy and the work vectors and converts the factor as it is now (waits for the device); idempotent.  A failure
+ * part-way leaves the handle unprepared and frees what was allocated */
+int mi_bilu4sp_prepare(mi_bilu4_t F);
+int mi_bilu4sp_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s);
+int mi_bilu4sp_solve(mi_bilu4_t F, const double* b, double* x, int sweeps_fwd, int sweeps_bwd); /* host vectors: copied in and out */
+/* waits for the device, hence for the last conversion; MI_OK with *bad_block_row = -1 and *overflowed = 0 (also before prepare), or
+ * MI_ERR_ARG naming the smallest block row with a value that overflowed to Inf, and their number.  Outputs may be NULL */
+int mi_bilu4sp_status(mi_bilu4_t F, int* bad_block_row, long long* overflowed);
+/* waits, then copies the single-precision copy to the host in the HOST factor's block order (that of mi_bilu4_factor_host):
+ * 16 floats per block, row-major, cap_blocks >= nblocks.  MI_ERR_STATE on a handle that is not prepared */
+int mi_bilu4sp_fetch(mi_bilu4_t F, float* val, long long cap_blocks);
+/* *prepared; *convert_launches = conversions enqueued so far, the one of prepare included (each is two launches: the record cleared,
+ * the values written); *launches_last = launches of the last single-precision sweep solve, after clamping (0 before the first);
+ * *copy_bytes of the copy, 64 per factor block (0 until prepared).  Any output may be NULL. */
+int mi_bilu4sp_info(mi_bilu4_t F, int* prepared, int* convert_launches, int* launches_last, long long* copy_bytes);
+
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r
  * owns global rows [row_starts[r], row_starts[r+1]) and the matching slice of

@@ -18,6 +18,10 @@
 // The exact solve keeps one block of look-ahead, written for short levels bound by latency; this kernel streams a whole triangle
 // and takes the software pipeline of spmv_bcsr4 (spmv_kernels.hpp): coefficients and gathered blocks P deep, block columns one
 // round ahead, indices clamped to the row's last block, unconditional loads.
+//
+// Stored type: the kernel is a template over the type the VALUES are stored in — the device factor's doubles (mi_bilu4sw_*) or the
+// opt-in single-precision copy of them (mi_bilu4sp_*; the conversion kernel that writes it is at the end of this file).  Pattern,
+// vectors, pipeline and arithmetic are the same: a float row of a block is one 16-byte load, widened exactly in registers.
 #pragma once
 #include "bilu4_solve.hpp"
 
@@ -28,10 +32,59 @@ namespace mi355 {
 // the product's, so a lane's few blocks are all in flight at P = 4 and the 134 VGPRs (3 waves per SIMD) cost less than they buy.
 // (The depths were compared through a run-time switch that the library no longer has: the depth is this constant.)
 constexpr int kBiluSweepDepth = 4;
+// ... and over the single-precision copy of the values (mi_bilu4sp_*): a stage holds 4 VGPRs of coefficients instead of 8.  4 and 8
+// were compared by building each (-DMI355_BILU_SWEEP_DEPTH_F32=n) and timing both on the GPU: profiles/NOTES.md R11.1.
+#ifndef MI355_BILU_SWEEP_DEPTH_F32
+#define MI355_BILU_SWEEP_DEPTH_F32 4
+#endif
+constexpr int kBiluSweepDepthF32 = MI355_BILU_SWEEP_DEPTH_F32;
+
+// The values a sweep streams, in the type they are STORED in: the device factor itself (double), or its single-precision copy
+// (float, mi_bilu4sp_*: v32 = (double)(float)v, round to nearest even, subnormals kept).  Pattern, positions and vectors are the
+// view's and double either way; the arithmetic is bilu4_chain in double on the widened values.
+template <class T>
+struct Bilu4SweepVals {
+    const T* val;  // 16 per block, row-major, in the view's block order
+    const T* dinv; // backward sweep: [16 * nb] by position; forward: null
+};
+
+// a quad lane's row of one block as it lies in registers between its load and its chain: two 16-byte loads of doubles, or ONE of
+// floats, widened (exactly) only where the chain takes it, so that a stage of the pipeline holds half the registers
+template <class T>
+struct Bilu4CoefRow;
+template <>
+struct Bilu4CoefRow<double> {
+    double2 a01, a23;
+    __device__ __forceinline__ void load(const double* p)
+    {
+        const double2* r = reinterpret_cast<const double2*>(p);
+        a01 = r[0];
+        a23 = r[1];
+    }
+    __device__ __forceinline__ double2 c01() const { return a01; }
+    __device__ __forceinline__ double2 c23() const { return a23; }
+};
+template <>
+struct Bilu4CoefRow<float> {
+    float4 a;
+    __device__ __forceinline__ void load(const float* p) { a = *reinterpret_cast<const float4*>(p); }
+    __device__ __forceinline__ double2 c01() const { return make_double2((double)a.x, (double)a.y); }
+    __device__ __forceinline__ double2 c23() const { return make_double2((double)a.z, (double)a.w); }
+};
+
+// the end of a backward row: Dinv_pos . s, the quad's four entries of s exchanged
+template <class T>
+__device__ __forceinline__ double bilu4_sweep_dinv(const T* dinv, int pos, int q, double s)
+{
+    const double sv[4] = {quad_bcast<0>(s), quad_bcast<1>(s), quad_bcast<2>(s), quad_bcast<3>(s)};
+    Bilu4CoefRow<T> d;
+    d.load(dinv + 16 * (size_t)pos + 4 * q);
+    return bilu4_chain(d.c01(), d.c23(), sv);
+}
 
 // one sweep: out_i = src_i - sum_k A_ik old_{col k} over the off-diagonal blocks of the view (BWD: then Dinv_i . that)
-template <bool BWD, bool AL, int P>
-__global__ __launch_bounds__(kWG) void bilu4_sweep(Bilu4SweepView V, int nb, const double* src, const double* __restrict__ old, double* out)
+template <bool BWD, bool AL, int P, class T>
+__global__ __launch_bounds__(kWG) void bilu4_sweep(Bilu4SweepView V, Bilu4SweepVals<T> A, int nb, const double* src, const double* __restrict__ old, double* out)
 {
     const int g = blockIdx.x * kWG + threadIdx.x;
     const int pos = g >> 2, q = g & 3;
@@ -42,16 +95,14 @@ __global__ __launch_bounds__(kWG) void bilu4_sweep(Bilu4SweepView V, int nb, con
     if (ia0 < ia1) {
         const int last = ia1 - 1;
         const unsigned* ucol = reinterpret_cast<const unsigned*>(V.col);
-        const double* cq = V.val + 4 * q;
-        double2 a01[P], a23[P];
+        const T* cq = A.val + 4 * q;
+        Bilu4CoefRow<T> a[P];
         double t[P][4];
         unsigned cn[P]; // columns of blocks ia+P+k
 #pragma unroll
         for (int k = 0; k < P; k++) {
             const int blk = min(ia0 + k, last);
-            const double2* r = reinterpret_cast<const double2*>(cq + 16 * (size_t)blk);
-            a01[k] = r[0];
-            a23[k] = r[1];
+            a[k].load(cq + 16 * (size_t)blk);
             cn[k] = ucol[blk];
         }
 #pragma unroll
@@ -61,38 +112,93 @@ __global__ __launch_bounds__(kWG) void bilu4_sweep(Bilu4SweepView V, int nb, con
         for (int ia = ia0; ia < ia1; ia += P) {
 #pragma unroll
             for (int k = 0; k < P; k++) {
-                const double2 c01 = a01[k], c23 = a23[k];
+                const double2 c01 = a[k].c01(), c23 = a[k].c23();
                 const double u[4] = {t[k][0], t[k][1], t[k][2], t[k][3]};
                 // refill stage k with block ia+k+P (its column arrived a round ago), then ask for the column of block ia+k+2P
                 const int nx = min(ia + k + P, last);
-                const double2* nr = reinterpret_cast<const double2*>(cq + 16 * (size_t)nx);
-                a01[k] = nr[0];
-                a23[k] = nr[1];
+                a[k].load(cq + 16 * (size_t)nx);
                 bilu4_load4<AL>(old, cn[k], t[k]);
                 cn[k] = ucol[min(ia + k + 2 * P, last)];
                 if (ia + k < ia1) s = __dsub_rn(s, bilu4_chain(c01, c23, u));
             }
         }
     }
-    if (BWD) {
-        const double sv[4] = {quad_bcast<0>(s), quad_bcast<1>(s), quad_bcast<2>(s), quad_bcast<3>(s)};
-        const double2* d = reinterpret_cast<const double2*>(V.dinv + 16 * (size_t)pos + 4 * q);
-        s = bilu4_chain(d[0], d[1], sv);
-    }
+    if (BWD) s = bilu4_sweep_dinv(A.dinv, pos, q, s);
     out[4 * (size_t)row + q] = s;
 }
 
 // the diagonal pass x^0_i = Dinv_i . t_i over the backward view: the end of the backward row, without its blocks.  t may be x0.
-__global__ __launch_bounds__(kWG) void bilu4_sweep_diag(Bilu4SweepView V, int nb, const double* t, double* x0)
+template <class T>
+__global__ __launch_bounds__(kWG) void bilu4_sweep_diag(Bilu4SweepView V, const T* dinv, int nb, const double* t, double* x0)
 {
     const int g = blockIdx.x * kWG + threadIdx.x;
     const int pos = g >> 2, q = g & 3;
     if (pos >= nb) return;
     const int row = V.perm[pos];
-    const double s = t[4 * (size_t)row + q];
-    const double sv[4] = {quad_bcast<0>(s), quad_bcast<1>(s), quad_bcast<2>(s), quad_bcast<3>(s)};
-    const double2* d = reinterpret_cast<const double2*>(V.dinv + 16 * (size_t)pos + 4 * q);
-    x0[4 * (size_t)row + q] = bilu4_chain(d[0], d[1], sv);
+    x0[4 * (size_t)row + q] = bilu4_sweep_dinv(dinv, pos, q, t[4 * (size_t)row + q]);
+}
+
+// ---------------------------------------------------------------- the single-precision copy (mi_bilu4sp_*)
+// What a conversion leaves behind for mi_bilu4sp_status: how many values were finite as double and are not as float, and the smallest
+// block row that holds one.
+constexpr int kBiluSpNoRow = 0x7fffffff;
+struct Bilu4SpRecord {
+    unsigned long long overflowed;
+    int row;
+};
+
+// the three arrays of the level-major factor a conversion walks, as one range of ROWS OF BLOCKS (4 values, one lane each):
+// [0, end[0]) the L blocks, [end[0], end[1]) the U blocks, [end[1], end[2]) the inverted diagonal blocks by backward position
+struct Bilu4SpConvert {
+    const double* src[3];
+    float* dst[3];
+    long long end[3];
+    const int* ptr[2];  // forward, backward: [nb + 1] by position, to name the block row of an overflow
+    const int* perm[2]; // position -> block row
+    int nb;
+    Bilu4SpRecord* rec;
+};
+
+__global__ void bilu4sp_reset(Bilu4SpRecord* rec)
+{
+    rec->overflowed = 0;
+    rec->row = kBiluSpNoRow;
+}
+
+// dst = (float)src, round to nearest even, for every value of the factor; one lane per row of a block: two 16-byte loads, one
+// 16-byte store.  The rare overflow looks its block row up (a binary search of the position pointers) and reports it.
+__global__ __launch_bounds__(kWG) void bilu4sp_convert(Bilu4SpConvert C)
+{
+    const long long g = (long long)blockIdx.x * kWG + threadIdx.x;
+    if (g >= C.end[2]) return;
+    const int part = g < C.end[0] ? 0 : g < C.end[1] ? 1 : 2;
+    const long long r = g - (part ? C.end[part - 1] : 0); // row r & 3 of block r >> 2 of its array
+    const double2* p = reinterpret_cast<const double2*>(C.src[part] + 4 * r);
+    const double2 v01 = p[0], v23 = p[1];
+    const double v[4] = {v01.x, v01.y, v23.x, v23.y};
+    const float4 f = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+    reinterpret_cast<float4*>(C.dst[part])[r] = f;
+    const float w[4] = {f.x, f.y, f.z, f.w};
+    int bad = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) bad += (isfinite(v[k]) && !isfinite(w[k])) ? 1 : 0;
+    if (bad) {
+        const long long blk = r >> 2;
+        int pos;
+        if (part == 2) {
+            pos = (int)blk;
+        } else { // the last position whose first block is <= blk (positions without blocks repeat the pointer: skipped)
+            const int* ptr = C.ptr[part];
+            int lo = 0, hi = C.nb; // ptr[lo] <= blk < ptr[hi]
+            while (hi - lo > 1) {
+                const int mid = lo + (hi - lo) / 2;
+                if (ptr[mid] <= blk) lo = mid; else hi = mid;
+            }
+            pos = lo;
+        }
+        atomicAdd(&C.rec->overflowed, (unsigned long long)bad);
+        atomicMin(&C.rec->row, C.perm[part == 0 ? 0 : 1][pos]);
+    }
 }
 
 } // namespace mi355

@@ -3,7 +3,8 @@
 // (bilu4_solve.hpp) or, where the handle was told so (mi_bilu4_set_solve_form), by ONE launch of persistent workgroups
 // (bilu4_solve_one.hpp, mi_bilu4one_*); mi_bilu4dev_* refactors on the GPU, into the same device copies, level by level
 // (bilu4_factor.hpp); mi_bilu4sw_* applies the same device factor by a fixed number of Jacobi sweeps per triangle, one launch per
-// sweep (bilu4_sweep.hpp).
+// sweep (bilu4_sweep.hpp); mi_bilu4sp_* the same sweeps over an opt-in single-precision copy of the factor's values, which every
+// entry point that writes the factor then keeps current.
 // No CPU fallback: the solve and the device refactor need a HIP device; the planning and host factorisation entry points need none.
 #include "capi_internal.hpp"
 #include "bilu4_plan.hpp"
@@ -62,6 +63,15 @@ struct Bilu4SweepWork {
     DevArray<double> w[3];
 };
 
+// the single-precision copy of the level-major values (mi_bilu4sp_prepare): L blocks, U blocks, inverted diagonal blocks, in the
+// order of lev[0].val, lev[1].val and lev[1].dinv; rec: what the last conversion found (Bilu4SpRecord)
+struct Bilu4SpCopy {
+    bool prepared = false;
+    int convert_launches = 0, launches_last = 0;
+    DevArray<float> val[2], dinv;
+    DevArray<Bilu4SpRecord> rec;
+};
+
 struct mi_bilu4_s {
     int device = -1; // -1: host-only handle (mi_bilu4_create_host)
     int fill = 0;
@@ -76,7 +86,8 @@ struct mi_bilu4_s {
     Bilu4DevTables dev;
     Bilu4OneTables one;
     Bilu4SweepWork sw;
-    ~mi_bilu4_s() { sw = {}, one = {}, lev[0] = {}, lev[1] = {}, d_b = {}, d_x = {}, dev = {}; } // the order the handle has always been freed in (sw: newest first)
+    Bilu4SpCopy sp;
+    ~mi_bilu4_s() { sp = {}, sw = {}, one = {}, lev[0] = {}, lev[1] = {}, d_b = {}, d_x = {}, dev = {}; } // the order the handle has always been freed in (newest first)
     const Bilu4Pattern& pat() const { return sched.pat; }
     Bilu4FactorView factor_view() const
     {
@@ -253,6 +264,28 @@ static int bilu_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, hipStre
     return bilu_solve_launch(F, d_b, d_x, s);
 }
 
+// The single-precision copy written from the level-major factor as it lies on the device now, on stream s: two launches (the record
+// of mi_bilu4sp_status cleared, then the values), nothing allocated or synchronised.  S: the copy to write — the handle's, or the
+// one mi_bilu4sp_prepare is still building.
+static int bilu_sp_convert(const mi_bilu4_s* F, Bilu4SpCopy& S, hipStream_t s)
+{
+    Bilu4SpConvert C{};
+    const long long nL = (long long)F->lev[0].src.size(), nU = (long long)F->lev[1].src.size(), nb = F->pat().nb;
+    const double* const src[3] = {F->lev[0].val, F->lev[1].val, F->lev[1].dinv};
+    float* const dst[3] = {S.val[0], S.val[1], S.dinv};
+    const long long blocks[3] = {nL, nU, nb};
+    long long end = 0;
+    for (int a = 0; a < 3; a++) C.src[a] = src[a], C.dst[a] = dst[a], C.end[a] = (end += 4 * blocks[a]);
+    for (int b = 0; b < 2; b++) C.ptr[b] = F->lev[b].ptr, C.perm[b] = F->lev[b].perm;
+    C.nb = (int)nb;
+    C.rec = S.rec;
+    hipLaunchKernelGGL(bilu4sp_reset, dim3(1), dim3(1), 0, s, C.rec);
+    hipLaunchKernelGGL(bilu4sp_convert, dim3((unsigned)((end + kWG - 1) / kWG)), dim3(kWG), 0, s, C);
+    HIP_TRY(hipGetLastError());
+    S.convert_launches++;
+    return MI_OK;
+}
+
 static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, bool device, mi_bilu4_t* out)
 {
     CHECK_ARG(out, "null output handle");
@@ -323,7 +356,11 @@ extern "C" int mi_bilu4_refactor(mi_bilu4_t F, const double* coef, int layout)
     if (F->device < 0) return MI_OK;
     // solves already enqueued read the old values: wait for them, then replace (a Newton step refactors between solves)
     HIP_TRY(hipDeviceSynchronize());
-    return bilu_move_values(F, true);
+    if ((rc = bilu_move_values(F, true)) || !F->sp.prepared) return rc;
+    // the single-precision copy follows the factor before the call returns
+    if ((rc = bilu_sp_convert(F, F->sp, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return MI_OK;
 }
 
 extern "C" int mi_bilu4_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s)
@@ -450,7 +487,7 @@ extern "C" int mi_bilu4dev_refactor(mi_bilu4_t F, const double* d_coef, int layo
         }
     }
     HIP_TRY(hipGetLastError());
-    return MI_OK;
+    return F->sp.prepared ? bilu_sp_convert(F, F->sp, st) : MI_OK; // behind the factorisation, on the same stream (and in the same graph)
 }
 
 extern "C" int mi_bilu4dev_status(mi_bilu4_t F, int* bad_row)
@@ -668,18 +705,23 @@ static int bilu_sw_max(const mi_bilu4_s* F, int b) { return std::max(F->sched.sw
 static dim3 bilu_sw_grid(int nb) { return dim3((unsigned)((nb + kBiluRowsPerWG - 1) / kBiluRowsPerWG)); }
 
 // one sweep; AL by the vector that is gathered (the work vectors are aligned, b need not be)
-template <bool BWD>
-static void bilu_sw_launch(const Bilu4SweepView& V, int nb, const double* src, const double* old, double* out, hipStream_t s)
+template <bool BWD, class T>
+static void bilu_sw_launch(const Bilu4SweepView& V, const Bilu4SweepVals<T>& A, int nb, const double* src, const double* old, double* out, hipStream_t s)
 {
+    constexpr int P = std::is_same<T, float>::value ? kBiluSweepDepthF32 : kBiluSweepDepth;
     bilu_by_alignment(old, [&](auto al) {
-        hipLaunchKernelGGL((bilu4_sweep<BWD, decltype(al)::value, kBiluSweepDepth>), bilu_sw_grid(nb), dim3(kWG), 0, s, V, nb, src, old, out);
+        hipLaunchKernelGGL((bilu4_sweep<BWD, decltype(al)::value, P, T>), bilu_sw_grid(nb), dim3(kWG), 0, s, V, A, nb, src, old, out);
         return 0;
     });
 }
 
 // sf forward sweeps, the diagonal pass, sb backward sweeps, on the caller's stream: launches only.  d_b is read by every forward
 // sweep and never written unless it is d_x; d_x is written by the LAST launch only, when d_b is no longer needed.
-static int bilu_sw_solve_launch(mi_bilu4_s* F, const double* d_b, double* d_x, int sf, int sb, hipStream_t s)
+// Lv, Uv: the values of the two triangles in the type they are streamed in (the factor's own, or its single-precision copy);
+// *launches_last: the count of the precision that was asked for.
+template <class T>
+static int bilu_sw_solve_launch(mi_bilu4_s* F, const Bilu4SweepVals<T>& Lv, const Bilu4SweepVals<T>& Uv, int* launches_last, const double* d_b, double* d_x, int sf, int sb,
+                                hipStream_t s)
 {
     static_assert(kBiluRowsPerWG * 4 == kWG, "four lanes per block row");
     const int nb = F->pat().nb;
@@ -689,19 +731,19 @@ static int bilu_sw_solve_launch(mi_bilu4_s* F, const double* d_b, double* d_x, i
     const Bilu4SweepView L = F->lev[0].view(), U = F->lev[1].view();
     const double* t = d_b; // t^0
     for (int k = 0; k < sf; k++) {
-        bilu_sw_launch<false>(L, nb, d_b, t, w[k & 1], s);
+        bilu_sw_launch<false>(L, Lv, nb, d_b, t, w[k & 1], s);
         t = w[k & 1];
     }
     double* const pong[2] = {t == w[0] ? w[1] : w[0], w[2]}; // free of t, whichever vector holds it
     double* x = sb == 0 ? d_x : pong[0];
-    hipLaunchKernelGGL(bilu4_sweep_diag, bilu_sw_grid(nb), dim3(kWG), 0, s, U, nb, t, x);
+    hipLaunchKernelGGL(bilu4_sweep_diag<T>, bilu_sw_grid(nb), dim3(kWG), 0, s, U, Uv.dinv, nb, t, x);
     for (int k = 0; k < sb; k++) {
         double* const out = k == sb - 1 ? d_x : pong[(k + 1) & 1];
-        bilu_sw_launch<true>(U, nb, t, x, out, s);
+        bilu_sw_launch<true>(U, Uv, nb, t, x, out, s);
         x = out;
     }
     HIP_TRY(hipGetLastError());
-    F->sw.launches_last = sf + 1 + sb;
+    *launches_last = sf + 1 + sb;
     return MI_OK;
 }
 
@@ -724,7 +766,7 @@ static int bilu_sw_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, int 
             return fail(MI_ERR_STATE, "mi_bilu4sw_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sw_prepare allocates: call it before the capture)");
         if (const int rc = mi_bilu4sw_prepare(F)) return rc;
     }
-    return bilu_sw_solve_launch(F, d_b, d_x, sf, sb, s);
+    return bilu_sw_solve_launch<double>(F, {F->lev[0].val, nullptr}, {F->lev[1].val, F->lev[1].dinv}, &F->sw.launches_last, d_b, d_x, sf, sb, s);
 }
 
 extern "C" int mi_bilu4sw_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s)
@@ -751,5 +793,98 @@ extern "C" int mi_bilu4sw_info(mi_bilu4_t F, int* prepared, int* max_fwd, int* m
     if (max_bwd) *max_bwd = bilu_sw_max(F, 1);
     if (launches_last) *launches_last = F->sw.launches_last;
     if (work_bytes) *work_bytes = F->sw.prepared ? 3LL * 4 * F->pat().nb * (long long)sizeof(double) : 0;
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------- mi_bilu4sp_*: the sweeps over a single-precision copy of the values
+extern "C" int mi_bilu4sp_prepare(mi_bilu4_t F)
+{
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_prepare"); rc != kBiluGo) return rc;
+    if (F->sp.prepared) return MI_OK;
+    Bilu4SpCopy S; // moves into the handle once it is complete; a failure on the way frees what there is
+    int rc;
+    if ((rc = dev_alloc(S.val[0], 16 * std::max<size_t>(F->lev[0].src.size(), 1))) || (rc = dev_alloc(S.val[1], 16 * std::max<size_t>(F->lev[1].src.size(), 1))) ||
+        (rc = dev_alloc(S.dinv, 16 * (size_t)F->pat().nb, 1)) || (rc = dev_alloc(S.rec, 1)))
+        return rc;
+    // the factor as it is now: behind everything that was enqueued to write it, and finished before the first solve on any stream
+    HIP_TRY(hipDeviceSynchronize());
+    if ((rc = bilu_sp_convert(F, S, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = mi_bilu4sw_prepare(F))) return rc; // the same three work vectors
+    S.prepared = true;
+    F->sp = std::move(S);
+    return MI_OK;
+}
+
+static int bilu_sp_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, int sf, int sb, hipStream_t s)
+{
+    if (!F->sp.prepared) {
+        if (stream_is_capturing(s))
+            return fail(MI_ERR_STATE, "mi_bilu4sp_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sp_prepare allocates and converts: call it before the capture)");
+        if (const int rc = mi_bilu4sp_prepare(F)) return rc;
+    }
+    return bilu_sw_solve_launch<float>(F, {F->sp.val[0], nullptr}, {F->sp.val[1], F->sp.dinv}, &F->sp.launches_last, d_b, d_x, sf, sb, s);
+}
+
+extern "C" int mi_bilu4sp_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s)
+{
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_solve_dev", bilu_sw_bad_counts(sweeps_fwd, sweeps_bwd), d_b && d_x ? nullptr : "null vector"); rc != kBiluGo) return rc;
+    return bilu_sp_solve_any(F, d_b, d_x, sweeps_fwd, sweeps_bwd, (hipStream_t)s);
+}
+
+extern "C" int mi_bilu4sp_solve(mi_bilu4_t F, const double* b, double* x, int sweeps_fwd, int sweeps_bwd)
+{
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_solve", bilu_sw_bad_counts(sweeps_fwd, sweeps_bwd), b && x ? nullptr : "null vector"); rc != kBiluGo) return rc;
+    const size_t bytes = sizeof(double) * 4 * (size_t)F->pat().nb;
+    HIP_TRY(hipMemcpy(F->d_b, b, bytes, hipMemcpyHostToDevice));
+    if (const int rc = bilu_sp_solve_any(F, F->d_b, F->d_x, sweeps_fwd, sweeps_bwd, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(x, F->d_x, bytes, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4sp_status(mi_bilu4_t F, int* bad_block_row, long long* overflowed)
+{
+    if (F && bad_block_row) *bad_block_row = -1;
+    if (F && overflowed) *overflowed = 0;
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_status"); rc != kBiluGo) return rc;
+    if (!F->sp.prepared) return MI_OK; // no copy yet
+    HIP_TRY(hipDeviceSynchronize());
+    Bilu4SpRecord R{};
+    HIP_TRY(hipMemcpy(&R, F->sp.rec, sizeof(R), hipMemcpyDeviceToHost));
+    if (R.overflowed == 0) return MI_OK;
+    if (bad_block_row) *bad_block_row = R.row;
+    if (overflowed) *overflowed = (long long)R.overflowed;
+    return fail(MI_ERR_ARG, "mi_bilu4sp: " + std::to_string(R.overflowed) + " finite value(s) of the factor are beyond the range of float and are Inf in the single-precision copy; the first in block row " +
+                                std::to_string(R.row));
+}
+
+extern "C" int mi_bilu4sp_fetch(mi_bilu4_t F, float* val, long long cap_blocks)
+{
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_fetch", nullptr, val ? nullptr : "null val"); rc != kBiluGo) return rc;
+    CHECK_ARG(cap_blocks >= F->pat().nblocks(), "array too short: need mi_bilu4_info's nblocks blocks of 16 floats");
+    if (!F->sp.prepared) return fail(MI_ERR_STATE, "mi_bilu4sp_fetch: the handle is not prepared (mi_bilu4sp_prepare)");
+    HIP_TRY(hipDeviceSynchronize());
+    // as bilu_move_values brings the double factor back: each level-major block to its place in the host factor's order
+    std::vector<float> v;
+    auto fetch = [&](const float* dev, size_t n, auto&& host_block) -> int {
+        if (!n) return MI_OK;
+        v.resize(16 * n);
+        HIP_TRY(hipMemcpy(v.data(), dev, sizeof(float) * v.size(), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < n; k++) memcpy(val + 16 * (size_t)host_block(k), &v[16 * k], sizeof(float) * 16);
+        return MI_OK;
+    };
+    int rc;
+    for (int b = 0; b < 2; b++)
+        if ((rc = fetch(F->sp.val[b], F->lev[b].src.size(), [&](size_t k) { return F->lev[b].src[k]; }))) return rc;
+    return fetch(F->sp.dinv, (size_t)F->pat().nb, [&](size_t q) { return F->pat().diag[F->sched.sweep[1].perm[q]]; });
+}
+
+extern "C" int mi_bilu4sp_info(mi_bilu4_t F, int* prepared, int* convert_launches, int* launches_last, long long* copy_bytes)
+{
+    CHECK_ARG(F, "null handle");
+    if (prepared) *prepared = F->sp.prepared ? 1 : 0;
+    if (convert_launches) *convert_launches = F->sp.convert_launches;
+    if (launches_last) *launches_last = F->sp.launches_last;
+    if (copy_bytes) *copy_bytes = F->sp.prepared ? (long long)(16 * sizeof(float)) * F->pat().nblocks() : 0;
     return MI_OK;
 }

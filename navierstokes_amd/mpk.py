@@ -184,6 +184,12 @@ def lib():
         "mi_bilu4sw_solve_dev": [_vp, _vp, _vp, i, i, _vp],
         "mi_bilu4sw_solve": [_vp, _vp, _vp, i, i],
         "mi_bilu4sw_info": [_vp, P(i), P(i), P(i), P(i), P(ll)],
+        "mi_bilu4sp_prepare": [_vp],
+        "mi_bilu4sp_solve_dev": [_vp, _vp, _vp, i, i, _vp],
+        "mi_bilu4sp_solve": [_vp, _vp, _vp, i, i],
+        "mi_bilu4sp_status": [_vp, P(i), P(ll)],
+        "mi_bilu4sp_fetch": [_vp, _vp, ll],
+        "mi_bilu4sp_info": [_vp, P(i), P(i), P(i), P(ll)],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -656,16 +662,44 @@ class bilu4:
         return dict(prepared=bool(pr.value), eligible=bool(el.value), workgroups=wg.value, nchunks=(nch[0], nch[1]), max_deps=(md[0], md[1]),
                     plan_bytes=by.value)
 
-    def sweeps(self, fwd, bwd=None):
+    def sweeps(self, fwd, bwd=None, precision="f64"):
         """The same factor applied by `fwd` Jacobi sweeps of the forward triangle and `bwd` (default: fwd) of the backward one
         instead of the exact solve (mi_bilu4sw_*): a view with .solve(x, b), which is what GMRES takes as M.  Counts above
-        levels - 1 are clamped: there the result is the exact solve's, bit for bit."""
-        return bilu4_sweeps(self, fwd, fwd if bwd is None else bwd)
+        levels - 1 are clamped: there the result is the exact solve's, bit for bit.  precision="f32": the sweeps stream the
+        single-precision copy of the factor's values (mi_bilu4sp_*); vectors and arithmetic stay double."""
+        return bilu4_sweeps(self, fwd, fwd if bwd is None else bwd, precision)
 
-    def prepare_sweeps(self):
-        """Allocate the work vectors of the sweep solve (mi_bilu4sw_prepare; idempotent): needed before a graph capture."""
-        check(lib().mi_bilu4sw_prepare(self.handle))
+    def prepare_sweeps(self, precision="f64"):
+        """Allocate the work vectors of the sweep solve (mi_bilu4sw_prepare; idempotent): needed before a graph capture.
+        precision="f32": also the single-precision copy of the factor, converted now and kept current by every refactor
+        (mi_bilu4sp_prepare)."""
+        check((lib().mi_bilu4sp_prepare if _sweep_precision(precision) else lib().mi_bilu4sw_prepare)(self.handle))
         return self
+
+    def sweep_status_f32(self):
+        """Wait for the last conversion to single precision; MiError (MI_ERR_ARG, naming the block row; .bad_block_row and
+        .overflowed on the exception) when finite values of the factor became Inf in the copy (mi_bilu4sp_status)."""
+        bad, cnt = _c.c_int(), _c.c_longlong()
+        status = lib().mi_bilu4sp_status(self.handle, _c.byref(bad), _c.byref(cnt))
+        try:
+            check(status)
+        except MiError as e:
+            e.bad_block_row, e.overflowed = bad.value, cnt.value
+            raise
+        return self
+
+    def fetch_f32(self):
+        """The single-precision copy as (nblocks, 4, 4) float32 in the host factor's block order (mi_bilu4sp_fetch)."""
+        nblk = self.info()["nblocks"]
+        val = np.zeros((max(nblk, 1), 4, 4), np.float32)
+        check(lib().mi_bilu4sp_fetch(self.handle, val.ctypes.data, max(nblk, 1)))
+        return val[:nblk]
+
+    def sweep_info_f32(self):
+        """dict(prepared, convert_launches, launches_last, copy_bytes) — mi_bilu4sp_info."""
+        pr, cv, la, by = _c.c_int(), _c.c_int(), _c.c_int(), _c.c_longlong()
+        check(lib().mi_bilu4sp_info(self.handle, _c.byref(pr), _c.byref(cv), _c.byref(la), _c.byref(by)))
+        return dict(prepared=bool(pr.value), convert_launches=cv.value, launches_last=la.value, copy_bytes=by.value)
 
     def sweep_info(self):
         """dict(prepared, max_fwd, max_bwd, launches_last, work_bytes) — mi_bilu4sw_info."""
@@ -707,11 +741,20 @@ class bilu4:
             pass
 
 
-class bilu4_sweeps:
-    """bilu4.sweeps(fwd, bwd): the factors of F applied by fixed numbers of Jacobi sweeps.  It shares F's handle and owns nothing."""
+def _sweep_precision(precision):
+    """False for "f64", True for "f32"."""
+    if precision not in ("f64", "f32"):
+        raise ValueError('bilu4: precision must be "f64" or "f32"')
+    return precision == "f32"
 
-    def __init__(self, F, fwd, bwd):
-        self.F, self.fwd, self.bwd = F, int(fwd), int(bwd)
+
+class bilu4_sweeps:
+    """bilu4.sweeps(fwd, bwd, precision): the factors of F applied by fixed numbers of Jacobi sweeps.  It shares F's handle and owns
+    nothing."""
+
+    def __init__(self, F, fwd, bwd, precision="f64"):
+        self.F, self.fwd, self.bwd, self.precision = F, int(fwd), int(bwd), precision
+        self._f32 = _sweep_precision(precision)
         if self.fwd < 0 or self.bwd < 0:
             raise ValueError("bilu4.sweeps: negative sweep count")
 
@@ -719,11 +762,14 @@ class bilu4_sweeps:
         """x = the sweep operator applied to b.  CUDA tensors: asynchronous on torch's current stream, x may be b; numpy arrays:
         copied in and out."""
         n = 4 * self.F.nbrows
+        L = lib()
         if _is_torch(b):
-            check(lib().mi_bilu4sw_solve_dev(self.F.handle, _dev_ptr(b, n, "b"), _dev_ptr(x, n, "x"), self.fwd, self.bwd, _stream_ptr()))
+            dev = L.mi_bilu4sp_solve_dev if self._f32 else L.mi_bilu4sw_solve_dev
+            check(dev(self.F.handle, _dev_ptr(b, n, "b"), _dev_ptr(x, n, "x"), self.fwd, self.bwd, _stream_ptr()))
         else:
             xx = _host_f64(x, n, "x", writable=True)
-            check(lib().mi_bilu4sw_solve(self.F.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data, self.fwd, self.bwd))
+            host = L.mi_bilu4sp_solve if self._f32 else L.mi_bilu4sw_solve
+            check(host(self.F.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data, self.fwd, self.bwd))
         return x
 
 

@@ -17,12 +17,21 @@ of the byte model s L + D + s (U + D) and the rate they amount to, and GMRES(30)
 M = F.sweeps(s), beside the exact solve's.  The record names the depth of the kernel's software pipeline the library was built
 with (pipeline_depth: kBiluSweepDepth of bilu4_sweep.hpp).
 
-    python3 tools/bench_ilu.py --sweeps 1,2,3,4,6,8 [--cells 68] [--fill 0]
+    python3 tools/bench_ilu.py --sweeps 1,2,3,4,6,8 [--cells 68] [--fill 0] [--precision f64|f32|both]
+
+--precision (with --sweeps; default f64): which values the sweeps stream — the double factor, its single-precision copy
+(mi_bilu4sp_*, mpk.bilu4.sweeps(.., precision="f32")), or both on the SAME handle in the same process.  With f32 the record carries
+per count the same figures for the copy under "f32" (byte model: 68 bytes per block and 64 per inverted diagonal block), the ratio
+f32 / f64 measured and modelled, the cost of one more sweep pair in each precision (from consecutive counts), the copy's bytes, the
+depth of the f32 pipeline, and the microseconds of ONE conversion: mi_bilu4dev_refactor timed on this handle before the copy
+exists and again with the conversion attached (median of single refactors between device events), and their difference.
 
 --refactor measures the two refactorisations instead, in one process, and appends one record (tool = "bench_ilu_refactor"): the
 wall time of the host path mi_bilu4_refactor (factor on host threads, wait for the device, upload; median of --host-reps calls),
 the time of mi_bilu4dev_refactor between device events (median of --reps single refactors after warm-ups), launches per refactor,
-the bytes of the device plan, and whether the fetched device factor equals the host factor bit for bit.
+the bytes of the device plan, and whether the fetched device factor equals the host factor bit for bit; then the device refactor
+again with the single-precision copy prepared (the conversion attached: two more launches), and whether the fetched copy is the
+rounded host factor bit for bit.
 
     python3 tools/bench_ilu.py --refactor [--cells 68] [--fill 0] [--reps 30] [--host-reps 3] [--no-append]
 """
@@ -49,6 +58,23 @@ def timed_us(fn, warm, reps):
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
+def dev_refactor_us(F, dcoef, reps):
+    """Single device refactors between device events, after warm-ups: the list of their microseconds."""
+    import torch
+    for _ in range(3):
+        F.refactor_dev(dcoef)
+    F.factor_status()
+    us = []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(reps):
+        e0.record()
+        F.refactor_dev(dcoef)
+        e1.record()
+        e1.synchronize()
+        us.append(e0.elapsed_time(e1) * 1e3)
+    return us
+
+
 def refactor_record(a):
     import numpy as np
     import torch
@@ -70,33 +96,31 @@ def refactor_record(a):
     F.prepare_dev()
     prepare_s = time.perf_counter() - t0
     dcoef = torch.from_numpy(np.ascontiguousarray(new)).cuda()
-    for _ in range(3):
-        F.refactor_dev(dcoef)
-    F.factor_status()
-    dev_us = []
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(a.reps):
-        e0.record()
-        F.refactor_dev(dcoef)
-        e1.record()
-        e1.synchronize()
-        dev_us.append(e0.elapsed_time(e1) * 1e3)
+    dev_us = dev_refactor_us(F, dcoef, a.reps)
     F.factor_status().fetch_factor()
     same = bool(np.array_equal(F.factor_host()[3].view(np.uint64), host_factor.view(np.uint64)))
     dinfo = F.info_dev()
     probe = mpk.bilu4dev_plan_probe(nb, bp, bc, a.fill)
     dev_med = float(np.median(dev_us))
+    F.prepare_sweeps(precision="f32")
+    sp_us = dev_refactor_us(F, dcoef, a.reps)
+    F.factor_status().sweep_status_f32()
+    with np.errstate(all="ignore"):
+        sp_same = bool(np.array_equal(F.fetch_f32().view(np.uint32), host_factor.astype(np.float32).view(np.uint32)))
+    sp_med = float(np.median(sp_us))
     out = dict(tool="bench_ilu_refactor", cells=a.cells, block_rows=nb, blocks=int(len(bc)), fill=a.fill, factor_blocks=info["nblocks"],
                fwd_levels=info["fwd_levels"], host_refactor_seconds=round(float(np.median(host_s)), 4), host_refactor_calls=a.host_reps,
                host_factor_only_seconds=round(host_only_s, 4), dev_refactor_us=round(dev_med, 1), dev_refactor_us_min=round(min(dev_us), 1),
                dev_refactor_us_max=round(max(dev_us), 1), dev_refactor_reps=a.reps, launches_per_refactor=dinfo["launches"],
                us_per_launch=round(dev_med / dinfo["launches"], 2), plan_bytes=dinfo["plan_bytes"], update_pairs=probe["update_pairs"],
-               prepare_seconds=round(prepare_s, 3), host_over_dev=round(float(np.median(host_s)) * 1e6 / dev_med, 1), device_factor_equals_host_bits=same)
+               prepare_seconds=round(prepare_s, 3), host_over_dev=round(float(np.median(host_s)) * 1e6 / dev_med, 1), device_factor_equals_host_bits=same,
+               dev_refactor_with_f32_copy_us=round(sp_med, 1), convert_us=round(sp_med - dev_med, 1), f32_copy_bytes=F.sweep_info_f32()["copy_bytes"],
+               f32_copy_equals_rounded_host_bits=sp_same)
     F.close()
     return out
 
 
-def sweeps_record(a, F, A, b, db, dx, dy):
+def sweeps_record(a, F, A, b, db, dx, dy, coef):
     """The sweep solve on the handle the forms were measured on (in whatever form it was left: the sweeps do not depend on it)."""
     import re
     import numpy as np
@@ -114,24 +138,59 @@ def sweeps_record(a, F, A, b, db, dx, dy):
     reps = max(a.solves, 200)
     rec = dict(pipeline_depth=depth, max=[F.sweep_info()["max_fwd"], F.sweep_info()["max_bwd"]], work_bytes=F.sweep_info()["work_bytes"], l_bytes=l_bytes, u_bytes=u_bytes,
                dinv_bytes=d_bytes, counts={})
+    precisions = ["f64", "f32"] if a.precision == "both" else [a.precision]
+    # per precision: bytes of a block with its column, of an inverted diagonal block
+    per_block = {"f64": (132, 128), "f32": (68, 64)}
+    if "f32" in precisions:
+        src = open(os.path.join(ROOT, "navierstokes_amd", "csrc", "bilu4_sweep.hpp")).read()
+        depth32 = int(os.environ.get("MI355_BILU_SWEEP_DEPTH_F32") or re.search(r"#define MI355_BILU_SWEEP_DEPTH_F32 (\d+)", src).group(1))
+        dcoef = torch.from_numpy(np.ascontiguousarray(coef)).cuda()  # the values the handle holds: the factor does not change
+        F.prepare_dev()
+        without = float(np.median(dev_refactor_us(F, dcoef, 30)))
+        F.prepare_sweeps(precision="f32")
+        attached = float(np.median(dev_refactor_us(F, dcoef, 30)))
+        F.factor_status().sweep_status_f32()
+        rec.update(pipeline_depth_f32=depth32, f32_copy_bytes=F.sweep_info_f32()["copy_bytes"], dev_refactor_us=round(without, 1),
+                   dev_refactor_with_f32_copy_us=round(attached, 1), convert_us=round(attached - without, 1))
     for s in [int(c) for c in a.sweeps.split(",") if c]:
-        V = F.sweeps(s)
-        us = timed_us(lambda: V.solve(dx, db), 20, reps)
-        launches = F.sweep_info()["launches_last"]
         sf, sb = min(s, rec["max"][0]), min(s, rec["max"][1])
-        model = sf * l_bytes + d_bytes + sb * (u_bytes + d_bytes) + launches * vec
-        dx.zero_()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        its, hist = mpk.GMRES(A, db, dx, M=V, restart=30, rtol=1e-8, maxiter=a.maxiter)
-        torch.cuda.synchronize()
-        sec = time.perf_counter() - t0
-        mpk.SpMV_BCSR(dy, dx, A)
-        true = float(np.linalg.norm(b - dy.cpu().numpy()) / np.linalg.norm(b))
-        rec["counts"][str(s)] = dict(us=round(us, 2), launches=launches, us_per_launch=round(us / launches, 2), model_bytes=model,
-                                     model_gb_per_s=round(model / us * 1e-3, 1),
-                                     gmres=dict(iterations=its, seconds=round(sec, 4), recurrence_residual=float(hist[-1]), true_residual=true,
-                                                converged=bool(hist[-1] <= 1e-8)))
+        entry = {}
+        for prec in precisions:
+            V = F.sweeps(s, precision=prec)
+            us = timed_us(lambda: V.solve(dx, db), 20, reps)
+            launches = (F.sweep_info_f32() if prec == "f32" else F.sweep_info())["launches_last"]
+            blk, dia = per_block[prec]
+            model = sf * n_l * blk + nb * dia + sb * (n_u * blk + nb * dia) + launches * vec
+            dx.zero_()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            its, hist = mpk.GMRES(A, db, dx, M=V, restart=30, rtol=1e-8, maxiter=a.maxiter)
+            torch.cuda.synchronize()
+            sec = time.perf_counter() - t0
+            mpk.SpMV_BCSR(dy, dx, A)
+            true = float(np.linalg.norm(b - dy.cpu().numpy()) / np.linalg.norm(b))
+            entry[prec] = dict(us=round(us, 2), launches=launches, us_per_launch=round(us / launches, 2), model_bytes=model,
+                               model_gb_per_s=round(model / us * 1e-3, 1),
+                               gmres=dict(iterations=its, seconds=round(sec, 4), recurrence_residual=float(hist[-1]), true_residual=true,
+                                          converged=bool(hist[-1] <= 1e-8)))
+        # (the double sweeps keep the record's earlier shape: their figures lie directly under the count)
+        out = dict(entry["f64"]) if "f64" in entry else {}
+        if "f32" in entry:
+            out["f32"] = entry["f32"]
+        if len(entry) == 2:
+            out["f32_over_f64"] = round(entry["f32"]["us"] / entry["f64"]["us"], 3)
+            out["f32_over_f64_model"] = round(entry["f32"]["model_bytes"] / entry["f64"]["model_bytes"], 3)
+        rec["counts"][str(s)] = out
+    # one more forward + backward sweep pair, from consecutive counts below the clamp
+    done = sorted(int(c) for c in rec["counts"])
+    pairs = {}
+    for lo, hi in zip(done, done[1:]):
+        if hi > min(rec["max"]):
+            continue
+        for prec in precisions:
+            at = (lambda c: rec["counts"][str(c)]["f32"] if prec == "f32" else rec["counts"][str(c)])
+            pairs.setdefault(prec, {})[f"{lo}->{hi}"] = round((at(hi)["us"] - at(lo)["us"]) / (hi - lo), 2)
+    rec["us_per_sweep_pair"] = pairs
     return rec
 
 
@@ -146,6 +205,7 @@ def main():
     ap.add_argument("--maxiter", type=int, default=300)
     ap.add_argument("--form", choices=("both", "0", "1"), default="both")
     ap.add_argument("--sweeps", default="", help="comma-separated sweep counts per triangle")
+    ap.add_argument("--precision", choices=("f64", "f32", "both"), default="f64", help="with --sweeps: the values the sweeps stream")
     ap.add_argument("--no-append", action="store_true")
     a = ap.parse_args()
     import numpy as np
@@ -209,7 +269,7 @@ def main():
         out["gmres"][label] = dict(iterations=its, seconds=round(sec, 4), recurrence_residual=float(hist[-1]), true_residual=true,
                                    converged=bool(hist[-1] <= 1e-8))
     if a.sweeps:
-        out["sweeps"] = sweeps_record(a, F, A, b, db, dx, dy)
+        out["sweeps"] = sweeps_record(a, F, A, b, db, dx, dy, bv)
     line = json.dumps(out)
     print(line)
     if not a.no_append:
