@@ -464,6 +464,19 @@ int mi_bcsr4_spmm_dev(mi_bcsr4_t A, int s, const double* d_X, long long ldx, dou
  * shared inside the quad through DPP, a finished slice's sums parked in LDS and stored behind the loads.  *form_in_use = what
  * the next product runs; us[f] = microseconds per launch measured for form f (0: not possible / not yet measured). */
 int mi_bcsr4_spmm_info(mi_bcsr4_t A, int s, int* tile_built, int* form_in_use, int* longest_list, double us[5]);
+/* The plan of forms 1-3 for a block pattern, built on the host by the function the handle calls at its first product (no device needed;
+ * nothing is kept): per = 128 for form 1, 64 for forms 2 and 3; ucap = the list length above which a cluster is halved (the handle takes
+ * 368 and 256, or MI355_SPMM_TILE_UCAP).  *refused != 0: no plan (a single block row with more than 65 535 distinct block columns, or
+ * no block at all) — the handle then runs form 0; the other outputs are 0 and nothing is copied.  Else *ntiles, *umax (the longest list,
+ * what mi_bcsr4_spmm_info reports as longest_list), *mean_list, and, where the pointer is not null, the arrays as they are uploaded:
+ * wg_ptr[ntiles + 1], nodes[wg_ptr[ntiles] + 1] (every list strictly ascending; one pad entry), slots[nblocks + 1] (block k's column is
+ * nodes[wg_ptr[t] + slots[k]] for the tile t of its row; one pad entry), rows[ntiles * per] (a block row, or -1 - r for an unused place
+ * that shadows row r of the same tile).  Each array comes with its capacity in elements; MI_ERR_ARG if one is too small (nbrows + 1,
+ * nblocks + 1, nblocks + 1 and nbrows * per always suffice).  A form is possible at s columns when its plan exists, the matrix has at
+ * least 4 096 blocks and umax * (4 s + 2) * 8 bytes fit the 160 KiB of LDS (form 1: s <= 4; forms 2, 3: s even, s <= 8). */
+int mi_bcsr4_spmm_plan_probe(int nbrows, const int* ptrow, const int* indcol, int per, int ucap, int* refused, int* ntiles, int* umax,
+                             double* mean_list, int* wg_ptr, long long wg_ptr_cap, unsigned* nodes, long long nodes_cap,
+                             unsigned short* slots, long long slots_cap, int* rows, long long rows_cap);
 /* the same for a CSR handle (MI_ARITH_CHAIN bits = SpMV_CSR_FMA per column): one launch over the blocked copy when the
  * matrix has exact 4x4 node-block structure, else s single-vector launches */
 int mi_spmm_dev(mi_csr_t A, int s, const double* d_X, long long ldx, double* d_Y, long long ldy, mi_stream_t st);

@@ -2,6 +2,7 @@
 // Built for gfx950 only; no CPU fallback anywhere: every compute entry point needs a HIP device.
 #include "capi_internal.hpp"
 #include "spmv_bcsr_sell.hpp"
+#include "spmm_tile_plan.hpp"
 
 static int sell_fill(mi_bcsr4_t A, hipStream_t s);
 
@@ -485,102 +486,62 @@ static void launch_spmm_s(const Bcsr4View& V, int arith, const double* X, long l
 
 // ---- the tile form (spmm_tile.hpp) ------------------------------------------------------------------------------------------
 
-// Tiles of the multi-vector product: groups of at most `per` block rows, the list of distinct block columns each group touches, and
-// every block's position in its group's list.  The groups are CLUSTERS of the block graph, not runs of consecutive rows: grown
-// breadth-first from the lowest unassigned row over unassigned rows (a "ball" of the mesh), because the tile's cost — its gather, its
-// LDS — is the number of distinct columns per row, and a ball of 128 nodes of a 3-D mesh touches ~2.5 per row where 128
-// consecutive nodes (1.9 mesh lines) touch 5.1 (FE matrix, 68^3 cells: lists of 321 against 654 entries on average).  A cluster
-// whose list would exceed `ucap` entries is cut in halves (in growth order) until it fits: the LDS footprint, hence the
-// workgroups per CU, is set by the LONGEST list.  rows[t * per + i] = block row of lane group i of tile t, or -1 - (a valid row of
-// the tile) for unused places (those lanes shadow that row and store nothing).
+// The plan itself — clusters, halving, lists, slots, rows, the 16-bit refusal — is spmm_tile_plan.hpp's build_spmm_tile_plan_host
+// (host only; mi_bcsr4_spmm_plan_probe below copies the same arrays out).  Here: the upload, unchanged.
+// MI355_SPMM_TILE_SORT=0: a tile's rows in growth order (A/B); read once per process.
+static bool spmm_tile_sort_rows()
+{
+    static const bool sort_rows = !env_is("MI355_SPMM_TILE_SORT", "0");
+    return sort_rows;
+}
+
 static int build_spmm_tile_plan(mi_bcsr4_t A, int per, int ucap, const std::vector<int>& ptrow, const std::vector<int>& indcol, SpmmTilePlan& out)
 {
-    const int nbr = A->nbrows;
-    std::vector<int> order;           // block rows in cluster growth order
-    std::vector<int> cuts;            // first position of every cluster, then cut further below
-    order.reserve((size_t)nbr);
-    {
-        std::vector<char> assigned((size_t)nbr, 0);
-        std::vector<int> stamp((size_t)nbr, 0), queue;
-        int seed = 0, tid = 0, in_cur = 0;
-        while (true) {
-            while (seed < nbr && assigned[seed]) seed++;
-            if (seed >= nbr) break;
-            if (in_cur == 0) {
-                tid++;
-                cuts.push_back((int)order.size());
-            }
-            queue.clear();
-            queue.push_back(seed);
-            stamp[seed] = tid;
-            for (size_t qh = 0; qh < queue.size() && in_cur < per; qh++) {
-                const int r = queue[qh];
-                order.push_back(r);
-                assigned[r] = 1;
-                in_cur++;
-                for (int k = ptrow[r]; k < ptrow[r + 1]; k++) {
-                    const int nb = indcol[k];
-                    if (nb < nbr && !assigned[nb] && stamp[nb] != tid) { // (columns beyond the rows: a rectangular matrix has no such node)
-                        stamp[nb] = tid;
-                        queue.push_back(nb);
-                    }
-                }
-            }
-            if (in_cur == per) in_cur = 0; // full; else the component ran dry: the next seed continues this cluster
-        }
-        cuts.push_back((int)order.size());
-    }
-    // lists; clusters over the cap are halved
-    std::vector<int> wg_ptr(1, 0), rows;
-    std::vector<unsigned> nodes, u;
-    std::vector<unsigned short> slots((size_t)A->nblocks + 1, 0);
-    int umax = 0;
-    std::vector<std::pair<int, int>> work; // [first, end) positions in `order`, processed in order (a stack keeps the order)
-    for (size_t t = cuts.size() - 1; t-- > 0;) work.push_back({cuts[t], cuts[t + 1]});
-    while (!work.empty()) {
-        const std::pair<int, int> w = work.back();
-        work.pop_back();
-        if (w.first >= w.second) continue;
-        u.clear();
-        for (int i = w.first; i < w.second; i++) u.insert(u.end(), indcol.begin() + ptrow[order[i]], indcol.begin() + ptrow[order[i] + 1]);
-        std::sort(u.begin(), u.end());
-        u.erase(std::unique(u.begin(), u.end()), u.end());
-        if ((int)u.size() > ucap && w.second - w.first > 1) {
-            const int mid = (w.first + w.second) / 2;
-            work.push_back({mid, w.second});
-            work.push_back({w.first, mid});
-            continue;
-        }
-        if (u.size() > 65535) return -1;
-        umax = std::max(umax, (int)u.size());
-        for (int i = w.first; i < w.second; i++)
-            for (int k = ptrow[order[i]]; k < ptrow[order[i] + 1]; k++)
-                slots[k] = (unsigned short)(std::lower_bound(u.begin(), u.end(), (unsigned)indcol[k]) - u.begin());
-        nodes.insert(nodes.end(), u.begin(), u.end());
-        wg_ptr.push_back((int)nodes.size());
-        // (round 5) the tile's rows in ASCENDING order, not in the order the cluster grew: neighbouring lane groups then stream
-        // neighbouring rows' blocks (one run of the coefficient array per run of consecutive rows) and store neighbouring pieces of Y.
-        // MI355_SPMM_TILE_SORT=0: growth order (A/B).
-        static const bool sort_rows = !env_is("MI355_SPMM_TILE_SORT", "0");
-        if (sort_rows) std::sort(order.begin() + w.first, order.begin() + w.second);
-        for (int i = 0; i < per; i++) rows.push_back(w.first + i < w.second ? order[w.first + i] : -1 - order[w.first]);
-    }
-    const int ntiles = (int)wg_ptr.size() - 1;
-    if (umax < 1 || ntiles < 1) return -1;
-    nodes.push_back(0);
+    SpmmTilePlanHost H;
+    if (build_spmm_tile_plan_host(A->nbrows, ptrow.data(), indcol.data(), per, ucap, spmm_tile_sort_rows(), H) != 1) return -1;
     SpmmTilePlan T;
-    if (T.d_ptr.alloc(wg_ptr.size()) != hipSuccess || T.d_nodes.alloc(nodes.size()) != hipSuccess || T.d_slots.alloc(slots.size()) != hipSuccess ||
-        T.d_rows.alloc(rows.size()) != hipSuccess || T.d_ptr.fill(wg_ptr) != hipSuccess || T.d_nodes.fill(nodes) != hipSuccess ||
-        T.d_slots.fill(slots) != hipSuccess || T.d_rows.fill(rows) != hipSuccess) {
+    if (T.d_ptr.alloc(H.wg_ptr.size()) != hipSuccess || T.d_nodes.alloc(H.nodes.size()) != hipSuccess || T.d_slots.alloc(H.slots.size()) != hipSuccess ||
+        T.d_rows.alloc(H.rows.size()) != hipSuccess || T.d_ptr.fill(H.wg_ptr) != hipSuccess || T.d_nodes.fill(H.nodes) != hipSuccess ||
+        T.d_slots.fill(H.slots) != hipSuccess || T.d_rows.fill(H.rows) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
     T.rows = per;
-    T.umax = umax;
-    T.ntiles = ntiles;
-    T.mean_list = (double)(nodes.size() - 1) / ntiles;
+    T.umax = H.umax;
+    T.ntiles = H.ntiles;
+    T.mean_list = H.mean_list;
     out = std::move(T);
     return 1;
+}
+
+// The plan without a device: the arrays build_spmm_tile_plan uploads for this pattern, `per` and `ucap`, copied out.
+extern "C" int mi_bcsr4_spmm_plan_probe(int nbrows, const int* ptrow, const int* indcol, int per, int ucap, int* refused, int* ntiles, int* umax,
+                                        double* mean_list, int* wg_ptr, long long wg_ptr_cap, unsigned* nodes, long long nodes_cap,
+                                        unsigned short* slots, long long slots_cap, int* rows, long long rows_cap)
+{
+    CHECK_ARG(nbrows >= 0 && ptrow && ptrow[0] == 0, "bad argument");
+    CHECK_ARG(per == 128 || per == 64, "per must be 128 or 64");
+    CHECK_ARG(ucap >= 1, "ucap must be positive");
+    for (int i = 0; i < nbrows; i++) CHECK_ARG(ptrow[i] <= ptrow[i + 1], "ptrow must be non-decreasing");
+    const long long nb = ptrow[nbrows];
+    CHECK_ARG(nb == 0 || indcol, "indcol is null");
+    for (long long k = 0; k < nb; k++) CHECK_ARG(indcol[k] >= 0, "negative block column");
+    SpmmTilePlanHost H;
+    const int rc = build_spmm_tile_plan_host(nbrows, ptrow, indcol, per, ucap, spmm_tile_sort_rows(), H);
+    if (refused) *refused = rc != 1;
+    if (ntiles) *ntiles = H.ntiles;
+    if (umax) *umax = H.umax;
+    if (mean_list) *mean_list = H.mean_list;
+    if (rc != 1) return MI_OK;
+    CHECK_ARG(!wg_ptr || wg_ptr_cap >= (long long)H.wg_ptr.size(), "wg_ptr buffer too small");
+    CHECK_ARG(!nodes || nodes_cap >= (long long)H.nodes.size(), "nodes buffer too small");
+    CHECK_ARG(!slots || slots_cap >= (long long)H.slots.size(), "slots buffer too small");
+    CHECK_ARG(!rows || rows_cap >= (long long)H.rows.size(), "rows buffer too small");
+    if (wg_ptr) std::copy(H.wg_ptr.begin(), H.wg_ptr.end(), wg_ptr);
+    if (nodes) std::copy(H.nodes.begin(), H.nodes.end(), nodes);
+    if (slots) std::copy(H.slots.begin(), H.slots.end(), slots);
+    if (rows) std::copy(H.rows.begin(), H.rows.end(), rows);
+    return MI_OK;
 }
 
 static int build_spmm_tile(mi_bcsr4_t A)

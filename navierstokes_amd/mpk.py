@@ -118,6 +118,7 @@ def lib():
         "mi_bcsr4_tile_info": [_vp, P(i), P(i), P(d), P(d)],
         "mi_bcsr4_sell_info": [_vp, P(i), P(i), P(ll), P(d), P(d)],
         "mi_bcsr4_sell_plan_probe": [i, _vp, _vp, i, P(i), P(ll), P(i), _vp, _vp, _vp],
+        "mi_bcsr4_spmm_plan_probe": [i, _vp, _vp, i, i, P(i), P(i), P(i), P(d), _vp, ll, _vp, ll, _vp, ll, _vp, ll],
         "mi_csr_mring_info": [_vp, P(i), P(i), P(i), P(d), P(d), P(i)],
         "mi_csr_sstream_info": [_vp, P(i), P(i), P(ll), P(d), P(d), P(i)],
         "mi_sstream_plan_probe": [i, i, _vp, _vp, P(i), P(i), P(ll), P(d)],
@@ -829,6 +830,29 @@ def bcsr4_sell_plan_probe(nbrows, ptrow, indcol, nwaves_max=1024):
     col = np.zeros((st.value + 48, 16), np.uint32)
     check(lib().mi_bcsr4_sell_plan_probe(*args, _c.byref(ns), _c.byref(st), _c.byref(nw), sptr.ctypes.data, wrng.ctypes.data, col.ctypes.data))
     return dict(nslices=ns.value, nsteps=st.value, nwaves=nw.value, sptr=sptr, wrng=wrng, col=col)
+
+
+def bcsr4_spmm_plan_probe(nbrows, ptrow, indcol, per=128, ucap=None):
+    """mi_bcsr4_spmm_plan_probe (no GPU): the tile plan of the multi-vector product's forms 1 (per = 128) and 2, 3 (per = 64) —
+    dict(refused, per, ntiles, umax, mean_list, wg_ptr, nodes, slots, rows): wg_ptr has ntiles + 1 entries, nodes wg_ptr[-1] (the pad
+    entry dropped), slots one per block (uint16; the pad entry dropped), rows (ntiles, per).  ucap None: the handle's default cap."""
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    nbrows, per = int(nbrows), int(per)
+    if ucap is None:
+        ucap = 368 if per == 128 else 256
+    nb = int(ptrow[nbrows]) if nbrows > 0 else 0
+    ref, nt, um, ml = _c.c_int(), _c.c_int(), _c.c_int(), _c.c_double()
+    wg, nodes = np.zeros(nbrows + 1, np.int32), np.zeros(nb + 1, np.uint32)
+    slots, rows = np.zeros(nb + 1, np.uint16), np.zeros(max(nbrows * per, 1), np.int32)
+    check(lib().mi_bcsr4_spmm_plan_probe(nbrows, ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, per, int(ucap), _c.byref(ref),
+                                         _c.byref(nt), _c.byref(um), _c.byref(ml), wg.ctypes.data, wg.size, nodes.ctypes.data, nodes.size,
+                                         slots.ctypes.data, slots.size, rows.ctypes.data, rows.size))
+    out = dict(refused=bool(ref.value), per=per, ntiles=nt.value, umax=um.value, mean_list=ml.value)
+    if not out["refused"]:
+        wg = wg[: nt.value + 1].copy()
+        out.update(wg_ptr=wg, nodes=nodes[: wg[-1]].copy(), slots=slots[:nb].copy(), rows=rows[: nt.value * per].reshape(nt.value, per).copy())
+    return out
 
 
 def MatSolve_SeqBAIJ_4(F, b, x):

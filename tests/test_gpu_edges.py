@@ -246,17 +246,20 @@ class Spmk(Csr):
 S_COLS = 3
 
 
-def _columns(x):
-    """s columns of X: the case's x, and two others that move its special entries to other rows."""
-    return np.stack([x, np.roll(x, 4) * 0.5, -np.roll(x, -4)])
+def _columns(x, s=S_COLS):
+    """s columns of X: the case's x, and others that move its special entries to other rows."""
+    return np.stack([x, np.roll(x, 4) * 0.5, -np.roll(x, -4), np.roll(x, 8) * -0.25][:s])
 
 
 class Spmm(Path):
     kind = "spmm"
 
-    def __init__(self, pid, api):
+    def __init__(self, pid, api, form=None, s=S_COLS):
+        """form: a tile form of the multi-vector product forced on (MI355_SPMM_TILE), which check() then requires; s: the columns."""
         super().__init__(pid, "fe14", {"MI355_BCSR_SELL": "1", "MI355_BCSR_SELL_FORM": "0"})
-        self.api = api
+        if form is not None:
+            self.env["MI355_SPMM_TILE"] = str(form)
+        self.api, self.form, self.s = api, form, s
 
     def make(self, p, c, v):
         n = len(p) - 1
@@ -271,8 +274,10 @@ class Spmm(Path):
     def check(self, H):
         if self.api == "bcsr":
             tb, form = ctypes.c_int(), ctypes.c_int()
-            mpk.check(mpk.lib().mi_bcsr4_spmm_info(H.handle, S_COLS, ctypes.byref(tb), ctypes.byref(form), None, None))
+            mpk.check(mpk.lib().mi_bcsr4_spmm_info(H.handle, self.s, ctypes.byref(tb), ctypes.byref(form), None, None))
             assert form.value >= 0, form.value
+            if self.form is not None:  # asked after a product: the lists are built at the first one
+                assert (tb.value, form.value) == (1, self.form), (self.id, tb.value, form.value)
         else:  # the multi-vector product of a CSR handle reads its blocked copy
             assert H.kernel_name().startswith("spmv_bcsr4"), H.kernel_name()
 
@@ -283,12 +288,12 @@ class Spmm(Path):
         """The C-ABI call with explicit leading dimensions (the torch wrapper passes contiguous (s, n) tensors only)."""
         L, vp = mpk.lib(), ctypes.c_void_p
         if self.api == "bcsr":
-            mpk.check(L.mi_bcsr4_spmm_dev(H.handle, S_COLS, vp(X_ptr), ldx, vp(Y_ptr), ldy, mpk.ARITH["chain"], mpk._stream_ptr()))
+            mpk.check(L.mi_bcsr4_spmm_dev(H.handle, self.s, vp(X_ptr), ldx, vp(Y_ptr), ldy, mpk.ARITH["chain"], mpk._stream_ptr()))
         else:
-            mpk.check(L.mi_spmm_dev(H.handle, S_COLS, vp(X_ptr), ldx, vp(Y_ptr), ldy, mpk._stream_ptr()))
+            mpk.check(L.mi_spmm_dev(H.handle, self.s, vp(X_ptr), ldx, vp(Y_ptr), ldy, mpk._stream_ptr()))
 
     def want(self, p, c, v, x):
-        return [np.stack([O.spmv(p, c, v, col) for col in _columns(x)])]
+        return [np.stack([O.spmv(p, c, v, col) for col in _columns(x, self.s)])]
 
 
 class Dot(Csr):
@@ -345,6 +350,7 @@ PATHS = (
     + [Spmk(f"spmk{k}-one-launch", k, True) for k in (2, 3, 4)]
     + [Spmk("spmk3-k-launches", 3, False),
        Spmm("spmm-bcsr", "bcsr"), Spmm("spmm-csr", "csr"),
+       Spmm("spmm-bcsr-tile", "bcsr", form=1), Spmm("spmm-bcsr-otile", "bcsr", form=2, s=4), Spmm("spmm-bcsr-otile-nt", "bcsr", form=3, s=4),
        Dot("dot-epilogue"),
        Dist("dist-n2")]
 )
@@ -364,7 +370,7 @@ def _outputs(P, n):
     if P.kind == "spmk":
         return [nans(n) for _ in range(P.k)]
     if P.kind == "spmm":
-        return [torch.full((S_COLS, n), float("nan"), dtype=torch.float64, device="cuda")]
+        return [torch.full((P.s, n), float("nan"), dtype=torch.float64, device="cuda")]
     if P.kind == "dot":
         return [nans(n), nans(1)]
     return [nans(P.n_out(n))]
@@ -374,7 +380,7 @@ def _x_arg(P, x):
     if P.kind == "dist":
         return x
     if P.kind == "spmm":
-        return dev(_columns(x))
+        return dev(_columns(x, P.s))
     return dev(x)
 
 
@@ -437,15 +443,16 @@ def test_views_that_are_only_8_byte_aligned(path, monkeypatch):
     try:
         if path.kind == "spmm":
             ld = n + 1  # odd: every other column starts 8 bytes off a 16-byte boundary
-            X = _columns(x)
+            S = path.s
+            X = _columns(x, S)
             for odd in ("X", "Y"):
-                bx = nans(S_COLS * ld + 2)
-                by = nans(S_COLS * ld + 2)
+                bx = nans(S * ld + 2)
+                by = nans(S * ld + 2)
                 if odd == "X":
-                    bx[:S_COLS * ld].view(S_COLS, ld)[:, :n] = dev(X)
+                    bx[:S * ld].view(S, ld)[:, :n] = dev(X)
                     xp, ldx, yp, ldy = bx.data_ptr(), ld, by.data_ptr() + 8, n
                 else:
-                    bx[:S_COLS * n] = dev(X.reshape(-1))
+                    bx[:S * n] = dev(X.reshape(-1))
                     xp, ldx, yp, ldy = bx.data_ptr(), n, by.data_ptr() + 8, ld
                 try:
                     path.run_ld(H, xp, ldx, yp, ldy)
@@ -455,10 +462,10 @@ def test_views_that_are_only_8_byte_aligned(path, monkeypatch):
                     continue
                 path.check(H)
                 b = by.cpu().numpy()
-                Y = np.stack([b[1 + j * ldy:1 + j * ldy + n] for j in range(S_COLS)])
+                Y = np.stack([b[1 + j * ldy:1 + j * ldy + n] for j in range(S)])
                 assert_same(Y, want[0], f"{path.id} odd leading dimension of {odd}")
                 written = np.zeros(len(b), bool)
-                for j in range(S_COLS):
+                for j in range(S):
                     written[1 + j * ldy:1 + j * ldy + n] = True
                 assert np.isnan(b[~written]).all(), f"{path.id}: wrote outside the columns of Y"
             return

@@ -1,5 +1,5 @@
 """Host-side planners under the address and undefined-behaviour sanitizers (CPU only: GPU sanitizers are not available on this pool, and
-nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp, bilu_asan.cpp) and say what they check."""
+nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp, bilu_asan.cpp, spmm_plan_asan.cpp) and say what they check."""
 import os
 import shutil
 import subprocess
@@ -49,3 +49,14 @@ def test_sliced_stream_planners_under_host_sanitizers(tmp_path):
     out = _run([hipcc, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-I" + CSRC,
                 "-I" + os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tools", "plan_asan.hip")], exe, tmp_path)
     assert "bad 0" in out and "eligible" in out, out
+
+
+def test_spmm_tile_planner_under_host_sanitizers(tmp_path):
+    """spmm_tile_plan.hpp: the tile plan of the multi-vector product's forms 1-3 on the pattern families of tests/spmm_tile_cases.py and on
+    random unsymmetric patterns, 128 and 64 rows per tile, default and small caps, rows sorted and in growth order, every array checked by
+    brute force; the 16-bit refusal and the matrices with nothing to list."""
+    if not shutil.which("g++"):
+        pytest.skip("g++ not found")
+    exe = str(tmp_path / "spmm_plan_asan")
+    out = _run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tools", "spmm_plan_asan.cpp")], exe, tmp_path)
+    assert "bad 0" in out, out

@@ -169,3 +169,11 @@ def test_spmm_every_tile_form_bitwise(form, s, monkeypatch):
                 Yh = Y.cpu().numpy()
                 for j in range(s):
                     assert_bit_equal(Yh[j], orc(bp, bc, bv, X[j]), f"{name} form {form} s={s} {arith} column {j} rep {rep}")
+        if form != "4":  # the lists exist from the first product on; these matrices' longest lists fit the LDS at every column count
+            import ctypes
+            for m in sorted({min(8, s - j0) for j0 in range(0, s, 8)}):
+                tb, fi, ll = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+                mpk.check(mpk.lib().mi_bcsr4_spmm_info(A.handle, m, ctypes.byref(tb), ctypes.byref(fi), ctypes.byref(ll), None))
+                assert tb.value == 1 and 0 < ll.value and ll.value * (4 * m + 2) * 8 <= 160 * 1024, (name, tb.value, ll.value)
+                possible = m <= 4 if form == "1" else m % 2 == 0
+                assert fi.value == (int(form) if possible else 0), f"{name} form {form} forced, batch of {m} columns: form_in_use {fi.value}"
