@@ -722,6 +722,78 @@ int mi_bilu4sp_fetch(mi_bilu4_t F, float* val, long long cap_blocks);
  * *copy_bytes of the copy, 64 per factor block (0 until prepared).  Any output may be NULL. */
 int mi_bilu4sp_info(mi_bilu4_t F, int* prepared, int* convert_launches, int* launches_last, long long* copy_bytes);
 
+/* ---- right-preconditioned restarted GMRES with a whole cycle on the device (mi_gmres_*) ----
+ * KSPGMRES of src/solve_newton.c:1156-1164, 1265 as one call: the products, the block ILU in any of its three forms, CGS2 out of
+ * mi_cgs_dev and the small least-squares problem all run on the caller's stream; the host reads a 64-byte record (plus the
+ * history entries so far of the cycle) every `check_every` iterations instead of draining the stream at every one.
+ * ALL DEVICE STATE, THE RESULT INCLUDED, IS INDEPENDENT OF check_every: x, history, iterations and reason are the same bits for
+ * every value; only the number of read-backs and of wasted steps (below) changes.
+ * DEFINITION (part of the interface; m = restart; A M^-1 u = b, x = x0 + M^-1 u):
+ *   solve      bnorm = mi_norm2_dev(b), or 1 if that is 0;  its = 0
+ *   cycle      w = A x;  r_i = b_i - w_i (one rounded subtraction);  beta = the bits of mi_norm2_dev(r)
+ *              the first cycle sets history[0] = beta / bnorm
+ *              the solve ends here if beta / bnorm <= rtol (reason 0 when its == 0, else 1), else if its >= maxiter (2), else
+ *              if beta is not finite (4);  V_0 = r / beta (IEEE division);  g_0 = beta
+ *   step k     V_{k+1} = A (M^-1 V_k), written straight into row k + 1 of V;  mi_cgs_dev(passes = 2) in place against V_0..V_k
+ *              gives h_0..h_k and nrm, kept untouched as hraw[k (m + 2) + j], nrm at j = k + 1 (mi_krylov_basis_cgs_dev's
+ *              layout);  the small problem (below);  V_{k+1} = V_{k+1} / nrm (IEEE division)
+ *   small      on a copy c of the raw column, for j < k:  t = cs_j c_j + sn_j c_{j+1};  c_{j+1} = (-sn_j) c_j + cs_j c_{j+1};
+ *              c_j = t.  rho = sqrt(c_k c_k + nrm nrm); rho == 0 or not finite: reason 4, the step is NOT counted.  Else
+ *              cs_k = c_k / rho, sn_k = nrm / rho;  R_kk = rho, R_jk = c_j (j < k);  g_{k+1} = (-sn_k) g_k, then g_k = cs_k g_k;
+ *              its += 1;  history[its] = |g_{k+1}| / bnorm;  history[its] <= rtol: reason 1; otherwise nrm == 0: reason 3
+ *              (with nrm == 0 the new g_{k+1} is 0: reason 3 can only be seen with a negative rtol)
+ *   frozen     once a reason is set every later small-problem launch of the cycle returns at once; the Arnoldi launches already
+ *              enqueued behind it still run and their output is never read: columns past the frozen k are not used by the
+ *              update and not reported by mi_gmres_fetch_cycle
+ *   cycle end  after m steps, at maxiter or frozen, with k counted steps (k == 0: no update): for i = k-1 .. 0:  s = g_i;
+ *              s = s - R_ij y_j for j = i+1 .. k-1 ascending;  y_i = s / R_ii.  With M: u = 0, mi_maxpy_dev(y, V_0..V_{k-1}, u),
+ *              z = M^-1 u, x_i = fma(1, z_i, x_i) (mi_axpy_dev).  Without M: mi_maxpy_dev(y, V_0..V_{k-1}, x).  The solve ends
+ *              here with the cycle's reason, or with 2 when its >= maxiter; else the next cycle starts
+ * ARITHMETIC of the small problem: every product, every sum, every difference, every division and the square root is rounded
+ * once, to nearest; NOTHING is contracted into an fma.  tests/gmres_dev_model.py restates it in float64 scalars.
+ * reason: 0 the initial guess already met rtol; 1 converged at rtol; 2 maxiter reached; 3 the Krylov space is exhausted (a new
+ * direction of norm 0); 4 a non-finite quantity or rho = 0.  history (host, maxiter + 1 doubles, or NULL) receives
+ * iterations + 1 entries.
+ * HOST LOOP: steps are enqueued in batches of check_every (a cycle's first batch: check_every - 1, so that the record of the
+ * cycle's start arrives one step early), clipped at the cycle's end and at maxiter; behind each batch the record
+ * is copied to one of two pinned slots and an event recorded; the NEXT batch is enqueued before the host waits for the previous
+ * batch's event, so the GPU never waits for the host inside a cycle.  The price: when a cycle freezes, the rest of its batch and
+ * the batch behind it have run for nothing: at most 2 check_every - 1 steps, once per solve (*wasted_steps_last).  A cycle's end
+ * is the one point where the host waits with nothing enqueued behind: the update takes k as a launch parameter.  Read-backs per
+ * solve: at most ceil(iterations / check_every) + cycles + 1.  check_every = 1 still never lets the GPU wait inside a cycle and
+ * measured fastest (profiles/NOTES.md R12.1); larger values spare the host thread.  A solve allocates nothing, copies only to pinned memory and never
+ * synchronises the device.  x is complete on the stream when the call returns, not on the host.
+ * The handle owns V (m + 1 rows, even leading dimension), two work vectors, the small state and the two pinned slots; it does
+ * NOT own A or F: both must outlive it.  MI_GMRES_PC_EXACT calls mi_bilu4_solve_dev with the handle's current solve form, the
+ * two sweep kinds mi_bilu4sw_solve_dev / mi_bilu4sp_solve_dev with the counts given; mi_gmres_set_precond prepares F for them.
+ * ONE solve at a time per handle.  F's sweep work vectors are F's: two solvers on one F must not overlap.  Vectors need 8-byte
+ * alignment only.  Under stream capture mi_gmres_solve_dev returns MI_ERR_STATE (it reads back) and enqueues nothing.
+ * MI_ERR_ARG, before the device is touched: a null handle or vector, n < 1, restart outside 1..64, an operator or preconditioner
+ * whose row count is not n, a mapped or non-square operator, check_every < 1, maxiter < 0, an unknown kind, a negative count;
+ * MI_ERR_STATE: no operator set; MI_ERR_NODEVICE: no GPU (mi_gmres_create): there is no CPU fallback. */
+typedef struct mi_gmres_s* mi_gmres_t;
+enum { MI_GMRES_PC_EXACT = 0, MI_GMRES_PC_SWEEPS = 1, MI_GMRES_PC_SWEEPS_F32 = 2 };
+int mi_gmres_create(int n, int restart, mi_gmres_t* out);
+int mi_gmres_set_operator_csr(mi_gmres_t G, mi_csr_t A);     /* square, unmapped, n rows: the arithmetic of mi_spmv_dev */
+int mi_gmres_set_operator_bcsr4(mi_gmres_t G, mi_bcsr4_t A); /* 4 nbrows == n: the chain arithmetic of mi_bcsr4_spmv_dev */
+/* F == NULL: no preconditioner (kind and counts ignored) */
+int mi_gmres_set_precond(mi_gmres_t G, mi_bilu4_t F, int kind, int sweeps_fwd, int sweeps_bwd);
+/* d_x holds the initial guess and receives the solution; iterations, reason and history may be NULL */
+int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, double rtol, int maxiter, int check_every, int* iterations,
+                       int* reason, double* history, mi_stream_t s);
+/* host vectors: copied in and out (two more device vectors, allocated by the first call) */
+int mi_gmres_solve(mi_gmres_t G, const double* b, double* x, double rtol, int maxiter, int check_every, int* iterations, int* reason,
+                   double* history);
+/* the LAST cycle of the last solve (waits for the device): *k its counted steps; hraw [restart (restart + 2)] the raw columns
+ * 0..k-1 in the layout above, zeros elsewhere; y [restart] the least-squares solution, zeros past k; *beta its ||r0||.  Any output
+ * may be NULL */
+int mi_gmres_fetch_cycle(mi_gmres_t G, int* k, double* hraw, double* y, double* beta);
+/* *device_bytes of V, the work vectors and the small state; of the last solve: *readbacks_last, *launches_last (kernels of this
+ * section and library calls enqueued, a product, a preconditioner application or an mi_cgs_dev each counted once),
+ * *wasted_steps_last.  Any output may be NULL */
+int mi_gmres_info(mi_gmres_t G, int* restart, long long* device_bytes, int* readbacks_last, int* launches_last, int* wasted_steps_last);
+int mi_gmres_destroy(mi_gmres_t G);
+
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r
  * owns global rows [row_starts[r], row_starts[r+1]) and the matching slice of

@@ -7,6 +7,7 @@
 // result depends only on (n, data), never on scheduling, alignment, stream or
 // the non-temporal choice: deterministic run to run, though not the CPU's
 // left-to-right order.  oracle/cpu_ref.c models every tree bit for bit.
+// Several translation units include this header: the kernels that are not templates are static.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(kRedWG) void reduce_stage2(int np, const double* __
 }
 
 // y += a x
-__global__ __launch_bounds__(256) void axpy_kernel(int n, double a, const double* __restrict__ x,
+static __global__ __launch_bounds__(256) void axpy_kernel(int n, double a, const double* __restrict__ x,
                                                    double* __restrict__ y)
 {
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -170,6 +171,14 @@ __global__ __launch_bounds__(256) void axpy_kernel(int n, double a, const double
     } else {
         for (long long i = t; i < n; i += stride) y[i] = fma(a, x[i], y[i]);
     }
+}
+
+// y[i] /= *d (IEEE division by a scalar read from device memory); in every translation unit that normalises a basis vector
+static __global__ __launch_bounds__(256) void div_by_scalar_kernel(int n, const double* __restrict__ d, double* __restrict__ y)
+{
+    const double q = d[0];
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] = __ddiv_rn(y[i], q);
 }
 
 // out = x1 - (alpha * beta) * b with beta read from device memory (no host round trip between the
@@ -266,7 +275,7 @@ __global__ __launch_bounds__(kRedWG) void mgs_step_kernel(int n, int seg, int np
 
 // dst[4j .. 4j+3] = src[idx[4j] .. idx[4j]+3]: the gather of a NODE renumbering (four dofs stay together and idx[4j] is a
 // multiple of 4), 32 bytes per thread as two 16-byte accesses instead of four 8-byte ones
-__global__ __launch_bounds__(256) void gather_nodes_kernel(int nnodes, const int* __restrict__ idx, const double* __restrict__ src,
+static __global__ __launch_bounds__(256) void gather_nodes_kernel(int nnodes, const int* __restrict__ idx, const double* __restrict__ src,
                                                            double* __restrict__ dst)
 {
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -280,7 +289,7 @@ __global__ __launch_bounds__(256) void gather_nodes_kernel(int nnodes, const int
 }
 
 // dst[i] = src[idx[i]]
-__global__ __launch_bounds__(256) void gather_kernel(int m, const int* __restrict__ idx,
+static __global__ __launch_bounds__(256) void gather_kernel(int m, const int* __restrict__ idx,
                                                      const double* __restrict__ src,
                                                      double* __restrict__ dst)
 {

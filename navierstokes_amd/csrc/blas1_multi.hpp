@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kRedWG) void mdot_stage1(int n, int seg, int m, con
 
 // One workgroup per column: the finishing tree of reduce_stage2<0> over that column's partials.  accum != nullptr: also
 // accum[j] = accum[j] + dots[j], ONE rounded add (the Hessenberg entry of a second Gram-Schmidt pass).
-__global__ __launch_bounds__(kRedWG) void mdot_stage2(int np, const double* __restrict__ partial, double* __restrict__ dots,
+static __global__ __launch_bounds__(kRedWG) void mdot_stage2(int np, const double* __restrict__ partial, double* __restrict__ dots,
                                                       double* __restrict__ accum)
 {
     __shared__ double s_part[4];

@@ -1,6 +1,7 @@
 // capi_bcsr.hip: BCSR 4x4 handles and products, multi-vector products, Krylov basis — part of libmi355spmv.so (see capi_internal.hpp for the layout of the library).
 // Built for gfx950 only; no CPU fallback anywhere: every compute entry point needs a HIP device.
 #include "capi_internal.hpp"
+#include "blas1_kernels.hpp"
 #include "spmv_bcsr_sell.hpp"
 #include "spmm_tile_plan.hpp"
 
@@ -758,14 +759,6 @@ extern "C" int mi_spmm_dev(mi_csr_t A, int s, const double* d_X, long long ldx, 
         if (rc) return rc;
     }
     return MI_OK;
-}
-
-// y[i] /= *d (IEEE division by a scalar read from device memory)
-__global__ __launch_bounds__(256) void div_by_scalar_kernel(int n, const double* __restrict__ d, double* __restrict__ y)
-{
-    const double q = d[0];
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] = __ddiv_rn(y[i], q);
 }
 
 // V[:, 0] = v0, V[:, k+1] = A V[:, k] for k < s: BuildKrylovBasis_AVX2, src/kernels/spmm_avx2.c:112-168 (a dense n x (s+1)

@@ -3,6 +3,7 @@
 #include "capi_internal.hpp"
 #include "blas1_kernels.hpp"
 #include "blas1_multi.hpp"
+#include "gmres_kernels.hpp"
 
 // Reduction workspace: partials of the two-stage reductions, one per (device, stream) so that
 // reductions enqueued on different streams (or by different rank threads of one process) never share
@@ -78,6 +79,22 @@ extern "C" int mi_norm2_dev(int n, const double* d_x, double* d_out, mi_stream_t
 extern "C" int mi_rel_error_dev(int n, const double* d_ref, const double* d_test, double* d_out, mi_stream_t s)
 {
     return reduce_dev<1, 2>(n, d_ref, d_test, d_out, (hipStream_t)s);
+}
+
+// r = b - w and ||r||_2 into d_out: the residual at the start of a GMRES cycle (gmres_kernels.hpp) in two launches, the norm with
+// the bits of mi_norm2_dev(r).  n > 0, arguments checked by the caller (capi_gmres.hip)
+int residual_norm_dev(int n, const double* d_b, const double* d_w, double* d_r, double* d_out, hipStream_t s)
+{
+    double* ws = nullptr;
+    int rc = get_ws(s, &ws);
+    if (rc) return rc;
+    int np, seg;
+    red_geometry(n, &np, &seg);
+    if (blas1_nt(n)) hipLaunchKernelGGL((gmres_residual<true>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_b, d_w, d_r, ws);
+    else hipLaunchKernelGGL((gmres_residual<false>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_b, d_w, d_r, ws);
+    hipLaunchKernelGGL((reduce_stage2<1>), dim3(1), dim3(kRedWG), 0, s, np, ws, ws + kMaxPartials, d_out);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
 }
 
 extern "C" int mi_axpy_dev(int n, double a, const double* d_x, double* d_y, mi_stream_t s)

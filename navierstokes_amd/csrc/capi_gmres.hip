@@ -1,0 +1,274 @@
+// capi_gmres.hip: mi_gmres_* — right-preconditioned restarted GMRES with a whole cycle enqueued on the device (include/mi355_spmv.h,
+// DESIGN.md 4.6) — part of libmi355spmv.so (see capi_internal.hpp for the layout of the library).  The vector work is the library's
+// own entry points (the products, mi_bilu4*_solve_dev, mi_cgs_dev, mi_maxpy_dev, mi_axpy_dev); what is new on the device is
+// gmres_kernels.hpp.  Built for gfx950 only; no CPU fallback: every entry point that computes needs a HIP device.
+#include "capi_internal.hpp"
+#include "gmres_kernels.hpp"
+
+struct mi_gmres_s {
+    int device = 0;
+    int n = 0, m = 0;       // rows; restart
+    long long ldv = 0;      // n rounded up to even: every row of V is 16-byte aligned
+    mi_csr_t A_csr = nullptr;       // the operator: one of the two (not owned)
+    mi_bcsr4_t A_bcsr = nullptr;
+    mi_bilu4_t F = nullptr;         // the preconditioner (not owned), or null
+    int pc_kind = MI_GMRES_PC_EXACT, sf = 0, sb = 0;
+    DevArray<double> V;             // (m + 1) rows of ldv
+    DevArray<double> w, z;          // the two work vectors
+    DevArray<double> small;         // GmresSmall (gmres_kernels.hpp)
+    DevArray<double> hb, hx;        // b and x of the host-pointer solve, allocated by its first call
+    PinnedArray<double> slot[2];    // read-back slots: the record and the cycle's history entries
+    OwnedEvent ev[2];
+    std::vector<const double*> Vptr; // the rows of V, as mi_cgs_dev / mi_maxpy_dev take them
+    int next_slot = 0;
+    int last_k = 0;                 // the last cycle: its counted steps and its ||r0||
+    double last_beta = 0.0;
+    int readbacks_last = 0, launches_last = 0, wasted_last = 0;
+    GmresSmall S() const { return GmresSmall{m, small.get()}; }
+    double* row(int k) const { return V.get() + (size_t)k * ldv; }
+    // freed in the order of allocation
+    ~mi_gmres_s() { V = {}, w = {}, z = {}, small = {}, hb = {}, hx = {}; }
+};
+
+constexpr size_t kGmresSlotDoubles = kGmresRecDoubles + kMultiMax;
+
+extern "C" int mi_gmres_create(int n, int restart, mi_gmres_t* out)
+{
+    CHECK_ARG(out, "null output handle");
+    *out = nullptr;
+    CHECK_ARG(n >= 1, "n must be at least 1");
+    CHECK_ARG(restart >= 1 && restart <= kMultiMax, "restart must be in 1..64");
+    int rc = need_device();
+    if (rc) return rc;
+    std::unique_ptr<mi_gmres_s> G(new (std::nothrow) mi_gmres_s);
+    if (!G) return fail(MI_ERR_ALLOC, "out of host memory");
+    HIP_TRY(hipGetDevice(&G->device));
+    G->n = n, G->m = restart, G->ldv = (long long)n + (n & 1);
+    if ((rc = dev_alloc(G->V, (size_t)(restart + 1) * G->ldv)) || (rc = dev_alloc(G->w, (size_t)G->ldv)) || (rc = dev_alloc(G->z, (size_t)G->ldv)) ||
+        (rc = dev_zeros(G->small, GmresSmall::doubles(restart))))
+        return rc;
+    for (int i = 0; i < 2; i++) {
+        HIP_TRY_AS("hipHostMalloc", G->slot[i].alloc(kGmresSlotDoubles));
+        if ((rc = dev_create(G->ev[i], hipEventDisableTiming))) return rc;
+    }
+    for (int k = 0; k <= restart; k++) G->Vptr.push_back(G->row(k));
+    *out = G.release();
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_destroy(mi_gmres_t G)
+{
+    if (!G) return MI_OK;
+    (void)hipDeviceSynchronize(); // a copy into a pinned slot may still be in flight behind the last solve
+    delete G;
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_set_operator_csr(mi_gmres_t G, mi_csr_t A)
+{
+    CHECK_ARG(G && A, "null handle");
+    CHECK_ARG(A->n == A->ncols && !A->mapped, "the operator must be a square, unmapped matrix");
+    CHECK_ARG(A->n == G->n, "the operator's row count is not the solver's n");
+    G->A_csr = A, G->A_bcsr = nullptr;
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_set_operator_bcsr4(mi_gmres_t G, mi_bcsr4_t A)
+{
+    CHECK_ARG(G && A, "null handle");
+    CHECK_ARG(A->nbrows == A->nbcols, "the operator must be square");
+    CHECK_ARG(4LL * A->nbrows == G->n, "the operator's row count (4 nbrows) is not the solver's n");
+    G->A_bcsr = A, G->A_csr = nullptr;
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_set_precond(mi_gmres_t G, mi_bilu4_t F, int kind, int sweeps_fwd, int sweeps_bwd)
+{
+    CHECK_ARG(G, "null handle");
+    if (!F) {
+        G->F = nullptr;
+        return MI_OK;
+    }
+    CHECK_ARG(kind == MI_GMRES_PC_EXACT || kind == MI_GMRES_PC_SWEEPS || kind == MI_GMRES_PC_SWEEPS_F32, "unknown preconditioner kind");
+    CHECK_ARG(kind == MI_GMRES_PC_EXACT || (sweeps_fwd >= 0 && sweeps_bwd >= 0), "negative sweep count");
+    int nb = 0, rc;
+    if ((rc = mi_bilu4_info(F, &nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
+    CHECK_ARG(4LL * nb == G->n, "the preconditioner's row count (4 nbrows) is not the solver's n");
+    // everything a solve would otherwise allocate on first use
+    if (kind == MI_GMRES_PC_SWEEPS && (rc = mi_bilu4sw_prepare(F))) return rc;
+    if (kind == MI_GMRES_PC_SWEEPS_F32 && (rc = mi_bilu4sp_prepare(F))) return rc;
+    G->F = F, G->pc_kind = kind, G->sf = sweeps_fwd, G->sb = sweeps_bwd;
+    return MI_OK;
+}
+
+static int gmres_mult(mi_gmres_s* G, const double* x, double* y, mi_stream_t s)
+{
+    return G->A_csr ? mi_spmv_dev(G->A_csr, x, y, s) : mi_bcsr4_spmv_dev(G->A_bcsr, x, y, s);
+}
+
+static int gmres_precond(mi_gmres_s* G, const double* in, double* out, mi_stream_t s)
+{
+    switch (G->pc_kind) {
+    case MI_GMRES_PC_SWEEPS: return mi_bilu4sw_solve_dev(G->F, in, out, G->sf, G->sb, s);
+    case MI_GMRES_PC_SWEEPS_F32: return mi_bilu4sp_solve_dev(G->F, in, out, G->sf, G->sb, s);
+    default: return mi_bilu4_solve_dev(G->F, in, out, s);
+    }
+}
+
+// step k of a cycle, enqueued: w = A M^-1 V_k straight into row k + 1, CGS2 in place with the raw column where the small problem
+// reads it, the small problem, the division
+static int gmres_enqueue_step(mi_gmres_s* G, int k, double rtol, int grid, hipStream_t st)
+{
+    const GmresSmall S = G->S();
+    mi_stream_t s = (mi_stream_t)st;
+    double* next = G->row(k + 1);
+    double* col = S.hraw() + (size_t)k * (G->m + 2);
+    int rc;
+    if (G->F) {
+        if ((rc = gmres_precond(G, G->row(k), G->z, s)) || (rc = gmres_mult(G, G->z, next, s))) return rc;
+        G->launches_last++;
+    } else if ((rc = gmres_mult(G, G->row(k), next, s))) {
+        return rc;
+    }
+    if ((rc = mi_cgs_dev(G->n, k + 1, G->Vptr.data(), next, 2, col, col + k + 1, s))) return rc;
+    hipLaunchKernelGGL(gmres_hess_step, dim3(1), dim3(64), 0, st, S, k, rtol);
+    hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, G->n, col + k + 1, next);
+    G->launches_last += 4;
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, double rtol, int maxiter, int check_every, int* iterations,
+                                  int* reason_out, double* history, mi_stream_t s)
+{
+    CHECK_ARG(check_every >= 1, "check_every must be at least 1");
+    CHECK_ARG(maxiter >= 0, "negative maxiter");
+    CHECK_ARG(G, "null handle");
+    CHECK_ARG(d_b && d_x, "null vector");
+    if (!G->A_csr && !G->A_bcsr) return fail(MI_ERR_STATE, "mi_gmres_solve_dev: no operator set (mi_gmres_set_operator_*)");
+    hipStream_t st = (hipStream_t)s;
+    if (stream_is_capturing(st)) return fail(MI_ERR_STATE, "mi_gmres_solve_dev: the stream is capturing and a solve reads back (it cannot be captured)");
+    const int n = G->n, m = G->m;
+    const GmresSmall S = G->S();
+    int grid = (n + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    G->readbacks_last = G->launches_last = G->wasted_last = 0;
+    G->last_k = 0;
+    int its = 0, reason = 0, rc;
+    bool first = true;
+    for (;;) {
+        // ---- the start of a cycle: r = b - A x into row 0, its norm, the record, V_0 = r / beta
+        if ((rc = gmres_mult(G, d_x, G->w, s)) || (rc = residual_norm_dev(n, d_b, G->w, G->row(0), S.beta(), st))) return rc;
+        if (first && (rc = mi_norm2_dev(n, d_b, S.bnorm(), s))) return rc;
+        hipLaunchKernelGGL(gmres_cycle_begin, dim3(1), dim3(64), 0, st, S, first ? 1 : 0, rtol, maxiter);
+        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, n, S.beta(), G->row(0));
+        HIP_TRY(hipGetLastError());
+        G->launches_last += first ? 6 : 5;
+        // ---- batches of steps; behind each the record and the cycle's history go to a pinned slot, and the host looks at a batch's
+        // slot only after the NEXT batch is enqueued
+        GmresRecord rec{};
+        int k_enq = 0, pending = -1;
+        for (;;) {
+            int cur = -1;
+            const int room = std::min(m - k_enq, maxiter - its - k_enq);
+            if (room > 0 || pending < 0) { // (room == 0 with nothing pending: maxiter == 0, the record alone)
+                // (a cycle's first batch is one step short: a solve that ends at the cycle's start, which only this batch's record
+                // tells, has then wasted 2 check_every - 1 steps at most, like one that freezes inside a batch)
+                const int nb = std::min(pending < 0 ? check_every - 1 : check_every, std::max(room, 0));
+                for (int j = 0; j < nb; j++)
+                    if ((rc = gmres_enqueue_step(G, k_enq + j, rtol, grid, st))) return rc;
+                k_enq += nb;
+                cur = G->next_slot;
+                G->next_slot ^= 1;
+                HIP_TRY(hipMemcpyAsync(G->slot[cur], S.base, sizeof(double) * (kGmresRecDoubles + (size_t)k_enq), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipEventRecord(G->ev[cur], st));
+            }
+            if (pending >= 0) {
+                HIP_TRY(hipEventSynchronize(G->ev[pending]));
+                G->readbacks_last++;
+                memcpy(&rec, G->slot[pending], sizeof(rec));
+                if (history) {
+                    if (first) history[0] = rec.rel0;
+                    for (int j = 0; j < rec.k; j++) history[its + 1 + j] = G->slot[pending][kGmresRecDoubles + j];
+                }
+                if (rec.reason != 0 || cur < 0) break; // frozen (what is enqueued behind it is wasted), or the cycle's last batch
+            }
+            pending = cur;
+        }
+        G->wasted_last += k_enq - rec.k;
+        its = rec.its;
+        G->last_k = rec.k, G->last_beta = rec.beta;
+        // ---- the end of a cycle: y on the device, then x += M^-1 (V y)
+        if (rec.k > 0) {
+            hipLaunchKernelGGL(gmres_backsolve, dim3(1), dim3(256), 0, st, S, rec.k);
+            HIP_TRY(hipGetLastError());
+            if (G->F) {
+                HIP_TRY(hipMemsetAsync(G->w, 0, sizeof(double) * (size_t)n, st));
+                if ((rc = mi_maxpy_dev(n, rec.k, S.y(), 0, G->Vptr.data(), G->w, nullptr, s)) || (rc = gmres_precond(G, G->w, G->z, s)) ||
+                    (rc = mi_axpy_dev(n, 1.0, G->z, d_x, s)))
+                    return rc;
+                G->launches_last += 5;
+            } else {
+                if ((rc = mi_maxpy_dev(n, rec.k, S.y(), 0, G->Vptr.data(), d_x, nullptr, s))) return rc;
+                G->launches_last += 2;
+            }
+        }
+        reason = rec.reason == kGmresMetAtStart ? 0 : rec.reason;
+        if (rec.reason != 0) break;
+        if (its >= maxiter) {
+            reason = 2;
+            break;
+        }
+        first = false;
+    }
+    if (iterations) *iterations = its;
+    if (reason_out) *reason_out = reason;
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_solve(mi_gmres_t G, const double* b, double* x, double rtol, int maxiter, int check_every, int* iterations, int* reason,
+                              double* history)
+{
+    CHECK_ARG(check_every >= 1, "check_every must be at least 1");
+    CHECK_ARG(maxiter >= 0, "negative maxiter");
+    CHECK_ARG(G, "null handle");
+    CHECK_ARG(b && x, "null vector");
+    int rc;
+    if (!G->hb && ((rc = dev_alloc(G->hb, (size_t)G->ldv)) || (rc = dev_alloc(G->hx, (size_t)G->ldv)))) return rc;
+    const size_t bytes = sizeof(double) * (size_t)G->n;
+    HIP_TRY(hipMemcpy(G->hb, b, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(G->hx, x, bytes, hipMemcpyHostToDevice));
+    if ((rc = mi_gmres_solve_dev(G, G->hb, G->hx, rtol, maxiter, check_every, iterations, reason, history, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(x, G->hx, bytes, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_fetch_cycle(mi_gmres_t G, int* k, double* hraw, double* y, double* beta)
+{
+    CHECK_ARG(G, "null handle");
+    const int m = G->m, kk = G->last_k;
+    const GmresSmall S = G->S();
+    if (k) *k = kk;
+    if (beta) *beta = G->last_beta;
+    if (hraw || y) HIP_TRY(hipDeviceSynchronize());
+    if (hraw) { // columns past the last counted step were never used: reported as zeros (as the places past a column's norm are)
+        memset(hraw, 0, sizeof(double) * (size_t)m * (m + 2));
+        if (kk) HIP_TRY(hipMemcpy(hraw, S.hraw(), sizeof(double) * (size_t)kk * (m + 2), hipMemcpyDeviceToHost));
+    }
+    if (y) {
+        memset(y, 0, sizeof(double) * (size_t)m);
+        if (kk) HIP_TRY(hipMemcpy(y, S.y(), sizeof(double) * (size_t)kk, hipMemcpyDeviceToHost));
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_info(mi_gmres_t G, int* restart, long long* device_bytes, int* readbacks_last, int* launches_last, int* wasted_steps_last)
+{
+    CHECK_ARG(G, "null handle");
+    if (restart) *restart = G->m;
+    if (device_bytes)
+        *device_bytes = (long long)sizeof(double) * ((long long)(G->m + 3) * G->ldv + (long long)GmresSmall::doubles(G->m) + (G->hb ? 2 * G->ldv : 0));
+    if (readbacks_last) *readbacks_last = G->readbacks_last;
+    if (launches_last) *launches_last = G->launches_last;
+    if (wasted_steps_last) *wasted_steps_last = G->wasted_last;
+    return MI_OK;
+}

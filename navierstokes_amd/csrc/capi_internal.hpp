@@ -2,7 +2,7 @@
 // error helpers, the handle structs, and the few functions one unit needs from another.  The library is
 // built from capi_lib.hip (library / device / cache flush), capi_csr.hip (CSR handles: create, plans,
 // autotuner, products), launch_csr.hip (the CSR kernels' instantiations and launch_spmv), capi_blas1.hip,
-// capi_bcsr.hip (BCSR 4x4, multi-vector products, Krylov basis), capi_ilu.hip (block ILU preconditioner) and capi_part.hip
+// capi_bcsr.hip (BCSR 4x4, multi-vector products, Krylov basis), capi_ilu.hip (block ILU preconditioner), capi_gmres.hip (restarted GMRES) and capi_part.hip
 // (partition, RCCL and peer-push exchange); devtools.hip (mi355_devtools.h) is linked into libmi355spmv_dev.so only.
 #pragma once
 #include "mi355_spmv.h"
@@ -522,6 +522,7 @@ int gather_perm(mi_csr_t A, const double* d_x, double* d_xp, hipStream_t s);
 int ortho_update_from_parts(int n, int nparts, const double* parts, double alpha, const double* d_b, const double* d_x1, double* d_x3, double* d_beta_out,
                             hipStream_t s);
 int scatter_perm(mi_csr_t A, const double* d_src, double* d_dst, hipStream_t s);
+int residual_norm_dev(int n, const double* d_b, const double* d_w, double* d_r, double* d_out, hipStream_t s); // r = b - w, *d_out = ||r||_2
 // launch_spmm_tile.hip: the multi-vector product's tile form (spmm_tile.hpp), up to four columns
 constexpr size_t kLdsBytesPerCU = 160 * 1024;
 static inline size_t spmm_tile_lds(const SpmmTilePlan* T, int s) { return T ? (size_t)T->umax * (4 * s + 2) * sizeof(double) : (size_t)-1; }

@@ -191,6 +191,15 @@ def lib():
         "mi_bilu4sp_status": [_vp, P(i), P(ll)],
         "mi_bilu4sp_fetch": [_vp, _vp, ll],
         "mi_bilu4sp_info": [_vp, P(i), P(i), P(i), P(ll)],
+        "mi_gmres_create": [i, i, P(_vp)],
+        "mi_gmres_set_operator_csr": [_vp, _vp],
+        "mi_gmres_set_operator_bcsr4": [_vp, _vp],
+        "mi_gmres_set_precond": [_vp, _vp, i, i, i],
+        "mi_gmres_solve_dev": [_vp, _vp, _vp, d, i, i, P(i), P(i), _vp, _vp],
+        "mi_gmres_solve": [_vp, _vp, _vp, d, i, i, P(i), P(i), _vp],
+        "mi_gmres_fetch_cycle": [_vp, P(i), _vp, _vp, P(d)],
+        "mi_gmres_info": [_vp, P(i), P(ll), P(i), P(i), P(i)],
+        "mi_gmres_destroy": [_vp],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -1270,6 +1279,93 @@ def GMRES(A, b, x, M=None, restart=30, rtol=1e-8, maxiter=300):
             maxpy(y, [V[j] for j in range(k)], x)
         if hist[-1] <= rtol or its >= maxiter:
             return its, hist
+
+
+GMRES_PC_EXACT, GMRES_PC_SWEEPS, GMRES_PC_SWEEPS_F32 = 0, 1, 2
+GMRES_CHECK_EVERY = 1  # the default of gmres_solver.solve / GMRES_dev: what tools/bench_gmres.py measured fastest (profiles/NOTES.md R12.1)
+
+
+class gmres_solver:
+    """mi_gmres_t: GMRES's definition above with a whole restart cycle enqueued on the device — the products, M, CGS2, the Givens
+    rotations, the residual recurrence and the back-substitution — and one small read-back per check_every iterations instead of
+    one stream drain per iteration (include/mi355_spmv.h, mi_gmres_*; DESIGN.md 4.6).  A: a bcsr4x4_matrix or a square csrmatrix;
+    M: a bilu4 (the exact solve in the handle's current form), a bilu4_sweeps (either precision) or None.  The solver owns its
+    basis and work vectors; A and M must outlive it.  One solve at a time per solver, and per M."""
+
+    def __init__(self, A, M=None, restart=30):
+        self._h = None
+        self.A, self.M = A, M
+        self.n = 4 * A.nrows if isinstance(A, bcsr4x4_matrix) else A.n
+        self.restart = int(restart)
+        h = _vp()
+        check(lib().mi_gmres_create(self.n, self.restart, _c.byref(h)))
+        self._h = h
+        if isinstance(A, bcsr4x4_matrix):
+            check(lib().mi_gmres_set_operator_bcsr4(h, A.handle))
+        else:
+            check(lib().mi_gmres_set_operator_csr(h, A.handle))
+        if isinstance(M, bilu4_sweeps):
+            check(lib().mi_gmres_set_precond(h, M.F.handle, GMRES_PC_SWEEPS_F32 if M._f32 else GMRES_PC_SWEEPS, M.fwd, M.bwd))
+        elif M is not None:
+            check(lib().mi_gmres_set_precond(h, M.handle, GMRES_PC_EXACT, 0, 0))
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("gmres_solver: closed")
+        return self._h
+
+    def solve(self, b, x, rtol=1e-8, maxiter=300, check_every=GMRES_CHECK_EVERY):
+        """(iterations, history, reason).  CUDA tensors: on torch's current stream, x (the initial guess, then the solution) is
+        complete on that stream when the call returns; numpy arrays: copied in and out.  reason: 0 the initial guess met rtol,
+        1 converged, 2 maxiter, 3 Krylov space exhausted, 4 a non-finite quantity or rho = 0."""
+        its, reason = _c.c_int(), _c.c_int()
+        hist = np.zeros(max(int(maxiter), 0) + 1)
+        if _is_torch(b):
+            check(lib().mi_gmres_solve_dev(self.handle, _dev_ptr(b, self.n, "b"), _dev_ptr(x, self.n, "x"), float(rtol), int(maxiter),
+                                           int(check_every), _c.byref(its), _c.byref(reason), hist.ctypes.data, _stream_ptr()))
+        else:
+            xx = _host_f64(x, self.n, "x", writable=True)
+            check(lib().mi_gmres_solve(self.handle, _host_f64(b, self.n, "b").ctypes.data, xx.ctypes.data, float(rtol), int(maxiter),
+                                       int(check_every), _c.byref(its), _c.byref(reason), hist.ctypes.data))
+        return its.value, [float(v) for v in hist[: its.value + 1]], reason.value
+
+    def fetch_cycle(self):
+        """(k, hraw, y, beta) of the last cycle of the last solve (mi_gmres_fetch_cycle): hraw (restart, restart + 2), row c the raw
+        Gram-Schmidt column of step c with its norm at c + 1 (BuildKrylovBasis's layout); y (k,) the least-squares solution."""
+        m = self.restart
+        k, beta = _c.c_int(), _c.c_double()
+        hraw, y = np.zeros((m, m + 2)), np.zeros(m)
+        check(lib().mi_gmres_fetch_cycle(self.handle, _c.byref(k), hraw.ctypes.data, y.ctypes.data, _c.byref(beta)))
+        return k.value, hraw, y[: k.value], beta.value
+
+    def info(self):
+        """dict(restart, device_bytes, readbacks_last, launches_last, wasted_steps_last) — mi_gmres_info."""
+        m, rb, la, wa = (_c.c_int() for _ in range(4))
+        by = _c.c_longlong()
+        check(lib().mi_gmres_info(self.handle, _c.byref(m), _c.byref(by), _c.byref(rb), _c.byref(la), _c.byref(wa)))
+        return dict(restart=m.value, device_bytes=by.value, readbacks_last=rb.value, launches_last=la.value, wasted_steps_last=wa.value)
+
+    def close(self):
+        if self._h is not None:
+            lib().mi_gmres_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def GMRES_dev(A, b, x, M=None, restart=30, rtol=1e-8, maxiter=300, check_every=GMRES_CHECK_EVERY):
+    """GMRES(A, b, x, M, restart, rtol, maxiter) through a gmres_solver made for the call: (iterations, history)."""
+    S = gmres_solver(A, M, restart)
+    try:
+        its, hist, _ = S.solve(b, x, rtol, maxiter, check_every)
+    finally:
+        S.close()
+    return its, hist
 
 
 # ------------------------------------------------------------------- BLAS-1

@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Restarted GMRES(30) to rtol = 1e-8 on the FE matrix: mpk.GMRES (the Python loop: one read-back of the Hessenberg column per
+iteration) against mpk.gmres_solver (mi_gmres_*: a whole cycle enqueued on the device) at check_every = 1, 5 and restart, with
+the SAME matrix and factor handles, in one process.  Prints one JSON line per preconditioner and appends it to
+profiles/gmres_bench.jsonl.
+
+    python3 tools/bench_gmres.py [--cells 68] [--fill 0] [--sweeps 3] [--precision f64|f32|both] [--runs 5] [--no-append]
+
+Preconditioners per process: the sweeps (--sweeps per triangle) in each precision asked for, and the exact solve.  For each one a
+record (tool = "bench_gmres") with, per solver: iterations, wall seconds (median of --runs runs; the solvers ALTERNATE inside every
+run, after one warm-up each), the spread of the runs (max - min), microseconds per iteration, the true residual
+||b - A x|| / ||b||, and for gmres_solver readbacks_last and wasted_steps_last.  The yardstick is mpk.GMRES in the same process."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+RESTART, RTOL = 30, 1e-8
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cells", type=int, default=68)
+    ap.add_argument("--fill", type=int, default=0)
+    ap.add_argument("--sweeps", type=int, default=3)
+    ap.add_argument("--precision", choices=("f64", "f32", "both"), default="f64")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--maxiter", type=int, default=300)
+    ap.add_argument("--no-append", action="store_true")
+    a = ap.parse_args()
+    import torch
+    from navierstokes_amd import mpk, synth
+
+    bp, bc, bv = synth.csr_to_bcsr4(*synth.fe_matrix(a.cells))
+    nb = len(bp) - 1
+    n = 4 * nb
+    A = mpk.bcsr4x4_matrix(nb, bp, bc, bv)
+    F = mpk.bilu4(A, fill=a.fill)
+    b = synth.x_sin(0, n) + 1.0
+    db = torch.from_numpy(b).cuda()
+    dx, dy = torch.zeros_like(db), torch.zeros_like(db)
+    bnorm = float(np.linalg.norm(b))
+    preconds = [(f"sweeps{a.sweeps}_{p}", F.sweeps(a.sweeps, precision=p)) for p in (("f64", "f32") if a.precision == "both" else (a.precision,))]
+    preconds.append(("exact", F))
+    for label, M in preconds:
+        S = mpk.gmres_solver(A, M, RESTART)
+        solvers = [("mpk.GMRES", None)] + [(f"gmres_solver_ce{ce}", ce) for ce in (1, 5, RESTART)]
+
+        def run(ce):
+            dx.zero_()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if ce is None:
+                its, hist = mpk.GMRES(A, db, dx, M=M, restart=RESTART, rtol=RTOL, maxiter=a.maxiter)
+            else:
+                its, hist, _ = S.solve(db, dx, rtol=RTOL, maxiter=a.maxiter, check_every=ce)
+            torch.cuda.synchronize()
+            sec = time.perf_counter() - t0
+            mpk.SpMV_BCSR(dy, dx, A)
+            true = float(np.linalg.norm(b - dy.cpu().numpy()) / bnorm)
+            return its, sec, true, float(hist[-1])
+
+        for _, ce in solvers:  # one warm-up each
+            run(ce)
+        secs = {name: [] for name, _ in solvers}
+        last = {}
+        for _ in range(a.runs):  # the solvers alternate inside every run
+            for name, ce in solvers:
+                its, sec, true, rec = run(ce)
+                secs[name].append(sec)
+                last[name] = dict(iterations=its, true_residual=true, recurrence_residual=rec)
+                if ce is not None:
+                    info = S.info()
+                    last[name].update(readbacks_last=info["readbacks_last"], wasted_steps_last=info["wasted_steps_last"], launches_last=info["launches_last"])
+        out = dict(tool="bench_gmres", cells=a.cells, rows=n, fill=a.fill, precond=label, restart=RESTART, rtol=RTOL, runs=a.runs,
+                   default_check_every=mpk.GMRES_CHECK_EVERY, solvers={})
+        for name, _ in solvers:
+            med = statistics.median(secs[name])
+            out["solvers"][name] = dict(last[name], seconds=round(med, 6), spread_seconds=round(max(secs[name]) - min(secs[name]), 6),
+                                        us_per_iteration=round(med * 1e6 / max(last[name]["iterations"], 1), 2),
+                                        spread_us_per_iteration=round((max(secs[name]) - min(secs[name])) * 1e6 / max(last[name]["iterations"], 1), 2))
+        line = json.dumps(out)
+        print(line, flush=True)
+        if not a.no_append:
+            with open(os.path.join(ROOT, "profiles", "gmres_bench.jsonl"), "a") as f:
+                f.write(line + "\n")
+        S.close()
+    F.close()
+    A.close()
+
+
+if __name__ == "__main__":
+    main()
