@@ -381,6 +381,24 @@ int mi_maxpy_dev(int n, int m, const double* d_coef /* device [m] */, int negate
  * MI_ERR_ARG: as for mi_mdot, or passes outside {1, 2}. */
 int mi_cgs_dev(int n, int m, const double* const* d_basis, double* d_y, int passes, double* d_h /* device [m] */,
                double* d_norm /* device [1] */, mi_stream_t s);
+/* The three calls above against a basis stored in SINGLE PRECISION (the basis of a MI_BASIS_F32 solver, mi_gmres_* below): every
+ * basis entry f is used as widen(f) = (double)f, which is exact; y, the coefficients, the accumulators and every fma stay double.
+ * The results are, BIT FOR BIT, those of mi_mdot_dev / mi_maxpy_dev / mi_cgs_dev on the widened vectors — the same segments, lane
+ * pairs and finishing tree — whatever the tile, y's alignment, the stream or the non-temporal choice; a lane loads its pair of
+ * basis entries with one 8-byte load, so the basis costs half the bytes.  Argument rules: those of the double calls, and every
+ * float vector must be 8-BYTE ALIGNED (MI_ERR_ARG otherwise); all are checked before the device is touched.  Nothing is allocated
+ * per call beyond the per-stream workspace of the double calls; all three can be captured into a graph. */
+int mi_mdot_f32_dev(int n, int m, const float* const* d_basis /* HOST array of m device pointers */, const double* d_y,
+                    double* d_dots /* device [m] */, mi_stream_t s);
+int mi_maxpy_f32_dev(int n, int m, const double* d_coef /* device [m] */, int negate, const float* const* d_basis, double* d_y,
+                     double* d_norm_out, mi_stream_t s);
+int mi_cgs_f32_dev(int n, int m, const float* const* d_basis, double* d_y, int passes, double* d_h /* device [m] */,
+                   double* d_norm /* device [1] */, mi_stream_t s);
+/* d_out32[i] = round32(d_x[i] / *d_div) — the IEEE division in double, then round32 as mi_gmres_* defines it below; d_div NULL
+ * (else device [1]): no division — and d_out64[i] = widen(d_out32[i]), in one pass and one launch.  d_out64 NULL: not written;
+ * d_out64 == d_x is allowed (in place).  d_out32 needs 4-byte alignment, the double vectors 8; d_out32 must not be one of them.
+ * MI_ERR_ARG before the device is touched: n < 0, d_x or d_out32 null, a misaligned vector.  n == 0: nothing is done. */
+int mi_round_f32_dev(int n, const double* d_x, const double* d_div, float* d_out32, double* d_out64, mi_stream_t s);
 /* sqrt(sum x^2) (norm2, mpk/utils.cpp:131-136) and ||ref-test||/||ref|| (rel_error, :138-143) */
 int mi_norm2(int n, const double* x, double* out);
 int mi_norm2_dev(int n, const double* d_x, double* d_out, mi_stream_t s);
@@ -793,6 +811,45 @@ int mi_gmres_fetch_cycle(mi_gmres_t G, int* k, double* hraw, double* y, double* 
  * *wasted_steps_last.  Any output may be NULL */
 int mi_gmres_info(mi_gmres_t G, int* restart, long long* device_bytes, int* readbacks_last, int* launches_last, int* wasted_steps_last);
 int mi_gmres_destroy(mi_gmres_t G);
+
+/* ---- mi_gmres_* with an opt-in SINGLE-PRECISION KRYLOV BASIS (MI_BASIS_F32) ----
+ * CGS2 reads the whole basis four times per iteration, and the basis is the largest object a solver owns.  Nothing in GMRES needs
+ * 53 bits of every basis entry: if every projection is taken against the basis AS STORED, the Arnoldi relation holds to float
+ * rounding, and the cycle's update and the next cycle's true residual remove that error (the compressed-basis GMRES of Aliaga,
+ * Anzt et al.).  Nothing chooses this automatically: mi_gmres_create is mi_gmres_create_ex(.., MI_BASIS_F64), and with
+ * MI_BASIS_F64 nothing changes, bit for bit, mi_gmres_info's device_bytes included.  The operator a MI_BASIS_F32 solve sees is
+ * that of the rounded basis: its history and iteration count are close to the double basis's, not equal to them.
+ * DEFINITION (part of the interface):
+ *   round32(v) = (float)v    rounded to nearest, ties to EVEN (what numpy's astype(float32) does); float SUBNORMALS are kept, not
+ *                            flushed; a finite v beyond the float range becomes +-Inf; -0 stays -0; NaN stays NaN
+ *   widen(f)   = (double)f   exact
+ * and a MI_BASIS_F32 solve is the DEFINITION of mi_gmres_* above with these changes and no others (the small problem and its
+ * ARITHMETIC, hraw, R, g, y, the frozen state, the batches and check_every stay; the result stays independent of check_every):
+ *   storage    V32: restart + 1 float rows, the leading dimension rounded up to a multiple of 4 (every row 16-byte aligned); one
+ *              double vector q; the two double work vectors.  There is no double V
+ *   cycle      r = b - A x into a work vector, beta as before;  V32_0[i] = round32(r_i / beta) (IEEE division), q_i = widen(V32_0[i])
+ *   step k     w = A (M^-1 q) into a work vector;  mi_cgs_f32_dev(passes = 2) of w in place against V32_0..V32_k: d_j has the
+ *              bits of mi_dot_dev(w, widen(V32_j)), the update is w_i = fma(-d_j, widen(V32_j[i]), w_i) in basis order, nrm has
+ *              the bits of mi_norm2_dev of the new w, h = d(pass 1) + d(pass 2), one rounded add;  the small problem on the raw
+ *              column, unchanged;  V32_{k+1}[i] = round32(w_i / nrm), q_i = widen(V32_{k+1}[i]) (mi_round_f32_dev): the vector
+ *              fed to the next product is the STORED basis vector, not the unrounded one
+ *   cycle end  as before, with mi_maxpy_f32_dev(y, V32_0..V32_{k-1}, .) in place of mi_maxpy_dev
+ *   confirmed  the recurrence's residual is exact only to float rounding of the basis, so convergence is confirmed, not assumed:
+ *              when a step sets reason 1 the cycle freezes and its update runs as before, but the solve does not end: the next
+ *              cycle starts, and its start check (beta / bnorm <= rtol: the TRUE residual) reports reason 1; otherwise the solve
+ *              goes on, or ends with reason 2 when its >= maxiter.  Reasons 0, 3 and 4 end the solve as before.  history keeps
+ *              iterations + 1 entries: a confirming start adds none.  After a confirmed solve mi_gmres_fetch_cycle reports that
+ *              last cycle: k = 0 and beta = the confirmed true residual norm.  A claim that the start behind it does not confirm
+ *              is counted (refused_last).  COST: one product and one residual pass more per converged solve than the double
+ *              basis (plus the check_every - 1 steps enqueued behind a cycle's start, which run for nothing as before)
+ * mi_gmres_info's device_bytes counts what such a handle owns (V32, q, two work vectors, the small state).
+ * MI_ERR_ARG: an unknown basis, and the rules of mi_gmres_create. */
+enum { MI_BASIS_F64 = 0, MI_BASIS_F32 = 1 };
+int mi_gmres_create_ex(int n, int restart, int basis, mi_gmres_t* out);
+/* *basis the handle's; *basis_bytes of V (MI_BASIS_F64: 8 (restart + 1) ldv, ldv = n rounded up to even) or of V32 and q
+ * (MI_BASIS_F32: 4 (restart + 1) ldv32 + 8 ldv, ldv32 = n rounded up to a multiple of 4); *refused_last: the unconfirmed claims of
+ * the last solve (always 0 with MI_BASIS_F64).  Any output may be NULL */
+int mi_gmres_basis_info(mi_gmres_t G, int* basis, long long* basis_bytes, int* refused_last);
 
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r

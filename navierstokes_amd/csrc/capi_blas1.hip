@@ -306,8 +306,25 @@ static int mdot_tile()
     return t;
 }
 
-// the argument rules shared by mi_mdot_dev / mi_maxpy_dev / mi_cgs_dev; nothing here touches the device
-static int multi_check(int n, int m, const double* const* basis, const double* y)
+// the float basis (mi_*_f32_dev): 8 or 16 vectors per pass; MI355_MDOT_TILE_F32=8|16 forces the other compiled value (the bits do not
+// depend on it).  The default is what tools/bench_orth.py --basis f32 measured fastest (profiles/NOTES.md R13.1)
+#ifndef MI355_MDOT_TILE_F32_DEFAULT
+#define MI355_MDOT_TILE_F32_DEFAULT 8
+#endif
+static int mdot_tile_f32()
+{
+    static const int t = [] {
+        const int e = getenv("MI355_MDOT_TILE_F32") ? atoi(getenv("MI355_MDOT_TILE_F32")) : 0;
+        return (e == 8 || e == 16) ? e : MI355_MDOT_TILE_F32_DEFAULT;
+    }();
+    return t;
+}
+static int multi_tile(const double*) { return mdot_tile(); }
+static int multi_tile(const float*) { return mdot_tile_f32(); }
+
+// the argument rules shared by mi_mdot_dev / mi_maxpy_dev / mi_cgs_dev and their float-basis twins; nothing here touches the device
+template <typename T>
+static int multi_check(int n, int m, const T* const* basis, const double* y)
 {
     CHECK_ARG(n >= 0, "negative n");
     CHECK_ARG(m >= 0 && m <= kMultiMax, "m must be in 0..64");
@@ -316,74 +333,84 @@ static int multi_check(int n, int m, const double* const* basis, const double* y
     CHECK_ARG(y, "null y");
     for (int j = 0; j < m; j++) {
         CHECK_ARG(basis[j], "null basis vector");
-        CHECK_ARG(basis[j] != y, "y is one of the basis vectors");
+        CHECK_ARG((const void*)basis[j] != (const void*)y, "y is one of the basis vectors");
+        if (sizeof(T) == 4) CHECK_ARG(((uintptr_t)basis[j] & 7) == 0, "a float basis vector is not 8-byte aligned (the kernels load pairs)");
     }
     return MI_OK;
 }
 
-template <int TILE>
-static void mdot_launch(int n, int seg, int np, int m, const double* y, const MultiVec& B, double* part, bool nt, hipStream_t s)
+template <int TILE, typename T>
+static void mdot_launch(int n, int seg, int np, int m, const double* y, const MultiVecT<T>& B, double* part, bool nt, hipStream_t s)
 {
     const dim3 grid(np, (m + TILE - 1) / TILE);
-    if (nt) hipLaunchKernelGGL((mdot_stage1<TILE, true>), grid, dim3(kRedWG), 0, s, n, seg, m, y, B, part);
-    else hipLaunchKernelGGL((mdot_stage1<TILE, false>), grid, dim3(kRedWG), 0, s, n, seg, m, y, B, part);
+    if (nt) hipLaunchKernelGGL((mdot_stage1<TILE, true, T>), grid, dim3(kRedWG), 0, s, n, seg, m, y, B, part);
+    else hipLaunchKernelGGL((mdot_stage1<TILE, false, T>), grid, dim3(kRedWG), 0, s, n, seg, m, y, B, part);
 }
 
 // dots[j] = y . v_j (and accum[j] += dots[j] when accum is given); n > 0, m > 0, arguments checked
-static int mdot_run(int n, int m, const MultiVec& B, const double* y, double* d_dots, double* d_accum, double* ws, hipStream_t s)
+template <typename T>
+static int mdot_run(int n, int m, const MultiVecT<T>& B, const double* y, double* d_dots, double* d_accum, double* ws, hipStream_t s)
 {
     int np, seg;
     red_geometry(n, &np, &seg);
     const bool nt = blas1_nt(n);
-    switch (mdot_tile()) {
-    case 4: mdot_launch<4>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
-    case 16: mdot_launch<16>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
-    default: mdot_launch<8>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
+    switch (multi_tile(B.v[0])) {
+    case 4:
+        if constexpr (sizeof(T) == 8) mdot_launch<4, T>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); // (never chosen for a float basis)
+        break;
+    case 16: mdot_launch<16, T>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
+    default: mdot_launch<8, T>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
     }
     hipLaunchKernelGGL(mdot_stage2, dim3(m), dim3(kRedWG), 0, s, np, ws + kWsMdot, d_dots, d_accum);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
 
-template <int TILE>
-static void maxpy_launch(int n, int seg, int np, int m, const double* coef, int negate, const MultiVec& B, double* y, double* part,
+template <int TILE, typename T>
+static void maxpy_launch(int n, int seg, int np, int m, const double* coef, int negate, const MultiVecT<T>& B, double* y, double* part,
                          bool norm, bool nt, hipStream_t s)
 {
     for (int first = 0; first < m; first += TILE) { // one chunk per launch: each continues the chain from the stored y
         const int cnt = std::min(TILE, m - first);
         const bool last = norm && first + TILE >= m;
-        if (nt && last) hipLaunchKernelGGL((maxpy_kernel<TILE, true, true>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
-        else if (nt) hipLaunchKernelGGL((maxpy_kernel<TILE, true, false>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
-        else if (last) hipLaunchKernelGGL((maxpy_kernel<TILE, false, true>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
-        else hipLaunchKernelGGL((maxpy_kernel<TILE, false, false>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
+        if (nt && last) hipLaunchKernelGGL((maxpy_kernel<TILE, true, true, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
+        else if (nt) hipLaunchKernelGGL((maxpy_kernel<TILE, true, false, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
+        else if (last) hipLaunchKernelGGL((maxpy_kernel<TILE, false, true, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
+        else hipLaunchKernelGGL((maxpy_kernel<TILE, false, false, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
     }
 }
 
 // y <- y + sum a_j v_j and, when d_norm_out is given, the norm of the new y from the last chunk's partials; n > 0, m > 0
-static int maxpy_run(int n, int m, const double* d_coef, int negate, const MultiVec& B, double* y, double* d_norm_out, double* ws,
+template <typename T>
+static int maxpy_run(int n, int m, const double* d_coef, int negate, const MultiVecT<T>& B, double* y, double* d_norm_out, double* ws,
                      hipStream_t s)
 {
     int np, seg;
     red_geometry(n, &np, &seg);
     const bool nt = blas1_nt(n), norm = d_norm_out != nullptr;
-    switch (mdot_tile()) {
-    case 4: maxpy_launch<4>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
-    case 16: maxpy_launch<16>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
-    default: maxpy_launch<8>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
+    switch (multi_tile(B.v[0])) {
+    case 4:
+        if constexpr (sizeof(T) == 8) maxpy_launch<4, T>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s);
+        break;
+    case 16: maxpy_launch<16, T>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
+    default: maxpy_launch<8, T>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
     }
     if (norm) hipLaunchKernelGGL((reduce_stage2<1>), dim3(1), dim3(kRedWG), 0, s, np, ws, ws + kMaxPartials, d_norm_out);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
 
-static MultiVec multi_vec(int m, const double* const* basis)
+template <typename T>
+static MultiVecT<T> multi_vec(int m, const T* const* basis)
 {
-    MultiVec B;
+    MultiVecT<T> B;
     for (int j = 0; j < kMultiMax; j++) B.v[j] = j < m ? basis[j] : nullptr;
     return B;
 }
 
-extern "C" int mi_mdot_dev(int n, int m, const double* const* d_basis, const double* d_y, double* d_dots, mi_stream_t s_)
+// mi_mdot_dev / mi_maxpy_dev / mi_cgs_dev and their float-basis twins: one body each, T the basis's element type
+template <typename T>
+static int mdot_dev(int n, int m, const T* const* d_basis, const double* d_y, double* d_dots, mi_stream_t s_)
 {
     int rc = multi_check(n, m, d_basis, d_y);
     if (rc) return rc;
@@ -399,8 +426,8 @@ extern "C" int mi_mdot_dev(int n, int m, const double* const* d_basis, const dou
     return mdot_run(n, m, multi_vec(m, d_basis), d_y, d_dots, nullptr, ws, s);
 }
 
-extern "C" int mi_maxpy_dev(int n, int m, const double* d_coef, int negate, const double* const* d_basis, double* d_y,
-                            double* d_norm_out, mi_stream_t s_)
+template <typename T>
+static int maxpy_dev(int n, int m, const double* d_coef, int negate, const T* const* d_basis, double* d_y, double* d_norm_out, mi_stream_t s_)
 {
     int rc = multi_check(n, m, d_basis, d_y);
     if (rc) return rc;
@@ -413,8 +440,8 @@ extern "C" int mi_maxpy_dev(int n, int m, const double* d_coef, int negate, cons
     return maxpy_run(n, m, d_coef, negate, multi_vec(m, d_basis), d_y, d_norm_out, ws, s);
 }
 
-extern "C" int mi_cgs_dev(int n, int m, const double* const* d_basis, double* d_y, int passes, double* d_h, double* d_norm,
-                          mi_stream_t s_)
+template <typename T>
+static int cgs_dev(int n, int m, const T* const* d_basis, double* d_y, int passes, double* d_h, double* d_norm, mi_stream_t s_)
 {
     int rc = multi_check(n, m, d_basis, d_y);
     if (rc) return rc;
@@ -425,7 +452,7 @@ extern "C" int mi_cgs_dev(int n, int m, const double* const* d_basis, double* d_
     if (m == 0 || n == 0) return mi_norm2_dev(n, d_y, d_norm, s_);
     double* ws = nullptr;
     if ((rc = get_ws(s, &ws))) return rc;
-    const MultiVec B = multi_vec(m, d_basis);
+    const MultiVecT<T> B = multi_vec(m, d_basis);
     // per pass: every dot against the SAME y, then one update with the negated dots; the norm rides on the last update
     if ((rc = mdot_run(n, m, B, d_y, d_h, nullptr, ws, s))) return rc;
     if ((rc = maxpy_run(n, m, d_h, 1, B, d_y, passes == 1 ? d_norm : nullptr, ws, s))) return rc;
@@ -434,6 +461,58 @@ extern "C" int mi_cgs_dev(int n, int m, const double* const* d_basis, double* d_
         if ((rc = mdot_run(n, m, B, d_y, d2, d_h, ws, s))) return rc; // h_j = h_j + d2_j, one rounded add
         if ((rc = maxpy_run(n, m, d2, 1, B, d_y, d_norm, ws, s))) return rc;
     }
+    return MI_OK;
+}
+
+extern "C" int mi_mdot_dev(int n, int m, const double* const* d_basis, const double* d_y, double* d_dots, mi_stream_t s)
+{
+    return mdot_dev(n, m, d_basis, d_y, d_dots, s);
+}
+
+extern "C" int mi_maxpy_dev(int n, int m, const double* d_coef, int negate, const double* const* d_basis, double* d_y,
+                            double* d_norm_out, mi_stream_t s)
+{
+    return maxpy_dev(n, m, d_coef, negate, d_basis, d_y, d_norm_out, s);
+}
+
+extern "C" int mi_cgs_dev(int n, int m, const double* const* d_basis, double* d_y, int passes, double* d_h, double* d_norm,
+                          mi_stream_t s)
+{
+    return cgs_dev(n, m, d_basis, d_y, passes, d_h, d_norm, s);
+}
+
+extern "C" int mi_mdot_f32_dev(int n, int m, const float* const* d_basis, const double* d_y, double* d_dots, mi_stream_t s)
+{
+    return mdot_dev(n, m, d_basis, d_y, d_dots, s);
+}
+
+extern "C" int mi_maxpy_f32_dev(int n, int m, const double* d_coef, int negate, const float* const* d_basis, double* d_y,
+                                double* d_norm_out, mi_stream_t s)
+{
+    return maxpy_dev(n, m, d_coef, negate, d_basis, d_y, d_norm_out, s);
+}
+
+extern "C" int mi_cgs_f32_dev(int n, int m, const float* const* d_basis, double* d_y, int passes, double* d_h, double* d_norm,
+                              mi_stream_t s)
+{
+    return cgs_dev(n, m, d_basis, d_y, passes, d_h, d_norm, s);
+}
+
+// out32 = round32(x / *d_div), out64 = widen(out32) (gmres_kernels.hpp): one launch, nothing allocated, capturable
+extern "C" int mi_round_f32_dev(int n, const double* d_x, const double* d_div, float* d_out32, double* d_out64, mi_stream_t s)
+{
+    CHECK_ARG(n >= 0, "negative n");
+    if (n == 0) return MI_OK;
+    CHECK_ARG(d_x && d_out32, "null vector");
+    CHECK_ARG(((uintptr_t)d_out32 & 3) == 0 && (((uintptr_t)d_x | (uintptr_t)d_out64) & 7) == 0, "a misaligned vector");
+    CHECK_ARG((const void*)d_out32 != (const void*)d_x && (const void*)d_out32 != (const void*)d_out64, "out32 is one of the double vectors");
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev)); // (MI_ERR_NODEVICE without a GPU, like the entry points that need the workspace)
+    int grid = (n / 2 + 255) / 256;
+    grid = grid < 1 ? 1 : (grid > 2048 ? 2048 : grid);
+    if (d_div) hipLaunchKernelGGL(round_f32_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)s, n, d_x, d_div, d_out32, d_out64);
+    else hipLaunchKernelGGL(round_f32_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)s, n, d_x, d_div, d_out32, d_out64);
+    HIP_TRY(hipGetLastError());
     return MI_OK;
 }
 

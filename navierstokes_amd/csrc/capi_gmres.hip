@@ -1,7 +1,8 @@
 // capi_gmres.hip: mi_gmres_* — right-preconditioned restarted GMRES with a whole cycle enqueued on the device (include/mi355_spmv.h,
 // DESIGN.md 4.6) — part of libmi355spmv.so (see capi_internal.hpp for the layout of the library).  The vector work is the library's
 // own entry points (the products, mi_bilu4*_solve_dev, mi_cgs_dev, mi_maxpy_dev, mi_axpy_dev); what is new on the device is
-// gmres_kernels.hpp.  Built for gfx950 only; no CPU fallback: every entry point that computes needs a HIP device.
+// gmres_kernels.hpp.  A handle created with MI_BASIS_F32 stores its Krylov basis in float: the same loop with mi_cgs_f32_dev /
+// mi_maxpy_f32_dev / mi_round_f32_dev, and a converged recurrence confirmed by the next cycle's start.  Built for gfx950 only; no CPU fallback: every entry point that computes needs a HIP device.
 #include "capi_internal.hpp"
 #include "gmres_kernels.hpp"
 
@@ -9,49 +10,72 @@ struct mi_gmres_s {
     int device = 0;
     int n = 0, m = 0;       // rows; restart
     long long ldv = 0;      // n rounded up to even: every row of V is 16-byte aligned
+    int basis = MI_BASIS_F64;
+    long long ldv32 = 0;    // MI_BASIS_F32: n rounded up to a multiple of 4: every row of V32 is 16-byte aligned
     mi_csr_t A_csr = nullptr;       // the operator: one of the two (not owned)
     mi_bcsr4_t A_bcsr = nullptr;
     mi_bilu4_t F = nullptr;         // the preconditioner (not owned), or null
     int pc_kind = MI_GMRES_PC_EXACT, sf = 0, sb = 0;
-    DevArray<double> V;             // (m + 1) rows of ldv
+    DevArray<double> V;             // (m + 1) rows of ldv (MI_BASIS_F64 only)
+    DevArray<float> V32;            // (m + 1) rows of ldv32 (MI_BASIS_F32 only), and q: widen(the newest row), what the next product reads
+    DevArray<double> q;
     DevArray<double> w, z;          // the two work vectors
     DevArray<double> small;         // GmresSmall (gmres_kernels.hpp)
     DevArray<double> hb, hx;        // b and x of the host-pointer solve, allocated by its first call
     PinnedArray<double> slot[2];    // read-back slots: the record and the cycle's history entries
     OwnedEvent ev[2];
     std::vector<const double*> Vptr; // the rows of V, as mi_cgs_dev / mi_maxpy_dev take them
+    std::vector<const float*> V32ptr; // the rows of V32, as mi_cgs_f32_dev / mi_maxpy_f32_dev take them
+    int refused_last = 0;           // MI_BASIS_F32: claims of the recurrence that the next cycle's true residual did not confirm
     int next_slot = 0;
     int last_k = 0;                 // the last cycle: its counted steps and its ||r0||
     double last_beta = 0.0;
     int readbacks_last = 0, launches_last = 0, wasted_last = 0;
     GmresSmall S() const { return GmresSmall{m, small.get()}; }
     double* row(int k) const { return V.get() + (size_t)k * ldv; }
+    float* row32(int k) const { return V32.get() + (size_t)k * ldv32; }
+    bool f32() const { return basis == MI_BASIS_F32; }
     // freed in the order of allocation
-    ~mi_gmres_s() { V = {}, w = {}, z = {}, small = {}, hb = {}, hx = {}; }
+    ~mi_gmres_s() { V = {}, V32 = {}, q = {}, w = {}, z = {}, small = {}, hb = {}, hx = {}; }
 };
 
 constexpr size_t kGmresSlotDoubles = kGmresRecDoubles + kMultiMax;
 
 extern "C" int mi_gmres_create(int n, int restart, mi_gmres_t* out)
 {
+    return mi_gmres_create_ex(n, restart, MI_BASIS_F64, out);
+}
+
+extern "C" int mi_gmres_create_ex(int n, int restart, int basis, mi_gmres_t* out)
+{
     CHECK_ARG(out, "null output handle");
     *out = nullptr;
     CHECK_ARG(n >= 1, "n must be at least 1");
     CHECK_ARG(restart >= 1 && restart <= kMultiMax, "restart must be in 1..64");
+    CHECK_ARG(basis == MI_BASIS_F64 || basis == MI_BASIS_F32, "unknown basis (MI_BASIS_F64 or MI_BASIS_F32)");
     int rc = need_device();
     if (rc) return rc;
     std::unique_ptr<mi_gmres_s> G(new (std::nothrow) mi_gmres_s);
     if (!G) return fail(MI_ERR_ALLOC, "out of host memory");
     HIP_TRY(hipGetDevice(&G->device));
     G->n = n, G->m = restart, G->ldv = (long long)n + (n & 1);
-    if ((rc = dev_alloc(G->V, (size_t)(restart + 1) * G->ldv)) || (rc = dev_alloc(G->w, (size_t)G->ldv)) || (rc = dev_alloc(G->z, (size_t)G->ldv)) ||
+    G->basis = basis, G->ldv32 = ((long long)n + 3) / 4 * 4;
+    if (G->f32()) {
+        if ((rc = dev_alloc(G->V32, (size_t)(restart + 1) * G->ldv32)) || (rc = dev_alloc(G->q, (size_t)G->ldv))) return rc;
+    } else if ((rc = dev_alloc(G->V, (size_t)(restart + 1) * G->ldv))) {
+        return rc;
+    }
+    if ((rc = dev_alloc(G->w, (size_t)G->ldv)) || (rc = dev_alloc(G->z, (size_t)G->ldv)) ||
         (rc = dev_zeros(G->small, GmresSmall::doubles(restart))))
         return rc;
     for (int i = 0; i < 2; i++) {
         HIP_TRY_AS("hipHostMalloc", G->slot[i].alloc(kGmresSlotDoubles));
         if ((rc = dev_create(G->ev[i], hipEventDisableTiming))) return rc;
     }
-    for (int k = 0; k <= restart; k++) G->Vptr.push_back(G->row(k));
+    for (int k = 0; k <= restart; k++) {
+        if (G->f32()) G->V32ptr.push_back(G->row32(k));
+        else G->Vptr.push_back(G->row(k));
+    }
     *out = G.release();
     return MI_OK;
 }
@@ -106,6 +130,14 @@ static int gmres_mult(mi_gmres_s* G, const double* x, double* y, mi_stream_t s)
     return G->A_csr ? mi_spmv_dev(G->A_csr, x, y, s) : mi_bcsr4_spmv_dev(G->A_bcsr, x, y, s);
 }
 
+// out += sum y_j V_j over the k counted steps of the cycle (the basis as stored)
+static int gmres_combine(mi_gmres_s* G, int k, double* out, mi_stream_t s)
+{
+    const GmresSmall S = G->S();
+    return G->f32() ? mi_maxpy_f32_dev(G->n, k, S.y(), 0, G->V32ptr.data(), out, nullptr, s)
+                    : mi_maxpy_dev(G->n, k, S.y(), 0, G->Vptr.data(), out, nullptr, s);
+}
+
 static int gmres_precond(mi_gmres_s* G, const double* in, double* out, mi_stream_t s)
 {
     switch (G->pc_kind) {
@@ -137,6 +169,27 @@ static int gmres_enqueue_step(mi_gmres_s* G, int k, double rtol, int grid, hipSt
     return MI_OK;
 }
 
+// the same step with the float basis: w = A M^-1 q into a work vector (q = widen(V32_k), the STORED vector), CGS2 of w against
+// V32_0..V32_k, the small problem unchanged, then V32_{k+1} = round32(w / nrm) and q = widen(V32_{k+1}) in one launch
+static int gmres_enqueue_step_f32(mi_gmres_s* G, int k, double rtol, hipStream_t st)
+{
+    const GmresSmall S = G->S();
+    mi_stream_t s = (mi_stream_t)st;
+    double* col = S.hraw() + (size_t)k * (G->m + 2);
+    int rc;
+    if (G->F) {
+        if ((rc = gmres_precond(G, G->q, G->z, s)) || (rc = gmres_mult(G, G->z, G->w, s))) return rc;
+        G->launches_last++;
+    } else if ((rc = gmres_mult(G, G->q, G->w, s))) {
+        return rc;
+    }
+    if ((rc = mi_cgs_f32_dev(G->n, k + 1, G->V32ptr.data(), G->w, 2, col, col + k + 1, s))) return rc;
+    hipLaunchKernelGGL(gmres_hess_step, dim3(1), dim3(64), 0, st, S, k, rtol);
+    if ((rc = mi_round_f32_dev(G->n, G->w, col + k + 1, G->row32(k + 1), G->q, s))) return rc;
+    G->launches_last += 4;
+    return MI_OK;
+}
+
 extern "C" int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, double rtol, int maxiter, int check_every, int* iterations,
                                   int* reason_out, double* history, mi_stream_t s)
 {
@@ -151,16 +204,23 @@ extern "C" int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, 
     const GmresSmall S = G->S();
     int grid = (n + 255) / 256;
     if (grid > 2048) grid = 2048;
-    G->readbacks_last = G->launches_last = G->wasted_last = 0;
+    G->readbacks_last = G->launches_last = G->wasted_last = G->refused_last = 0;
+    const bool f32 = G->f32();
+    bool claimed = false; // MI_BASIS_F32: the last cycle froze with reason 1 and this cycle's start has to confirm it
     G->last_k = 0;
     int its = 0, reason = 0, rc;
     bool first = true;
     for (;;) {
-        // ---- the start of a cycle: r = b - A x into row 0, its norm, the record, V_0 = r / beta
-        if ((rc = gmres_mult(G, d_x, G->w, s)) || (rc = residual_norm_dev(n, d_b, G->w, G->row(0), S.beta(), st))) return rc;
+        // ---- the start of a cycle: r = b - A x into row 0, its norm, the record, V_0 = r / beta (the float basis: r into a work
+        // vector, then V32_0 = round32(r / beta) and q = widen(V32_0))
+        if ((rc = gmres_mult(G, d_x, G->w, s)) || (rc = residual_norm_dev(n, d_b, G->w, f32 ? G->z.get() : G->row(0), S.beta(), st))) return rc;
         if (first && (rc = mi_norm2_dev(n, d_b, S.bnorm(), s))) return rc;
         hipLaunchKernelGGL(gmres_cycle_begin, dim3(1), dim3(64), 0, st, S, first ? 1 : 0, rtol, maxiter);
-        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, n, S.beta(), G->row(0));
+        if (f32) {
+            if ((rc = mi_round_f32_dev(n, G->z, S.beta(), G->row32(0), G->q, s))) return rc;
+        } else {
+            hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, n, S.beta(), G->row(0));
+        }
         HIP_TRY(hipGetLastError());
         G->launches_last += first ? 6 : 5;
         // ---- batches of steps; behind each the record and the cycle's history go to a pinned slot, and the host looks at a batch's
@@ -175,7 +235,7 @@ extern "C" int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, 
                 // tells, has then wasted 2 check_every - 1 steps at most, like one that freezes inside a batch)
                 const int nb = std::min(pending < 0 ? check_every - 1 : check_every, std::max(room, 0));
                 for (int j = 0; j < nb; j++)
-                    if ((rc = gmres_enqueue_step(G, k_enq + j, rtol, grid, st))) return rc;
+                    if ((rc = f32 ? gmres_enqueue_step_f32(G, k_enq + j, rtol, st) : gmres_enqueue_step(G, k_enq + j, rtol, grid, st))) return rc;
                 k_enq += nb;
                 cur = G->next_slot;
                 G->next_slot ^= 1;
@@ -203,16 +263,24 @@ extern "C" int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, 
             HIP_TRY(hipGetLastError());
             if (G->F) {
                 HIP_TRY(hipMemsetAsync(G->w, 0, sizeof(double) * (size_t)n, st));
-                if ((rc = mi_maxpy_dev(n, rec.k, S.y(), 0, G->Vptr.data(), G->w, nullptr, s)) || (rc = gmres_precond(G, G->w, G->z, s)) ||
+                if ((rc = gmres_combine(G, rec.k, G->w, s)) || (rc = gmres_precond(G, G->w, G->z, s)) ||
                     (rc = mi_axpy_dev(n, 1.0, G->z, d_x, s)))
                     return rc;
                 G->launches_last += 5;
             } else {
-                if ((rc = mi_maxpy_dev(n, rec.k, S.y(), 0, G->Vptr.data(), d_x, nullptr, s))) return rc;
+                if ((rc = gmres_combine(G, rec.k, d_x, s))) return rc;
                 G->launches_last += 2;
             }
         }
         reason = rec.reason == kGmresMetAtStart ? 0 : rec.reason;
+        // the float basis: the recurrence is exact only to float rounding of the basis, so a step's reason 1 (rec.k > 0) is a CLAIM:
+        // the update above has run, and the next cycle's start — the true residual — confirms it (reason 1 with k = 0) or not
+        if (claimed && !(rec.reason == 1 && rec.k == 0)) G->refused_last++;
+        claimed = f32 && rec.reason == 1 && rec.k > 0;
+        if (claimed) {
+            first = false;
+            continue;
+        }
         if (rec.reason != 0) break;
         if (its >= maxiter) {
             reason = 2;
@@ -261,12 +329,27 @@ extern "C" int mi_gmres_fetch_cycle(mi_gmres_t G, int* k, double* hraw, double* 
     return MI_OK;
 }
 
+// V, or V32 and q
+static long long gmres_basis_bytes(const mi_gmres_s* G)
+{
+    return G->f32() ? 4LL * (G->m + 1) * G->ldv32 + 8LL * G->ldv : 8LL * (G->m + 1) * G->ldv;
+}
+
+extern "C" int mi_gmres_basis_info(mi_gmres_t G, int* basis, long long* basis_bytes, int* refused_last)
+{
+    CHECK_ARG(G, "null handle");
+    if (basis) *basis = G->basis;
+    if (basis_bytes) *basis_bytes = gmres_basis_bytes(G);
+    if (refused_last) *refused_last = G->refused_last;
+    return MI_OK;
+}
+
 extern "C" int mi_gmres_info(mi_gmres_t G, int* restart, long long* device_bytes, int* readbacks_last, int* launches_last, int* wasted_steps_last)
 {
     CHECK_ARG(G, "null handle");
     if (restart) *restart = G->m;
-    if (device_bytes)
-        *device_bytes = (long long)sizeof(double) * ((long long)(G->m + 3) * G->ldv + (long long)GmresSmall::doubles(G->m) + (G->hb ? 2 * G->ldv : 0));
+    if (device_bytes) // what the handle owns: the basis (gmres_basis_bytes), the two work vectors, the small state, b and x of the host form
+        *device_bytes = gmres_basis_bytes(G) + (long long)sizeof(double) * (2 * G->ldv + (long long)GmresSmall::doubles(G->m) + (G->hb ? 2 * G->ldv : 0));
     if (readbacks_last) *readbacks_last = G->readbacks_last;
     if (launches_last) *launches_last = G->launches_last;
     if (wasted_steps_last) *wasted_steps_last = G->wasted_last;

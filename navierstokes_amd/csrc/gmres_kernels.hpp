@@ -1,6 +1,7 @@
 // gmres_kernels.hpp — the device side of mi_gmres_* (capi_gmres.hip) that the library did not have yet: the residual of a cycle's
 // start with the first stage of its norm in one pass, and the small least-squares problem of restarted GMRES (Givens rotations,
-// the residual recurrence, the back-substitution) as one-workgroup kernels, so that a cycle never needs the host for arithmetic.
+// the residual recurrence, the back-substitution) as one-workgroup kernels, so that a cycle never needs the host for arithmetic;
+// and round_f32_kernel, which normalises, rounds and stores a vector of the single-precision basis (MI_BASIS_F32) in one pass.
 // The ARITHMETIC below is part of the interface (include/mi355_spmv.h, mi_gmres_*; tests/gmres_dev_model.py restates
 // it in numpy scalars): every product and every sum of the small problem is rounded on its own, nothing is contracted into an fma.
 #pragma once
@@ -93,6 +94,43 @@ __global__ __launch_bounds__(kRedWG) void gmres_residual(int n, int seg, const d
     }
     const double t = block_sum(s, s_part);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+// The float basis (MI_BASIS_F32; mi_round_f32_dev): out32[i] = round32(x[i] / *div) — the IEEE division (DIV) and the conversion,
+// to nearest even, subnormals kept, beyond the float range +-Inf — and out64[i] = widen(out32[i]) where out64 is given, in one pass:
+// what div_by_scalar_kernel is to the double basis, with the stored vector and the one the next product reads written together.
+// Elementwise, so the bits do not depend on the path: pairs (16-byte load, 8-byte and 16-byte store) where the three bases allow
+// them, else scalars.  out64 may be x itself (every element is read before it is written, by the same lane).
+template <bool DIV>
+__global__ __launch_bounds__(256) void round_f32_kernel(int n, const double* x, const double* __restrict__ div, float* __restrict__ out32,
+                                                        double* out64)
+{
+    const double q = DIV ? div[0] : 1.0;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool pairs = ((((uintptr_t)x | (uintptr_t)out64) & 15) | ((uintptr_t)out32 & 7)) == 0;
+    if (pairs) {
+        const long long n2 = n >> 1;
+        for (long long i = t; i < n2; i += stride) {
+            const double2 v = reinterpret_cast<const double2*>(x)[i];
+            f2v_ f;
+            f.x = (float)(DIV ? __ddiv_rn(v.x, q) : v.x);
+            f.y = (float)(DIV ? __ddiv_rn(v.y, q) : v.y);
+            reinterpret_cast<f2v_*>(out32)[i] = f;
+            if (out64) reinterpret_cast<double2*>(out64)[i] = make_double2((double)f.x, (double)f.y);
+        }
+        if ((n & 1) && t == 0) {
+            const float f = (float)(DIV ? __ddiv_rn(x[n - 1], q) : x[n - 1]);
+            out32[n - 1] = f;
+            if (out64) out64[n - 1] = (double)f;
+        }
+    } else {
+        for (long long i = t; i < n; i += stride) {
+            const float f = (float)(DIV ? __ddiv_rn(x[i], q) : x[i]);
+            out32[i] = f;
+            if (out64) out64[i] = (double)f;
+        }
+    }
 }
 
 // The start of a cycle, behind the residual's norm (one thread): beta and ||b|| into the record, g_0 = beta, the cycle's step count

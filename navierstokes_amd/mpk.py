@@ -200,6 +200,12 @@ def lib():
         "mi_gmres_fetch_cycle": [_vp, P(i), _vp, _vp, P(d)],
         "mi_gmres_info": [_vp, P(i), P(ll), P(i), P(i), P(i)],
         "mi_gmres_destroy": [_vp],
+        "mi_gmres_create_ex": [i, i, i, P(_vp)],
+        "mi_gmres_basis_info": [_vp, P(i), P(ll), P(i)],
+        "mi_round_f32_dev": [i, _vp, _vp, _vp, _vp, _vp],
+        "mi_mdot_f32_dev": [i, i, _vp, _vp, _vp, _vp],
+        "mi_maxpy_f32_dev": [i, i, _vp, i, _vp, _vp, _vp, _vp],
+        "mi_cgs_f32_dev": [i, i, _vp, _vp, i, _vp, _vp, _vp],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -284,11 +290,12 @@ def _stream_ptr():
     return _vp(torch.cuda.current_stream().cuda_stream)
 
 
-def _dev_ptr(t, n=None, what="vector"):
+def _dev_ptr(t, n=None, what="vector", dtype=None):
     import torch
 
-    if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-        raise TypeError(f"{what}: expected a contiguous float64 CUDA tensor, got {t.dtype} on {t.device}")
+    dtype = dtype or torch.float64
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise TypeError(f"{what}: expected a contiguous {str(dtype)[6:]} CUDA tensor, got {t.dtype} on {t.device}")
     if n is not None and t.numel() < n:
         raise ValueError(f"{what}: needs {n} entries, has {t.numel()}")
     return _vp(t.data_ptr())
@@ -1282,6 +1289,7 @@ def GMRES(A, b, x, M=None, restart=30, rtol=1e-8, maxiter=300):
 
 
 GMRES_PC_EXACT, GMRES_PC_SWEEPS, GMRES_PC_SWEEPS_F32 = 0, 1, 2
+GMRES_BASIS = {"f64": 0, "f32": 1}  # MI_BASIS_F64, MI_BASIS_F32
 GMRES_CHECK_EVERY = 1  # the default of gmres_solver.solve / GMRES_dev: what tools/bench_gmres.py measured fastest (profiles/NOTES.md R12.1)
 
 
@@ -1290,15 +1298,20 @@ class gmres_solver:
     rotations, the residual recurrence and the back-substitution — and one small read-back per check_every iterations instead of
     one stream drain per iteration (include/mi355_spmv.h, mi_gmres_*; DESIGN.md 4.6).  A: a bcsr4x4_matrix or a square csrmatrix;
     M: a bilu4 (the exact solve in the handle's current form), a bilu4_sweeps (either precision) or None.  The solver owns its
-    basis and work vectors; A and M must outlive it.  One solve at a time per solver, and per M."""
+    basis and work vectors; A and M must outlive it.  One solve at a time per solver, and per M.
+    basis="f32" (MI_BASIS_F32, opt-in): the Krylov basis is stored in single precision, every projection is taken against the
+    stored basis, and a converged recurrence is confirmed by the next cycle's true residual (basis_info())."""
 
-    def __init__(self, A, M=None, restart=30):
+    def __init__(self, A, M=None, restart=30, basis="f64"):
         self._h = None
+        if basis not in GMRES_BASIS:
+            raise ValueError(f"basis: expected 'f64' or 'f32', got {basis!r}")
+        self.basis = basis
         self.A, self.M = A, M
         self.n = 4 * A.nrows if isinstance(A, bcsr4x4_matrix) else A.n
         self.restart = int(restart)
         h = _vp()
-        check(lib().mi_gmres_create(self.n, self.restart, _c.byref(h)))
+        check(lib().mi_gmres_create_ex(self.n, self.restart, GMRES_BASIS[basis], _c.byref(h)))
         self._h = h
         if isinstance(A, bcsr4x4_matrix):
             check(lib().mi_gmres_set_operator_bcsr4(h, A.handle))
@@ -1346,6 +1359,14 @@ class gmres_solver:
         check(lib().mi_gmres_info(self.handle, _c.byref(m), _c.byref(by), _c.byref(rb), _c.byref(la), _c.byref(wa)))
         return dict(restart=m.value, device_bytes=by.value, readbacks_last=rb.value, launches_last=la.value, wasted_steps_last=wa.value)
 
+    def basis_info(self):
+        """dict(basis, basis_bytes, refused_last) — mi_gmres_basis_info: "f64" or "f32", the bytes of the stored basis, and the
+        claims of the last solve's recurrence that the next cycle's true residual did not confirm (always 0 for "f64")."""
+        kind, refused = _c.c_int(), _c.c_int()
+        by = _c.c_longlong()
+        check(lib().mi_gmres_basis_info(self.handle, _c.byref(kind), _c.byref(by), _c.byref(refused)))
+        return dict(basis="f32" if kind.value == GMRES_BASIS["f32"] else "f64", basis_bytes=by.value, refused_last=refused.value)
+
     def close(self):
         if self._h is not None:
             lib().mi_gmres_destroy(self._h)
@@ -1358,9 +1379,9 @@ class gmres_solver:
             pass
 
 
-def GMRES_dev(A, b, x, M=None, restart=30, rtol=1e-8, maxiter=300, check_every=GMRES_CHECK_EVERY):
+def GMRES_dev(A, b, x, M=None, restart=30, rtol=1e-8, maxiter=300, check_every=GMRES_CHECK_EVERY, basis="f64"):
     """GMRES(A, b, x, M, restart, rtol, maxiter) through a gmres_solver made for the call: (iterations, history)."""
-    S = gmres_solver(A, M, restart)
+    S = gmres_solver(A, M, restart, basis)
     try:
         its, hist, _ = S.solve(b, x, rtol, maxiter, check_every)
     finally:
@@ -1452,8 +1473,27 @@ def orthonormalize_against_basis(basis, y):
     return dots
 
 
-def _dev_basis(basis, n):
-    return (_vp * max(len(basis), 1))(*[_dev_ptr(b, n, f"basis[{j}]").value for j, b in enumerate(basis)])
+def _dev_basis(basis, n, dtype=None):
+    return (_vp * max(len(basis), 1))(*[_dev_ptr(b, n, f"basis[{j}]", dtype).value for j, b in enumerate(basis)])
+
+
+def _basis_f32(basis):
+    """A basis of torch.float32 CUDA vectors (the stored basis of a basis="f32" solver): the mi_*_f32_dev forms, y staying float64."""
+    import torch
+    return len(basis) > 0 and _is_torch(basis[0]) and basis[0].dtype == torch.float32
+
+
+def round_f32(x, div=None):
+    """(x32, x64) of mi_round_f32_dev: x32 = round32(x / div) as a float32 tensor — the division in float64 by the device scalar
+    div (a 1-element CUDA tensor; None: no division), then rounded to nearest even, subnormals kept — and x64 = x32 widened to
+    float64, in one pass.  x: a float64 CUDA tensor, left as it is."""
+    import torch
+    n = int(x.numel())
+    x32 = torch.empty(n, dtype=torch.float32, device=x.device)
+    x64 = torch.empty(n, dtype=torch.float64, device=x.device)
+    check(lib().mi_round_f32_dev(n, _dev_ptr(x), _dev_ptr(div, 1, "div") if div is not None else None, _dev_ptr(x32, n, "x32", torch.float32),
+                                 _dev_ptr(x64), _stream_ptr()))
+    return x32, x64
 
 
 def _host_basis(basis, n):
@@ -1469,7 +1509,10 @@ def mdot(basis, y):
         import torch
         n = int(y.numel())
         dots = torch.empty(max(m, 1), dtype=torch.float64, device=y.device)
-        check(lib().mi_mdot_dev(n, m, _dev_basis(basis, n), _dev_ptr(y), _dev_ptr(dots), _stream_ptr()))
+        if _basis_f32(basis):
+            check(lib().mi_mdot_f32_dev(n, m, _dev_basis(basis, n, torch.float32), _dev_ptr(y), _dev_ptr(dots), _stream_ptr()))
+        else:
+            check(lib().mi_mdot_dev(n, m, _dev_basis(basis, n), _dev_ptr(y), _dev_ptr(dots), _stream_ptr()))
         return dots[:m]
     yy = _host_f64(y)
     n = yy.size
@@ -1491,8 +1534,10 @@ def maxpy(coef, basis, y, negate=False, norm=False):
         if not _is_torch(coef):
             coef = torch.as_tensor(np.asarray(coef, dtype=np.float64), device=y.device)
         out = _scalar_dev() if norm else None
-        check(lib().mi_maxpy_dev(n, m, _dev_ptr(coef, m, "coef") if m else None, 1 if negate else 0, _dev_basis(basis, n), _dev_ptr(y),
-                                 _dev_ptr(out) if norm else None, _stream_ptr()))
+        f32 = _basis_f32(basis)
+        call = lib().mi_maxpy_f32_dev if f32 else lib().mi_maxpy_dev
+        check(call(n, m, _dev_ptr(coef, m, "coef") if m else None, 1 if negate else 0, _dev_basis(basis, n, torch.float32 if f32 else None),
+                   _dev_ptr(y), _dev_ptr(out) if norm else None, _stream_ptr()))
         return (y, out) if norm else y
     yy = _host_f64(y, None, "y", writable=True)
     n = yy.size
@@ -1515,7 +1560,9 @@ def cgs(basis, y, passes=2):
         n = int(y.numel())
         h = torch.empty(max(m, 1), dtype=torch.float64, device=y.device)
         nrm = _scalar_dev()
-        check(lib().mi_cgs_dev(n, m, _dev_basis(basis, n), _dev_ptr(y), passes, _dev_ptr(h), _dev_ptr(nrm), _stream_ptr()))
+        f32 = _basis_f32(basis)
+        call = lib().mi_cgs_f32_dev if f32 else lib().mi_cgs_dev
+        check(call(n, m, _dev_basis(basis, n, torch.float32 if f32 else None), _dev_ptr(y), passes, _dev_ptr(h), _dev_ptr(nrm), _stream_ptr()))
         return h[:m], nrm
     h = mdot(basis, y)
     maxpy(h, basis, y, negate=True)

@@ -4,7 +4,12 @@ iteration) against mpk.gmres_solver (mi_gmres_*: a whole cycle enqueued on the d
 the SAME matrix and factor handles, in one process.  Prints one JSON line per preconditioner and appends it to
 profiles/gmres_bench.jsonl.
 
-    python3 tools/bench_gmres.py [--cells 68] [--fill 0] [--sweeps 3] [--precision f64|f32|both] [--runs 5] [--no-append]
+    python3 tools/bench_gmres.py [--cells 68] [--fill 0] [--sweeps 3] [--precision f64|f32|both] [--basis f64|f32|both] [--runs 5] [--no-append]
+
+--basis f64 (the default) is the comparison above.  --basis f32 or both compares the solver handles instead: one gmres_solver per
+basis asked for (basis="f64": the yardstick, the code path of the default; basis="f32": the single-precision Krylov basis), both at
+check_every = 1 on the same matrix and factor handles, alternating inside every run; the records also carry basis_bytes and the
+refused claims of the last solve (refused_last).
 
 Preconditioners per process: the sweeps (--sweeps per triangle) in each precision asked for, and the exact solve.  For each one a
 record (tool = "bench_gmres") with, per solver: iterations, wall seconds (median of --runs runs; the solvers ALTERNATE inside every
@@ -31,6 +36,7 @@ def main():
     ap.add_argument("--fill", type=int, default=0)
     ap.add_argument("--sweeps", type=int, default=3)
     ap.add_argument("--precision", choices=("f64", "f32", "both"), default="f64")
+    ap.add_argument("--basis", choices=("f64", "f32", "both"), default="f64")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--maxiter", type=int, default=300)
     ap.add_argument("--no-append", action="store_true")
@@ -50,8 +56,13 @@ def main():
     preconds = [(f"sweeps{a.sweeps}_{p}", F.sweeps(a.sweeps, precision=p)) for p in (("f64", "f32") if a.precision == "both" else (a.precision,))]
     preconds.append(("exact", F))
     for label, M in preconds:
-        S = mpk.gmres_solver(A, M, RESTART)
-        solvers = [("mpk.GMRES", None)] + [(f"gmres_solver_ce{ce}", ce) for ce in (1, 5, RESTART)]
+        if a.basis == "f64":
+            S = mpk.gmres_solver(A, M, RESTART)
+            handles = [S]
+            solvers = [("mpk.GMRES", None)] + [(f"gmres_solver_ce{ce}", (S, ce)) for ce in (1, 5, RESTART)]
+        else:
+            handles = [mpk.gmres_solver(A, M, RESTART, basis=k) for k in (("f64", "f32") if a.basis == "both" else (a.basis,))]
+            solvers = [(f"gmres_solver_{h.basis}_ce1", (h, 1)) for h in handles]
 
         def run(ce):
             dx.zero_()
@@ -60,7 +71,7 @@ def main():
             if ce is None:
                 its, hist = mpk.GMRES(A, db, dx, M=M, restart=RESTART, rtol=RTOL, maxiter=a.maxiter)
             else:
-                its, hist, _ = S.solve(db, dx, rtol=RTOL, maxiter=a.maxiter, check_every=ce)
+                its, hist, _ = ce[0].solve(db, dx, rtol=RTOL, maxiter=a.maxiter, check_every=ce[1])
             torch.cuda.synchronize()
             sec = time.perf_counter() - t0
             mpk.SpMV_BCSR(dy, dx, A)
@@ -77,8 +88,10 @@ def main():
                 secs[name].append(sec)
                 last[name] = dict(iterations=its, true_residual=true, recurrence_residual=rec)
                 if ce is not None:
-                    info = S.info()
+                    info = ce[0].info()
                     last[name].update(readbacks_last=info["readbacks_last"], wasted_steps_last=info["wasted_steps_last"], launches_last=info["launches_last"])
+                    if a.basis != "f64":
+                        last[name].update(ce[0].basis_info(), device_bytes=info["device_bytes"])
         out = dict(tool="bench_gmres", cells=a.cells, rows=n, fill=a.fill, precond=label, restart=RESTART, rtol=RTOL, runs=a.runs,
                    default_check_every=mpk.GMRES_CHECK_EVERY, solvers={})
         for name, _ in solvers:
@@ -91,7 +104,8 @@ def main():
         if not a.no_append:
             with open(os.path.join(ROOT, "profiles", "gmres_bench.jsonl"), "a") as f:
                 f.write(line + "\n")
-        S.close()
+        for h in handles:
+            h.close()
     F.close()
     A.close()
 
