@@ -1,5 +1,5 @@
 """Host-side planners under the address and undefined-behaviour sanitizers (CPU only: GPU sanitizers are not available on this pool, and
-nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp, bilu_asan.cpp, spmm_plan_asan.cpp) and say what they check."""
+nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp, bilu_asan.cpp, spmm_plan_asan.cpp, reorder_asan.cpp) and say what they check."""
 import os
 import shutil
 import subprocess
@@ -60,3 +60,15 @@ def test_spmm_tile_planner_under_host_sanitizers(tmp_path):
     exe = str(tmp_path / "spmm_plan_asan")
     out = _run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tools", "spmm_plan_asan.cpp")], exe, tmp_path)
     assert "bad 0" in out, out
+
+
+def test_relabelling_under_host_sanitizers(tmp_path):
+    """reorder.hpp: the node graph, Cuthill-McKee, the permutation and the permuted CSR with its value offsets, checked by brute force on the
+    pattern families of tests/reorder_cases.py (generated in C++) and on 220 random patterns with empty rows, repeated columns and a 300-entry
+    row, each as a scalar matrix (block 1) and expanded to 4x4 node blocks (block 4); the spread figures against a direct sum."""
+    if not shutil.which("g++"):
+        pytest.skip("g++ not found")
+    exe = str(tmp_path / "reorder_asan")
+    out = _run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tools", "reorder_asan.cpp")], exe, tmp_path)
+    assert "bad 0" in out and "reorder patterns" in out, out
+    assert int(out.split("reorder patterns")[1].split()[0]) >= 2 * 200, out

@@ -1,5 +1,6 @@
 """Create-time locality reordering (navierstokes_amd/csrc/reorder.hpp): the host-side planner on CPU; the
-bitwise GPU checks are in test_gpu_parity.py::test_permuted_*."""
+bitwise GPU checks are in test_reorder_gpu.py (benchmark-sized matrices, the measured decision) and test_gpu_reorder_limits.py
+(the pattern families of reorder_cases.py at every limit of the relabelled twin)."""
 import ctypes
 
 import numpy as np
