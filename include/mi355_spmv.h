@@ -851,6 +851,78 @@ int mi_gmres_create_ex(int n, int restart, int basis, mi_gmres_t* out);
  * the last solve (always 0 with MI_BASIS_F64).  Any output may be NULL */
 int mi_gmres_basis_info(mi_gmres_t G, int* basis, long long* basis_bytes, int* refused_last);
 
+/* ---- capturable GMRES: a whole cycle with no read-back, and the solve as replayed graphs (opt-in) ----
+ * mi_gmres_solve_dev cannot be captured into a graph: it reads a record back between batches and hands the cycle's end the
+ * counted steps k as a launch parameter.  Here a cycle is a FIXED sequence of launches: its start, all `restart` steps, its end;
+ * what the host decided there is decided on the device.  Nothing chooses any of this automatically, mi_gmres_solve_dev keeps
+ * refusing a capturing stream, and its results do not change by a bit.
+ * DEFINITION: the arithmetic is that of mi_gmres_* above (and of MI_BASIS_F32), with these rules in place of the host's:
+ *   step k     is not counted once the record holds a reason (frozen, as above) or once its >= maxiter: such a step's
+ *              small-problem launch returns at once and writes no reason; its Arnoldi launches run and their output is never read
+ *   cycle end  k is read from the record by the back-substitution and by the update (mi_maxpy_upto*_dev below); the final
+ *              x_i = fma(1, z_i, x_i) runs only when k > 0: a cycle that counted no step leaves x untouched, bit for bit
+ * so x, the record, hraw and y after mi_gmres_cycle_dev are those the same cycle of mi_gmres_solve_dev leaves, and for every
+ * `segment` mi_gmres_plan_solve's x, history, iterations, reason, mi_gmres_fetch_cycle and refused_last are, bit for bit, those of
+ * mi_gmres_solve_dev with the same arguments.
+ * CAPTURE: mi_gmres_cycle_dev enqueues kernels and one memset, allocates nothing and copies nothing to the host, PROVIDED the
+ * stream was prepared: the first reduction on a stream allocates its workspace and the first product of a relabelled operator on
+ * a stream its gather buffer, and neither may happen under capture.  mi_gmres_prepare_stream does both outside capture;
+ * mi_gmres_cycle_dev on a capturing stream that was not prepared returns MI_ERR_STATE ("not prepared"), enqueues nothing and
+ * leaves the capture valid.  Setting the operator again forgets the prepared streams.  An exact ILU in the one-launch form is
+ * recorded as the level-by-level form, as mi_bilu4_solve_dev does under capture (the same bits).  The captured launches name the
+ * vectors, rtol, maxiter and the handles' device arrays: they hold as long as those do.  No kernel waits, spins or polls a flag.
+ * WASTE: steps that run for nothing.  A raw cycle always runs all `restart` steps: restart - k of them are not counted.  A planned
+ * solve enqueues whole segments and looks at a segment's record only after the next one is enqueued (a cycle's start counts as
+ * a segment of no steps): when a cycle freezes or reaches maxiter, the rest of its segment and the segment behind it have run
+ * for nothing, AT MOST 2 segment - 1 STEPS PER CYCLE THAT ENDS EARLY.  With MI_BASIS_F64 a solve has one such cycle; with
+ * MI_BASIS_F32 a claimed cycle is one and its confirming start (segment steps behind it, at most) another.  *wasted_steps_last
+ * is the sum over the solve. */
+/* y <- mi_maxpy_dev(n, c, d_coef, negate, d_basis, y, NULL) with c = *d_count (DEVICE memory) clamped to [0, m]: the same
+ * segments, lane pairs and per-element fma chain in basis order, so the new y has those bits.  Vectors and coefficients with
+ * index >= c are never loaded (they may hold NaN or Inf); c == 0 leaves every bit of y alone.  Always ceil(m / tile) launches,
+ * of which those past c return at once.  Nothing is allocated, nothing copied to the host; capturable on any stream.
+ * MI_ERR_ARG, before the device is touched: the rules of mi_maxpy*_dev for the m vectors (m in 0..64, no null among the m
+ * pointers, d_y not one of them, float vectors 8-byte aligned), or d_count null. */
+int mi_maxpy_upto_dev(int n, int m, const int* d_count, const double* d_coef, int negate, const double* const* d_basis, double* d_y,
+                      mi_stream_t s);
+int mi_maxpy_upto_f32_dev(int n, int m, const int* d_count, const double* d_coef, int negate, const float* const* d_basis, double* d_y,
+                          mi_stream_t s);
+/* allocate, outside capture, whatever a first use on s would allocate (the reduction workspace; a relabelled operator's gather
+ * buffer, via a throwaway product on the solver's own work vectors: not while a solve of G is in flight); idempotent.
+ * MI_ERR_STATE: no operator set, or s is capturing */
+int mi_gmres_prepare_stream(mi_gmres_t G, mi_stream_t s);
+/* ONE whole restart cycle, enqueued with no read-back: the cycle start of the DEFINITION (first != 0: also ||b||, its = 0,
+ * history[0]), `restart` steps, the cycle end with the device-side k.  Steps behind a reason, or at its >= maxiter, run but are
+ * not counted.  The caller decides between cycles with mi_gmres_state, by mi_gmres_solve_dev's rule: stop when *done, or when
+ * its >= maxiter (reason 2); else the next cycle with first = 0.  With MI_BASIS_F32 a reason 1 with k > 0 is a CLAIM, as in
+ * mi_gmres_solve_dev: its update has run, and the next cycle (first = 0) confirms it (reason 1 with k = 0) or goes on. */
+int mi_gmres_cycle_dev(mi_gmres_t G, const double* d_b, double* d_x, int first, double rtol, int maxiter, mi_stream_t s);
+/* copies the record and the cycle's history entries to pinned memory behind s and waits for them (MI_ERR_STATE on a capturing
+ * stream).  *its, *k, *reason (0..4 as mi_gmres_solve_dev reports them), *last the last history value, *beta the cycle's ||r0||;
+ * *done != 0: the record holds a reason (rtol met at the start of a solve included, which *reason reports as 0);
+ * history_cycle [restart]: the entries of the k counted steps, zeros behind.  Also what mi_gmres_fetch_cycle then reports.
+ * Any output may be NULL */
+int mi_gmres_state(mi_gmres_t G, mi_stream_t s, int* its, int* k, int* done, int* reason, double* last, double* beta,
+                   double* history_cycle /* [restart] or NULL */);
+/* The solve as replayed graphs.  mi_gmres_plan_create captures, once, on a private stream of the plan (prepared first, captured
+ * in thread-local capture mode): one graph for the start of a solve, one for the start of a later cycle, one per segment (steps
+ * j segment .. min(restart, (j + 1) segment) - 1) and one for the cycle's end; segment is clamped to restart:
+ * 3 + ceil(restart / segment) graphs.  The plan bakes in d_b, d_x, rtol, maxiter and the operator and preconditioner settings
+ * of G: refill b and x IN PLACE between solves; every mi_gmres_set_* on G makes the plan stale (mi_gmres_plan_solve: MI_ERR_STATE).
+ * mi_gmres_plan_solve replays them on s with mi_gmres_solve_dev's host loop, the segments as batches: the next segment is
+ * launched before the host waits for the previous segment's record; the cycle's end is replayed when a record shows a reason,
+ * after the last segment or at its >= maxiter (not at all when k == 0); the end of the solve, the reasons, the float basis's
+ * claim / confirm and refused_last are mi_gmres_solve_dev's.  history: maxiter + 1 doubles or NULL.  MI_ERR_STATE on a
+ * capturing stream.  ONE solve at a time per G and per F, planned or not; G must outlive its plans' solves.
+ * mi_gmres_plan_info: *graphs, *segment (as clamped), and of the last solve *replays_last (graph launches), *readbacks_last,
+ * *wasted_steps_last (WASTE above).  Any output may be NULL.
+ * MI_ERR_ARG, before the device is touched: segment < 1, maxiter < 0, a null handle, vector or output. */
+typedef struct mi_gmres_plan_s* mi_gmres_plan_t;
+int mi_gmres_plan_create(mi_gmres_t G, const double* d_b, double* d_x, double rtol, int maxiter, int segment, mi_gmres_plan_t* out);
+int mi_gmres_plan_solve(mi_gmres_plan_t P, int* iterations, int* reason, double* history, mi_stream_t s);
+int mi_gmres_plan_info(mi_gmres_plan_t P, int* graphs, int* segment, int* replays_last, int* readbacks_last, int* wasted_steps_last);
+int mi_gmres_plan_destroy(mi_gmres_plan_t P);
+
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r
  * owns global rows [row_starts[r], row_starts[r+1]) and the matching slice of

@@ -255,4 +255,21 @@ __global__ __launch_bounds__(kRedWG) void maxpy_kernel(int n, int seg, int first
     maxpy_dispatch<TILE, NT, NORM, T>(cnt, n, seg, coef, negate, B, first, y, partial, s_part);
 }
 
+// The same chunk with the vector count in DEVICE memory (mi_maxpy_upto*_dev: the update of a captured GMRES cycle, whose counted
+// steps only the device knows): c = *count clamped to [0, m], and this launch takes the vectors first .. min(first + TILE, c) - 1.
+// The host always launches ceil(m / TILE) chunks; one that starts at or past c returns at once (uniform: every lane reads the same
+// word) and has loaded no vector, no coefficient and no y.  What runs is maxpy_kernel's body on maxpy_kernel's geometry, so y has
+// the bits of mi_maxpy*_dev(n, c, ..) and is not touched at all when c == 0.
+template <int TILE, bool NT, typename T>
+__global__ __launch_bounds__(kRedWG) void maxpy_upto_kernel(int n, int seg, int first, int m, const int* __restrict__ count,
+                                                            const double* __restrict__ coef, int negate, const MultiVecT<T> B, double* y)
+{
+    __shared__ double s_part[4];
+    int c = count[0];
+    c = c < 0 ? 0 : (c > m ? m : c);
+    const int cnt = (c - first < TILE) ? c - first : TILE;
+    if (cnt <= 0) return;
+    maxpy_dispatch<TILE, NT, false, T>(cnt, n, seg, coef, negate, B, first, y, nullptr, s_part);
+}
+
 } // namespace mi355

@@ -440,6 +440,43 @@ static int maxpy_dev(int n, int m, const double* d_coef, int negate, const T* co
     return maxpy_run(n, m, d_coef, negate, multi_vec(m, d_basis), d_y, d_norm_out, ws, s);
 }
 
+template <int TILE, typename T>
+static void maxpy_upto_launch(int n, int seg, int np, int m, const int* count, const double* coef, int negate, const MultiVecT<T>& B, double* y,
+                              bool nt, hipStream_t s)
+{
+    for (int first = 0; first < m; first += TILE) { // every chunk of the m vectors, whatever the count will be: the kernel decides
+        if (nt) hipLaunchKernelGGL((maxpy_upto_kernel<TILE, true, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, m, count, coef, negate, B, y);
+        else hipLaunchKernelGGL((maxpy_upto_kernel<TILE, false, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, m, count, coef, negate, B, y);
+    }
+}
+
+// mi_maxpy_upto_dev and its float-basis twin: mi_maxpy*_dev's geometry and tile, the count read by the kernels
+template <typename T>
+static int maxpy_upto_dev(int n, int m, const int* d_count, const double* d_coef, int negate, const T* const* d_basis, double* d_y, mi_stream_t s_)
+{
+    int rc = multi_check(n, m, d_basis, d_y);
+    if (rc) return rc;
+    CHECK_ARG(d_count, "null count");
+    CHECK_ARG(m == 0 || d_coef, "null coefficients");
+    if (m == 0 || n == 0) return MI_OK;
+    hipStream_t s = (hipStream_t)s_;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev)); // (MI_ERR_NODEVICE without a GPU; no norm, so no workspace: nothing is allocated, on any stream)
+    int np, seg;
+    red_geometry(n, &np, &seg);
+    const bool nt = blas1_nt(n);
+    const MultiVecT<T> B = multi_vec(m, d_basis);
+    switch (multi_tile(B.v[0])) {
+    case 4:
+        if constexpr (sizeof(T) == 8) maxpy_upto_launch<4, T>(n, seg, np, m, d_count, d_coef, negate, B, d_y, nt, s);
+        break;
+    case 16: maxpy_upto_launch<16, T>(n, seg, np, m, d_count, d_coef, negate, B, d_y, nt, s); break;
+    default: maxpy_upto_launch<8, T>(n, seg, np, m, d_count, d_coef, negate, B, d_y, nt, s); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
 template <typename T>
 static int cgs_dev(int n, int m, const T* const* d_basis, double* d_y, int passes, double* d_h, double* d_norm, mi_stream_t s_)
 {
@@ -490,6 +527,18 @@ extern "C" int mi_maxpy_f32_dev(int n, int m, const double* d_coef, int negate, 
                                 double* d_norm_out, mi_stream_t s)
 {
     return maxpy_dev(n, m, d_coef, negate, d_basis, d_y, d_norm_out, s);
+}
+
+extern "C" int mi_maxpy_upto_dev(int n, int m, const int* d_count, const double* d_coef, int negate, const double* const* d_basis, double* d_y,
+                                 mi_stream_t s)
+{
+    return maxpy_upto_dev(n, m, d_count, d_coef, negate, d_basis, d_y, s);
+}
+
+extern "C" int mi_maxpy_upto_f32_dev(int n, int m, const int* d_count, const double* d_coef, int negate, const float* const* d_basis, double* d_y,
+                                     mi_stream_t s)
+{
+    return maxpy_upto_dev(n, m, d_count, d_coef, negate, d_basis, d_y, s);
 }
 
 extern "C" int mi_cgs_f32_dev(int n, int m, const float* const* d_basis, double* d_y, int passes, double* d_h, double* d_norm,

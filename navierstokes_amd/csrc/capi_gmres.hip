@@ -2,9 +2,13 @@
 // DESIGN.md 4.6) — part of libmi355spmv.so (see capi_internal.hpp for the layout of the library).  The vector work is the library's
 // own entry points (the products, mi_bilu4*_solve_dev, mi_cgs_dev, mi_maxpy_dev, mi_axpy_dev); what is new on the device is
 // gmres_kernels.hpp.  A handle created with MI_BASIS_F32 stores its Krylov basis in float: the same loop with mi_cgs_f32_dev /
-// mi_maxpy_f32_dev / mi_round_f32_dev, and a converged recurrence confirmed by the next cycle's start.  Built for gfx950 only; no CPU fallback: every entry point that computes needs a HIP device.
+// mi_maxpy_f32_dev / mi_round_f32_dev, and a converged recurrence confirmed by the next cycle's start.  At the end of the file: a
+// whole cycle with no read-back (mi_gmres_cycle_dev: the counted steps stay on the device) and the solve as replayed graphs
+// (mi_gmres_plan_*), both with the bits of mi_gmres_solve_dev.  Built for gfx950 only; no CPU fallback: every entry point that computes needs a HIP device.
 #include "capi_internal.hpp"
 #include "gmres_kernels.hpp"
+
+#include <set>
 
 struct mi_gmres_s {
     int device = 0;
@@ -31,6 +35,8 @@ struct mi_gmres_s {
     int last_k = 0;                 // the last cycle: its counted steps and its ||r0||
     double last_beta = 0.0;
     int readbacks_last = 0, launches_last = 0, wasted_last = 0;
+    unsigned gen = 0;               // bumped by every mi_gmres_set_*: a plan (mi_gmres_plan_*) made before it is stale
+    std::set<hipStream_t> prepared; // streams mi_gmres_prepare_stream has seen since the operator was set
     GmresSmall S() const { return GmresSmall{m, small.get()}; }
     double* row(int k) const { return V.get() + (size_t)k * ldv; }
     float* row32(int k) const { return V32.get() + (size_t)k * ldv32; }
@@ -94,6 +100,7 @@ extern "C" int mi_gmres_set_operator_csr(mi_gmres_t G, mi_csr_t A)
     CHECK_ARG(A->n == A->ncols && !A->mapped, "the operator must be a square, unmapped matrix");
     CHECK_ARG(A->n == G->n, "the operator's row count is not the solver's n");
     G->A_csr = A, G->A_bcsr = nullptr;
+    G->gen++, G->prepared.clear();
     return MI_OK;
 }
 
@@ -103,6 +110,7 @@ extern "C" int mi_gmres_set_operator_bcsr4(mi_gmres_t G, mi_bcsr4_t A)
     CHECK_ARG(A->nbrows == A->nbcols, "the operator must be square");
     CHECK_ARG(4LL * A->nbrows == G->n, "the operator's row count (4 nbrows) is not the solver's n");
     G->A_bcsr = A, G->A_csr = nullptr;
+    G->gen++, G->prepared.clear();
     return MI_OK;
 }
 
@@ -111,6 +119,7 @@ extern "C" int mi_gmres_set_precond(mi_gmres_t G, mi_bilu4_t F, int kind, int sw
     CHECK_ARG(G, "null handle");
     if (!F) {
         G->F = nullptr;
+        G->gen++;
         return MI_OK;
     }
     CHECK_ARG(kind == MI_GMRES_PC_EXACT || kind == MI_GMRES_PC_SWEEPS || kind == MI_GMRES_PC_SWEEPS_F32, "unknown preconditioner kind");
@@ -122,6 +131,7 @@ extern "C" int mi_gmres_set_precond(mi_gmres_t G, mi_bilu4_t F, int kind, int sw
     if (kind == MI_GMRES_PC_SWEEPS && (rc = mi_bilu4sw_prepare(F))) return rc;
     if (kind == MI_GMRES_PC_SWEEPS_F32 && (rc = mi_bilu4sp_prepare(F))) return rc;
     G->F = F, G->pc_kind = kind, G->sf = sweeps_fwd, G->sb = sweeps_bwd;
+    G->gen++;
     return MI_OK;
 }
 
@@ -149,7 +159,7 @@ static int gmres_precond(mi_gmres_s* G, const double* in, double* out, mi_stream
 
 // step k of a cycle, enqueued: w = A M^-1 V_k straight into row k + 1, CGS2 in place with the raw column where the small problem
 // reads it, the small problem, the division
-static int gmres_enqueue_step(mi_gmres_s* G, int k, double rtol, int grid, hipStream_t st)
+static int gmres_enqueue_step(mi_gmres_s* G, int k, double rtol, int maxiter, int grid, hipStream_t st)
 {
     const GmresSmall S = G->S();
     mi_stream_t s = (mi_stream_t)st;
@@ -163,7 +173,7 @@ static int gmres_enqueue_step(mi_gmres_s* G, int k, double rtol, int grid, hipSt
         return rc;
     }
     if ((rc = mi_cgs_dev(G->n, k + 1, G->Vptr.data(), next, 2, col, col + k + 1, s))) return rc;
-    hipLaunchKernelGGL(gmres_hess_step, dim3(1), dim3(64), 0, st, S, k, rtol);
+    hipLaunchKernelGGL(gmres_hess_step, dim3(1), dim3(64), 0, st, S, k, rtol, maxiter);
     hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, G->n, col + k + 1, next);
     G->launches_last += 4;
     return MI_OK;
@@ -171,7 +181,7 @@ static int gmres_enqueue_step(mi_gmres_s* G, int k, double rtol, int grid, hipSt
 
 // the same step with the float basis: w = A M^-1 q into a work vector (q = widen(V32_k), the STORED vector), CGS2 of w against
 // V32_0..V32_k, the small problem unchanged, then V32_{k+1} = round32(w / nrm) and q = widen(V32_{k+1}) in one launch
-static int gmres_enqueue_step_f32(mi_gmres_s* G, int k, double rtol, hipStream_t st)
+static int gmres_enqueue_step_f32(mi_gmres_s* G, int k, double rtol, int maxiter, hipStream_t st)
 {
     const GmresSmall S = G->S();
     mi_stream_t s = (mi_stream_t)st;
@@ -184,7 +194,7 @@ static int gmres_enqueue_step_f32(mi_gmres_s* G, int k, double rtol, hipStream_t
         return rc;
     }
     if ((rc = mi_cgs_f32_dev(G->n, k + 1, G->V32ptr.data(), G->w, 2, col, col + k + 1, s))) return rc;
-    hipLaunchKernelGGL(gmres_hess_step, dim3(1), dim3(64), 0, st, S, k, rtol);
+    hipLaunchKernelGGL(gmres_hess_step, dim3(1), dim3(64), 0, st, S, k, rtol, maxiter);
     if ((rc = mi_round_f32_dev(G->n, G->w, col + k + 1, G->row32(k + 1), G->q, s))) return rc;
     G->launches_last += 4;
     return MI_OK;
@@ -235,7 +245,7 @@ extern "C" int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, 
                 // tells, has then wasted 2 check_every - 1 steps at most, like one that freezes inside a batch)
                 const int nb = std::min(pending < 0 ? check_every - 1 : check_every, std::max(room, 0));
                 for (int j = 0; j < nb; j++)
-                    if ((rc = f32 ? gmres_enqueue_step_f32(G, k_enq + j, rtol, st) : gmres_enqueue_step(G, k_enq + j, rtol, grid, st))) return rc;
+                    if ((rc = f32 ? gmres_enqueue_step_f32(G, k_enq + j, rtol, maxiter, st) : gmres_enqueue_step(G, k_enq + j, rtol, maxiter, grid, st))) return rc;
                 k_enq += nb;
                 cur = G->next_slot;
                 G->next_slot ^= 1;
@@ -353,5 +363,294 @@ extern "C" int mi_gmres_info(mi_gmres_t G, int* restart, long long* device_bytes
     if (readbacks_last) *readbacks_last = G->readbacks_last;
     if (launches_last) *launches_last = G->launches_last;
     if (wasted_steps_last) *wasted_steps_last = G->wasted_last;
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------- a cycle with no read-back, and the solve as replayed graphs
+// (include/mi355_spmv.h, "capturable GMRES")
+
+// the start of a cycle, enqueued: the launches of mi_gmres_solve_dev's own cycle start (whose host loop keeps them inline)
+static int gmres_enqueue_start(mi_gmres_s* G, const double* d_b, double* d_x, bool first, double rtol, int maxiter, int grid, hipStream_t st)
+{
+    const GmresSmall S = G->S();
+    mi_stream_t s = (mi_stream_t)st;
+    const int n = G->n;
+    const bool f32 = G->f32();
+    int rc;
+    if ((rc = gmres_mult(G, d_x, G->w, s)) || (rc = residual_norm_dev(n, d_b, G->w, f32 ? G->z.get() : G->row(0), S.beta(), st))) return rc;
+    if (first && (rc = mi_norm2_dev(n, d_b, S.bnorm(), s))) return rc;
+    hipLaunchKernelGGL(gmres_cycle_begin, dim3(1), dim3(64), 0, st, S, first ? 1 : 0, rtol, maxiter);
+    if (f32) {
+        if ((rc = mi_round_f32_dev(n, G->z, S.beta(), G->row32(0), G->q, s))) return rc;
+    } else {
+        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, n, S.beta(), G->row(0));
+    }
+    HIP_TRY(hipGetLastError());
+    G->launches_last += first ? 6 : 5;
+    return MI_OK;
+}
+
+static int gmres_grid(int n)
+{
+    const int grid = (n + 255) / 256;
+    return grid > 2048 ? 2048 : grid;
+}
+
+// the end of a cycle, enqueued, with the counted steps k where only the device has them (the record): y, then x += M^-1 (V y) over
+// the first k vectors; k == 0 changes no bit of x
+static int gmres_enqueue_end(mi_gmres_s* G, double* d_x, hipStream_t st)
+{
+    const GmresSmall S = G->S();
+    mi_stream_t s = (mi_stream_t)st;
+    const int n = G->n, m = G->m;
+    const int* d_k = &S.rec()->k;
+    int rc;
+    hipLaunchKernelGGL(gmres_backsolve_counted, dim3(1), dim3(256), 0, st, S);
+    HIP_TRY(hipGetLastError());
+    double* out = G->F ? G->w.get() : d_x;
+    if (G->F) HIP_TRY(hipMemsetAsync(G->w, 0, sizeof(double) * (size_t)n, st));
+    if ((rc = G->f32() ? mi_maxpy_upto_f32_dev(n, m, d_k, S.y(), 0, G->V32ptr.data(), out, s)
+                       : mi_maxpy_upto_dev(n, m, d_k, S.y(), 0, G->Vptr.data(), out, s)))
+        return rc;
+    if (G->F) {
+        if ((rc = gmres_precond(G, G->w, G->z, s))) return rc;
+        int grid = (n / 2 + 255) / 256;
+        grid = grid < 1 ? 1 : (grid > 2048 ? 2048 : grid);
+        hipLaunchKernelGGL(gmres_update_x, dim3(grid), dim3(256), 0, st, n, S.rec(), G->z, d_x);
+        HIP_TRY(hipGetLastError());
+    }
+    return MI_OK;
+}
+
+static int gmres_enqueue_steps(mi_gmres_s* G, int k0, int k1, double rtol, int maxiter, hipStream_t st)
+{
+    const int grid = gmres_grid(G->n);
+    for (int k = k0; k < k1; k++)
+        if (const int rc = G->f32() ? gmres_enqueue_step_f32(G, k, rtol, maxiter, st) : gmres_enqueue_step(G, k, rtol, maxiter, grid, st)) return rc;
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_prepare_stream(mi_gmres_t G, mi_stream_t s)
+{
+    CHECK_ARG(G, "null handle");
+    if (!G->A_csr && !G->A_bcsr) return fail(MI_ERR_STATE, "mi_gmres_prepare_stream: no operator set (mi_gmres_set_operator_*)");
+    hipStream_t st = (hipStream_t)s;
+    if (stream_is_capturing(st)) return fail(MI_ERR_STATE, "mi_gmres_prepare_stream: the stream is capturing (preparing allocates: call it before the capture)");
+    if (G->prepared.count(st)) return MI_OK;
+    double* ws = nullptr;
+    int rc;
+    // the reduction workspace of (device, s), and whatever the operator allocates at its first product on s (a relabelled handle's
+    // gather buffer): a throwaway product on the work vectors, which every cycle overwrites before it reads them
+    if ((rc = get_ws(st, &ws)) || (rc = gmres_mult(G, G->z, G->w, s))) return rc;
+    G->prepared.insert(st);
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_cycle_dev(mi_gmres_t G, const double* d_b, double* d_x, int first, double rtol, int maxiter, mi_stream_t s)
+{
+    CHECK_ARG(maxiter >= 0, "negative maxiter");
+    CHECK_ARG(G, "null handle");
+    CHECK_ARG(d_b && d_x, "null vector");
+    if (!G->A_csr && !G->A_bcsr) return fail(MI_ERR_STATE, "mi_gmres_cycle_dev: no operator set (mi_gmres_set_operator_*)");
+    hipStream_t st = (hipStream_t)s;
+    if (stream_is_capturing(st) && !G->prepared.count(st))
+        return fail(MI_ERR_STATE, "mi_gmres_cycle_dev: the stream is capturing and was not prepared (mi_gmres_prepare_stream allocates: call it before the capture)");
+    int rc;
+    if ((rc = gmres_enqueue_start(G, d_b, d_x, first != 0, rtol, maxiter, gmres_grid(G->n), st)) ||
+        (rc = gmres_enqueue_steps(G, 0, G->m, rtol, maxiter, st)) || (rc = gmres_enqueue_end(G, d_x, st)))
+        return rc;
+    return MI_OK;
+}
+
+// the record and the cycle's history entries into a pinned slot behind st, and the event that says so
+static int gmres_enqueue_readback(mi_gmres_s* G, int entries, int* slot, hipStream_t st)
+{
+    const int cur = G->next_slot;
+    G->next_slot ^= 1;
+    HIP_TRY(hipMemcpyAsync(G->slot[cur], G->S().base, sizeof(double) * (kGmresRecDoubles + (size_t)entries), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(G->ev[cur], st));
+    *slot = cur;
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_state(mi_gmres_t G, mi_stream_t s, int* its, int* k, int* done, int* reason, double* last, double* beta,
+                              double* history_cycle)
+{
+    CHECK_ARG(G, "null handle");
+    hipStream_t st = (hipStream_t)s;
+    if (stream_is_capturing(st)) return fail(MI_ERR_STATE, "mi_gmres_state: the stream is capturing and the state is read back (it cannot be captured)");
+    int cur = 0, rc;
+    if ((rc = gmres_enqueue_readback(G, G->m, &cur, st))) return rc;
+    HIP_TRY(hipEventSynchronize(G->ev[cur]));
+    GmresRecord rec{};
+    memcpy(&rec, G->slot[cur], sizeof(rec));
+    G->last_k = rec.k, G->last_beta = rec.beta; // (what mi_gmres_fetch_cycle reports)
+    if (its) *its = rec.its;
+    if (k) *k = rec.k;
+    if (done) *done = rec.reason != 0;
+    if (reason) *reason = rec.reason == kGmresMetAtStart ? 0 : rec.reason;
+    if (last) *last = rec.last;
+    if (beta) *beta = rec.beta;
+    if (history_cycle)
+        for (int j = 0; j < G->m; j++) history_cycle[j] = j < rec.k ? G->slot[cur][kGmresRecDoubles + j] : 0.0;
+    return MI_OK;
+}
+
+struct mi_gmres_plan_s {
+    mi_gmres_s* G = nullptr;
+    unsigned gen = 0;
+    const double* d_b = nullptr;
+    double* d_x = nullptr;
+    double rtol = 0.0;
+    int maxiter = 0, segment = 0, nseg = 0;
+    OwnedStream cap; // the private stream the graphs were captured on (nothing ever runs on it but the preparing product)
+    // [0] the start of a solve, [1] the start of a later cycle, [2 .. 2 + nseg) the segments, [2 + nseg] the cycle's end
+    std::vector<hipGraph_t> graph;
+    std::vector<hipGraphExec_t> exec;
+    int replays_last = 0, readbacks_last = 0, wasted_last = 0;
+    ~mi_gmres_plan_s()
+    {
+        for (hipGraphExec_t e : exec) (void)hipGraphExecDestroy(e);
+        for (hipGraph_t g : graph) (void)hipGraphDestroy(g);
+    }
+};
+
+// one graph out of what `enqueue` puts on the private stream; thread-local capture mode: what other threads do meanwhile is their own
+template <class F>
+static int plan_capture(mi_gmres_plan_s* P, F&& enqueue)
+{
+    hipStream_t st = P->cap;
+    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue(st);
+    const std::string why = g_err; // (ending the capture must not replace the reason)
+    hipGraph_t g = nullptr;
+    const hipError_t e = hipStreamEndCapture(st, &g);
+    if (rc || e != hipSuccess) {
+        if (g) (void)hipGraphDestroy(g);
+        (void)hipGetLastError();
+        return rc ? fail(rc, why) : hip_fail(e, "hipStreamEndCapture");
+    }
+    P->graph.push_back(g);
+    hipGraphExec_t x = nullptr;
+    HIP_TRY(hipGraphInstantiate(&x, g, nullptr, nullptr, 0));
+    P->exec.push_back(x);
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_plan_create(mi_gmres_t G, const double* d_b, double* d_x, double rtol, int maxiter, int segment, mi_gmres_plan_t* out)
+{
+    CHECK_ARG(out, "null output handle");
+    *out = nullptr;
+    CHECK_ARG(segment >= 1, "segment must be at least 1");
+    CHECK_ARG(maxiter >= 0, "negative maxiter");
+    CHECK_ARG(G, "null handle");
+    CHECK_ARG(d_b && d_x, "null vector");
+    if (!G->A_csr && !G->A_bcsr) return fail(MI_ERR_STATE, "mi_gmres_plan_create: no operator set (mi_gmres_set_operator_*)");
+    std::unique_ptr<mi_gmres_plan_s> P(new (std::nothrow) mi_gmres_plan_s);
+    if (!P) return fail(MI_ERR_ALLOC, "out of host memory");
+    const int m = G->m;
+    P->G = G, P->gen = G->gen, P->d_b = d_b, P->d_x = d_x, P->rtol = rtol, P->maxiter = maxiter;
+    P->segment = std::min(segment, m), P->nseg = (m + P->segment - 1) / P->segment;
+    int rc;
+    if ((rc = dev_create(P->cap, hipStreamNonBlocking)) || (rc = mi_gmres_prepare_stream(G, (mi_stream_t)(hipStream_t)P->cap))) return rc;
+    HIP_TRY(hipStreamSynchronize(P->cap)); // the preparing product wrote the work vectors: over before anything else uses them
+    const int launches = G->launches_last; // (the enqueue helpers count for mi_gmres_info, which describes the last mi_gmres_solve_dev)
+    const int grid = gmres_grid(G->n);
+    for (int first = 1; first >= 0 && !rc; first--)
+        rc = plan_capture(P.get(), [&](hipStream_t st) { return gmres_enqueue_start(G, d_b, d_x, first != 0, rtol, maxiter, grid, st); });
+    for (int j = 0; j < P->nseg && !rc; j++)
+        rc = plan_capture(P.get(), [&](hipStream_t st) { return gmres_enqueue_steps(G, j * P->segment, std::min(m, (j + 1) * P->segment), rtol, maxiter, st); });
+    if (!rc) rc = plan_capture(P.get(), [&](hipStream_t st) { return gmres_enqueue_end(G, d_x, st); });
+    G->launches_last = launches;
+    if (rc) return rc;
+    *out = P.release();
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_plan_solve(mi_gmres_plan_t P, int* iterations, int* reason_out, double* history, mi_stream_t s)
+{
+    CHECK_ARG(P, "null handle");
+    mi_gmres_s* G = P->G;
+    if (P->gen != G->gen) return fail(MI_ERR_STATE, "mi_gmres_plan_solve: the solver's operator or preconditioner was set again after the plan was made (make a new plan)");
+    hipStream_t st = (hipStream_t)s;
+    if (stream_is_capturing(st)) return fail(MI_ERR_STATE, "mi_gmres_plan_solve: the stream is capturing and a solve reads back (capture mi_gmres_cycle_dev instead)");
+    const int m = G->m, maxiter = P->maxiter, nseg = P->nseg;
+    const bool f32 = G->f32();
+    auto replay = [&](int g) {
+        P->replays_last++;
+        return hipGraphLaunch(P->exec[(size_t)g], st);
+    };
+    P->replays_last = P->readbacks_last = P->wasted_last = 0;
+    G->refused_last = 0, G->last_k = 0;
+    bool claimed = false, first = true;
+    int its = 0, reason = 0, rc;
+    for (;;) {
+        HIP_TRY_AS("hipGraphLaunch", replay(first ? 0 : 1));
+        // mi_gmres_solve_dev's loop with the segments as batches (the first batch of a cycle: no step, the record of its start)
+        GmresRecord rec{};
+        int k_enq = 0, seg = 0, pending = -1, rec_slot = -1;
+        for (;;) {
+            int cur = -1;
+            const int room = std::min(m - k_enq, maxiter - its - k_enq);
+            if (pending < 0 || room > 0) {
+                if (pending >= 0) {
+                    HIP_TRY_AS("hipGraphLaunch", replay(2 + seg));
+                    k_enq = std::min(m, (seg + 1) * P->segment), seg++;
+                }
+                if ((rc = gmres_enqueue_readback(G, k_enq, &cur, st))) return rc;
+            }
+            if (pending >= 0) {
+                HIP_TRY(hipEventSynchronize(G->ev[pending]));
+                P->readbacks_last++;
+                rec_slot = pending;
+                memcpy(&rec, G->slot[pending], sizeof(rec));
+                if (rec.reason != 0 || cur < 0) break; // frozen (what is enqueued behind it is wasted), or nothing more to enqueue
+            }
+            pending = cur;
+        }
+        if (history) {
+            if (first) history[0] = rec.rel0;
+            for (int j = 0; j < rec.k; j++) history[its + 1 + j] = G->slot[rec_slot][kGmresRecDoubles + j];
+        }
+        P->wasted_last += k_enq - rec.k;
+        its = rec.its;
+        G->last_k = rec.k, G->last_beta = rec.beta;
+        if (rec.k > 0) HIP_TRY_AS("hipGraphLaunch", replay(2 + nseg)); // (with k == 0 the end would change nothing: not launched, as in mi_gmres_solve_dev)
+        // the end of a solve, the reasons and the float basis's claim / confirm: mi_gmres_solve_dev's
+        reason = rec.reason == kGmresMetAtStart ? 0 : rec.reason;
+        if (claimed && !(rec.reason == 1 && rec.k == 0)) G->refused_last++;
+        claimed = f32 && rec.reason == 1 && rec.k > 0;
+        if (claimed) {
+            first = false;
+            continue;
+        }
+        if (rec.reason != 0) break;
+        if (its >= maxiter) {
+            reason = 2;
+            break;
+        }
+        first = false;
+    }
+    if (iterations) *iterations = its;
+    if (reason_out) *reason_out = reason;
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_plan_info(mi_gmres_plan_t P, int* graphs, int* segment, int* replays_last, int* readbacks_last, int* wasted_steps_last)
+{
+    CHECK_ARG(P, "null handle");
+    if (graphs) *graphs = (int)P->exec.size();
+    if (segment) *segment = P->segment;
+    if (replays_last) *replays_last = P->replays_last;
+    if (readbacks_last) *readbacks_last = P->readbacks_last;
+    if (wasted_steps_last) *wasted_steps_last = P->wasted_last;
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_plan_destroy(mi_gmres_plan_t P)
+{
+    if (!P) return MI_OK;
+    (void)hipDeviceSynchronize(); // a replay may still be in flight behind the last solve
+    delete P;
     return MI_OK;
 }

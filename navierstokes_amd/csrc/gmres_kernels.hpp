@@ -2,6 +2,8 @@
 // start with the first stage of its norm in one pass, and the small least-squares problem of restarted GMRES (Givens rotations,
 // the residual recurrence, the back-substitution) as one-workgroup kernels, so that a cycle never needs the host for arithmetic;
 // and round_f32_kernel, which normalises, rounds and stores a vector of the single-precision basis (MI_BASIS_F32) in one pass.
+// For a cycle enqueued whole (mi_gmres_cycle_dev, mi_gmres_plan_*) the counted steps are a device-side value: the step kernel stops
+// counting at maxiter, gmres_backsolve_counted reads k from the record and gmres_update_x updates x only when a step was counted.
 // The ARITHMETIC below is part of the interface (include/mi355_spmv.h, mi_gmres_*; tests/gmres_dev_model.py restates
 // it in numpy scalars): every product and every sum of the small problem is rounded on its own, nothing is contracted into an fma.
 #pragma once
@@ -166,14 +168,16 @@ static __global__ __launch_bounds__(64) void gmres_cycle_begin(GmresSmall S, int
 
 // Step k of the small problem, behind the step's Gram-Schmidt (one wave; lane 0 walks the rotation chain, which is serial by nature;
 // the lanes move the column): the rotations 0..k-1 applied to a copy of raw column k, the new rotation, R's column, g, the history
-// entry, the stopping rule.  FROZEN STATE: once the record holds a reason every later launch of the cycle returns at once.
-static __global__ __launch_bounds__(64) void gmres_hess_step(GmresSmall S, int k, double rtol)
+// entry, the stopping rule.  FROZEN STATE: once the record holds a reason every later launch of the cycle returns at once.  A step
+// at its >= maxiter returns at once too and writes no reason: a cycle enqueued whole (mi_gmres_cycle_dev) cannot be clipped by the
+// host, and mi_gmres_solve_dev, which clips its batches, never launches such a step.
+static __global__ __launch_bounds__(64) void gmres_hess_step(GmresSmall S, int k, double rtol, int maxiter)
 {
 #pragma clang fp contract(off) // every operator below is one rounded operation: nothing is fused (the __d*_rn intrinsics would be
                                // inlined with their own header's setting and fused all the same)
     __shared__ double c[kMultiMax + 2], s_cs[kMultiMax], s_sn[kMultiMax];
     GmresRecord* rec = S.rec();
-    if (rec->reason != 0) return; // (uniform: every lane reads the same word, and nothing below writes it before the barrier)
+    if (rec->reason != 0 || rec->its >= maxiter) return; // (uniform: every lane reads the same words, and nothing below writes them before the barrier)
     const int m = S.m, lane = threadIdx.x;
     const double* col = S.hraw() + (size_t)k * (m + 2);
     for (int j = lane; j <= k + 1; j += 64) c[j] = col[j];
@@ -219,7 +223,7 @@ static __global__ __launch_bounds__(64) void gmres_hess_step(GmresSmall S, int k
 // The end of a cycle of k counted steps (one workgroup; the rows are serial by nature): R y = g by back-substitution, for
 // i = k-1 .. 0: s = g_i, s = s - R_ij y_j for j = i+1 .. k-1 ascending, y_i = s / R_ii — each product, each difference and the
 // division rounded once.  y stays in device memory: mi_maxpy_dev reads it there.
-static __global__ __launch_bounds__(256) void gmres_backsolve(GmresSmall S, int k)
+__device__ __forceinline__ void gmres_backsolve_body(const GmresSmall& S, int k)
 {
 #pragma clang fp contract(off) // every operator below is one rounded operation: nothing is fused (the __d*_rn intrinsics would be
                                // inlined with their own header's setting and fused all the same)
@@ -240,6 +244,43 @@ static __global__ __launch_bounds__(256) void gmres_backsolve(GmresSmall S, int 
     }
     __syncthreads();
     for (int i = threadIdx.x; i < k; i += blockDim.x) S.y()[i] = sy[i];
+}
+
+static __global__ __launch_bounds__(256) void gmres_backsolve(GmresSmall S, int k)
+{
+    gmres_backsolve_body(S, k);
+}
+
+// ... with k read from the record (the end of a cycle enqueued whole: only the device knows how many steps were counted).  k == 0
+// writes nothing.
+static __global__ __launch_bounds__(256) void gmres_backsolve_counted(GmresSmall S)
+{
+    int k = S.rec()->k; // (uniform; nothing in this launch writes the record)
+    k = k < 0 ? 0 : (k > S.m ? S.m : k);
+    gmres_backsolve_body(S, k);
+}
+
+// x_i = fma(1, z_i, x_i), mi_axpy_dev's arithmetic, only when the cycle counted a step (rec->k > 0): with k == 0 the cycle's end
+// leaves every bit of x alone, as the host-driven solve does by not launching the update.
+static __global__ __launch_bounds__(256) void gmres_update_x(int n, const GmresRecord* __restrict__ rec, const double* __restrict__ z,
+                                                             double* __restrict__ x)
+{
+    if (rec->k <= 0) return; // (uniform)
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if ((((uintptr_t)z | (uintptr_t)x) & 15) == 0) {
+        const long long n2 = n >> 1;
+        for (long long i = t; i < n2; i += stride) {
+            const double2 zv = reinterpret_cast<const double2*>(z)[i];
+            double2 xv = reinterpret_cast<double2*>(x)[i];
+            xv.x = fma(1.0, zv.x, xv.x);
+            xv.y = fma(1.0, zv.y, xv.y);
+            reinterpret_cast<double2*>(x)[i] = xv;
+        }
+        if ((n & 1) && t == 0) x[n - 1] = fma(1.0, z[n - 1], x[n - 1]);
+    } else {
+        for (long long i = t; i < n; i += stride) x[i] = fma(1.0, z[i], x[i]);
+    }
 }
 
 } // namespace mi355

@@ -206,6 +206,15 @@ def lib():
         "mi_mdot_f32_dev": [i, i, _vp, _vp, _vp, _vp],
         "mi_maxpy_f32_dev": [i, i, _vp, i, _vp, _vp, _vp, _vp],
         "mi_cgs_f32_dev": [i, i, _vp, _vp, i, _vp, _vp, _vp],
+        "mi_maxpy_upto_dev": [i, i, _vp, _vp, i, _vp, _vp, _vp],
+        "mi_maxpy_upto_f32_dev": [i, i, _vp, _vp, i, _vp, _vp, _vp],
+        "mi_gmres_prepare_stream": [_vp, _vp],
+        "mi_gmres_cycle_dev": [_vp, _vp, _vp, i, d, i, _vp],
+        "mi_gmres_state": [_vp, _vp, P(i), P(i), P(i), P(i), P(d), P(d), _vp],
+        "mi_gmres_plan_create": [_vp, _vp, _vp, d, i, i, P(_vp)],
+        "mi_gmres_plan_solve": [_vp, P(i), P(i), _vp, _vp],
+        "mi_gmres_plan_info": [_vp, P(i), P(i), P(i), P(i), P(i)],
+        "mi_gmres_plan_destroy": [_vp],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -1300,7 +1309,10 @@ class gmres_solver:
     M: a bilu4 (the exact solve in the handle's current form), a bilu4_sweeps (either precision) or None.  The solver owns its
     basis and work vectors; A and M must outlive it.  One solve at a time per solver, and per M.
     basis="f32" (MI_BASIS_F32, opt-in): the Krylov basis is stored in single precision, every projection is taken against the
-    stored basis, and a converged recurrence is confirmed by the next cycle's true residual (basis_info())."""
+    stored basis, and a converged recurrence is confirmed by the next cycle's true residual (basis_info()).
+    Opt-in, with the bits of solve(): plan(b, x, ..) is the solve as graphs captured once and replayed; cycle() enqueues one whole
+    restart cycle with no read-back, which the caller can capture into a graph of their own after prepare_stream(), and state()
+    reads what it did."""
 
     def __init__(self, A, M=None, restart=30, basis="f64"):
         self._h = None
@@ -1367,9 +1379,80 @@ class gmres_solver:
         check(lib().mi_gmres_basis_info(self.handle, _c.byref(kind), _c.byref(by), _c.byref(refused)))
         return dict(basis="f32" if kind.value == GMRES_BASIS["f32"] else "f64", basis_bytes=by.value, refused_last=refused.value)
 
+    def prepare_stream(self):
+        """Allocate, outside capture, whatever a first use on torch's current stream would allocate (mi_gmres_prepare_stream): call
+        it on the stream a cycle() is going to be captured on."""
+        check(lib().mi_gmres_prepare_stream(self.handle, _stream_ptr()))
+
+    def cycle(self, b, x, first, rtol=1e-8, maxiter=300):
+        """ONE whole restart cycle on torch's current stream with no read-back (mi_gmres_cycle_dev): capturable once the stream is
+        prepared.  first: the start of a solve.  state() tells what it did."""
+        check(lib().mi_gmres_cycle_dev(self.handle, _dev_ptr(b, self.n, "b"), _dev_ptr(x, self.n, "x"), 1 if first else 0, float(rtol),
+                                       int(maxiter), _stream_ptr()))
+
+    def state(self):
+        """dict(its, k, done, reason, last, beta, history) of the record behind torch's current stream (mi_gmres_state; waits):
+        history holds the entries of the cycle's k counted steps."""
+        its, k, done, reason = (_c.c_int() for _ in range(4))
+        last, beta = _c.c_double(), _c.c_double()
+        hist = np.zeros(self.restart)
+        check(lib().mi_gmres_state(self.handle, _stream_ptr(), _c.byref(its), _c.byref(k), _c.byref(done), _c.byref(reason), _c.byref(last),
+                                   _c.byref(beta), hist.ctypes.data))
+        return dict(its=its.value, k=k.value, done=bool(done.value), reason=reason.value, last=last.value, beta=beta.value,
+                    history=[float(v) for v in hist[: k.value]])
+
+    def plan(self, b, x, rtol=1e-8, maxiter=300, segment=None):
+        """A gmres_plan: solve(b, x, rtol, maxiter) as replayed graphs of `segment` steps each (default: restart, one graph of
+        steps per cycle).  b and x are baked in: refill them in place between solves."""
+        return gmres_plan(self, b, x, rtol, maxiter, self.restart if segment is None else segment)
+
     def close(self):
         if self._h is not None:
             lib().mi_gmres_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class gmres_plan:
+    """mi_gmres_plan_t (gmres_solver.plan): the solve of b, x (CUDA tensors, baked in: refill them in place) as graphs captured once
+    and replayed, `segment` steps per graph; bit for bit gmres_solver.solve with the same arguments.  Stale (MiError, status 6)
+    once the solver's operator or preconditioner is set again.  The solver, b and x must outlive it."""
+
+    def __init__(self, S, b, x, rtol, maxiter, segment):
+        self._h = None
+        self.S, self.b, self.x, self.maxiter = S, b, x, int(maxiter)
+        h = _vp()
+        check(lib().mi_gmres_plan_create(S.handle, _dev_ptr(b, S.n, "b"), _dev_ptr(x, S.n, "x"), float(rtol), self.maxiter, int(segment),
+                                         _c.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("gmres_plan: closed")
+        return self._h
+
+    def solve(self):
+        """(iterations, history, reason) on torch's current stream; x is complete on that stream when the call returns."""
+        its, reason = _c.c_int(), _c.c_int()
+        hist = np.zeros(max(self.maxiter, 0) + 1)
+        check(lib().mi_gmres_plan_solve(self.handle, _c.byref(its), _c.byref(reason), hist.ctypes.data, _stream_ptr()))
+        return its.value, [float(v) for v in hist[: its.value + 1]], reason.value
+
+    def info(self):
+        """dict(graphs, segment, replays_last, readbacks_last, wasted_steps_last) — mi_gmres_plan_info."""
+        g, sg, rp, rb, wa = (_c.c_int() for _ in range(5))
+        check(lib().mi_gmres_plan_info(self.handle, _c.byref(g), _c.byref(sg), _c.byref(rp), _c.byref(rb), _c.byref(wa)))
+        return dict(graphs=g.value, segment=sg.value, replays_last=rp.value, readbacks_last=rb.value, wasted_steps_last=wa.value)
+
+    def close(self):
+        if self._h is not None:
+            lib().mi_gmres_plan_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -1545,6 +1628,23 @@ def maxpy(coef, basis, y, negate=False, norm=False):
     cc = _host_f64(coef, m, "coef")
     check(lib().mi_maxpy(n, m, cc.ctypes.data if m else None, 1 if negate else 0, ptrs, yy.ctypes.data))
     return (y, norm2(yy)) if norm else y
+
+
+def maxpy_upto(count, coef, basis, y, negate=False):
+    """maxpy(coef[:c], basis[:c], y, negate) with c = count[0] clamped to [0, len(basis)] and count an int32 CUDA tensor that the
+    KERNELS read (mi_maxpy_upto*_dev): the call can be captured into a graph and replayed with another count.  The same bits as
+    maxpy at that count; vectors and coefficients from c on are never loaded, and c = 0 leaves y as it is.  A float32 basis takes
+    the float form.  Device tensors only.  Returns y."""
+    import torch
+    m = len(basis)
+    if not (_is_torch(y) and _is_torch(count) and _is_torch(coef)):
+        raise TypeError("maxpy_upto: count, coef and y must be CUDA tensors (there is no host form)")
+    n = int(y.numel())
+    f32 = _basis_f32(basis)
+    call = lib().mi_maxpy_upto_f32_dev if f32 else lib().mi_maxpy_upto_dev
+    check(call(n, m, _dev_ptr(count, 1, "count", torch.int32), _dev_ptr(coef, m, "coef") if m else None, 1 if negate else 0,
+               _dev_basis(basis, n, torch.float32 if f32 else None), _dev_ptr(y), _stream_ptr()))
+    return y
 
 
 def cgs(basis, y, passes=2):

@@ -5,11 +5,16 @@ the SAME matrix and factor handles, in one process.  Prints one JSON line per pr
 profiles/gmres_bench.jsonl.
 
     python3 tools/bench_gmres.py [--cells 68] [--fill 0] [--sweeps 3] [--precision f64|f32|both] [--basis f64|f32|both] [--runs 5] [--no-append]
+                                 [--graph SEG[,SEG...]]
 
 --basis f64 (the default) is the comparison above.  --basis f32 or both compares the solver handles instead: one gmres_solver per
 basis asked for (basis="f64": the yardstick, the code path of the default; basis="f32": the single-precision Krylov basis), both at
 check_every = 1 on the same matrix and factor handles, alternating inside every run; the records also carry basis_bytes and the
 refused claims of the last solve (refused_last).
+
+--graph 1,5,30 adds the PLANNED solve (gmres_solver.plan: graphs captured once and replayed, SEG steps per graph) as further solvers
+gmres_plan_segSEG on every solver handle of the run, inside the same alternating runs; their records carry the graphs of the plan
+and replays_last, readbacks_last and wasted_steps_last of the last solve.  The plans are captured before the warm-up.
 
 Preconditioners per process: the sweeps (--sweeps per triangle) in each precision asked for, and the exact solve.  For each one a
 record (tool = "bench_gmres") with, per solver: iterations, wall seconds (median of --runs runs; the solvers ALTERNATE inside every
@@ -40,6 +45,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--maxiter", type=int, default=300)
     ap.add_argument("--no-append", action="store_true")
+    ap.add_argument("--graph", default="", help="segments of the planned solve, e.g. 1,5,30")
     a = ap.parse_args()
     import torch
     from navierstokes_amd import mpk, synth
@@ -63,6 +69,11 @@ def main():
         else:
             handles = [mpk.gmres_solver(A, M, RESTART, basis=k) for k in (("f64", "f32") if a.basis == "both" else (a.basis,))]
             solvers = [(f"gmres_solver_{h.basis}_ce1", (h, 1)) for h in handles]
+        plans = []
+        for seg in (int(t) for t in a.graph.split(",") if t):
+            for h in handles:
+                plans.append(h.plan(db, dx, rtol=RTOL, maxiter=a.maxiter, segment=seg))
+                solvers.append((f"gmres_plan_seg{seg}" + ("" if a.basis == "f64" else f"_{h.basis}"), (h, plans[-1])))
 
         def run(ce):
             dx.zero_()
@@ -70,6 +81,8 @@ def main():
             t0 = time.perf_counter()
             if ce is None:
                 its, hist = mpk.GMRES(A, db, dx, M=M, restart=RESTART, rtol=RTOL, maxiter=a.maxiter)
+            elif isinstance(ce[1], mpk.gmres_plan):
+                its, hist, _ = ce[1].solve()
             else:
                 its, hist, _ = ce[0].solve(db, dx, rtol=RTOL, maxiter=a.maxiter, check_every=ce[1])
             torch.cuda.synchronize()
@@ -87,7 +100,11 @@ def main():
                 its, sec, true, rec = run(ce)
                 secs[name].append(sec)
                 last[name] = dict(iterations=its, true_residual=true, recurrence_residual=rec)
-                if ce is not None:
+                if ce is not None and isinstance(ce[1], mpk.gmres_plan):
+                    last[name].update(ce[1].info())
+                    if a.basis != "f64":
+                        last[name].update(ce[0].basis_info())
+                elif ce is not None:
                     info = ce[0].info()
                     last[name].update(readbacks_last=info["readbacks_last"], wasted_steps_last=info["wasted_steps_last"], launches_last=info["launches_last"])
                     if a.basis != "f64":
@@ -104,7 +121,7 @@ def main():
         if not a.no_append:
             with open(os.path.join(ROOT, "profiles", "gmres_bench.jsonl"), "a") as f:
                 f.write(line + "\n")
-        for h in handles:
+        for h in plans + handles:
             h.close()
     F.close()
     A.close()
