@@ -808,7 +808,8 @@ int mi_gmres_solve(mi_gmres_t G, const double* b, double* x, double rtol, int ma
 int mi_gmres_fetch_cycle(mi_gmres_t G, int* k, double* hraw, double* y, double* beta);
 /* *device_bytes of V, the work vectors and the small state; of the last solve: *readbacks_last, *launches_last (kernels of this
  * section and library calls enqueued, a product, a preconditioner application or an mi_cgs_dev each counted once),
- * *wasted_steps_last.  Any output may be NULL */
+ * *wasted_steps_last.  Only mi_gmres_solve_dev (and mi_gmres_solve through it) writes these three: mi_gmres_cycle_dev and
+ * mi_gmres_plan_* leave them as the last such solve left them, 0 before any.  Any output may be NULL */
 int mi_gmres_info(mi_gmres_t G, int* restart, long long* device_bytes, int* readbacks_last, int* launches_last, int* wasted_steps_last);
 int mi_gmres_destroy(mi_gmres_t G);
 

@@ -4,8 +4,9 @@
 // gmres_kernels.hpp.  A handle created with MI_BASIS_F32 stores its Krylov basis in float: the same loop with mi_cgs_f32_dev /
 // mi_maxpy_f32_dev / mi_round_f32_dev, and a converged recurrence confirmed by the next cycle's start.  At the end of the file: a
 // whole cycle with no read-back (mi_gmres_cycle_dev: the counted steps stay on the device) and the solve as replayed graphs
-// (mi_gmres_plan_*), both with the bits of mi_gmres_solve_dev.  Built for gfx950 only; no CPU fallback: every entry point that computes needs a HIP device.
+// (mi_gmres_plan_*), both with the bits of mi_gmres_solve_dev.  The host loop of both solves is gmres_drive.hpp's.  Built for gfx950 only; no CPU fallback: every entry point that computes needs a HIP device.
 #include "capi_internal.hpp"
+#include "gmres_drive.hpp"
 #include "gmres_kernels.hpp"
 
 #include <set>
@@ -140,10 +141,15 @@ static int gmres_mult(mi_gmres_s* G, const double* x, double* y, mi_stream_t s)
     return G->A_csr ? mi_spmv_dev(G->A_csr, x, y, s) : mi_bcsr4_spmv_dev(G->A_bcsr, x, y, s);
 }
 
-// out += sum y_j V_j over the k counted steps of the cycle (the basis as stored)
+constexpr int kCountedOnDevice = -1; // in place of a cycle's counted steps k: only the record has them
+
+// out += sum y_j V_j over the k counted steps of the cycle (the basis as stored); kCountedOnDevice: over the record's k
 static int gmres_combine(mi_gmres_s* G, int k, double* out, mi_stream_t s)
 {
     const GmresSmall S = G->S();
+    if (k == kCountedOnDevice)
+        return G->f32() ? mi_maxpy_upto_f32_dev(G->n, G->m, &S.rec()->k, S.y(), 0, G->V32ptr.data(), out, s)
+                        : mi_maxpy_upto_dev(G->n, G->m, &S.rec()->k, S.y(), 0, G->Vptr.data(), out, s);
     return G->f32() ? mi_maxpy_f32_dev(G->n, k, S.y(), 0, G->V32ptr.data(), out, nullptr, s)
                     : mi_maxpy_dev(G->n, k, S.y(), 0, G->Vptr.data(), out, nullptr, s);
 }
@@ -157,48 +163,140 @@ static int gmres_precond(mi_gmres_s* G, const double* in, double* out, mi_stream
     }
 }
 
-// step k of a cycle, enqueued: w = A M^-1 V_k straight into row k + 1, CGS2 in place with the raw column where the small problem
-// reads it, the small problem, the division
-static int gmres_enqueue_step(mi_gmres_s* G, int k, double rtol, int maxiter, int grid, hipStream_t st)
+// workgroups of 256 for an elementwise kernel over `items` (gmres_update_x: n / 2 pairs)
+static int gmres_grid(int items)
+{
+    return std::min(std::max((items + 255) / 256, 1), 2048);
+}
+
+static int gmres_need_operator(const mi_gmres_s* G, const char* who)
+{
+    return G->A_csr || G->A_bcsr ? MI_OK : fail(MI_ERR_STATE, std::string(who) + ": no operator set (mi_gmres_set_operator_*)");
+}
+
+// The enqueue helpers add what they enqueued to `launches`, by the rule of mi_gmres_info (kernels of this file and library calls, each
+// counted once); only mi_gmres_solve_dev keeps the sum.
+
+// the start of a cycle, enqueued: r = b - A x into row 0, its norm, the record, V_0 = r / beta (the float basis: r into a work
+// vector, then V32_0 = round32(r / beta) and q = widen(V32_0))
+static int gmres_enqueue_start(mi_gmres_s* G, const double* d_b, double* d_x, bool first, double rtol, int maxiter, hipStream_t st, int& launches)
 {
     const GmresSmall S = G->S();
     mi_stream_t s = (mi_stream_t)st;
-    double* next = G->row(k + 1);
-    double* col = S.hraw() + (size_t)k * (G->m + 2);
+    const int n = G->n;
+    const bool f32 = G->f32();
     int rc;
-    if (G->F) {
-        if ((rc = gmres_precond(G, G->row(k), G->z, s)) || (rc = gmres_mult(G, G->z, next, s))) return rc;
-        G->launches_last++;
-    } else if ((rc = gmres_mult(G, G->row(k), next, s))) {
-        return rc;
+    if ((rc = gmres_mult(G, d_x, G->w, s)) || (rc = residual_norm_dev(n, d_b, G->w, f32 ? G->z.get() : G->row(0), S.beta(), st))) return rc;
+    if (first && (rc = mi_norm2_dev(n, d_b, S.bnorm(), s))) return rc;
+    hipLaunchKernelGGL(gmres_cycle_begin, dim3(1), dim3(64), 0, st, S, first ? 1 : 0, rtol, maxiter);
+    if (f32) {
+        if ((rc = mi_round_f32_dev(n, G->z, S.beta(), G->row32(0), G->q, s))) return rc;
+    } else {
+        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(gmres_grid(n)), dim3(256), 0, st, n, S.beta(), G->row(0));
     }
-    if ((rc = mi_cgs_dev(G->n, k + 1, G->Vptr.data(), next, 2, col, col + k + 1, s))) return rc;
-    hipLaunchKernelGGL(gmres_hess_step, dim3(1), dim3(64), 0, st, S, k, rtol, maxiter);
-    hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, G->n, col + k + 1, next);
-    G->launches_last += 4;
+    HIP_TRY(hipGetLastError());
+    launches += first ? 6 : 5;
     return MI_OK;
 }
 
-// the same step with the float basis: w = A M^-1 q into a work vector (q = widen(V32_k), the STORED vector), CGS2 of w against
-// V32_0..V32_k, the small problem unchanged, then V32_{k+1} = round32(w / nrm) and q = widen(V32_{k+1}) in one launch
-static int gmres_enqueue_step_f32(mi_gmres_s* G, int k, double rtol, int maxiter, hipStream_t st)
+// step k of a cycle, enqueued: w = A M^-1 v, CGS2 of w in place with the raw column where the small problem reads it, the small
+// problem, the division.  The double basis: v = V_k and w is row k + 1 itself.  The float basis: v = q = widen(V32_k), the STORED
+// vector, w a work vector, CGS2 against V32_0..V32_k, and V32_{k+1} = round32(w / nrm) with q = widen(V32_{k+1}) in one launch
+static int gmres_enqueue_step(mi_gmres_s* G, int k, double rtol, int maxiter, hipStream_t st, int& launches)
 {
     const GmresSmall S = G->S();
     mi_stream_t s = (mi_stream_t)st;
+    const bool f32 = G->f32();
+    const double* v = f32 ? G->q.get() : G->row(k);
+    double* w = f32 ? G->w.get() : G->row(k + 1);
     double* col = S.hraw() + (size_t)k * (G->m + 2);
     int rc;
-    if (G->F) {
-        if ((rc = gmres_precond(G, G->q, G->z, s)) || (rc = gmres_mult(G, G->z, G->w, s))) return rc;
-        G->launches_last++;
-    } else if ((rc = gmres_mult(G, G->q, G->w, s))) {
+    if (G->F && (rc = gmres_precond(G, v, G->z, s))) return rc;
+    if ((rc = gmres_mult(G, G->F ? G->z.get() : v, w, s))) return rc;
+    if ((rc = f32 ? mi_cgs_f32_dev(G->n, k + 1, G->V32ptr.data(), w, 2, col, col + k + 1, s)
+                  : mi_cgs_dev(G->n, k + 1, G->Vptr.data(), w, 2, col, col + k + 1, s)))
         return rc;
-    }
-    if ((rc = mi_cgs_f32_dev(G->n, k + 1, G->V32ptr.data(), G->w, 2, col, col + k + 1, s))) return rc;
     hipLaunchKernelGGL(gmres_hess_step, dim3(1), dim3(64), 0, st, S, k, rtol, maxiter);
-    if ((rc = mi_round_f32_dev(G->n, G->w, col + k + 1, G->row32(k + 1), G->q, s))) return rc;
-    G->launches_last += 4;
+    if (f32) {
+        if ((rc = mi_round_f32_dev(G->n, w, col + k + 1, G->row32(k + 1), G->q, s))) return rc;
+    } else {
+        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(gmres_grid(G->n)), dim3(256), 0, st, G->n, col + k + 1, w);
+    }
+    launches += G->F ? 5 : 4;
     return MI_OK;
 }
+
+static int gmres_enqueue_steps(mi_gmres_s* G, int k0, int k1, double rtol, int maxiter, hipStream_t st, int& launches)
+{
+    for (int k = k0; k < k1; k++)
+        if (const int rc = gmres_enqueue_step(G, k, rtol, maxiter, st, launches)) return rc;
+    return MI_OK;
+}
+
+// the end of a cycle, enqueued: y on the device, then x += M^-1 (V y) over the first k vectors.  k from the host (k > 0), or
+// kCountedOnDevice: the back-substitution and the update read the record, and k == 0 changes no bit of x
+static int gmres_enqueue_end(mi_gmres_s* G, double* d_x, int k, hipStream_t st, int& launches)
+{
+    const GmresSmall S = G->S();
+    mi_stream_t s = (mi_stream_t)st;
+    const int n = G->n;
+    int rc;
+    if (k == kCountedOnDevice) hipLaunchKernelGGL(gmres_backsolve_counted, dim3(1), dim3(256), 0, st, S);
+    else hipLaunchKernelGGL(gmres_backsolve, dim3(1), dim3(256), 0, st, S, k);
+    HIP_TRY(hipGetLastError());
+    if (G->F) HIP_TRY(hipMemsetAsync(G->w, 0, sizeof(double) * (size_t)n, st));
+    if ((rc = gmres_combine(G, k, G->F ? G->w.get() : d_x, s))) return rc;
+    if (G->F) {
+        if ((rc = gmres_precond(G, G->w, G->z, s))) return rc;
+        if (k == kCountedOnDevice) {
+            hipLaunchKernelGGL(gmres_update_x, dim3(gmres_grid(n / 2)), dim3(256), 0, st, n, S.rec(), G->z, d_x);
+            HIP_TRY(hipGetLastError());
+        } else if ((rc = mi_axpy_dev(n, 1.0, G->z, d_x, s))) {
+            return rc;
+        }
+    }
+    launches += G->F ? 5 : 2;
+    return MI_OK;
+}
+
+// what both solves' backends (gmres_drive.hpp) and mi_gmres_state do with the two pinned slots, behind st
+struct GmresSlots {
+    mi_gmres_s* G;
+    hipStream_t st;
+    // the record and the cycle's history entries into the next slot, and the event that says so
+    int readback(int entries, int* slot)
+    {
+        const int cur = *slot = G->next_slot;
+        G->next_slot ^= 1;
+        HIP_TRY(hipMemcpyAsync(G->slot[cur], G->S().base, sizeof(double) * (kGmresRecDoubles + (size_t)entries), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(G->ev[cur], st));
+        return MI_OK;
+    }
+    int wait(int slot, GmresRecord* rec, const double** entries)
+    {
+        HIP_TRY(hipEventSynchronize(G->ev[slot]));
+        memcpy(rec, G->slot[slot], sizeof(*rec));
+        *entries = G->slot[slot] + kGmresRecDoubles;
+        return MI_OK;
+    }
+};
+
+// mi_gmres_solve_dev to gmres_drive: launches with the host's k, batches of check_every steps
+struct GmresEager : GmresSlots {
+    const double* d_b;
+    double* d_x;
+    double rtol;
+    int maxiter, check_every;
+    int launches = 0;
+    int start(bool first) { return gmres_enqueue_start(G, d_b, d_x, first, rtol, maxiter, st, launches); }
+    int batch(int& k_enq, int room, bool first_batch)
+    {
+        const int k0 = k_enq;
+        k_enq = gmres_eager_batch(k0, room, first_batch, check_every);
+        return gmres_enqueue_steps(G, k0, k_enq, rtol, maxiter, st, launches);
+    }
+    int end(int k) { return gmres_enqueue_end(G, d_x, k, st, launches); }
+};
 
 extern "C" int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, double rtol, int maxiter, int check_every, int* iterations,
                                   int* reason_out, double* history, mi_stream_t s)
@@ -207,99 +305,18 @@ extern "C" int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, 
     CHECK_ARG(maxiter >= 0, "negative maxiter");
     CHECK_ARG(G, "null handle");
     CHECK_ARG(d_b && d_x, "null vector");
-    if (!G->A_csr && !G->A_bcsr) return fail(MI_ERR_STATE, "mi_gmres_solve_dev: no operator set (mi_gmres_set_operator_*)");
+    if (const int rc = gmres_need_operator(G, "mi_gmres_solve_dev")) return rc;
     hipStream_t st = (hipStream_t)s;
     if (stream_is_capturing(st)) return fail(MI_ERR_STATE, "mi_gmres_solve_dev: the stream is capturing and a solve reads back (it cannot be captured)");
-    const int n = G->n, m = G->m;
-    const GmresSmall S = G->S();
-    int grid = (n + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    G->readbacks_last = G->launches_last = G->wasted_last = G->refused_last = 0;
-    const bool f32 = G->f32();
-    bool claimed = false; // MI_BASIS_F32: the last cycle froze with reason 1 and this cycle's start has to confirm it
-    G->last_k = 0;
-    int its = 0, reason = 0, rc;
-    bool first = true;
-    for (;;) {
-        // ---- the start of a cycle: r = b - A x into row 0, its norm, the record, V_0 = r / beta (the float basis: r into a work
-        // vector, then V32_0 = round32(r / beta) and q = widen(V32_0))
-        if ((rc = gmres_mult(G, d_x, G->w, s)) || (rc = residual_norm_dev(n, d_b, G->w, f32 ? G->z.get() : G->row(0), S.beta(), st))) return rc;
-        if (first && (rc = mi_norm2_dev(n, d_b, S.bnorm(), s))) return rc;
-        hipLaunchKernelGGL(gmres_cycle_begin, dim3(1), dim3(64), 0, st, S, first ? 1 : 0, rtol, maxiter);
-        if (f32) {
-            if ((rc = mi_round_f32_dev(n, G->z, S.beta(), G->row32(0), G->q, s))) return rc;
-        } else {
-            hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, n, S.beta(), G->row(0));
-        }
-        HIP_TRY(hipGetLastError());
-        G->launches_last += first ? 6 : 5;
-        // ---- batches of steps; behind each the record and the cycle's history go to a pinned slot, and the host looks at a batch's
-        // slot only after the NEXT batch is enqueued
-        GmresRecord rec{};
-        int k_enq = 0, pending = -1;
-        for (;;) {
-            int cur = -1;
-            const int room = std::min(m - k_enq, maxiter - its - k_enq);
-            if (room > 0 || pending < 0) { // (room == 0 with nothing pending: maxiter == 0, the record alone)
-                // (a cycle's first batch is one step short: a solve that ends at the cycle's start, which only this batch's record
-                // tells, has then wasted 2 check_every - 1 steps at most, like one that freezes inside a batch)
-                const int nb = std::min(pending < 0 ? check_every - 1 : check_every, std::max(room, 0));
-                for (int j = 0; j < nb; j++)
-                    if ((rc = f32 ? gmres_enqueue_step_f32(G, k_enq + j, rtol, maxiter, st) : gmres_enqueue_step(G, k_enq + j, rtol, maxiter, grid, st))) return rc;
-                k_enq += nb;
-                cur = G->next_slot;
-                G->next_slot ^= 1;
-                HIP_TRY(hipMemcpyAsync(G->slot[cur], S.base, sizeof(double) * (kGmresRecDoubles + (size_t)k_enq), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(G->ev[cur], st));
-            }
-            if (pending >= 0) {
-                HIP_TRY(hipEventSynchronize(G->ev[pending]));
-                G->readbacks_last++;
-                memcpy(&rec, G->slot[pending], sizeof(rec));
-                if (history) {
-                    if (first) history[0] = rec.rel0;
-                    for (int j = 0; j < rec.k; j++) history[its + 1 + j] = G->slot[pending][kGmresRecDoubles + j];
-                }
-                if (rec.reason != 0 || cur < 0) break; // frozen (what is enqueued behind it is wasted), or the cycle's last batch
-            }
-            pending = cur;
-        }
-        G->wasted_last += k_enq - rec.k;
-        its = rec.its;
-        G->last_k = rec.k, G->last_beta = rec.beta;
-        // ---- the end of a cycle: y on the device, then x += M^-1 (V y)
-        if (rec.k > 0) {
-            hipLaunchKernelGGL(gmres_backsolve, dim3(1), dim3(256), 0, st, S, rec.k);
-            HIP_TRY(hipGetLastError());
-            if (G->F) {
-                HIP_TRY(hipMemsetAsync(G->w, 0, sizeof(double) * (size_t)n, st));
-                if ((rc = gmres_combine(G, rec.k, G->w, s)) || (rc = gmres_precond(G, G->w, G->z, s)) ||
-                    (rc = mi_axpy_dev(n, 1.0, G->z, d_x, s)))
-                    return rc;
-                G->launches_last += 5;
-            } else {
-                if ((rc = gmres_combine(G, rec.k, d_x, s))) return rc;
-                G->launches_last += 2;
-            }
-        }
-        reason = rec.reason == kGmresMetAtStart ? 0 : rec.reason;
-        // the float basis: the recurrence is exact only to float rounding of the basis, so a step's reason 1 (rec.k > 0) is a CLAIM:
-        // the update above has run, and the next cycle's start — the true residual — confirms it (reason 1 with k = 0) or not
-        if (claimed && !(rec.reason == 1 && rec.k == 0)) G->refused_last++;
-        claimed = f32 && rec.reason == 1 && rec.k > 0;
-        if (claimed) {
-            first = false;
-            continue;
-        }
-        if (rec.reason != 0) break;
-        if (its >= maxiter) {
-            reason = 2;
-            break;
-        }
-        first = false;
-    }
-    if (iterations) *iterations = its;
-    if (reason_out) *reason_out = reason;
+    GmresEager B{{G, st}, d_b, d_x, rtol, maxiter, check_every};
+    GmresOutcome out;
+    out.last_beta = G->last_beta;
+    const int rc = gmres_drive(B, G->m, maxiter, G->f32(), history, out);
+    G->readbacks_last = out.readbacks, G->launches_last = B.launches, G->wasted_last = out.wasted, G->refused_last = out.refused;
+    G->last_k = out.last_k, G->last_beta = out.last_beta;
+    if (rc) return rc;
+    if (iterations) *iterations = out.its;
+    if (reason_out) *reason_out = out.reason;
     return MI_OK;
 }
 
@@ -369,76 +386,15 @@ extern "C" int mi_gmres_info(mi_gmres_t G, int* restart, long long* device_bytes
 // ---------------------------------------------------------------- a cycle with no read-back, and the solve as replayed graphs
 // (include/mi355_spmv.h, "capturable GMRES")
 
-// the start of a cycle, enqueued: the launches of mi_gmres_solve_dev's own cycle start (whose host loop keeps them inline)
-static int gmres_enqueue_start(mi_gmres_s* G, const double* d_b, double* d_x, bool first, double rtol, int maxiter, int grid, hipStream_t st)
-{
-    const GmresSmall S = G->S();
-    mi_stream_t s = (mi_stream_t)st;
-    const int n = G->n;
-    const bool f32 = G->f32();
-    int rc;
-    if ((rc = gmres_mult(G, d_x, G->w, s)) || (rc = residual_norm_dev(n, d_b, G->w, f32 ? G->z.get() : G->row(0), S.beta(), st))) return rc;
-    if (first && (rc = mi_norm2_dev(n, d_b, S.bnorm(), s))) return rc;
-    hipLaunchKernelGGL(gmres_cycle_begin, dim3(1), dim3(64), 0, st, S, first ? 1 : 0, rtol, maxiter);
-    if (f32) {
-        if ((rc = mi_round_f32_dev(n, G->z, S.beta(), G->row32(0), G->q, s))) return rc;
-    } else {
-        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(grid), dim3(256), 0, st, n, S.beta(), G->row(0));
-    }
-    HIP_TRY(hipGetLastError());
-    G->launches_last += first ? 6 : 5;
-    return MI_OK;
-}
-
-static int gmres_grid(int n)
-{
-    const int grid = (n + 255) / 256;
-    return grid > 2048 ? 2048 : grid;
-}
-
-// the end of a cycle, enqueued, with the counted steps k where only the device has them (the record): y, then x += M^-1 (V y) over
-// the first k vectors; k == 0 changes no bit of x
-static int gmres_enqueue_end(mi_gmres_s* G, double* d_x, hipStream_t st)
-{
-    const GmresSmall S = G->S();
-    mi_stream_t s = (mi_stream_t)st;
-    const int n = G->n, m = G->m;
-    const int* d_k = &S.rec()->k;
-    int rc;
-    hipLaunchKernelGGL(gmres_backsolve_counted, dim3(1), dim3(256), 0, st, S);
-    HIP_TRY(hipGetLastError());
-    double* out = G->F ? G->w.get() : d_x;
-    if (G->F) HIP_TRY(hipMemsetAsync(G->w, 0, sizeof(double) * (size_t)n, st));
-    if ((rc = G->f32() ? mi_maxpy_upto_f32_dev(n, m, d_k, S.y(), 0, G->V32ptr.data(), out, s)
-                       : mi_maxpy_upto_dev(n, m, d_k, S.y(), 0, G->Vptr.data(), out, s)))
-        return rc;
-    if (G->F) {
-        if ((rc = gmres_precond(G, G->w, G->z, s))) return rc;
-        int grid = (n / 2 + 255) / 256;
-        grid = grid < 1 ? 1 : (grid > 2048 ? 2048 : grid);
-        hipLaunchKernelGGL(gmres_update_x, dim3(grid), dim3(256), 0, st, n, S.rec(), G->z, d_x);
-        HIP_TRY(hipGetLastError());
-    }
-    return MI_OK;
-}
-
-static int gmres_enqueue_steps(mi_gmres_s* G, int k0, int k1, double rtol, int maxiter, hipStream_t st)
-{
-    const int grid = gmres_grid(G->n);
-    for (int k = k0; k < k1; k++)
-        if (const int rc = G->f32() ? gmres_enqueue_step_f32(G, k, rtol, maxiter, st) : gmres_enqueue_step(G, k, rtol, maxiter, grid, st)) return rc;
-    return MI_OK;
-}
-
 extern "C" int mi_gmres_prepare_stream(mi_gmres_t G, mi_stream_t s)
 {
     CHECK_ARG(G, "null handle");
-    if (!G->A_csr && !G->A_bcsr) return fail(MI_ERR_STATE, "mi_gmres_prepare_stream: no operator set (mi_gmres_set_operator_*)");
+    int rc;
+    if ((rc = gmres_need_operator(G, "mi_gmres_prepare_stream"))) return rc;
     hipStream_t st = (hipStream_t)s;
     if (stream_is_capturing(st)) return fail(MI_ERR_STATE, "mi_gmres_prepare_stream: the stream is capturing (preparing allocates: call it before the capture)");
     if (G->prepared.count(st)) return MI_OK;
     double* ws = nullptr;
-    int rc;
     // the reduction workspace of (device, s), and whatever the operator allocates at its first product on s (a relabelled handle's
     // gather buffer): a throwaway product on the work vectors, which every cycle overwrites before it reads them
     if ((rc = get_ws(st, &ws)) || (rc = gmres_mult(G, G->z, G->w, s))) return rc;
@@ -451,25 +407,14 @@ extern "C" int mi_gmres_cycle_dev(mi_gmres_t G, const double* d_b, double* d_x, 
     CHECK_ARG(maxiter >= 0, "negative maxiter");
     CHECK_ARG(G, "null handle");
     CHECK_ARG(d_b && d_x, "null vector");
-    if (!G->A_csr && !G->A_bcsr) return fail(MI_ERR_STATE, "mi_gmres_cycle_dev: no operator set (mi_gmres_set_operator_*)");
+    int rc, launches = 0; // (not kept: mi_gmres_info describes the last mi_gmres_solve_dev)
+    if ((rc = gmres_need_operator(G, "mi_gmres_cycle_dev"))) return rc;
     hipStream_t st = (hipStream_t)s;
     if (stream_is_capturing(st) && !G->prepared.count(st))
         return fail(MI_ERR_STATE, "mi_gmres_cycle_dev: the stream is capturing and was not prepared (mi_gmres_prepare_stream allocates: call it before the capture)");
-    int rc;
-    if ((rc = gmres_enqueue_start(G, d_b, d_x, first != 0, rtol, maxiter, gmres_grid(G->n), st)) ||
-        (rc = gmres_enqueue_steps(G, 0, G->m, rtol, maxiter, st)) || (rc = gmres_enqueue_end(G, d_x, st)))
+    if ((rc = gmres_enqueue_start(G, d_b, d_x, first != 0, rtol, maxiter, st, launches)) ||
+        (rc = gmres_enqueue_steps(G, 0, G->m, rtol, maxiter, st, launches)) || (rc = gmres_enqueue_end(G, d_x, kCountedOnDevice, st, launches)))
         return rc;
-    return MI_OK;
-}
-
-// the record and the cycle's history entries into a pinned slot behind st, and the event that says so
-static int gmres_enqueue_readback(mi_gmres_s* G, int entries, int* slot, hipStream_t st)
-{
-    const int cur = G->next_slot;
-    G->next_slot ^= 1;
-    HIP_TRY(hipMemcpyAsync(G->slot[cur], G->S().base, sizeof(double) * (kGmresRecDoubles + (size_t)entries), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(G->ev[cur], st));
-    *slot = cur;
     return MI_OK;
 }
 
@@ -479,20 +424,21 @@ extern "C" int mi_gmres_state(mi_gmres_t G, mi_stream_t s, int* its, int* k, int
     CHECK_ARG(G, "null handle");
     hipStream_t st = (hipStream_t)s;
     if (stream_is_capturing(st)) return fail(MI_ERR_STATE, "mi_gmres_state: the stream is capturing and the state is read back (it cannot be captured)");
-    int cur = 0, rc;
-    if ((rc = gmres_enqueue_readback(G, G->m, &cur, st))) return rc;
-    HIP_TRY(hipEventSynchronize(G->ev[cur]));
+    GmresSlots io{G, st};
     GmresRecord rec{};
-    memcpy(&rec, G->slot[cur], sizeof(rec));
+    const double* entries = nullptr;
+    int cur = 0, rc, why = 0;
+    if ((rc = io.readback(G->m, &cur)) || (rc = io.wait(cur, &rec, &entries))) return rc;
+    const bool is_done = gmres_decode(rec, &why);
     G->last_k = rec.k, G->last_beta = rec.beta; // (what mi_gmres_fetch_cycle reports)
     if (its) *its = rec.its;
     if (k) *k = rec.k;
-    if (done) *done = rec.reason != 0;
-    if (reason) *reason = rec.reason == kGmresMetAtStart ? 0 : rec.reason;
+    if (done) *done = is_done;
+    if (reason) *reason = why;
     if (last) *last = rec.last;
     if (beta) *beta = rec.beta;
     if (history_cycle)
-        for (int j = 0; j < G->m; j++) history_cycle[j] = j < rec.k ? G->slot[cur][kGmresRecDoubles + j] : 0.0;
+        for (int j = 0; j < G->m; j++) history_cycle[j] = j < rec.k ? entries[j] : 0.0;
     return MI_OK;
 }
 
@@ -545,27 +491,43 @@ extern "C" int mi_gmres_plan_create(mi_gmres_t G, const double* d_b, double* d_x
     CHECK_ARG(maxiter >= 0, "negative maxiter");
     CHECK_ARG(G, "null handle");
     CHECK_ARG(d_b && d_x, "null vector");
-    if (!G->A_csr && !G->A_bcsr) return fail(MI_ERR_STATE, "mi_gmres_plan_create: no operator set (mi_gmres_set_operator_*)");
+    int rc, launches = 0; // (not kept: mi_gmres_info describes the last mi_gmres_solve_dev)
+    if ((rc = gmres_need_operator(G, "mi_gmres_plan_create"))) return rc;
     std::unique_ptr<mi_gmres_plan_s> P(new (std::nothrow) mi_gmres_plan_s);
     if (!P) return fail(MI_ERR_ALLOC, "out of host memory");
     const int m = G->m;
     P->G = G, P->gen = G->gen, P->d_b = d_b, P->d_x = d_x, P->rtol = rtol, P->maxiter = maxiter;
     P->segment = std::min(segment, m), P->nseg = (m + P->segment - 1) / P->segment;
-    int rc;
     if ((rc = dev_create(P->cap, hipStreamNonBlocking)) || (rc = mi_gmres_prepare_stream(G, (mi_stream_t)(hipStream_t)P->cap))) return rc;
     HIP_TRY(hipStreamSynchronize(P->cap)); // the preparing product wrote the work vectors: over before anything else uses them
-    const int launches = G->launches_last; // (the enqueue helpers count for mi_gmres_info, which describes the last mi_gmres_solve_dev)
-    const int grid = gmres_grid(G->n);
     for (int first = 1; first >= 0 && !rc; first--)
-        rc = plan_capture(P.get(), [&](hipStream_t st) { return gmres_enqueue_start(G, d_b, d_x, first != 0, rtol, maxiter, grid, st); });
+        rc = plan_capture(P.get(), [&](hipStream_t st) { return gmres_enqueue_start(G, d_b, d_x, first != 0, rtol, maxiter, st, launches); });
     for (int j = 0; j < P->nseg && !rc; j++)
-        rc = plan_capture(P.get(), [&](hipStream_t st) { return gmres_enqueue_steps(G, j * P->segment, std::min(m, (j + 1) * P->segment), rtol, maxiter, st); });
-    if (!rc) rc = plan_capture(P.get(), [&](hipStream_t st) { return gmres_enqueue_end(G, d_x, st); });
-    G->launches_last = launches;
+        rc = plan_capture(P.get(), [&](hipStream_t st) { return gmres_enqueue_steps(G, j * P->segment, std::min(m, (j + 1) * P->segment), rtol, maxiter, st, launches); });
+    if (!rc) rc = plan_capture(P.get(), [&](hipStream_t st) { return gmres_enqueue_end(G, d_x, kCountedOnDevice, st, launches); });
     if (rc) return rc;
     *out = P.release();
     return MI_OK;
 }
+
+// mi_gmres_plan_solve to gmres_drive: every launch is a replayed graph, the segments are the batches
+struct GmresPlanned : GmresSlots {
+    mi_gmres_plan_s* P;
+    int replay(int g)
+    {
+        P->replays_last++;
+        HIP_TRY_AS("hipGraphLaunch", hipGraphLaunch(P->exec[(size_t)g], st));
+        return MI_OK;
+    }
+    int start(bool first) { return replay(first ? 0 : 1); }
+    int batch(int& k_enq, int, bool first_batch)
+    {
+        int seg;
+        k_enq = gmres_plan_batch(k_enq, G->m, first_batch, P->segment, &seg);
+        return seg < 0 ? MI_OK : replay(2 + seg);
+    }
+    int end(int) { return replay(2 + P->nseg); } // (the graph reads k from the record)
+};
 
 extern "C" int mi_gmres_plan_solve(mi_gmres_plan_t P, int* iterations, int* reason_out, double* history, mi_stream_t s)
 {
@@ -574,65 +536,16 @@ extern "C" int mi_gmres_plan_solve(mi_gmres_plan_t P, int* iterations, int* reas
     if (P->gen != G->gen) return fail(MI_ERR_STATE, "mi_gmres_plan_solve: the solver's operator or preconditioner was set again after the plan was made (make a new plan)");
     hipStream_t st = (hipStream_t)s;
     if (stream_is_capturing(st)) return fail(MI_ERR_STATE, "mi_gmres_plan_solve: the stream is capturing and a solve reads back (capture mi_gmres_cycle_dev instead)");
-    const int m = G->m, maxiter = P->maxiter, nseg = P->nseg;
-    const bool f32 = G->f32();
-    auto replay = [&](int g) {
-        P->replays_last++;
-        return hipGraphLaunch(P->exec[(size_t)g], st);
-    };
-    P->replays_last = P->readbacks_last = P->wasted_last = 0;
-    G->refused_last = 0, G->last_k = 0;
-    bool claimed = false, first = true;
-    int its = 0, reason = 0, rc;
-    for (;;) {
-        HIP_TRY_AS("hipGraphLaunch", replay(first ? 0 : 1));
-        // mi_gmres_solve_dev's loop with the segments as batches (the first batch of a cycle: no step, the record of its start)
-        GmresRecord rec{};
-        int k_enq = 0, seg = 0, pending = -1, rec_slot = -1;
-        for (;;) {
-            int cur = -1;
-            const int room = std::min(m - k_enq, maxiter - its - k_enq);
-            if (pending < 0 || room > 0) {
-                if (pending >= 0) {
-                    HIP_TRY_AS("hipGraphLaunch", replay(2 + seg));
-                    k_enq = std::min(m, (seg + 1) * P->segment), seg++;
-                }
-                if ((rc = gmres_enqueue_readback(G, k_enq, &cur, st))) return rc;
-            }
-            if (pending >= 0) {
-                HIP_TRY(hipEventSynchronize(G->ev[pending]));
-                P->readbacks_last++;
-                rec_slot = pending;
-                memcpy(&rec, G->slot[pending], sizeof(rec));
-                if (rec.reason != 0 || cur < 0) break; // frozen (what is enqueued behind it is wasted), or nothing more to enqueue
-            }
-            pending = cur;
-        }
-        if (history) {
-            if (first) history[0] = rec.rel0;
-            for (int j = 0; j < rec.k; j++) history[its + 1 + j] = G->slot[rec_slot][kGmresRecDoubles + j];
-        }
-        P->wasted_last += k_enq - rec.k;
-        its = rec.its;
-        G->last_k = rec.k, G->last_beta = rec.beta;
-        if (rec.k > 0) HIP_TRY_AS("hipGraphLaunch", replay(2 + nseg)); // (with k == 0 the end would change nothing: not launched, as in mi_gmres_solve_dev)
-        // the end of a solve, the reasons and the float basis's claim / confirm: mi_gmres_solve_dev's
-        reason = rec.reason == kGmresMetAtStart ? 0 : rec.reason;
-        if (claimed && !(rec.reason == 1 && rec.k == 0)) G->refused_last++;
-        claimed = f32 && rec.reason == 1 && rec.k > 0;
-        if (claimed) {
-            first = false;
-            continue;
-        }
-        if (rec.reason != 0) break;
-        if (its >= maxiter) {
-            reason = 2;
-            break;
-        }
-        first = false;
-    }
-    if (iterations) *iterations = its;
-    if (reason_out) *reason_out = reason;
+    GmresPlanned B{{G, st}, P};
+    GmresOutcome out;
+    out.last_beta = G->last_beta;
+    P->replays_last = 0;
+    const int rc = gmres_drive(B, G->m, P->maxiter, G->f32(), history, out);
+    P->readbacks_last = out.readbacks, P->wasted_last = out.wasted;
+    G->refused_last = out.refused, G->last_k = out.last_k, G->last_beta = out.last_beta;
+    if (rc) return rc;
+    if (iterations) *iterations = out.its;
+    if (reason_out) *reason_out = out.reason;
     return MI_OK;
 }
 

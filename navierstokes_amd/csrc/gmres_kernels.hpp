@@ -9,6 +9,7 @@
 #pragma once
 #include "blas1_kernels.hpp"
 #include "blas1_multi.hpp"
+#include "gmres_record.hpp"
 
 namespace mi355 {
 
@@ -18,20 +19,7 @@ namespace mi355 {
 //   then  hraw [m (m + 2)] raw Gram-Schmidt columns, mi_krylov_basis_cgs_dev's layout: column k at k (m + 2), the norm at j = k + 1
 //         R    [m m]       the rotated columns, column-major: R_jk at j + k m
 //         cs, sn [m] each, g [m + 1], y [m], then two scalars: ||b|| as mi_norm2_dev wrote it, the cycle's ||r0||
-struct GmresRecord {
-    int its;      // iterations counted so far in this solve
-    int k;        // counted steps of the current cycle
-    int reason;   // 0 while running; 1, 2, 3, 4 as mi_gmres_solve_dev reports them; kGmresMetAtStart: rtol met at a cycle's start
-    int pad;
-    double last;  // the last history value written
-    double beta;  // ||r0|| of the current cycle
-    double rel0;  // beta / bnorm
-    double bnorm; // ||b||, or 1 where that is 0
-    double spare[2];
-};
-static_assert(sizeof(GmresRecord) == 64, "the record is 64 bytes");
-constexpr int kGmresMetAtStart = 5;
-constexpr int kGmresRecDoubles = 8;
+// (GmresRecord, kGmresMetAtStart and kGmresRecDoubles: gmres_record.hpp, shared with the host loop of gmres_drive.hpp)
 
 struct GmresSmall {
     int m;

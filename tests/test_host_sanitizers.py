@@ -1,5 +1,5 @@
 """Host-side planners under the address and undefined-behaviour sanitizers (CPU only: GPU sanitizers are not available on this pool, and
-nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp, bilu_asan.cpp, spmm_plan_asan.cpp, reorder_asan.cpp) and say what they check."""
+nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp, bilu_asan.cpp, spmm_plan_asan.cpp, reorder_asan.cpp, gmres_drive_check.cpp) and say what they check."""
 import os
 import shutil
 import subprocess
@@ -72,3 +72,15 @@ def test_relabelling_under_host_sanitizers(tmp_path):
     out = _run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tools", "reorder_asan.cpp")], exe, tmp_path)
     assert "bad 0" in out and "reorder patterns" in out, out
     assert int(out.split("reorder patterns")[1].split()[0]) >= 2 * 200, out
+
+
+def test_gmres_host_loop_under_host_sanitizers(tmp_path):
+    """gmres_drive.hpp: the host loop of mi_gmres_solve_dev and mi_gmres_plan_solve over a scripted device, eager and planned, restart
+    in {1, 2, 5} x six maxiter x four check_every / segment x both bases x (6 restart + 6) scripts: results against a loop with no
+    pipeline, slot safety, no idle device inside a cycle, what may be enqueued, the header's waste and read-back bounds."""
+    if not shutil.which("g++"):
+        pytest.skip("g++ not found")
+    exe = str(tmp_path / "gmres_drive_check")
+    out = _run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tools", "gmres_drive_check.cpp")], exe, tmp_path)
+    assert "bad 0" in out and "gmres_drive cases" in out, out
+    assert int(out.split("gmres_drive cases")[1].split()[0]) >= sum(6 * 4 * 2 * (6 * m + 6) for m in (1, 2, 5)), out
