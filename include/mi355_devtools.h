@@ -38,6 +38,10 @@ int mi_debug_part_ext_mode(mi_part_t P, int mode);
 int mi_debug_part_ext_trace(mi_part_t P, double* d_x_ext, double* d_y_local, int max_wgs, long long* host_out, int* wgs_out, int* modes_out);
 /* development aid (tools/sim_rank.py): preset every flag slot of this rank's window */
 int mi_part_push_debug_preset(mi_part_t P, unsigned value);
+/* tests of the one-launch powers step (tests/test_gpu_spmk_limits.py): on a handle whose step is set up (it has run a k-step in that
+ * form; else MI_ERR_STATE) set the epoch the next launch counts from to e and every run's flag to e - 1 — the state a step ending at
+ * e - 1 leaves — then synchronise */
+int mi_debug_spmk_set_epoch(mi_csr_t A, unsigned e);
 
 #ifdef __cplusplus
 }

@@ -304,6 +304,16 @@ int mi_csr_spmk_info(mi_csr_t A, int k, int* eligible, int* one_launch, double* 
  * a run names or loads belongs to a run on its list; MI_ERR_STATE names the first violation).  *eligible = 0 when the plan cannot
  * carry the step (rows outside the ring loop, or a band so wide that a run would wait for more than 64 others). */
 int mi_spmk_plan_probe(int n, const int* ptrow, const int* indcol, int* eligible, int* runs, int* max_deps);
+/* host-only: the plan and the lists that probe checks, copied out for a test to restate the kernel's loads against (built by the
+ * same two calls; nothing is checked here).  info[8] = {T, row blocks, runs (= workgroups of the grid), blocks per run of the uniform
+ * deal, 1 if the deal IS the uniform one (the kernel derives run g = blocks [g * bpw, (g + 1) * bpw) itself; else it reads run_rng),
+ * 1 if every row is computed inside the LEAN ring loop (only then are there lists), entries of dep_run, 1 if the plan is LEAN}; all
+ * zero for a matrix without rows or nonzeros.  Optional arrays, sizes from a first call with nulls: plan[8 * blocks] = {first row,
+ * first nonzero, rows, nonzeros, new_lo, new_cnt, ring base, flags} per block (cap_blocks >= blocks); run_rng[2 * runs] = {first
+ * block, end block} per run and dep_ptr[runs + 1] (cap_runs >= runs); dep_run[dep_ptr[g] .. dep_ptr[g + 1]) = the runs whose
+ * flags run g waits for (cap_deps >= entries). */
+int mi_spmk_plan_dump(int n, const int* ptrow, const int* indcol, int info[8], int* plan, int* run_rng, int* dep_ptr, int* dep_run,
+                      int cap_blocks, int cap_runs, int cap_deps);
 
 /* ---- BLAS-1 between SpMVs ---------------------------------------------- */
 /* out = sum x_i y_i  (std::inner_product, mpk/SpMVmulti.cpp:147).  Fixed

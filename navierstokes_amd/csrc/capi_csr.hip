@@ -1198,17 +1198,16 @@ extern "C" int mi_ring_plan_probe(int n, const int* ptrow, const int* indcol, in
     return MI_OK;
 }
 
-// host-only: the run dependencies of the one-launch powers step exactly as mi_csr_create derives them (ring configuration 4),
-// checked against the matrix: every column a run's rows NAME, and every column its lanes LOAD when the plan is replayed (window
-// fills, the T lanes behind a block's new columns, the empty blocks behind the run), lies in the rows of a run on its list.
-extern "C" int mi_spmk_plan_probe(int n, const int* ptrow, const int* indcol, int* eligible, int* runs, int* max_deps)
+// host-only: ring configuration 4's plan of a square pattern and the run dependencies of the one-launch powers step, built by the two
+// calls mi_csr_create makes (build_ring_plan, build_run_deps) — the one source of what mi_spmk_plan_probe checks and
+// mi_spmk_plan_dump copies out.  in_loop: every row is computed inside the LEAN ring loop; without that no lists are built.
+struct SpmkPlanHost {
+    RingPlanHost P;
+    bool in_loop = false;
+    std::vector<int> dep_ptr, dep_run;
+};
+static int build_spmk_plan_host(int n, const int* ptrow, const int* indcol, SpmkPlanHost& S)
 {
-    CHECK_ARG(n >= 0 && ptrow && ptrow[0] == 0 && eligible, "bad argument");
-    CHECK_ARG(ptrow[n] == 0 || indcol, "indcol is null");
-    *eligible = 0;
-    if (runs) *runs = 0;
-    if (max_deps) *max_deps = 0;
-    if (n == 0 || ptrow[n] == 0) return MI_OK;
     std::vector<int> row_min((size_t)n), row_max((size_t)n);
     for (int i = 0; i < n; i++) {
         int lo = 0x7fffffff, hi = -1;
@@ -1220,13 +1219,31 @@ extern "C" int mi_spmk_plan_probe(int n, const int* ptrow, const int* indcol, in
         row_min[i] = lo;
         row_max[i] = hi;
     }
-    RingPlanHost P;
-    build_ring_plan(kRingConfigs[3], n, ptrow, row_min.data(), row_max.data(), P);
-    bool all_in_loop = P.lean && P.nblk > 0;
-    for (int g = 0; g < P.wgs; g++) all_in_loop = all_in_loop && P.run_ok[g] == 1;
-    if (!all_in_loop) return MI_OK; // such a handle runs k launches
-    std::vector<int> dp, dr;
-    build_run_deps(P, n, dp, dr);
+    build_ring_plan(kRingConfigs[3], n, ptrow, row_min.data(), row_max.data(), S.P);
+    S.in_loop = S.P.lean && S.P.nblk > 0;
+    for (int g = 0; g < S.P.wgs; g++) S.in_loop = S.in_loop && S.P.run_ok[g] == 1;
+    S.dep_ptr.clear();
+    S.dep_run.clear();
+    if (S.in_loop) build_run_deps(S.P, n, S.dep_ptr, S.dep_run);
+    return MI_OK;
+}
+
+// host-only: the run dependencies of the one-launch powers step exactly as mi_csr_create derives them (ring configuration 4),
+// checked against the matrix: every column a run's rows NAME, and every column its lanes LOAD when the plan is replayed (window
+// fills, the T lanes behind a block's new columns, the empty blocks behind the run), lies in the rows of a run on its list.
+extern "C" int mi_spmk_plan_probe(int n, const int* ptrow, const int* indcol, int* eligible, int* runs, int* max_deps)
+{
+    CHECK_ARG(n >= 0 && ptrow && ptrow[0] == 0 && eligible, "bad argument");
+    CHECK_ARG(ptrow[n] == 0 || indcol, "indcol is null");
+    *eligible = 0;
+    if (runs) *runs = 0;
+    if (max_deps) *max_deps = 0;
+    if (n == 0 || ptrow[n] == 0) return MI_OK;
+    SpmkPlanHost S;
+    if (int rc = build_spmk_plan_host(n, ptrow, indcol, S)) return rc;
+    if (!S.in_loop) return MI_OK; // such a handle runs k launches
+    const RingPlanHost& P = S.P;
+    const std::vector<int>&dp = S.dep_ptr, &dr = S.dep_run;
     const int W = P.wgs, T = P.cfg.threads;
     std::vector<int> owner((size_t)n, -1);
     for (int g = 0; g < W; g++)
@@ -1254,6 +1271,47 @@ extern "C" int mi_spmk_plan_probe(int n, const int* ptrow, const int* indcol, in
     *eligible = md <= 64 ? 1 : 0;
     if (runs) *runs = W;
     if (max_deps) *max_deps = md;
+    return MI_OK;
+}
+
+// host-only: the plan and the lists mi_spmk_plan_probe checks, copied out (sizes from a first call without arrays)
+extern "C" int mi_spmk_plan_dump(int n, const int* ptrow, const int* indcol, int info[8], int* plan, int* run_rng, int* dep_ptr, int* dep_run,
+                                 int cap_blocks, int cap_runs, int cap_deps)
+{
+    CHECK_ARG(n >= 0 && ptrow && ptrow[0] == 0 && info, "bad argument");
+    CHECK_ARG(ptrow[n] == 0 || indcol, "indcol is null");
+    for (int j = 0; j < 8; j++) info[j] = 0;
+    if (n == 0 || ptrow[n] == 0) return MI_OK;
+    SpmkPlanHost S;
+    if (int rc = build_spmk_plan_host(n, ptrow, indcol, S)) return rc;
+    const RingPlanHost& P = S.P;
+    bool uniform = true; // the comparison fill_ring_table makes: the kernel derives the runs from bpw, else reads run_rng
+    for (int g = 0; g < P.wgs; g++)
+        uniform = uniform && P.run_rng[2 * g] == std::min(P.nblk, g * P.bpw) && P.run_rng[2 * g + 1] == std::min(P.nblk, (g + 1) * P.bpw);
+    info[0] = P.cfg.threads;
+    info[1] = P.nblk;
+    info[2] = P.wgs;
+    info[3] = P.bpw;
+    info[4] = uniform ? 1 : 0;
+    info[5] = S.in_loop ? 1 : 0;
+    info[6] = (int)S.dep_run.size();
+    info[7] = P.lean ? 1 : 0;
+    if (plan) {
+        CHECK_ARG(cap_blocks >= P.nblk, "plan: room for 8 ints per block needed");
+        std::copy(P.plan.begin(), P.plan.end(), plan);
+    }
+    if (run_rng) {
+        CHECK_ARG(cap_runs >= P.wgs, "run_rng: room for 2 ints per run needed");
+        std::copy(P.run_rng.begin(), P.run_rng.end(), run_rng);
+    }
+    if (dep_ptr) {
+        CHECK_ARG(cap_runs >= P.wgs, "dep_ptr: room for runs + 1 ints needed");
+        for (int g = 0; g <= P.wgs; g++) dep_ptr[g] = S.in_loop ? S.dep_ptr[g] : 0;
+    }
+    if (dep_run) {
+        CHECK_ARG(cap_deps >= (int)S.dep_run.size(), "dep_run: too small");
+        std::copy(S.dep_run.begin(), S.dep_run.end(), dep_run);
+    }
     return MI_OK;
 }
 

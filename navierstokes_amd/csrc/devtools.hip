@@ -78,6 +78,23 @@ extern "C" int mi_part_push_debug_preset(mi_part_t P, unsigned value)
     return MI_OK;
 }
 
+// tests of the one-launch powers step's flag arithmetic: put a handle whose step is set up (it has run a k-step in that form) into the
+// state a step ending at epoch e - 1 leaves — every run's flag e - 1, the next launch counting from e — so that the epoch's passage
+// through 2^31 and 2^32 is a matter of three launches, not of a day of them
+#include "spmk_ring.hpp"
+extern "C" int mi_debug_spmk_set_epoch(mi_csr_t A, unsigned e)
+{
+    CHECK_ARG(A, "null handle");
+    if (A->inner) A = A->inner;
+    if (A->kstep_setup != 1 || !A->kstep.flags) return fail(MI_ERR_STATE, "the one-launch powers step of this handle is not set up");
+    HIP_TRY(hipDeviceSynchronize()); // (a step in flight still reads and writes the flags)
+    std::vector<unsigned> f((size_t)A->ring.wgs * kSpmkFlagStride, e - 1u);
+    HIP_TRY(hipMemcpy(A->kstep.flags, f.data(), sizeof(unsigned) * f.size(), hipMemcpyHostToDevice));
+    A->kstep_epoch = e;
+    HIP_TRY(hipDeviceSynchronize());
+    return MI_OK;
+}
+
 // the multi-window ring kernel's timeline: one launch of the TRACE instantiation (depth 4, non-temporal, unmapped) on the handle's
 // own tables (the relabelled twin's, if there is one); out[4 * i] = {start, end (100 MHz ticks), XCD, blocks (< 0: plain path)} of
 // workgroup i.  x and y are device vectors in the numbering of the matrix that runs.

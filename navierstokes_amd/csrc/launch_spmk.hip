@@ -156,7 +156,7 @@ extern "C" int mi_csr_spmk_info(mi_csr_t A, int k, int* eligible, int* one_launc
     mi_csr_t H = A->inner ? A->inner : A;
     const bool small = k <= kSpmkFusedMaxK;
     if (eligible) *eligible = small && k >= 2 && H->kstep_setup == 1;
-    if (one_launch) *one_launch = small && (env_is("MI355_SPMK_FUSED", "1") ? H->kstep_setup == 1 : H->kstep_choice[k] == 1);
+    if (one_launch) *one_launch = small && k >= 2 && (env_is("MI355_SPMK_FUSED", "1") ? H->kstep_setup == 1 : H->kstep_choice[k] == 1);
     if (us_k_launches) *us_k_launches = small ? H->kstep_us[k][0] : 0.0;
     if (us_one_launch) *us_one_launch = small ? H->kstep_us[k][1] : 0.0;
     return MI_OK;

@@ -137,6 +137,7 @@ def lib():
         "mi_spmk_dev": [_vp, i, _vp, _vp, _vp],
         "mi_csr_spmk_info": [_vp, i, P(i), P(i), P(d), P(d)],
         "mi_spmk_plan_probe": [i, _vp, _vp, P(i), P(i), P(i)],
+        "mi_spmk_plan_dump": [i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, i, i, i],
         "mi_dot": [i, _vp, _vp, P(d)],
         "mi_dot_dev": [i, _vp, _vp, _vp, _vp],
         "mi_axpy": [i, d, _vp, _vp],
@@ -273,7 +274,8 @@ def lib():
     # MI355_SPMV_LIBRARY), never in the product library
     for name, argt in {"mi_debug_xcc_map": [i, _vp], "mi_debug_touch_pages": [_vp, i, _vp, ll, _vp, ll],
                        "mi_part_push_debug_preset": [_vp, _c.c_uint], "mi_debug_part_push_trace": [_vp, _vp, _vp, i, _vp, P(i), _vp],
-                       "mi_debug_part_ext_mode": [_vp, i], "mi_debug_part_ext_trace": [_vp, _vp, _vp, i, _vp, P(i), _vp]}.items():
+                       "mi_debug_part_ext_mode": [_vp, i], "mi_debug_part_ext_trace": [_vp, _vp, _vp, i, _vp, P(i), _vp],
+                       "mi_debug_spmk_set_epoch": [_vp, _c.c_uint]}.items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes = argt
@@ -841,6 +843,33 @@ def bilu4one_plan_probe(nbrows, ptrow, indcol, fill=0, workgroups=0):
     return dict(eligible=bool(el.value), why=why, nchunks=(nch[0], nch[1]), max_deps=(md[0], md[1]), plan_bytes=by.value,
                 chunk_pos=tuple(tabs[0]), chunk_lev=tuple(tabs[1]), dep_ptr=tuple(tabs[2]),
                 dep=tuple(dep[b][: int(tabs[2][b][-1])] for b in range(2)))
+
+
+def spmk_plan_probe(n, ptrow, indcol):
+    """mi_spmk_plan_probe (no GPU): (eligible, runs, max_deps) of the one-launch powers step's plan, checked in C++."""
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    e, r, m = _c.c_int(), _c.c_int(), _c.c_int()
+    check(lib().mi_spmk_plan_probe(int(n), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, _c.byref(e), _c.byref(r), _c.byref(m)))
+    return bool(e.value), r.value, m.value
+
+
+def spmk_plan_dump(n, ptrow, indcol):
+    """mi_spmk_plan_dump (no GPU): dict(T, nblk, wgs, bpw, uniform, in_loop, lean, plan (nblk, 8), run_rng (wgs, 2), dep_ptr
+    (wgs + 1), dep_run) — ring configuration 4's plan and the one-launch powers step's dependency lists as mi_csr_create builds them."""
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    info = np.zeros(8, np.int32)
+    args = (int(n), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, info.ctypes.data)
+    check(lib().mi_spmk_plan_dump(*args, None, None, None, None, 0, 0, 0))
+    T, nblk, wgs, bpw, uniform, in_loop, ndep, lean = (int(t) for t in info)
+    plan = np.zeros((max(nblk, 1), 8), np.int32)
+    rng = np.zeros((max(wgs, 1), 2), np.int32)
+    dptr = np.zeros(wgs + 1, np.int32)
+    drun = np.zeros(max(ndep, 1), np.int32)
+    check(lib().mi_spmk_plan_dump(*args, plan.ctypes.data, rng.ctypes.data, dptr.ctypes.data, drun.ctypes.data, nblk, wgs, ndep))
+    return dict(T=T, nblk=nblk, wgs=wgs, bpw=bpw, uniform=bool(uniform), in_loop=bool(in_loop), lean=bool(lean), plan=plan[:nblk],
+                run_rng=rng[:wgs], dep_ptr=dptr, dep_run=drun[:ndep])
 
 
 def bcsr4_sell_plan_probe(nbrows, ptrow, indcol, nwaves_max=1024):

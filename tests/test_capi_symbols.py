@@ -28,7 +28,7 @@ def test_header_declares_a_real_api():
     syms = declared_symbols()
     assert len(syms) >= 40
     for must in ("mi_csr_create", "mi_spmv", "mi_spmv_dev", "mi_spmk", "mi_dot", "mi_axpy", "mi_orthogonalize",
-                 "mi_part_create", "mi_bcsr4_spmv"):
+                 "mi_part_create", "mi_bcsr4_spmv", "mi_spmk_plan_probe", "mi_spmk_plan_dump"):
         assert must in syms
 
 
