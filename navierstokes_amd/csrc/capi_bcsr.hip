@@ -178,21 +178,27 @@ static int sell_fill(mi_bcsr4_t A, hipStream_t s)
     return MI_OK;
 }
 
+// fn(CAP, grid) for a refresh kernel: the slice capacity it is compiled for, by the handle's largest slice, and its grid.
+// 4096: 32 KB of LDS, four workgroups per CU (the FE rows of 56-60: 3 584-3 840 values per slice); 0: no LDS staging
+template <class Fn>
+static void by_slice_cap(const mi_bcsr4_s* A, int nslices, Fn&& fn)
+{
+    const int grid = std::max(1, std::min(nslices, 2048));
+    const int cap = A->max_slice_vals <= 4096 ? 4096 : (A->max_slice_vals <= 16384 ? 16384 : 0);
+    pick_int<4096, 16384, 0>(cap, [&](auto CAP) { fn(CAP, (unsigned)(CAP() == 16384 ? std::min(grid, 256) : grid)); });
+}
+
 // the blocked copy of a CSR handle from that handle's (new) CSR values, d_src — and, when d_csr_out is given, the handle's CSR value
 // array — in one pass (bcsr4_refresh_kernel); every copy the blocked kernels read is current when this returns (in stream order)
 int bcsr4_refresh_from_csr(mi_bcsr4_s* A, const int* d_csr_ptrow, const double* d_src, double* d_csr_out, hipStream_t s)
 {
     if (!A || A->nbrows == 0) return MI_OK;
     const int nslices = (A->nbrows + kSellRows - 1) / kSellRows;
-    const int grid = std::max(1, std::min(nslices, 2048));
     const int* sptr = A->sell.val ? A->sell.sptr : nullptr;
     double* sv = A->sell.val;
-    if (A->max_slice_vals <= 4096) // 32 KB of LDS: four workgroups per CU (the FE rows of 56-60: 3 584-3 840 values per slice)
-        hipLaunchKernelGGL((bcsr4_refresh_kernel<4096>), dim3((unsigned)grid), dim3(256), 0, s, nslices, A->nbrows, d_csr_ptrow, d_src, d_csr_out, A->d_ptrow, A->d_coef, sptr, sv);
-    else if (A->max_slice_vals <= 16384)
-        hipLaunchKernelGGL((bcsr4_refresh_kernel<16384>), dim3((unsigned)std::min(grid, 256)), dim3(256), 0, s, nslices, A->nbrows, d_csr_ptrow, d_src, d_csr_out, A->d_ptrow, A->d_coef, sptr, sv);
-    else
-        hipLaunchKernelGGL((bcsr4_refresh_kernel<0>), dim3((unsigned)grid), dim3(256), 0, s, nslices, A->nbrows, d_csr_ptrow, d_src, d_csr_out, A->d_ptrow, A->d_coef, sptr, sv);
+    by_slice_cap(A, nslices, [&](auto CAP, unsigned grid) {
+        hipLaunchKernelGGL((bcsr4_refresh_kernel<CAP()>), dim3(grid), dim3(256), 0, s, nslices, A->nbrows, d_csr_ptrow, d_src, d_csr_out, A->d_ptrow, A->d_coef, sptr, sv);
+    });
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -202,16 +208,15 @@ static int bcsr4_refresh_from_blocks(mi_bcsr4_s* A, const double* d_src, bool co
 {
     if (!A || A->nbrows == 0 || A->nblocks == 0) return MI_OK;
     const int nslices = (A->nbrows + kSellRows - 1) / kSellRows;
-    const int grid = std::max(1, std::min(nslices, 2048));
     const int* sptr = A->sell.val ? A->sell.sptr : nullptr;
     double* out = d_src == A->d_coef ? nullptr : A->d_coef;
     if (colmajor && !out) return fail(MI_ERR_ARG, "column-major blocks cannot be transposed in place");
     if (!out && !A->sell.val) return MI_OK;
-#define BR_LAUNCH(CAP_, CM_, G_) hipLaunchKernelGGL((bcsr4_blocks_refresh_kernel<CAP_, CM_>), dim3((unsigned)(G_)), dim3(256), 0, s, nslices, A->nbrows, A->d_ptrow, d_src, out, sptr, A->sell.val)
-    if (A->max_slice_vals <= 4096) { if (colmajor) BR_LAUNCH(4096, true, grid); else BR_LAUNCH(4096, false, grid); }
-    else if (A->max_slice_vals <= 16384) { if (colmajor) BR_LAUNCH(16384, true, std::min(grid, 256)); else BR_LAUNCH(16384, false, std::min(grid, 256)); }
-    else { if (colmajor) BR_LAUNCH(0, true, grid); else BR_LAUNCH(0, false, grid); }
-#undef BR_LAUNCH
+    by_slice_cap(A, nslices, [&](auto CAP, unsigned grid) {
+        pick([&](auto CM) {
+            hipLaunchKernelGGL((bcsr4_blocks_refresh_kernel<CAP(), CM()>), dim3(grid), dim3(256), 0, s, nslices, A->nbrows, A->d_ptrow, d_src, out, sptr, A->sell.val);
+        }, colmajor);
+    });
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -356,12 +361,10 @@ int launch_bcsr4(mi_bcsr4_t A, const double* d_x, double* d_y, mi_stream_t s, bo
         const bool two = A->sell_form == 2;
         SellView S{A->sell.val, A->sell.col, A->sell.sptr, two ? A->sell.wrng2 : A->sell.wrng, A->sell_nslices, A->nbrows, V.browmap};
         const int swg = two ? A->sell_nwaves2 / 8 : A->sell_nwaves / 4;
-        switch (A->sell_form) {
-        case 0: hipLaunchKernelGGL((spmv_bcsr4_sell<8, true, 0, 2, 4>), dim3((unsigned)swg), dim3(256), 0, (hipStream_t)s, S, d_x, d_y, swg); break;
-        case 1: hipLaunchKernelGGL((spmv_bcsr4_sell<8, false, 0, 2, 4>), dim3((unsigned)swg), dim3(256), 0, (hipStream_t)s, S, d_x, d_y, swg); break;
-        case 2: hipLaunchKernelGGL((spmv_bcsr4_sell<4, true, 0, 2, 8>), dim3((unsigned)swg), dim3(512), 0, (hipStream_t)s, S, d_x, d_y, swg); break;
-        default: hipLaunchKernelGGL((spmv_bcsr4_sell<12, true, 0, 2, 4>), dim3((unsigned)swg), dim3(256), 0, (hipStream_t)s, S, d_x, d_y, swg); break;
-        }
+        pick_int<0, 1, 2, 3>(A->sell_form, [&](auto F) {
+            constexpr int DEPTH = F() == 2 ? 4 : (F() == 3 ? 12 : 8), WAVES = F() == 2 ? 8 : 4;
+            hipLaunchKernelGGL((spmv_bcsr4_sell<DEPTH, F() != 1, 0, 2, WAVES>), dim3((unsigned)swg), dim3(64 * WAVES), 0, (hipStream_t)s, S, d_x, d_y, swg);
+        });
         HIP_TRY(hipGetLastError());
         return MI_OK;
     }
@@ -459,30 +462,14 @@ static void launch_spmm_s(const Bcsr4View& V, int arith, const double* X, long l
         // measured on the FE matrix (bench.py fe_spmm4 / fe_spmm8, MI355_SPMM_DEPTH): 4 columns 254 / 168 / 168 / 173 us at depth 1 / 2 / 3 / 4
         // (registers cost occupancy: 7 / 5 / 4 / 3 waves per SIMD), 8 columns 223 / 232 / 237 us at depth 1 / 2 / 3
         const int depth = depth_env >= 1 && depth_env <= 4 ? depth_env : (S == 4 ? 2 : 1);
-#define MI_SPMM_QUAD(PD)                                                                                                               \
-    do {                                                                                                                               \
-        if (xcd) {                                                                                                                     \
-            if (arith == MI_ARITH_BLOCKACC) hipLaunchKernelGGL((spmm_bcsr4_quad<SQ, 1, true, PD>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg); \
-            else hipLaunchKernelGGL((spmm_bcsr4_quad<SQ, 0, true, PD>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg);                    \
-        } else {                                                                                                                       \
-            if (arith == MI_ARITH_BLOCKACC) hipLaunchKernelGGL((spmm_bcsr4_quad<SQ, 1, false, PD>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg); \
-            else hipLaunchKernelGGL((spmm_bcsr4_quad<SQ, 0, false, PD>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg);                   \
-        }                                                                                                                              \
-    } while (0)
-        if (depth == 1) MI_SPMM_QUAD(1);
-        else if (depth == 2) MI_SPMM_QUAD(2);
-        else if (depth == 3) MI_SPMM_QUAD(3);
-        else MI_SPMM_QUAD(4);
-#undef MI_SPMM_QUAD
+        pick_int<1, 2, 3, 4>(depth, [&](auto PD) {
+            pick([&](auto BA, auto XCD) { hipLaunchKernelGGL((spmm_bcsr4_quad<SQ, BA() ? 1 : 0, XCD(), PD()>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg); },
+                 arith == MI_ARITH_BLOCKACC, xcd);
+        });
         return;
     }
-    if (xcd) {
-        if (arith == MI_ARITH_BLOCKACC) hipLaunchKernelGGL((spmm_bcsr4<S, 1, PF, true>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg);
-        else hipLaunchKernelGGL((spmm_bcsr4<S, 0, PF, true>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg);
-    } else {
-        if (arith == MI_ARITH_BLOCKACC) hipLaunchKernelGGL((spmm_bcsr4<S, 1, PF, false>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg);
-        else hipLaunchKernelGGL((spmm_bcsr4<S, 0, PF, false>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg);
-    }
+    pick([&](auto BA, auto XCD) { hipLaunchKernelGGL((spmm_bcsr4<S, BA() ? 1 : 0, PF, XCD()>), grid, block, 0, s, V, X, ldx, Y, ldy, nwg); },
+         arith == MI_ARITH_BLOCKACC, xcd);
 }
 
 // ---- the tile form (spmm_tile.hpp) ------------------------------------------------------------------------------------------
@@ -588,16 +575,7 @@ static bool spmm_form_possible(const mi_bcsr4_s* A, int s, int form, bool mapped
 
 static void launch_spmm_gather(const Bcsr4View& V, int m, int arith, const double* Xj, long long ldx, double* Yj, long long ldy, hipStream_t st)
 {
-    switch (m) {
-    case 1: launch_spmm_s<1>(V, arith, Xj, ldx, Yj, ldy, st); break;
-    case 2: launch_spmm_s<2>(V, arith, Xj, ldx, Yj, ldy, st); break;
-    case 3: launch_spmm_s<3>(V, arith, Xj, ldx, Yj, ldy, st); break;
-    case 4: launch_spmm_s<4>(V, arith, Xj, ldx, Yj, ldy, st); break;
-    case 5: launch_spmm_s<5>(V, arith, Xj, ldx, Yj, ldy, st); break;
-    case 6: launch_spmm_s<6>(V, arith, Xj, ldx, Yj, ldy, st); break;
-    case 7: launch_spmm_s<7>(V, arith, Xj, ldx, Yj, ldy, st); break;
-    default: launch_spmm_s<8>(V, arith, Xj, ldx, Yj, ldy, st); break;
-    }
+    pick_int<1, 2, 3, 4, 5, 6, 7, 8>(m, [&](auto S) { launch_spmm_s<S()>(V, arith, Xj, ldx, Yj, ldy, st); });
 }
 
 static int launch_spmm(mi_bcsr4_t A, int s, int arith, const double* X, long long ldx, double* Y, long long ldy, hipStream_t st,
@@ -616,13 +594,10 @@ static int launch_spmm(mi_bcsr4_t A, int s, int arith, const double* X, long lon
             if (form == kSpmmSell) {
                 SellView Sv{A->sell.val, A->sell.col, A->sell.sptr, A->sell.wrng, A->sell_nslices, A->nbrows, V.browmap};
                 const int swg = A->sell_nwaves / 4;
-                if (m == 4) {
-                    if (arith == MI_ARITH_CHAIN) hipLaunchKernelGGL((spmm_bcsr4_sell<4, 0, 6, true>), dim3((unsigned)swg), dim3(256), 0, st, Sv, Xj, ldx, Yj, ldy, swg);
-                    else hipLaunchKernelGGL((spmm_bcsr4_sell<4, 1, 6, true>), dim3((unsigned)swg), dim3(256), 0, st, Sv, Xj, ldx, Yj, ldy, swg);
-                } else {
-                    if (arith == MI_ARITH_CHAIN) hipLaunchKernelGGL((spmm_bcsr4_sell<8, 0, 6, true>), dim3((unsigned)swg), dim3(256), 0, st, Sv, Xj, ldx, Yj, ldy, swg);
-                    else hipLaunchKernelGGL((spmm_bcsr4_sell<8, 1, 6, true>), dim3((unsigned)swg), dim3(256), 0, st, Sv, Xj, ldx, Yj, ldy, swg);
-                }
+                pick_int<4, 8>(m, [&](auto M) {
+                    pick([&](auto CHAIN) { hipLaunchKernelGGL((spmm_bcsr4_sell<M(), CHAIN() ? 0 : 1, 6, true>), dim3((unsigned)swg), dim3(256), 0, st, Sv, Xj, ldx, Yj, ldy, swg); },
+                         arith == MI_ARITH_CHAIN);
+                });
                 return hipGetLastError();
             }
             if (form == kSpmmTile) return spmm_tile_launch(A, spmm_plan_of(A, m), V, m, arith, Xj, ldx, Yj, ldy, st);
@@ -780,8 +755,7 @@ extern "C" int mi_krylov_basis_dev(mi_csr_t A, int s, const double* d_v0, double
     CHECK_ARG(!orth || d_coef, "null coefficient array");
     hipStream_t st = (hipStream_t)st_;
     const int n = A->n;
-    int grid = (n + 255) / 256;
-    if (grid > 2048) grid = 2048;
+    const int grid = launch_grid(n, 256, 2048);
     int rc;
     if (d_V != d_v0) HIP_TRY(hipMemcpyAsync(d_V, d_v0, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
     if (orth) {
@@ -821,8 +795,7 @@ extern "C" int mi_krylov_basis_cgs_dev(mi_csr_t A, int s, const double* d_v0, do
     CHECK_ARG(d_v0 && d_V && d_coef && ldv >= A->n, "bad argument");
     hipStream_t st = (hipStream_t)st_;
     const int n = A->n;
-    int grid = (n + 255) / 256;
-    if (grid > 2048) grid = 2048;
+    const int grid = launch_grid(n, 256, 2048);
     int rc;
     if (d_V != d_v0) HIP_TRY(hipMemcpyAsync(d_V, d_v0, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
     double* nrm0 = d_coef + (size_t)s * (s + 2);

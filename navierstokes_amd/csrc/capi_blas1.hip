@@ -59,8 +59,7 @@ static int reduce_dev(int n, const double* a, const double* b, double* d_out, hi
     if (rc) return rc;
     int np, seg;
     red_geometry(n, &np, &seg);
-    if (blas1_nt(n)) hipLaunchKernelGGL((reduce_stage1<MODE, true>), dim3(np), dim3(kRedWG), 0, s, n, seg, a, b, ws, ws + kMaxPartials);
-    else hipLaunchKernelGGL((reduce_stage1<MODE, false>), dim3(np), dim3(kRedWG), 0, s, n, seg, a, b, ws, ws + kMaxPartials);
+    pick([&](auto NT) { hipLaunchKernelGGL((reduce_stage1<MODE, NT()>), dim3(np), dim3(kRedWG), 0, s, n, seg, a, b, ws, ws + kMaxPartials); }, blas1_nt(n));
     hipLaunchKernelGGL((reduce_stage2<FIN>), dim3(1), dim3(kRedWG), 0, s, np, ws, ws + kMaxPartials, d_out);
     HIP_TRY(hipGetLastError());
     return MI_OK;
@@ -90,8 +89,7 @@ int residual_norm_dev(int n, const double* d_b, const double* d_w, double* d_r, 
     if (rc) return rc;
     int np, seg;
     red_geometry(n, &np, &seg);
-    if (blas1_nt(n)) hipLaunchKernelGGL((gmres_residual<true>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_b, d_w, d_r, ws);
-    else hipLaunchKernelGGL((gmres_residual<false>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_b, d_w, d_r, ws);
+    pick([&](auto NT) { hipLaunchKernelGGL((gmres_residual<NT()>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_b, d_w, d_r, ws); }, blas1_nt(n));
     hipLaunchKernelGGL((reduce_stage2<1>), dim3(1), dim3(kRedWG), 0, s, np, ws, ws + kMaxPartials, d_out);
     HIP_TRY(hipGetLastError());
     return MI_OK;
@@ -102,10 +100,7 @@ extern "C" int mi_axpy_dev(int n, double a, const double* d_x, double* d_y, mi_s
     CHECK_ARG(n >= 0, "negative n");
     CHECK_ARG(n == 0 || (d_x && d_y), "null vector");
     if (n == 0) return MI_OK;
-    int grid = (n / 2 + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(axpy_kernel, dim3(grid), dim3(256), 0, (hipStream_t)s, n, a, d_x, d_y);
+    hipLaunchKernelGGL(axpy_kernel, dim3(launch_grid(n / 2, 256, 2048, 1)), dim3(256), 0, (hipStream_t)s, n, a, d_x, d_y);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -124,15 +119,11 @@ extern "C" int mi_orthogonalize_dev(int n, const double* d_b, const double* d_x1
     if (rc) return rc;
     int np, seg;
     red_geometry(n, &np, &seg);
-    int grid = (n + kRedWG - 1) / kRedWG;
-    if (grid > 2048) grid = 2048;
-    if (blas1_nt(n)) {
-        hipLaunchKernelGGL((reduce_stage1<0, true>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_b, d_x1, ws, ws + kMaxPartials);
-        hipLaunchKernelGGL(ortho_update_kernel<true>, dim3(grid), dim3(kRedWG), 0, s, n, alpha, np, ws, d_beta_out, d_b, d_x1, d_x3);
-    } else {
-        hipLaunchKernelGGL((reduce_stage1<0, false>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_b, d_x1, ws, ws + kMaxPartials);
-        hipLaunchKernelGGL(ortho_update_kernel<false>, dim3(grid), dim3(kRedWG), 0, s, n, alpha, np, ws, d_beta_out, d_b, d_x1, d_x3);
-    }
+    const int grid = launch_grid(n, kRedWG, 2048);
+    pick([&](auto NT) {
+        hipLaunchKernelGGL((reduce_stage1<0, NT()>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_b, d_x1, ws, ws + kMaxPartials);
+        hipLaunchKernelGGL(ortho_update_kernel<NT()>, dim3(grid), dim3(kRedWG), 0, s, n, alpha, np, ws, d_beta_out, d_b, d_x1, d_x3);
+    }, blas1_nt(n));
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -143,10 +134,8 @@ int ortho_update_from_parts(int n, int nparts, const double* parts, double alpha
 {
     CHECK_ARG(n >= 0 && nparts >= 1 && nparts <= 64 && parts, "bad argument");
     CHECK_ARG(n == 0 || (d_b && d_x1 && d_x3), "null vector");
-    int grid = (n + kRedWG - 1) / kRedWG;
-    grid = grid < 1 ? 1 : (grid > 2048 ? 2048 : grid);
-    if (blas1_nt(n)) hipLaunchKernelGGL(ortho_update_ranks_kernel<true>, dim3(grid), dim3(kRedWG), 0, s, n, alpha, nparts, parts, d_beta_out, d_b, d_x1, d_x3);
-    else hipLaunchKernelGGL(ortho_update_ranks_kernel<false>, dim3(grid), dim3(kRedWG), 0, s, n, alpha, nparts, parts, d_beta_out, d_b, d_x1, d_x3);
+    const int grid = launch_grid(n, kRedWG, 2048, 1);
+    pick([&](auto NT) { hipLaunchKernelGGL(ortho_update_ranks_kernel<NT()>, dim3(grid), dim3(kRedWG), 0, s, n, alpha, nparts, parts, d_beta_out, d_b, d_x1, d_x3); }, blas1_nt(n));
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -166,8 +155,7 @@ static int spmv_with_dot_partials(mi_csr_t A, const double* d_x, double* d_y, co
     if ((rc = launch_spmv(A, d_x, d_y, s))) return rc;
     int seg;
     red_geometry(A->n, np, &seg);
-    if (blas1_nt(A->n)) hipLaunchKernelGGL((reduce_stage1<0, true>), dim3(*np), dim3(kRedWG), 0, s, A->n, seg, d_b, d_y, ws, ws + kMaxPartials);
-    else hipLaunchKernelGGL((reduce_stage1<0, false>), dim3(*np), dim3(kRedWG), 0, s, A->n, seg, d_b, d_y, ws, ws + kMaxPartials);
+    pick([&](auto NT) { hipLaunchKernelGGL((reduce_stage1<0, NT()>), dim3(*np), dim3(kRedWG), 0, s, A->n, seg, d_b, d_y, ws, ws + kMaxPartials); }, blas1_nt(A->n));
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -251,10 +239,8 @@ extern "C" int mi_spmv_orthogonalize_dev(mi_csr_t A, const double* d_x, double* 
     int rc = get_ws(s, &ws), np = 0;
     if (rc) return rc;
     if ((rc = spmv_with_dot_partials(A, d_x, d_x1, d_b, s, ws, &np))) return rc;
-    int grid = (n + kRedWG - 1) / kRedWG;
-    if (grid > 2048) grid = 2048;
-    if (blas1_nt(n)) hipLaunchKernelGGL(ortho_update_kernel<true>, dim3(grid), dim3(kRedWG), 0, s, n, alpha, np, ws, d_beta_out, d_b, d_x1, d_x3);
-    else hipLaunchKernelGGL(ortho_update_kernel<false>, dim3(grid), dim3(kRedWG), 0, s, n, alpha, np, ws, d_beta_out, d_b, d_x1, d_x3);
+    const int grid = launch_grid(n, kRedWG, 2048);
+    pick([&](auto NT) { hipLaunchKernelGGL(ortho_update_kernel<NT()>, dim3(grid), dim3(kRedWG), 0, s, n, alpha, np, ws, d_beta_out, d_b, d_x1, d_x3); }, blas1_nt(n));
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -278,15 +264,14 @@ extern "C" int mi_orthonormalize_against_basis_dev(int n, int m, const double* c
     int np, seg;
     red_geometry(n, &np, &seg);
     double* part[2] = {ws, ws + kMaxPartials};
-    const bool nt = blas1_nt(n);
     // dot of the first vector, then one launch per vector: finish dot j, update y, partials of dot j+1
-    if (nt) hipLaunchKernelGGL((reduce_stage1<0, true>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_y, d_basis[0], part[0], part[1]);
-    else hipLaunchKernelGGL((reduce_stage1<0, false>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_y, d_basis[0], part[0], part[1]);
-    for (int j = 0; j < m; j++) {
-        const double* vn = j + 1 < m ? d_basis[j + 1] : nullptr;
-        if (nt) hipLaunchKernelGGL(mgs_step_kernel<true>, dim3(np), dim3(kRedWG), 0, s, n, seg, np, part[j & 1], d_dots + j, d_basis[j], vn, d_y, part[(j + 1) & 1]);
-        else hipLaunchKernelGGL(mgs_step_kernel<false>, dim3(np), dim3(kRedWG), 0, s, n, seg, np, part[j & 1], d_dots + j, d_basis[j], vn, d_y, part[(j + 1) & 1]);
-    }
+    pick([&](auto NT) {
+        hipLaunchKernelGGL((reduce_stage1<0, NT()>), dim3(np), dim3(kRedWG), 0, s, n, seg, d_y, d_basis[0], part[0], part[1]);
+        for (int j = 0; j < m; j++) {
+            const double* vn = j + 1 < m ? d_basis[j + 1] : nullptr;
+            hipLaunchKernelGGL(mgs_step_kernel<NT()>, dim3(np), dim3(kRedWG), 0, s, n, seg, np, part[j & 1], d_dots + j, d_basis[j], vn, d_y, part[(j + 1) & 1]);
+        }
+    }, blas1_nt(n));
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -319,8 +304,13 @@ static int mdot_tile_f32()
     }();
     return t;
 }
-static int multi_tile(const double*) { return mdot_tile(); }
-static int multi_tile(const float*) { return mdot_tile_f32(); }
+// fn(TILE) with the compiled tile of a basis of T: {4, 8, 16} for doubles, {8, 16} for floats (tile 4 is not instantiated for them)
+template <typename T, class Fn>
+static void with_multi_tile(Fn&& fn)
+{
+    if constexpr (sizeof(T) == 8) pick_int<4, 16, 8>(mdot_tile(), fn);
+    else pick_int<16, 8>(mdot_tile_f32(), fn);
+}
 
 // the argument rules shared by mi_mdot_dev / mi_maxpy_dev / mi_cgs_dev and their float-basis twins; nothing here touches the device
 template <typename T>
@@ -339,14 +329,6 @@ static int multi_check(int n, int m, const T* const* basis, const double* y)
     return MI_OK;
 }
 
-template <int TILE, typename T>
-static void mdot_launch(int n, int seg, int np, int m, const double* y, const MultiVecT<T>& B, double* part, bool nt, hipStream_t s)
-{
-    const dim3 grid(np, (m + TILE - 1) / TILE);
-    if (nt) hipLaunchKernelGGL((mdot_stage1<TILE, true, T>), grid, dim3(kRedWG), 0, s, n, seg, m, y, B, part);
-    else hipLaunchKernelGGL((mdot_stage1<TILE, false, T>), grid, dim3(kRedWG), 0, s, n, seg, m, y, B, part);
-}
-
 // dots[j] = y . v_j (and accum[j] += dots[j] when accum is given); n > 0, m > 0, arguments checked
 template <typename T>
 static int mdot_run(int n, int m, const MultiVecT<T>& B, const double* y, double* d_dots, double* d_accum, double* ws, hipStream_t s)
@@ -354,30 +336,13 @@ static int mdot_run(int n, int m, const MultiVecT<T>& B, const double* y, double
     int np, seg;
     red_geometry(n, &np, &seg);
     const bool nt = blas1_nt(n);
-    switch (multi_tile(B.v[0])) {
-    case 4:
-        if constexpr (sizeof(T) == 8) mdot_launch<4, T>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); // (never chosen for a float basis)
-        break;
-    case 16: mdot_launch<16, T>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
-    default: mdot_launch<8, T>(n, seg, np, m, y, B, ws + kWsMdot, nt, s); break;
-    }
+    with_multi_tile<T>([&](auto TILE) {
+        const dim3 grid(np, (m + TILE() - 1) / TILE());
+        pick([&](auto NT) { hipLaunchKernelGGL((mdot_stage1<TILE(), NT(), T>), grid, dim3(kRedWG), 0, s, n, seg, m, y, B, ws + kWsMdot); }, nt);
+    });
     hipLaunchKernelGGL(mdot_stage2, dim3(m), dim3(kRedWG), 0, s, np, ws + kWsMdot, d_dots, d_accum);
     HIP_TRY(hipGetLastError());
     return MI_OK;
-}
-
-template <int TILE, typename T>
-static void maxpy_launch(int n, int seg, int np, int m, const double* coef, int negate, const MultiVecT<T>& B, double* y, double* part,
-                         bool norm, bool nt, hipStream_t s)
-{
-    for (int first = 0; first < m; first += TILE) { // one chunk per launch: each continues the chain from the stored y
-        const int cnt = std::min(TILE, m - first);
-        const bool last = norm && first + TILE >= m;
-        if (nt && last) hipLaunchKernelGGL((maxpy_kernel<TILE, true, true, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
-        else if (nt) hipLaunchKernelGGL((maxpy_kernel<TILE, true, false, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
-        else if (last) hipLaunchKernelGGL((maxpy_kernel<TILE, false, true, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
-        else hipLaunchKernelGGL((maxpy_kernel<TILE, false, false, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, coef, negate, B, y, part);
-    }
 }
 
 // y <- y + sum a_j v_j and, when d_norm_out is given, the norm of the new y from the last chunk's partials; n > 0, m > 0
@@ -388,13 +353,14 @@ static int maxpy_run(int n, int m, const double* d_coef, int negate, const Multi
     int np, seg;
     red_geometry(n, &np, &seg);
     const bool nt = blas1_nt(n), norm = d_norm_out != nullptr;
-    switch (multi_tile(B.v[0])) {
-    case 4:
-        if constexpr (sizeof(T) == 8) maxpy_launch<4, T>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s);
-        break;
-    case 16: maxpy_launch<16, T>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
-    default: maxpy_launch<8, T>(n, seg, np, m, d_coef, negate, B, y, ws, norm, nt, s); break;
-    }
+    with_multi_tile<T>([&](auto TILE) {
+        for (int first = 0; first < m; first += TILE()) { // one chunk per launch: each continues the chain from the stored y
+            const int cnt = std::min(TILE(), m - first);
+            pick([&](auto NT, auto LAST) {
+                hipLaunchKernelGGL((maxpy_kernel<TILE(), NT(), LAST(), T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, cnt, d_coef, negate, B, y, ws);
+            }, nt, norm && first + TILE() >= m);
+        }
+    });
     if (norm) hipLaunchKernelGGL((reduce_stage2<1>), dim3(1), dim3(kRedWG), 0, s, np, ws, ws + kMaxPartials, d_norm_out);
     HIP_TRY(hipGetLastError());
     return MI_OK;
@@ -440,16 +406,6 @@ static int maxpy_dev(int n, int m, const double* d_coef, int negate, const T* co
     return maxpy_run(n, m, d_coef, negate, multi_vec(m, d_basis), d_y, d_norm_out, ws, s);
 }
 
-template <int TILE, typename T>
-static void maxpy_upto_launch(int n, int seg, int np, int m, const int* count, const double* coef, int negate, const MultiVecT<T>& B, double* y,
-                              bool nt, hipStream_t s)
-{
-    for (int first = 0; first < m; first += TILE) { // every chunk of the m vectors, whatever the count will be: the kernel decides
-        if (nt) hipLaunchKernelGGL((maxpy_upto_kernel<TILE, true, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, m, count, coef, negate, B, y);
-        else hipLaunchKernelGGL((maxpy_upto_kernel<TILE, false, T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, m, count, coef, negate, B, y);
-    }
-}
-
 // mi_maxpy_upto_dev and its float-basis twin: mi_maxpy*_dev's geometry and tile, the count read by the kernels
 template <typename T>
 static int maxpy_upto_dev(int n, int m, const int* d_count, const double* d_coef, int negate, const T* const* d_basis, double* d_y, mi_stream_t s_)
@@ -466,13 +422,10 @@ static int maxpy_upto_dev(int n, int m, const int* d_count, const double* d_coef
     red_geometry(n, &np, &seg);
     const bool nt = blas1_nt(n);
     const MultiVecT<T> B = multi_vec(m, d_basis);
-    switch (multi_tile(B.v[0])) {
-    case 4:
-        if constexpr (sizeof(T) == 8) maxpy_upto_launch<4, T>(n, seg, np, m, d_count, d_coef, negate, B, d_y, nt, s);
-        break;
-    case 16: maxpy_upto_launch<16, T>(n, seg, np, m, d_count, d_coef, negate, B, d_y, nt, s); break;
-    default: maxpy_upto_launch<8, T>(n, seg, np, m, d_count, d_coef, negate, B, d_y, nt, s); break;
-    }
+    with_multi_tile<T>([&](auto TILE) {
+        for (int first = 0; first < m; first += TILE()) // every chunk of the m vectors, whatever the count will be: the kernel decides
+            pick([&](auto NT) { hipLaunchKernelGGL((maxpy_upto_kernel<TILE(), NT(), T>), dim3(np), dim3(kRedWG), 0, s, n, seg, first, m, d_count, d_coef, negate, B, d_y); }, nt);
+    });
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -557,10 +510,8 @@ extern "C" int mi_round_f32_dev(int n, const double* d_x, const double* d_div, f
     CHECK_ARG((const void*)d_out32 != (const void*)d_x && (const void*)d_out32 != (const void*)d_out64, "out32 is one of the double vectors");
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev)); // (MI_ERR_NODEVICE without a GPU, like the entry points that need the workspace)
-    int grid = (n / 2 + 255) / 256;
-    grid = grid < 1 ? 1 : (grid > 2048 ? 2048 : grid);
-    if (d_div) hipLaunchKernelGGL(round_f32_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)s, n, d_x, d_div, d_out32, d_out64);
-    else hipLaunchKernelGGL(round_f32_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)s, n, d_x, d_div, d_out32, d_out64);
+    const int grid = launch_grid(n / 2, 256, 2048, 1);
+    pick([&](auto DIV) { hipLaunchKernelGGL(round_f32_kernel<DIV()>, dim3(grid), dim3(256), 0, (hipStream_t)s, n, d_x, d_div, d_out32, d_out64); }, d_div != nullptr);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -570,9 +521,7 @@ extern "C" int mi_gather_dev(int m, const int* d_idx, const double* d_src, doubl
     CHECK_ARG(m >= 0, "negative m");
     if (m == 0) return MI_OK;
     CHECK_ARG(d_idx && d_src && d_dst, "null pointer");
-    int grid = (m + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(256), 0, (hipStream_t)s, m, d_idx, d_src, d_dst);
+    hipLaunchKernelGGL(gather_kernel, dim3(launch_grid(m, 256, 2048)), dim3(256), 0, (hipStream_t)s, m, d_idx, d_src, d_dst);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -717,9 +666,7 @@ int gather_perm(mi_csr_t A, const double* d_x, double* d_xp, hipStream_t s)
 {
     if (A->reorder_block == 4 && (((uintptr_t)d_x | (uintptr_t)d_xp) & 15) == 0) {
         const int nn = A->n / 4;
-        int grid = (nn + 255) / 256;
-        if (grid > 4096) grid = 4096;
-        hipLaunchKernelGGL(gather_nodes_kernel, dim3(grid), dim3(256), 0, s, nn, A->d_iperm, d_x, d_xp);
+        hipLaunchKernelGGL(gather_nodes_kernel, dim3(launch_grid(nn, 256, 4096)), dim3(256), 0, s, nn, A->d_iperm, d_x, d_xp);
         HIP_TRY(hipGetLastError());
         return MI_OK;
     }
@@ -738,9 +685,7 @@ __global__ __launch_bounds__(256) void scatter_kernel(int m, const int* __restri
 // a vector in a reordered handle's numbering back into the caller's: dst[iperm[r']] = src[r']
 int scatter_perm(mi_csr_t A, const double* d_src, double* d_dst, hipStream_t s)
 {
-    int grid = (A->n + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(scatter_kernel, dim3(grid), dim3(256), 0, s, A->n, A->d_iperm, d_src, d_dst);
+    hipLaunchKernelGGL(scatter_kernel, dim3(launch_grid(A->n, 256, 2048)), dim3(256), 0, s, A->n, A->d_iperm, d_src, d_dst);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }

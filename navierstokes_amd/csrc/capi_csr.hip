@@ -105,32 +105,15 @@ int launch_sstream(mi_csr_t A, const double* d_x, double* d_y, const int* rowmap
     if (T.mw) {
         if (comm) return fail(MI_ERR_STATE, "the cut-ring sliced stream has no fused multi-GPU form");
         SsMwView V{S, T.dev.winK};
-        if (T.deep) {
-            if (T.nt) hipLaunchKernelGGL((spmv_sstream_mw<12, true>), dim3((unsigned)T.nwg), dim3(256), 0, s, V, d_x, yy);
-            else hipLaunchKernelGGL((spmv_sstream_mw<12, false>), dim3((unsigned)T.nwg), dim3(256), 0, s, V, d_x, yy);
-        } else {
-            if (T.nt) hipLaunchKernelGGL((spmv_sstream_mw<8, true>), dim3((unsigned)T.nwg), dim3(256), 0, s, V, d_x, yy);
-            else hipLaunchKernelGGL((spmv_sstream_mw<8, false>), dim3((unsigned)T.nwg), dim3(256), 0, s, V, d_x, yy);
-        }
+        pick([&](auto DEEP, auto NT) { hipLaunchKernelGGL((spmv_sstream_mw<DEEP() ? 12 : 8, NT()>), dim3((unsigned)T.nwg), dim3(256), 0, s, V, d_x, yy); }, T.deep, T.nt);
         HIP_TRY(hipGetLastError());
         return MI_OK;
     }
-    if (comm) {
-        const unsigned grid = (unsigned)(T.nwg + comm->push_wgs);
-        if (T.deep) {
-            if (T.nt) hipLaunchKernelGGL((spmv_sstream_fused<12, true>), dim3(grid), dim3(256), 0, s, S, d_x, yy, *comm);
-            else hipLaunchKernelGGL((spmv_sstream_fused<12, false>), dim3(grid), dim3(256), 0, s, S, d_x, yy, *comm);
-        } else {
-            if (T.nt) hipLaunchKernelGGL((spmv_sstream_fused<8, true>), dim3(grid), dim3(256), 0, s, S, d_x, yy, *comm);
-            else hipLaunchKernelGGL((spmv_sstream_fused<8, false>), dim3(grid), dim3(256), 0, s, S, d_x, yy, *comm);
-        }
-    } else if (T.deep) {
-        if (T.nt) hipLaunchKernelGGL((spmv_sstream<12, true>), dim3((unsigned)T.nwg), dim3(256), 0, s, S, d_x, yy);
-        else hipLaunchKernelGGL((spmv_sstream<12, false>), dim3((unsigned)T.nwg), dim3(256), 0, s, S, d_x, yy);
-    } else {
-        if (T.nt) hipLaunchKernelGGL((spmv_sstream<8, true>), dim3((unsigned)T.nwg), dim3(256), 0, s, S, d_x, yy);
-        else hipLaunchKernelGGL((spmv_sstream<8, false>), dim3((unsigned)T.nwg), dim3(256), 0, s, S, d_x, yy);
-    }
+    pick([&](auto DEEP, auto NT) {
+        constexpr int DEPTH = DEEP() ? 12 : 8;
+        if (comm) hipLaunchKernelGGL((spmv_sstream_fused<DEPTH, NT()>), dim3((unsigned)(T.nwg + comm->push_wgs)), dim3(256), 0, s, S, d_x, yy, *comm);
+        else hipLaunchKernelGGL((spmv_sstream<DEPTH, NT()>), dim3((unsigned)T.nwg), dim3(256), 0, s, S, d_x, yy);
+    }, T.deep, T.nt);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -1011,7 +994,7 @@ extern "C" int mi_csr_update_values_dev(mi_csr_t A, const double* d_coef, mi_str
     hipStream_t s = (hipStream_t)s_;
     if (A->inner) {
         mi_csr_t I = A->inner;
-        hipLaunchKernelGGL(permute_values_kernel, dim3((unsigned)std::max(1, std::min((A->n + 63) / 64, 4096))), dim3(256), 0, s, A->n, I->d_ptrow, A->d_src_start, d_coef, I->d_coef);
+        hipLaunchKernelGGL(permute_values_kernel, dim3(launch_grid(A->n, 64, 4096, 1)), dim3(256), 0, s, A->n, I->d_ptrow, A->d_src_start, d_coef, I->d_coef);
         HIP_TRY(hipGetLastError());
         return refresh_blocked_values(I, s);
     }

@@ -163,12 +163,6 @@ static int gmres_precond(mi_gmres_s* G, const double* in, double* out, mi_stream
     }
 }
 
-// workgroups of 256 for an elementwise kernel over `items` (gmres_update_x: n / 2 pairs)
-static int gmres_grid(int items)
-{
-    return std::min(std::max((items + 255) / 256, 1), 2048);
-}
-
 static int gmres_need_operator(const mi_gmres_s* G, const char* who)
 {
     return G->A_csr || G->A_bcsr ? MI_OK : fail(MI_ERR_STATE, std::string(who) + ": no operator set (mi_gmres_set_operator_*)");
@@ -192,7 +186,7 @@ static int gmres_enqueue_start(mi_gmres_s* G, const double* d_b, double* d_x, bo
     if (f32) {
         if ((rc = mi_round_f32_dev(n, G->z, S.beta(), G->row32(0), G->q, s))) return rc;
     } else {
-        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(gmres_grid(n)), dim3(256), 0, st, n, S.beta(), G->row(0));
+        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(launch_grid(n, 256, 2048, 1)), dim3(256), 0, st, n, S.beta(), G->row(0));
     }
     HIP_TRY(hipGetLastError());
     launches += first ? 6 : 5;
@@ -220,7 +214,7 @@ static int gmres_enqueue_step(mi_gmres_s* G, int k, double rtol, int maxiter, hi
     if (f32) {
         if ((rc = mi_round_f32_dev(G->n, w, col + k + 1, G->row32(k + 1), G->q, s))) return rc;
     } else {
-        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(gmres_grid(G->n)), dim3(256), 0, st, G->n, col + k + 1, w);
+        hipLaunchKernelGGL(div_by_scalar_kernel, dim3(launch_grid(G->n, 256, 2048, 1)), dim3(256), 0, st, G->n, col + k + 1, w);
     }
     launches += G->F ? 5 : 4;
     return MI_OK;
@@ -249,7 +243,7 @@ static int gmres_enqueue_end(mi_gmres_s* G, double* d_x, int k, hipStream_t st, 
     if (G->F) {
         if ((rc = gmres_precond(G, G->w, G->z, s))) return rc;
         if (k == kCountedOnDevice) {
-            hipLaunchKernelGGL(gmres_update_x, dim3(gmres_grid(n / 2)), dim3(256), 0, st, n, S.rec(), G->z, d_x);
+            hipLaunchKernelGGL(gmres_update_x, dim3(launch_grid(n / 2, 256, 2048, 1)), dim3(256), 0, st, n, S.rec(), G->z, d_x);
             HIP_TRY(hipGetLastError());
         } else if ((rc = mi_axpy_dev(n, 1.0, G->z, d_x, s))) {
             return rc;

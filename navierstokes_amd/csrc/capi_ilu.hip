@@ -195,7 +195,7 @@ static int bilu_move_values(mi_bilu4_s* F, bool to_device)
 template <class Fn>
 static auto bilu_by_alignment(const double* d_x, Fn&& fn)
 {
-    return (((uintptr_t)d_x) & 15) == 0 ? fn(std::true_type{}) : fn(std::false_type{});
+    return pick(fn, (((uintptr_t)d_x) & 15) == 0);
 }
 
 template <bool BWD, bool AL>
@@ -218,7 +218,6 @@ static int bilu_solve_launch(mi_bilu4_s* F, const double* d_b, double* d_x, hipS
     bilu_by_alignment(d_x, [&](auto al) {
         bilu_sweep_launch<false, decltype(al)::value>(F->sched.sweep[0], F->lev[0].view(), d_b, d_x, s);
         bilu_sweep_launch<true, decltype(al)::value>(F->sched.sweep[1], F->lev[1].view(), d_x, d_x, s);
-        return 0;
     });
     HIP_TRY(hipGetLastError());
     return MI_OK;

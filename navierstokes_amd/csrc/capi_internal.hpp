@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "dev_array.hpp"
+#include "dispatch.hpp"
 #include "partition.hpp"
 #include "push_exchange.hpp"
 #include "ring_plan.hpp"

@@ -857,16 +857,16 @@ int part_ext_launch(mi_part_s* P, const double* d_x_ext, double* d_y_local, unsi
         int rc = get_table(A, 1024, &T);
         if (rc) return rc;
         CsrView V{A->n, A->ncols, A->d_ptrow, A->d_indcol, A->d_coef, nullptr, T->d_blk, nullptr, T->nblk};
-        if (trace) hipLaunchKernelGGL((spmv_csr_fused_ext<1024, false, true>), grid, dim3(kWG), 0, s, V, d_x_ext, d_y_local, C, P->one.d_ext_order);
-        else if (A->stream_nt) hipLaunchKernelGGL((spmv_csr_fused_ext<1024, true>), grid, dim3(kWG), 0, s, V, d_x_ext, d_y_local, C, P->one.d_ext_order);
-        else hipLaunchKernelGGL((spmv_csr_fused_ext<1024, false>), grid, dim3(kWG), 0, s, V, d_x_ext, d_y_local, C, P->one.d_ext_order);
+        pick([&](auto NT, auto TRACE) { // (the traced form exists with temporal loads only)
+            hipLaunchKernelGGL((spmv_csr_fused_ext<1024, NT() && !TRACE(), TRACE()>), grid, dim3(kWG), 0, s, V, d_x_ext, d_y_local, C, P->one.d_ext_order);
+        }, A->stream_nt, trace != nullptr);
         if (split) { // the blocks that name ghosts, behind the exchange by stream order
             ExtComm C2 = C;
             C2.xwgs = C2.n_work = 0;
             C2.nowait = 1;
             const dim3 g2(P->one.n_ext_units - P->one.n_ext_plain);
-            if (A->stream_nt) hipLaunchKernelGGL((spmv_csr_fused_ext<1024, true>), g2, dim3(kWG), 0, s, V, d_x_ext, d_y_local, C2, P->one.d_ext_order + P->one.n_ext_plain);
-            else hipLaunchKernelGGL((spmv_csr_fused_ext<1024, false>), g2, dim3(kWG), 0, s, V, d_x_ext, d_y_local, C2, P->one.d_ext_order + P->one.n_ext_plain);
+            pick([&](auto NT) { hipLaunchKernelGGL((spmv_csr_fused_ext<1024, NT()>), g2, dim3(kWG), 0, s, V, d_x_ext, d_y_local, C2, P->one.d_ext_order + P->one.n_ext_plain); },
+                 A->stream_nt);
         }
         HIP_TRY(hipGetLastError());
         return MI_OK;
@@ -879,14 +879,9 @@ int part_ext_launch(mi_part_s* P, const double* d_x_ext, double* d_y_local, unsi
         return MI_OK;
     }
     static const int depth = getenv("MI355_PUSH_EXT_DEPTH") ? atoi(getenv("MI355_PUSH_EXT_DEPTH")) : 24; // (A/B: blocks in flight, 4-lane rows / 16-lane rows)
-#define EXT_LAUNCH(P_, U_) hipLaunchKernelGGL((spmv_bcsr4_fused_ext<P_, U_, kWG>), grid, dim3(kWG), 0, s, V, d_x_ext, d_y_local, C, P->one.d_ext_units)
-    switch (depth) {
-    case 22: EXT_LAUNCH(2, 2); break;
-    case 23: EXT_LAUNCH(2, 3); break;
-    case 27: EXT_LAUNCH(2, 7); break;
-    default: EXT_LAUNCH(2, 4); break;
-    }
-#undef EXT_LAUNCH
+    pick_int<22, 23, 27, 24>(depth, [&](auto PU) { // (A/B: the two digits are the kernel's <P, U>)
+        hipLaunchKernelGGL((spmv_bcsr4_fused_ext<PU() / 10, PU() % 10, kWG>), grid, dim3(kWG), 0, s, V, d_x_ext, d_y_local, C, P->one.d_ext_units);
+    });
     if (split) { // the units that name ghosts, behind the exchange by stream order
         ExtComm C2 = C;
         C2.xwgs = C2.n_work = 0;

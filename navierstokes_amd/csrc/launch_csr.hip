@@ -92,25 +92,21 @@ int launch_spmv(mi_csr_t A, const double* d_x, double* d_y, hipStream_t s, bool 
         V.nblk = M.nblk;
         const int4* plan = reinterpret_cast<const int4*>(M.d_plan.get());
         const int2* rng = reinterpret_cast<const int2*>(M.d_rng.get());
-#define MRING_L(D_, MP_, NT_, SK_) hipLaunchKernelGGL((spmv_csr_mring<kMringThreads, kMringNnzb, D_, kMringMaxB, MP_, NT_, SK_>), dim3(M.wgs), dim3(kMringThreads), 0, s, V, plan, reinterpret_cast<const int4*>(M.d_first.get()), M.d_ok, M.d_slots, d_x, d_y, rng, M.wgs)
-#define MRING_L3(D_, MP_) do { if (M.nt) { if (M.skew) MRING_L(D_, MP_, true, true); else MRING_L(D_, MP_, true, false); } \
-                               else { if (M.skew) MRING_L(D_, MP_, false, true); else MRING_L(D_, MP_, false, false); } } while (0)
-#define MRING_L2(D_) do { if (V.rowmap) MRING_L3(D_, true); else MRING_L3(D_, false); } while (0)
         int depth = M.depth;
         if (const char* e = getenv("MI355_RING_DEPTH")) depth = atoi(e);
-        if (depth == 4) MRING_L2(4);
-        else MRING_L2(2);
-#undef MRING_L2
-#undef MRING_L3
-#undef MRING_L
+        pick_int<4, 2>(depth, [&](auto D) {
+            pick([&](auto MP, auto NT, auto SK) {
+                hipLaunchKernelGGL((spmv_csr_mring<kMringThreads, kMringNnzb, D(), kMringMaxB, MP(), NT(), SK()>), dim3(M.wgs), dim3(kMringThreads), 0, s, V, plan,
+                                   reinterpret_cast<const int4*>(M.d_first.get()), M.d_ok, M.d_slots, d_x, d_y, rng, M.wgs);
+            }, V.rowmap != nullptr, M.nt, M.skew);
+        });
     } else if (kid == MI_KERNEL_TILE) {
         const TileTable& T = A->tile;
         const int grid = kNXCD * ((T.nblk + kNXCD - 1) / kNXCD);
         const int4* desc = reinterpret_cast<const int4*>(T.d_desc.get());
-#define TILE_LAUNCH(NT_, SK_) hipLaunchKernelGGL((spmv_csr_tile<kTileNnzb, NT_, SK_>), dim3(grid), dim3(kTileThreads), 0, s, V, desc, T.nblk, T.d_ulist, T.d_slots, d_x, d_y)
-        if (T.nt) { if (T.skew) TILE_LAUNCH(true, true); else TILE_LAUNCH(true, false); }
-        else { if (T.skew) TILE_LAUNCH(false, true); else TILE_LAUNCH(false, false); }
-#undef TILE_LAUNCH
+        pick([&](auto NT, auto SK) {
+            hipLaunchKernelGGL((spmv_csr_tile<kTileNnzb, NT(), SK()>), dim3(grid), dim3(kTileThreads), 0, s, V, desc, T.nblk, T.d_ulist, T.d_slots, d_x, d_y);
+        }, T.nt, T.skew);
     } else if (kid == MI_KERNEL_ROWPAR) {
         hipLaunchKernelGGL(spmv_csr_rowpar, dim3((A->n + kWG - 1) / kWG), dim3(kWG), 0, s, V, d_x, d_y);
     } else if (kid == MI_KERNEL_RING) {
@@ -123,8 +119,7 @@ int launch_spmv(mi_csr_t A, const double* d_x, double* d_y, hipStream_t s, bool 
         V.blk = T->d_blk;
         V.nblk = T->nblk;
         const int grid = kNXCD * ((T->nblk + kNXCD - 1) / kNXCD);
-        if (A->stream_nt) hipLaunchKernelGGL((spmv_csr_stream<1024, true>), dim3(grid), dim3(kWG), 0, s, V, d_x, d_y);
-        else hipLaunchKernelGGL((spmv_csr_stream<1024, false>), dim3(grid), dim3(kWG), 0, s, V, d_x, d_y);
+        pick([&](auto NT) { hipLaunchKernelGGL((spmv_csr_stream<1024, NT()>), dim3(grid), dim3(kWG), 0, s, V, d_x, d_y); }, A->stream_nt);
     }
     HIP_TRY(hipGetLastError());
     return MI_OK;

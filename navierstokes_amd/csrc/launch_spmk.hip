@@ -15,13 +15,9 @@ static hipError_t launch_fused_t(const mi_csr_s* H, const CsrView& V, const Spmk
 
 static hipError_t launch_fused(const mi_csr_s* H, const CsrView& V, const SpmkArgs& K, hipStream_t s, bool query = false, int* max_blocks = nullptr)
 {
-    const bool nt = H->ring.nt, sk = H->ring.skew;
-    if (H->ring.cfg.depth == 4) {
-        if (nt) return sk ? launch_fused_t<4, true, true>(H, V, K, s, query, max_blocks) : launch_fused_t<4, true, false>(H, V, K, s, query, max_blocks);
-        return sk ? launch_fused_t<4, false, true>(H, V, K, s, query, max_blocks) : launch_fused_t<4, false, false>(H, V, K, s, query, max_blocks);
-    }
-    if (nt) return sk ? launch_fused_t<2, true, true>(H, V, K, s, query, max_blocks) : launch_fused_t<2, true, false>(H, V, K, s, query, max_blocks);
-    return sk ? launch_fused_t<2, false, true>(H, V, K, s, query, max_blocks) : launch_fused_t<2, false, false>(H, V, K, s, query, max_blocks);
+    return pick_int<4, 2>(H->ring.cfg.depth, [&](auto D) {
+        return pick([&](auto NT, auto SKEW) { return launch_fused_t<D(), NT(), SKEW()>(H, V, K, s, query, max_blocks); }, H->ring.nt, H->ring.skew);
+    });
 }
 
 // a wait of a one-launch step gave up since the word was last cleared

@@ -38,35 +38,20 @@ static hipError_t launch_ot(const mi_bcsr4_s* A, const SpmmTilePlan* Pl, const B
     return hipGetLastError();
 }
 
-template <int S>
-static hipError_t launch_ot_s(const mi_bcsr4_s* A, const SpmmTilePlan* Pl, const Bcsr4View& V, int arith, bool nt, const double* X, long long ldx, double* Y, long long ldy, hipStream_t st)
-{
-    if (arith == MI_ARITH_BLOCKACC) return nt ? launch_ot<S, 1, true>(A, Pl, V, X, ldx, Y, ldy, st) : launch_ot<S, 1, false>(A, Pl, V, X, ldx, Y, ldy, st);
-    return nt ? launch_ot<S, 0, true>(A, Pl, V, X, ldx, Y, ldy, st) : launch_ot<S, 0, false>(A, Pl, V, X, ldx, Y, ldy, st);
-}
-
 hipError_t spmm_otile_launch(const mi_bcsr4_s* A, const SpmmTilePlan* Pl, const Bcsr4View& V, int s, int arith, bool nt, const double* X, long long ldx,
                              double* Y, long long ldy, hipStream_t st)
 {
-    if (Pl->rows != 64) return hipErrorInvalidValue;
-    switch (s) {
-    case 2: return launch_ot_s<2>(A, Pl, V, arith, nt, X, ldx, Y, ldy, st);
-    case 4: return launch_ot_s<4>(A, Pl, V, arith, nt, X, ldx, Y, ldy, st);
-    case 6: return launch_ot_s<6>(A, Pl, V, arith, nt, X, ldx, Y, ldy, st);
-    case 8: return launch_ot_s<8>(A, Pl, V, arith, nt, X, ldx, Y, ldy, st);
-    default: return hipErrorInvalidValue;
-    }
+    if (Pl->rows != 64 || s < 2 || s > 8 || s % 2) return hipErrorInvalidValue;
+    return pick_int<2, 4, 6, 8>(s, [&](auto S) {
+        return pick([&](auto BA, auto NT) { return launch_ot<S(), BA() ? 1 : 0, NT()>(A, Pl, V, X, ldx, Y, ldy, st); }, arith == MI_ARITH_BLOCKACC, nt);
+    });
 }
 
 hipError_t spmm_tile_launch(const mi_bcsr4_s* A, const SpmmTilePlan* Pl, const Bcsr4View& V, int s, int arith, const double* X, long long ldx,
                             double* Y, long long ldy, hipStream_t st)
 {
-    const bool ba = arith == MI_ARITH_BLOCKACC;
-    switch (s) {
-    case 1: return ba ? launch_t<1, 1>(A, Pl, V, X, ldx, Y, ldy, st) : launch_t<1, 0>(A, Pl, V, X, ldx, Y, ldy, st);
-    case 2: return ba ? launch_t<2, 1>(A, Pl, V, X, ldx, Y, ldy, st) : launch_t<2, 0>(A, Pl, V, X, ldx, Y, ldy, st);
-    case 3: return ba ? launch_t<3, 1>(A, Pl, V, X, ldx, Y, ldy, st) : launch_t<3, 0>(A, Pl, V, X, ldx, Y, ldy, st);
-    case 4: return ba ? launch_t<4, 1>(A, Pl, V, X, ldx, Y, ldy, st) : launch_t<4, 0>(A, Pl, V, X, ldx, Y, ldy, st);
-    default: return hipErrorInvalidValue;
-    }
+    if (s < 1 || s > 4) return hipErrorInvalidValue;
+    return pick_int<1, 2, 3, 4>(s, [&](auto S) {
+        return pick([&](auto BA) { return launch_t<S(), BA() ? 1 : 0>(A, Pl, V, X, ldx, Y, ldy, st); }, arith == MI_ARITH_BLOCKACC);
+    });
 }

@@ -1,5 +1,5 @@
 """Host-side planners under the address and undefined-behaviour sanitizers (CPU only: GPU sanitizers are not available on this pool, and
-nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp, bilu_asan.cpp, spmm_plan_asan.cpp, reorder_asan.cpp, gmres_drive_check.cpp) and say what they check."""
+nothing here launches a kernel).  The harnesses live under tools/ (plan_asan.hip, part_asan.cpp, bilu_asan.cpp, spmm_plan_asan.cpp, reorder_asan.cpp, gmres_drive_check.cpp, dispatch_check.cpp) and say what they check."""
 import os
 import shutil
 import subprocess
@@ -84,3 +84,15 @@ def test_gmres_host_loop_under_host_sanitizers(tmp_path):
     out = _run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tools", "gmres_drive_check.cpp")], exe, tmp_path)
     assert "bad 0" in out and "gmres_drive cases" in out, out
     assert int(out.split("gmres_drive cases")[1].split()[0]) >= sum(6 * 4 * 2 * (6 * m + 6) for m in (1, 2, 5)), out
+
+
+def test_launch_dispatch_helpers_under_host_sanitizers(tmp_path):
+    """dispatch.hpp: pick hands fn the compile-time twins of one to four runtime flags (all 2 + 4 + 8 + 16 combinations), calls it once and
+    returns its value; pick_int hands over every listed value as itself and an unlisted one (negative, zero, one past the largest, INT_MAX)
+    as the last listed; launch_grid gives the grids the launch sites used to write out."""
+    if not shutil.which("g++"):
+        pytest.skip("g++ not found")
+    exe = str(tmp_path / "dispatch_check")
+    out = _run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tools", "dispatch_check.cpp")], exe, tmp_path)
+    assert "bad 0" in out and "dispatch cases" in out, out
+    assert int(out.split("dispatch cases")[1].split()[0]) >= 2 + 4 + 8 + 16, out
