@@ -750,6 +750,51 @@ int mi_bilu4sp_fetch(mi_bilu4_t F, float* val, long long cap_blocks);
  * *copy_bytes of the copy, 64 per factor block (0 until prepared).  Any output may be NULL. */
 int mi_bilu4sp_info(mi_bilu4_t F, int* prepared, int* convert_launches, int* launches_last, long long* copy_bytes);
 
+/* ---- 4x4-block ILU(k): an opt-in MULTICOLOUR ORDERING behind the handle (mi_bilu4_create_ordered, mi_bilu4_order_*) ----
+ * In the caller's (natural) ordering the exact solve is a chain of dependent levels (2 x (3 nx + 1) on the FE family).  Under a
+ * multicolour numbering of the block rows, an exact ILU(0) solve has at most as many levels per sweep as there are colours — about
+ * a dozen on the FE family, at most 1 + the largest block-row degree — and every level is a wide, contiguous, independent range
+ * of rows.  The price: the handle factors B = Q A Q^T, and ILU of B is NOT ILU of A — a different, usually weaker preconditioner,
+ * whose iteration counts are known only for the matrices that were measured (profiles/NOTES.md R15.1).  So the ordering is opt-in:
+ * nothing chooses it, and mi_bilu4_create / mi_bilu4_create_host are untouched.
+ * THE RULE (part of the interface): greedy colouring of the symmetrised block graph — the pattern of A + A^T without the diagonal,
+ * so unsymmetric patterns are legal — block rows taken in ascending natural order, each taking the smallest colour that no
+ * already-coloured neighbour holds.  New numbering: colour ascending, inside a colour the old row number ascending;
+ * perm[old] = new (the convention of mi_csr_perm).  B's block columns are re-sorted ascending in the new numbering; symbolic
+ * ILU(fill), levels, folding, both factorisations, the one-launch form, the sweeps and the f32 copy then run on B exactly as they
+ * run on A in a natural-order handle.  At fill 0 fwd_levels and bwd_levels (mi_bilu4_info) are each <= ncolours; at fill > 0 the
+ * ordering is allowed but promises nothing about levels (fill blocks join rows of one colour).
+ * Every call on an ordered handle keeps its meaning in the CALLER's numbering: b, x, coef / d_coef of the refactors, the block
+ * row a refused pivot or an overflow names — mi_bilu4_solve*, mi_bilu4_refactor, mi_bilu4dev_*, mi_bilu4_set_solve_form,
+ * mi_bilu4one_*, mi_bilu4sw_*, mi_bilu4sp_*, mi_gmres_set_precond, the planned GMRES and a captured mi_gmres_cycle_dev.  TWO
+ * EXCEPTIONS return the factor of B in the NEW numbering: mi_bilu4_factor_host and mi_bilu4sp_fetch.  ("The lowest refused row"
+ * is the lowest in the new numbering, reported by its caller's number.)
+ * Cost: an ordered handle owns two vectors of 4 nbrows doubles, allocated at create; every solve gathers b into the first and
+ * scatters x out of the second — two extra launches per solve, counted in mi_bilu4_info's *launches (not in the sweeps'
+ * launches_last; mi_bilu4_info's us[] time the factor's application on the internal vectors, without them) — and allocates nothing,
+ * so solves stay capturable.  Consequence: ONE solve at a time per ordered handle.
+ * d_x == d_b stays allowed; vectors need 8-byte alignment only.
+ * An unfolded level of at least kBiluWideMin block rows (64: measured, every unfolded level; MI355_BILU_WIDE_MIN=<rows> at create
+ * overrides it) is computed by a kernel written for wide levels (the sweeps' software pipeline); narrower ones by the kernel of
+ * natural-order handles.  The same bits either way.  A natural-order handle never takes it: its launches are what they were.
+ * mi_bilu4_create_ordered(.., MI_BILU_ORDER_NATURAL, ..) IS mi_bilu4_create (and _host_ordered _create_host): same factor, same
+ * launches.  MI_ERR_ARG: an unknown ordering, MI355_BILU_WIDE_MIN < 1, and whatever mi_bilu4_create refuses.  (The declarators
+ * are parenthesised like mi_bilu4_set_solve_form's: the `mi_bilu4_name(` entries are the level-by-level interface, a closed set;
+ * these four are a closed set of their own.)  nbrows == 0: every call is a no-op, and mi_bilu4_order_info reports the ordering asked for. */
+enum { MI_BILU_ORDER_NATURAL = 0, MI_BILU_ORDER_COLOUR = 1 };
+int (mi_bilu4_create_ordered)(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, int ordering,
+                            mi_bilu4_t* out);
+int (mi_bilu4_create_host_ordered)(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill,
+                                 int ordering, mi_bilu4_t* out);
+/* *ordering (MI_BILU_ORDER_*), *ncolours (0 in natural order), *wide_launches = launches of one exact solve in form 0 that take the
+ * wide-level kernel, perm [nbrows] (the identity in natural order).  Any output may be NULL. */
+int (mi_bilu4_order_info)(mi_bilu4_t F, int* ordering, int* ncolours, int* wide_launches, int* perm);
+/* host-only: the ordering exactly as mi_bilu4_create_ordered builds it.  It first CHECKS its own result — perm is a permutation,
+ * every colour an independent set of the symmetrised graph — and names the first violation with MI_ERR_STATE; only then does it
+ * return perm [nbrows], *ncolours and colour_sizes (cap entries; MI_ERR_ARG when cap < *ncolours).  Any output may be NULL. */
+int (mi_bilu4_order_probe)(int nbrows, const int* ptrow, const int* indcol, int ordering, int* perm, int* ncolours,
+                         int* colour_sizes, int cap);
+
 /* ---- right-preconditioned restarted GMRES with a whole cycle on the device (mi_gmres_*) ----
  * KSPGMRES of src/solve_newton.c:1156-1164, 1265 as one call: the products, the block ILU in any of its three forms, CGS2 out of
  * mi_cgs_dev and the small least-squares problem all run on the caller's stream; the host reads a 64-byte record (plus the

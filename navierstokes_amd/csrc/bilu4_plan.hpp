@@ -231,9 +231,10 @@ static inline bool bilu4_invert(double* a)
 }
 
 // one row of the IKJ factorisation (baij4_factor_avx2.c:114-170) into val; pos: a per-thread map block column -> place in the
-// row, all -1 on entry and on return.  false: zero pivot in this row.
+// row, all -1 on entry and on return.  false: zero pivot in this row.  src: null, or the caller's index of every block of
+// (ptrow, indcol) — an ordered handle's pattern is the permuted one (bilu4_order.hpp), coef stays the caller's.
 static inline bool bilu4_factor_row(const Bilu4Pattern& P, int i, const int* ptrow, const int* indcol, const double* coef, bool colmajor,
-                                    double* val, int* pos)
+                                    double* val, int* pos, const int* src = nullptr)
 {
     const int k0 = P.ptr[i], k1 = P.ptr[i + 1];
     double* w = val + 16 * (size_t)k0;
@@ -241,12 +242,12 @@ static inline bool bilu4_factor_row(const Bilu4Pattern& P, int i, const int* ptr
     for (int k = k0; k < k1; k++) pos[P.col[k]] = k - k0;
     for (int k = ptrow[i]; k < ptrow[i + 1]; k++) {
         double* dst = w + 16 * (size_t)pos[indcol[k]];
-        const double* src = coef + 16 * (size_t)k;
+        const double* from = coef + 16 * (size_t)(src ? src[k] : k);
         if (colmajor)
             for (int r = 0; r < 4; r++)
-                for (int q = 0; q < 4; q++) dst[4 * r + q] = src[4 * q + r];
+                for (int q = 0; q < 4; q++) dst[4 * r + q] = from[4 * q + r];
         else
-            std::memcpy(dst, src, sizeof(double) * 16);
+            std::memcpy(dst, from, sizeof(double) * 16);
     }
     double m[16], pr[16];
     for (int k = k0; k < P.diag[i]; k++) {
@@ -273,7 +274,7 @@ static inline bool bilu4_factor_row(const Bilu4Pattern& P, int i, const int* ptr
 // `threads` threads (contiguous shares); every row is computed by one thread in one fixed order, so the bits do not depend on
 // the thread count.  Returns -1, or the lowest block row whose pivot was refused (rows behind it are then not meaningful).
 inline int bilu4_factor(const Bilu4Pattern& P, const Bilu4Sweep& F, const int* ptrow, const int* indcol, const double* coef, bool colmajor,
-                        int threads, double* val)
+                        int threads, double* val, const int* src = nullptr)
 {
     const int nb = P.nb;
     threads = std::max(1, std::min(threads, 64));
@@ -289,7 +290,7 @@ inline int bilu4_factor(const Bilu4Pattern& P, const Bilu4Sweep& F, const int* p
         auto share = [&](int t) {
             const int a = p0 + (int)((long long)(p1 - p0) * t / T), b = p0 + (int)((long long)(p1 - p0) * (t + 1) / T);
             for (int q = a; q < b; q++)
-                if (!bilu4_factor_row(P, F.perm[q], ptrow, indcol, coef, colmajor, val, pos[t].data())) note(F.perm[q]);
+                if (!bilu4_factor_row(P, F.perm[q], ptrow, indcol, coef, colmajor, val, pos[t].data(), src)) note(F.perm[q]);
         };
         if (T == 1) {
             share(0);
@@ -326,7 +327,8 @@ struct Bilu4DevPlan {
     }
 };
 
-inline void bilu4dev_plan(const Bilu4Schedule& S, const int* ptrow, const int* indcol, Bilu4DevPlan* D)
+// (src: as in bilu4_factor_row)
+inline void bilu4dev_plan(const Bilu4Schedule& S, const int* ptrow, const int* indcol, Bilu4DevPlan* D, const int* src = nullptr)
 {
     const Bilu4Pattern& P = S.pat;
     const Bilu4Sweep& F = S.sweep[0];
@@ -350,7 +352,7 @@ inline void bilu4dev_plan(const Bilu4Schedule& S, const int* ptrow, const int* i
         int k = P.ptr[i]; // both column lists ascend, and the matrix's is a subset of the factor's
         for (int a = ptrow[i]; a < ptrow[i + 1]; a++) {
             while (P.col[k] != indcol[a]) k++;
-            D->gather[home[k]] = a;
+            D->gather[home[k]] = src ? src[a] : a;
         }
     }
     D->upd_ptr.assign(1, 0);

@@ -4,7 +4,9 @@
 // (bilu4_solve_one.hpp, mi_bilu4one_*); mi_bilu4dev_* refactors on the GPU, into the same device copies, level by level
 // (bilu4_factor.hpp); mi_bilu4sw_* applies the same device factor by a fixed number of Jacobi sweeps per triangle, one launch per
 // sweep (bilu4_sweep.hpp); mi_bilu4sp_* the same sweeps over an opt-in single-precision copy of the factor's values, which every
-// entry point that writes the factor then keeps current.
+// entry point that writes the factor then keeps current.  mi_bilu4_create_ordered puts a multicolour ordering behind the handle
+// (bilu4_order.hpp): the factor is then that of the permuted matrix, every solve is bracketed by a gather and a scatter
+// (bilu_in_order, the one place), and wide unfolded levels take bilu4_level_wide (bilu4_solve_wide.hpp).
 // No CPU fallback: the solve and the device refactor need a HIP device; the planning and host factorisation entry points need none.
 #include "capi_internal.hpp"
 #include "bilu4_plan.hpp"
@@ -12,6 +14,9 @@
 #include "bilu4_solve_one.hpp"
 #include "bilu4_factor.hpp"
 #include "bilu4_sweep.hpp"
+#include "bilu4_order.hpp"
+#include "bilu4_order_kernels.hpp"
+#include "bilu4_solve_wide.hpp"
 
 // ---------------------------------------------------------------- ownership
 // Every device array of this file is a DevArray, the give-up word a MappedWord (dev_array.hpp, the types all handles of the library
@@ -72,10 +77,20 @@ struct Bilu4SpCopy {
     DevArray<Bilu4SpRecord> rec;
 };
 
+// what an ordered handle (mi_bilu4_create_ordered) owns on the device: the numbering and the two vectors in it that every solve
+// passes through — allocated at create, so that a solve allocates nothing and stays capturable; hence one solve at a time per handle
+struct Bilu4OrderDev {
+    DevArray<int> perm;    // [nb] the caller's block row -> the factor's
+    DevArray<double> b, x; // [4 nb] right-hand side and solution in the factor's numbering
+    int wide_min = 0;      // block rows from which an unfolded level takes bilu4_level_wide; 0: never (natural order)
+};
+
 struct mi_bilu4_s {
     int device = -1; // -1: host-only handle (mi_bilu4_create_host)
     int fill = 0;
-    std::vector<int> a_ptr, a_col; // the matrix's pattern (refactor scatters new values through it)
+    Bilu4Order ord;                // the ordering behind the handle (natural: empty tables)
+    std::vector<int> a_ptr, a_col; // the pattern that is factored (refactor scatters new values through it): the caller's, or on an
+                                   // ordered handle that of the permuted matrix, whose blocks ord.src maps back to the caller's
     Bilu4Schedule sched;
     std::vector<double> val;       // host factor, row order, row-major blocks
     double factor_seconds = 0.0;
@@ -87,7 +102,8 @@ struct mi_bilu4_s {
     Bilu4OneTables one;
     Bilu4SweepWork sw;
     Bilu4SpCopy sp;
-    ~mi_bilu4_s() { sp = {}, sw = {}, one = {}, lev[0] = {}, lev[1] = {}, d_b = {}, d_x = {}, dev = {}; } // the order the handle has always been freed in (newest first)
+    Bilu4OrderDev ordd;
+    ~mi_bilu4_s() { ordd = {}, sp = {}, sw = {}, one = {}, lev[0] = {}, lev[1] = {}, d_b = {}, d_x = {}, dev = {}; } // the order the handle has always been freed in (newest first)
     const Bilu4Pattern& pat() const { return sched.pat; }
     Bilu4FactorView factor_view() const
     {
@@ -142,9 +158,10 @@ static int bilu_zero_pivot(int row)
 static int bilu_factor(mi_bilu4_s* F, const double* coef, int layout)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    const int bad = bilu4_factor(F->pat(), F->sched.sweep[0], F->a_ptr.data(), F->a_col.data(), coef, layout == MI_BLOCK_COLMAJOR, bilu_threads(), F->val.data());
+    const int bad = bilu4_factor(F->pat(), F->sched.sweep[0], F->a_ptr.data(), F->a_col.data(), coef, layout == MI_BLOCK_COLMAJOR, bilu_threads(), F->val.data(),
+                                 F->ord.src_or_null());
     F->factor_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return bad >= 0 ? bilu_zero_pivot(bad) : MI_OK;
+    return bad >= 0 ? bilu_zero_pivot(F->ord.caller_row(bad)) : MI_OK;
 }
 
 // the level-major copy of sweep b: its pattern, and room for its values
@@ -198,26 +215,73 @@ static auto bilu_by_alignment(const double* d_x, Fn&& fn)
     return pick(fn, (((uintptr_t)d_x) & 15) == 0);
 }
 
+// does launch L take the wide-level kernel?  wide_min: the handle's (0 on a natural-order handle: never)
+static bool bilu_wide(const Bilu4Launch& L, int wide_min) { return wide_min > 0 && !L.folded() && L.p1 - L.p0 >= wide_min; }
+
 template <bool BWD, bool AL>
-static void bilu_sweep_launch(const Bilu4Sweep& S, const Bilu4SweepView& V, const double* src, double* x, hipStream_t s)
+static void bilu_sweep_launch(const Bilu4Sweep& S, const Bilu4SweepView& V, const double* src, double* x, int wide_min, hipStream_t s)
 {
     for (int a = 0; a < S.nlaunch(); a++) {
         const Bilu4Launch L = S.launch(a);
         if (L.folded()) {
             hipLaunchKernelGGL((bilu4_folded<BWD, AL>), dim3(1), dim3(kWG), 0, s, V, L.l0, L.l1, src, x);
-        } else {
-            const int grid = (L.p1 - L.p0 + kBiluRowsPerWG - 1) / kBiluRowsPerWG;
-            hipLaunchKernelGGL((bilu4_level<BWD, AL>), dim3(grid), dim3(kWG), 0, s, V, L.p0, L.p1, src, x);
+            continue;
         }
+        const int grid = (L.p1 - L.p0 + kBiluRowsPerWG - 1) / kBiluRowsPerWG;
+        if constexpr (AL) { // (the wide kernel runs on an ordered handle's own vectors only: always aligned)
+            if (bilu_wide(L, wide_min)) {
+                hipLaunchKernelGGL((bilu4_level_wide<BWD, kBiluSweepDepth>), dim3(grid), dim3(kWG), 0, s, V, L.p0, L.p1, src, x);
+                continue;
+            }
+        }
+        hipLaunchKernelGGL((bilu4_level<BWD, AL>), dim3(grid), dim3(kWG), 0, s, V, L.p0, L.p1, src, x);
     }
+}
+
+// launches of one exact solve in form 0 that take the wide-level kernel
+static int bilu_wide_launches(const mi_bilu4_s* F)
+{
+    int n = 0;
+    for (const Bilu4Sweep& S : F->sched.sweep)
+        for (int a = 0; a < S.nlaunch(); a++) n += bilu_wide(S.launch(a), F->ordd.wide_min);
+    return n;
+}
+
+// THE ONE PLACE an ordering meets the caller's vectors: whatever applies the factor (levels, one launch, sweeps, sweeps in f32)
+// runs as inner(b, x) on vectors in the factor's numbering.  Natural order: the caller's own.  Ordered: the handle's two vectors,
+// with a gather in front and a scatter behind, on the same stream — two launches, nothing allocated or synchronised.  d_x may be d_b:
+// the gather has read all of it before the scatter writes.
+constexpr int kBiluOrderLaunches = 2;
+
+template <bool IN>
+static void bilu_order_move(const mi_bilu4_s* F, const double* from, double* to, const double* user, hipStream_t s)
+{
+    const int nb = F->pat().nb;
+    bilu_by_alignment(user, [&](auto al) {
+        constexpr bool AL = decltype(al)::value;
+        const int grid = launch_grid((long long)nb * kBiluOrderLanes<AL>, kWG, INT_MAX, 1);
+        hipLaunchKernelGGL((bilu4_order_move<IN, AL>), dim3(grid), dim3(kWG), 0, s, F->ordd.perm, nb, from, to);
+        return 0;
+    });
+}
+
+template <class Fn>
+static int bilu_in_order(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s, Fn&& inner)
+{
+    if (!F->ord.on()) return inner(d_b, d_x);
+    bilu_order_move<true>(F, d_b, F->ordd.b, d_b, s);
+    if (const int rc = inner((const double*)F->ordd.b, (double*)F->ordd.x)) return rc;
+    bilu_order_move<false>(F, F->ordd.x, d_x, d_x, s);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
 }
 
 // form A: one launch per (folded) level, forward then backward, on the caller's stream; nothing allocated or synchronised
 static int bilu_solve_launch(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
 {
     bilu_by_alignment(d_x, [&](auto al) {
-        bilu_sweep_launch<false, decltype(al)::value>(F->sched.sweep[0], F->lev[0].view(), d_b, d_x, s);
-        bilu_sweep_launch<true, decltype(al)::value>(F->sched.sweep[1], F->lev[1].view(), d_x, d_x, s);
+        bilu_sweep_launch<false, decltype(al)::value>(F->sched.sweep[0], F->lev[0].view(), d_b, d_x, F->ordd.wide_min, s);
+        bilu_sweep_launch<true, decltype(al)::value>(F->sched.sweep[1], F->lev[1].view(), d_x, d_x, F->ordd.wide_min, s);
     });
     HIP_TRY(hipGetLastError());
     return MI_OK;
@@ -259,8 +323,10 @@ static int bilu_solve_one_launch(mi_bilu4_s* F, const double* d_b, double* d_x, 
 static int bilu_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
 {
     if (bilu_one_gave_up(F)) return fail(MI_ERR_HIP, kOneGaveUp);
-    if (F->form == MI_BILU_FORM_ONE && !stream_is_capturing(s)) return bilu_solve_one_launch(F, d_b, d_x, s);
-    return bilu_solve_launch(F, d_b, d_x, s);
+    return bilu_in_order(F, d_b, d_x, s, [&](const double* b, double* x) {
+        if (F->form == MI_BILU_FORM_ONE && !stream_is_capturing(s)) return bilu_solve_one_launch(F, b, x, s);
+        return bilu_solve_launch(F, b, x, s);
+    });
 }
 
 // The single-precision copy written from the level-major factor as it lies on the device now, on stream s: two launches (the record
@@ -285,11 +351,28 @@ static int bilu_sp_convert(const mi_bilu4_s* F, Bilu4SpCopy& S, hipStream_t s)
     return MI_OK;
 }
 
-static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, bool device, mi_bilu4_t* out)
+static const char* bilu_bad_ordering(int ordering)
+{
+    return ordering == MI_BILU_ORDER_NATURAL || ordering == MI_BILU_ORDER_COLOUR ? nullptr : "unknown ordering (0: natural, 1: multicolour)";
+}
+
+// the ordering of a pattern that bilu_check_args has accepted, checked (bilu4_order_check) before anything relies on it
+static int bilu_order(int nbrows, const int* ptrow, const int* indcol, int ordering, const char* who, Bilu4Order* O)
+{
+    *O = Bilu4Order{};
+    if (ordering == MI_BILU_ORDER_NATURAL) return MI_OK;
+    bilu4_colour(nbrows, ptrow, indcol, O);
+    const std::string bad = bilu4_order_check(nbrows, ptrow, indcol, *O);
+    if (!bad.empty()) return fail(MI_ERR_STATE, std::string(who) + ": " + bad);
+    return MI_OK;
+}
+
+static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, int ordering, bool device, mi_bilu4_t* out)
 {
     CHECK_ARG(out, "null output handle");
     *out = nullptr;
     CHECK_ARG(!bilu_bad_layout(layout), bilu_bad_layout(layout));
+    CHECK_ARG(!bilu_bad_ordering(ordering), bilu_bad_ordering(ordering));
     int rc = bilu_check_args(nbrows, ptrow, indcol, fill);
     if (rc) return rc;
     CHECK_ARG(nbrows == 0 || coef, "null coef");
@@ -302,7 +385,16 @@ static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const do
     std::unique_ptr<mi_bilu4_s> F(new (std::nothrow) mi_bilu4_s);
     if (!F) return fail(MI_ERR_ALLOC, "host allocation failed");
     F->fill = fill;
-    if (nbrows > 0) {
+    if (nbrows == 0) F->ord.ordering = ordering; // (an empty matrix: no tables, but the handle says what it was asked for)
+    if (nbrows > 0 && ordering != MI_BILU_ORDER_NATURAL) {
+        if ((rc = bilu_order(nbrows, ptrow, indcol, ordering, "mi_bilu4_create_ordered", &F->ord))) return rc;
+        bilu4_permute_pattern(nbrows, ptrow, indcol, &F->ord, &F->a_ptr, &F->a_col);
+        F->ordd.wide_min = kBiluWideMin;
+        if (const char* e = getenv("MI355_BILU_WIDE_MIN")) {
+            CHECK_ARG(atoi(e) >= 1, "MI355_BILU_WIDE_MIN must be >= 1 (block rows)");
+            F->ordd.wide_min = atoi(e);
+        }
+    } else if (nbrows > 0) {
         F->a_ptr.assign(ptrow, ptrow + nbrows + 1);
         F->a_col.assign(indcol, indcol + ptrow[nbrows]);
     } else {
@@ -315,6 +407,8 @@ static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const do
         HIP_TRY(hipGetDevice(&F->device));
         if ((rc = bilu_upload_pattern(F.get(), 0, &F->lev[0])) || (rc = bilu_upload_pattern(F.get(), 1, &F->lev[1])) || (rc = bilu_move_values(F.get(), true)) ||
             (rc = dev_alloc(F->d_b, 4 * (size_t)nbrows, 1)) || (rc = dev_alloc(F->d_x, 4 * (size_t)nbrows, 1)))
+            return rc;
+        if (F->ord.on() && ((rc = dev_upload(F->ordd.perm, F->ord.perm, 1)) || (rc = dev_alloc(F->ordd.b, 4 * (size_t)nbrows, 1)) || (rc = dev_alloc(F->ordd.x, 4 * (size_t)nbrows, 1))))
             return rc;
         HIP_TRY(hipMemset(F->d_b, 0, sizeof(double) * 4 * nbrows));
         // the solve's time, through the library's one timing helper (zero right-hand side: the time does not depend on values)
@@ -330,12 +424,46 @@ static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const do
 
 extern "C" int mi_bilu4_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, mi_bilu4_t* out)
 {
-    return bilu_create(nbrows, ptrow, indcol, coef, layout, fill, true, out);
+    return bilu_create(nbrows, ptrow, indcol, coef, layout, fill, MI_BILU_ORDER_NATURAL, true, out);
 }
 
 extern "C" int mi_bilu4_create_host(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, mi_bilu4_t* out)
 {
-    return bilu_create(nbrows, ptrow, indcol, coef, layout, fill, false, out);
+    return bilu_create(nbrows, ptrow, indcol, coef, layout, fill, MI_BILU_ORDER_NATURAL, false, out);
+}
+
+extern "C" int mi_bilu4_create_ordered(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, int ordering, mi_bilu4_t* out)
+{
+    return bilu_create(nbrows, ptrow, indcol, coef, layout, fill, ordering, true, out);
+}
+
+extern "C" int mi_bilu4_create_host_ordered(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, int ordering, mi_bilu4_t* out)
+{
+    return bilu_create(nbrows, ptrow, indcol, coef, layout, fill, ordering, false, out);
+}
+
+extern "C" int mi_bilu4_order_info(mi_bilu4_t F, int* ordering, int* ncolours, int* wide_launches, int* perm)
+{
+    CHECK_ARG(F, "null handle");
+    if (ordering) *ordering = F->ord.ordering;
+    if (ncolours) *ncolours = F->ord.ncolours;
+    if (wide_launches) *wide_launches = bilu_wide_launches(F);
+    for (int i = 0; perm && i < F->pat().nb; i++) perm[i] = F->ord.on() ? F->ord.perm[i] : i;
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4_order_probe(int nbrows, const int* ptrow, const int* indcol, int ordering, int* perm, int* ncolours, int* colour_sizes, int cap)
+{
+    CHECK_ARG(!bilu_bad_ordering(ordering), bilu_bad_ordering(ordering));
+    int rc = bilu_check_args(nbrows, ptrow, indcol, 0);
+    if (rc) return rc;
+    Bilu4Order O;
+    if ((rc = bilu_order(nbrows, ptrow, indcol, ordering, "mi_bilu4_order_probe", &O))) return rc;
+    if (ncolours) *ncolours = O.ncolours;
+    CHECK_ARG(!colour_sizes || cap >= O.ncolours, "colour-size array too short");
+    for (int i = 0; perm && i < nbrows; i++) perm[i] = O.on() ? O.perm[i] : i;
+    for (int c = 0; colour_sizes && c < O.ncolours; c++) colour_sizes[c] = O.colour_ptr[c + 1] - O.colour_ptr[c];
+    return MI_OK;
 }
 
 extern "C" int mi_bilu4_destroy(mi_bilu4_t F)
@@ -388,7 +516,7 @@ extern "C" int mi_bilu4_info(mi_bilu4_t F, int* nbrows, long long* nblocks, int*
     if (nblocks) *nblocks = F->pat().nblocks();
     if (fwd_levels) *fwd_levels = S[0].nlev();
     if (bwd_levels) *bwd_levels = S[1].nlev();
-    if (launches) *launches = F->form == MI_BILU_FORM_ONE ? 1 : S[0].nlaunch() + S[1].nlaunch();
+    if (launches) *launches = (F->form == MI_BILU_FORM_ONE ? 1 : S[0].nlaunch() + S[1].nlaunch()) + (F->ord.on() ? kBiluOrderLaunches : 0);
     if (form) *form = F->form;
     if (us) us[0] = F->us_form[0], us[1] = F->us_form[1];
     if (factor_seconds) *factor_seconds = F->factor_seconds;
@@ -453,7 +581,7 @@ extern "C" int mi_bilu4dev_prepare(mi_bilu4_t F)
     if (const int rc = bilu_dev_guard(F, "mi_bilu4dev_prepare"); rc != kBiluGo) return rc;
     if (F->dev.prepared) return MI_OK;
     Bilu4DevPlan D;
-    bilu4dev_plan(F->sched, F->a_ptr.data(), F->a_col.data(), &D);
+    bilu4dev_plan(F->sched, F->a_ptr.data(), F->a_col.data(), &D, F->ord.src_or_null());
     Bilu4DevTables T; // moves into the handle once it is complete; a failure on the way frees what there is
     int rc;
     if ((rc = dev_upload(T.fpos, D.fpos, 1)) || (rc = dev_upload(T.bpos, D.bpos, 1)) || (rc = dev_upload(T.gather, D.gather, 1)) || (rc = dev_upload(T.upd, D.upd, 1)) ||
@@ -498,6 +626,7 @@ extern "C" int mi_bilu4dev_status(mi_bilu4_t F, int* bad_row)
     int bad = kBiluBadNone;
     HIP_TRY(hipMemcpy(&bad, F->dev.bad, sizeof(int), hipMemcpyDeviceToHost));
     if (bad == kBiluBadNone) return MI_OK;
+    bad = F->ord.caller_row(bad);
     if (bad_row) *bad_row = bad;
     return bilu_zero_pivot(bad);
 }
@@ -765,7 +894,9 @@ static int bilu_sw_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, int 
             return fail(MI_ERR_STATE, "mi_bilu4sw_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sw_prepare allocates: call it before the capture)");
         if (const int rc = mi_bilu4sw_prepare(F)) return rc;
     }
-    return bilu_sw_solve_launch<double>(F, {F->lev[0].val, nullptr}, {F->lev[1].val, F->lev[1].dinv}, &F->sw.launches_last, d_b, d_x, sf, sb, s);
+    return bilu_in_order(F, d_b, d_x, s, [&](const double* b, double* x) {
+        return bilu_sw_solve_launch<double>(F, {F->lev[0].val, nullptr}, {F->lev[1].val, F->lev[1].dinv}, &F->sw.launches_last, b, x, sf, sb, s);
+    });
 }
 
 extern "C" int mi_bilu4sw_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s)
@@ -822,7 +953,9 @@ static int bilu_sp_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, int 
             return fail(MI_ERR_STATE, "mi_bilu4sp_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sp_prepare allocates and converts: call it before the capture)");
         if (const int rc = mi_bilu4sp_prepare(F)) return rc;
     }
-    return bilu_sw_solve_launch<float>(F, {F->sp.val[0], nullptr}, {F->sp.val[1], F->sp.dinv}, &F->sp.launches_last, d_b, d_x, sf, sb, s);
+    return bilu_in_order(F, d_b, d_x, s, [&](const double* b, double* x) {
+        return bilu_sw_solve_launch<float>(F, {F->sp.val[0], nullptr}, {F->sp.val[1], F->sp.dinv}, &F->sp.launches_last, b, x, sf, sb, s);
+    });
 }
 
 extern "C" int mi_bilu4sp_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s)
@@ -851,6 +984,7 @@ extern "C" int mi_bilu4sp_status(mi_bilu4_t F, int* bad_block_row, long long* ov
     Bilu4SpRecord R{};
     HIP_TRY(hipMemcpy(&R, F->sp.rec, sizeof(R), hipMemcpyDeviceToHost));
     if (R.overflowed == 0) return MI_OK;
+    R.row = F->ord.caller_row(R.row);
     if (bad_block_row) *bad_block_row = R.row;
     if (overflowed) *overflowed = (long long)R.overflowed;
     return fail(MI_ERR_ARG, "mi_bilu4sp: " + std::to_string(R.overflowed) + " finite value(s) of the factor are beyond the range of float and are Inf in the single-precision copy; the first in block row " +

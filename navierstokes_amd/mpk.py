@@ -192,6 +192,10 @@ def lib():
         "mi_bilu4sp_status": [_vp, P(i), P(ll)],
         "mi_bilu4sp_fetch": [_vp, _vp, ll],
         "mi_bilu4sp_info": [_vp, P(i), P(i), P(i), P(ll)],
+        "mi_bilu4_create_ordered": [i, _vp, _vp, _vp, i, i, i, P(_vp)],
+        "mi_bilu4_create_host_ordered": [i, _vp, _vp, _vp, i, i, i, P(_vp)],
+        "mi_bilu4_order_info": [_vp, P(i), P(i), P(i), _vp],
+        "mi_bilu4_order_probe": [i, _vp, _vp, i, _vp, P(i), _vp, i],
         "mi_gmres_create": [i, i, P(_vp)],
         "mi_gmres_set_operator_csr": [_vp, _vp],
         "mi_gmres_set_operator_bcsr4": [_vp, _vp],
@@ -589,9 +593,13 @@ class bilu4:
     """mi_bilu4_t: the incomplete LU factors of a square 4x4-block matrix — PCILU on the BAIJ-4 Jacobian,
     src/solve_newton.c:1156-1164 — factored on the host at construction, solved on the GPU level by level.
     bilu4(A, fill=0) takes a bcsr4x4_matrix's host arrays (and its block layout); bilu4(nbrows, ptrow, indcol, coef, fill=0,
-    layout="row") the arrays themselves.  host_only=True: no device copy (pattern, schedule and factor values only)."""
+    layout="row") the arrays themselves.  host_only=True: no device copy (pattern, schedule and factor values only).
+    order="colour" (mi_bilu4_create_ordered): the factor of the matrix under a multicolour renumbering of its block rows — a
+    different, usually weaker preconditioner whose exact solve has about as many levels as colours; opt-in, never chosen for
+    you.  Every method keeps the caller's numbering except factor_host() and fetch_f32(), which return the permuted matrix's
+    factor; one solve at a time per ordered handle."""
 
-    def __init__(self, A, ptrow=None, indcol=None, coef=None, fill=0, layout="row", host_only=False):
+    def __init__(self, A, ptrow=None, indcol=None, coef=None, fill=0, layout="row", host_only=False, order="natural"):
         if isinstance(A, bcsr4x4_matrix):
             nbrows, ptrow, indcol, coef, lay = A.nrows, A.ptrow, A.indcol, A.coef, A.layout
         else:
@@ -609,9 +617,22 @@ class bilu4:
         self._nblocks_in = len(indcol)
         self._h = None
         h = _vp()
-        make = lib().mi_bilu4_create_host if host_only else lib().mi_bilu4_create
-        check(make(self.nbrows, ptrow.ctypes.data, indcol.ctypes.data, coef.ctypes.data, lay, self.fill, _c.byref(h)))
+        self.order = order
+        if order == "natural":  # the entry points natural-order handles have always been made by
+            make = lib().mi_bilu4_create_host if host_only else lib().mi_bilu4_create
+            check(make(self.nbrows, ptrow.ctypes.data, indcol.ctypes.data, coef.ctypes.data, lay, self.fill, _c.byref(h)))
+        else:
+            make = lib().mi_bilu4_create_host_ordered if host_only else lib().mi_bilu4_create_ordered
+            check(make(self.nbrows, ptrow.ctypes.data, indcol.ctypes.data, coef.ctypes.data, lay, self.fill, _bilu_order(order), _c.byref(h)))
         self._h = h
+
+    def order_info(self):
+        """dict(order, ncolours, wide_launches, perm) — mi_bilu4_order_info: perm[old block row] = new (the identity in natural
+        order); wide_launches: launches of one exact solve in form 0 that take the wide-level kernel."""
+        o, nc, wl = _c.c_int(), _c.c_int(), _c.c_int()
+        perm = np.zeros(max(self.nbrows, 1), np.int32)
+        check(lib().mi_bilu4_order_info(self.handle, _c.byref(o), _c.byref(nc), _c.byref(wl), perm.ctypes.data))
+        return dict(order=BILU_ORDERS[o.value], ncolours=nc.value, wide_launches=wl.value, perm=perm[: self.nbrows])
 
     @property
     def handle(self):
@@ -769,6 +790,15 @@ class bilu4:
             pass
 
 
+BILU_ORDERS = ("natural", "colour")  # MI_BILU_ORDER_*
+
+
+def _bilu_order(order):
+    if order not in BILU_ORDERS:
+        raise ValueError('bilu4: order must be "natural" or "colour"')
+    return BILU_ORDERS.index(order)
+
+
 def _sweep_precision(precision):
     """False for "f64", True for "f32"."""
     if precision not in ("f64", "f32"):
@@ -813,6 +843,18 @@ def bilu4_plan_probe(nbrows, ptrow, indcol, fill=0):
                                     _c.byref(fa), _c.byref(ba), fs.ctypes.data, bs.ctypes.data, cap))
     return dict(nblocks=nblk.value, fwd_levels=fl.value, bwd_levels=bl.value, fwd_launches=fa.value, bwd_launches=ba.value,
                 fwd_sizes=fs[: fl.value].copy(), bwd_sizes=bs[: bl.value].copy())
+
+
+def bilu4_order_probe(nbrows, ptrow, indcol, order="colour"):
+    """mi_bilu4_order_probe (no GPU): dict(perm, ncolours, colour_sizes) of the ordering exactly as bilu4(..., order=) builds it, checked
+    by the library before it is returned (MiError, status 6, naming the first violation)."""
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    cap = max(int(nbrows), 1)
+    perm, sizes, nc = np.zeros(cap, np.int32), np.zeros(cap, np.int32), _c.c_int()
+    check(lib().mi_bilu4_order_probe(int(nbrows), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, _bilu_order(order), perm.ctypes.data,
+                                     _c.byref(nc), sizes.ctypes.data, cap))
+    return dict(perm=perm[: int(nbrows)].copy(), ncolours=nc.value, colour_sizes=sizes[: nc.value].copy())
 
 
 def bilu4dev_plan_probe(nbrows, ptrow, indcol, fill=0):

@@ -5,7 +5,10 @@ the SAME matrix and factor handles, in one process.  Prints one JSON line per pr
 profiles/gmres_bench.jsonl.
 
     python3 tools/bench_gmres.py [--cells 68] [--fill 0] [--sweeps 3] [--precision f64|f32|both] [--basis f64|f32|both] [--runs 5] [--no-append]
-                                 [--graph SEG[,SEG...]]
+                                 [--graph SEG[,SEG...]] [--order natural,colour]
+
+--order natural,colour (default natural): the ordering of the block rows behind the factor handle (mpk.bilu4(order=)); one factor
+handle per ordering on the same matrix handle in one process, the records of each carry "order".
 
 --basis f64 (the default) is the comparison above.  --basis f32 or both compares the solver handles instead: one gmres_solver per
 basis asked for (basis="f64": the yardstick, the code path of the default; basis="f32": the single-precision Krylov basis), both at
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--maxiter", type=int, default=300)
     ap.add_argument("--no-append", action="store_true")
     ap.add_argument("--graph", default="", help="segments of the planned solve, e.g. 1,5,30")
+    ap.add_argument("--order", default="natural", help="comma-separated orderings of the block rows: natural, colour")
     a = ap.parse_args()
     import torch
     from navierstokes_amd import mpk, synth
@@ -54,14 +58,18 @@ def main():
     nb = len(bp) - 1
     n = 4 * nb
     A = mpk.bcsr4x4_matrix(nb, bp, bc, bv)
-    F = mpk.bilu4(A, fill=a.fill)
+    orders = [o for o in a.order.split(",") if o]
+    assert orders and all(o in mpk.BILU_ORDERS for o in orders), "--order: natural, colour"
+    factors = {o: mpk.bilu4(A, fill=a.fill, order=o) for o in orders}
     b = synth.x_sin(0, n) + 1.0
     db = torch.from_numpy(b).cuda()
     dx, dy = torch.zeros_like(db), torch.zeros_like(db)
     bnorm = float(np.linalg.norm(b))
-    preconds = [(f"sweeps{a.sweeps}_{p}", F.sweeps(a.sweeps, precision=p)) for p in (("f64", "f32") if a.precision == "both" else (a.precision,))]
-    preconds.append(("exact", F))
-    for label, M in preconds:
+    preconds = []
+    for o, F in factors.items():
+        preconds += [(o, f"sweeps{a.sweeps}_{p}", F.sweeps(a.sweeps, precision=p)) for p in (("f64", "f32") if a.precision == "both" else (a.precision,))]
+        preconds.append((o, "exact", F))
+    for order, label, M in preconds:
         if a.basis == "f64":
             S = mpk.gmres_solver(A, M, RESTART)
             handles = [S]
@@ -109,7 +117,7 @@ def main():
                     last[name].update(readbacks_last=info["readbacks_last"], wasted_steps_last=info["wasted_steps_last"], launches_last=info["launches_last"])
                     if a.basis != "f64":
                         last[name].update(ce[0].basis_info(), device_bytes=info["device_bytes"])
-        out = dict(tool="bench_gmres", cells=a.cells, rows=n, fill=a.fill, precond=label, restart=RESTART, rtol=RTOL, runs=a.runs,
+        out = dict(tool="bench_gmres", cells=a.cells, rows=n, fill=a.fill, order=order, precond=label, restart=RESTART, rtol=RTOL, runs=a.runs,
                    default_check_every=mpk.GMRES_CHECK_EVERY, solvers={})
         for name, _ in solvers:
             med = statistics.median(secs[name])
@@ -123,7 +131,8 @@ def main():
                 f.write(line + "\n")
         for h in plans + handles:
             h.close()
-    F.close()
+    for F in factors.values():
+        F.close()
     A.close()
 
 

@@ -26,6 +26,15 @@ f32 / f64 measured and modelled, the cost of one more sweep pair in each precisi
 depth of the f32 pipeline, and the microseconds of ONE conversion: mi_bilu4dev_refactor timed on this handle before the copy
 exists and again with the conversion attached (median of single refactors between device events), and their difference.
 
+--order natural,colour (default natural): which orderings of the block rows to measure, each on a handle of its own built on the
+SAME matrix in one process (mpk.bilu4(order=)); one JSON line per ordering, combinable with --form, --sweeps and --precision.  A
+colour-order record also carries the colours, the launches that take the wide-level kernel, and boundary_us: the cost of the two
+launches at the solve's boundary, measured as the diagonal-only sweep solve (0 sweeps: one launch) on the ordered handle minus the
+same on the natural-order handle (with both orderings asked for).  --wide-min 64,1024,...: for the colour order, form 0 timed on
+further handles created with MI355_BILU_WIDE_MIN set to each value (0: the wide kernel never) — wide_min_curve.
+
+    python3 tools/bench_ilu.py --order natural,colour [--wide-min 0,64,1024,4096,16384] [--sweeps 3,4] [--cells 68] [--fill 0]
+
 --refactor measures the two refactorisations instead, in one process, and appends one record (tool = "bench_ilu_refactor"): the
 wall time of the host path mi_bilu4_refactor (factor on host threads, wait for the device, upload; median of --host-reps calls),
 the time of mi_bilu4dev_refactor between device events (median of --reps single refactors after warm-ups), launches per refactor,
@@ -206,25 +215,58 @@ def main():
     ap.add_argument("--form", choices=("both", "0", "1"), default="both")
     ap.add_argument("--sweeps", default="", help="comma-separated sweep counts per triangle")
     ap.add_argument("--precision", choices=("f64", "f32", "both"), default="f64", help="with --sweeps: the values the sweeps stream")
+    ap.add_argument("--order", default="natural", help="comma-separated orderings of the block rows: natural, colour")
+    ap.add_argument("--wide-min", default="", help="with the colour order: comma-separated MI355_BILU_WIDE_MIN values to time form 0 at (0: never wide)")
     ap.add_argument("--no-append", action="store_true")
     a = ap.parse_args()
-    import numpy as np
     import torch
     from navierstokes_amd import mpk, synth
     assert torch.cuda.is_available(), "bench_ilu.py needs a GPU"
-    if a.refactor:
-        line = json.dumps(refactor_record(a))
+
+    def emit(rec):
+        line = json.dumps(rec)
         print(line)
         if not a.no_append:
             with open(os.path.join(ROOT, "profiles", "ilu_bench.jsonl"), "a") as f:
                 f.write(line + "\n")
+
+    if a.refactor:
+        emit(refactor_record(a))
         return
+    orders = [o for o in a.order.split(",") if o]
+    assert orders and all(o in mpk.BILU_ORDERS for o in orders), "--order: natural, colour"
     bp, bc, bv = synth.csr_to_bcsr4(*synth.fe_matrix(a.cells))
     nb = len(bp) - 1
-    n = 4 * nb
     A = mpk.bcsr4x4_matrix(nb, bp, bc, bv)
+    diag_only_us = {}
+    for order in orders:
+        emit(order_record(a, A, bv, order, diag_only_us if orders != ["natural"] else None))
+    A.close()
+
+
+def wide_min_handle(A, fill, wide_min):
+    """A colour-order handle created with MI355_BILU_WIDE_MIN=wide_min (0: a threshold no level reaches)."""
+    from navierstokes_amd import mpk
+    old = os.environ.get("MI355_BILU_WIDE_MIN")
+    os.environ["MI355_BILU_WIDE_MIN"] = str(wide_min if wide_min > 0 else 2 ** 31 - 1)
+    try:
+        return mpk.bilu4(A, fill=fill, order="colour")
+    finally:
+        if old is None:
+            del os.environ["MI355_BILU_WIDE_MIN"]
+        else:
+            os.environ["MI355_BILU_WIDE_MIN"] = old
+
+
+def order_record(a, A, bv, order, diag_only_us):
+    """Everything the tool measures, on a handle of `order` built on A.  diag_only_us: the orderings' diagonal-only times so far, or None."""
+    import numpy as np
+    import torch
+    from navierstokes_amd import mpk, synth
+    nb, bc = A.nrows, A.indcol
+    n = 4 * nb
     t0 = time.perf_counter()
-    F = mpk.bilu4(A, fill=a.fill)
+    F = mpk.bilu4(A, fill=a.fill, order=order)
     create_s = time.perf_counter() - t0
     info = F.info()
     b = synth.x_sin(0, n) + 1.0
@@ -248,7 +290,7 @@ def main():
         F.one_status()
     solve_us = us[forms[0]]
     spmv_us = timed_us(lambda: mpk.SpMV_BCSR(dy, db, A), 20, max(a.solves, 200))
-    out = dict(tool="bench_ilu", cells=a.cells, rows=n, block_rows=nb, blocks=int(len(bc)), fill=a.fill, factor_blocks=info["nblocks"],
+    out = dict(tool="bench_ilu", order=order, cells=a.cells, rows=n, block_rows=nb, blocks=int(len(bc)), fill=a.fill, factor_blocks=info["nblocks"],
                factor_bytes=info["factor_bytes"], host_factor_seconds=round(info["factor_seconds"], 4), create_seconds=round(create_s, 3),
                fwd_levels=info["fwd_levels"], bwd_levels=info["bwd_levels"], launches_per_solve=info["launches"], form_in_use=info["form"],
                solve_us={names[f]: (None if us[f] is None else round(us[f], 2)) for f in (0, 1)},
@@ -270,13 +312,24 @@ def main():
                                    converged=bool(hist[-1] <= 1e-8))
     if a.sweeps:
         out["sweeps"] = sweeps_record(a, F, A, b, db, dx, dy, bv)
-    line = json.dumps(out)
-    print(line)
-    if not a.no_append:
-        with open(os.path.join(ROOT, "profiles", "ilu_bench.jsonl"), "a") as f:
-            f.write(line + "\n")
+    # the diagonal-only sweep solve: ONE launch in natural order, the same plus the two boundary launches on an ordered handle
+    # (timed only when an ordering other than natural is among those asked for: diag_only_us is None otherwise)
+    if diag_only_us is not None:
+        diag_only_us[order] = timed_us(lambda: F.sweeps(0).solve(dx, db), 20, max(a.solves, 200))
+    if order != "natural":
+        oinfo = F.order_info()
+        sizes = mpk.bilu4_order_probe(nb, A.ptrow, A.indcol, order)["colour_sizes"]
+        out.update(ncolours=oinfo["ncolours"], colour_sizes=[int(c) for c in sizes], wide_launches=oinfo["wide_launches"], diag_only_us=round(diag_only_us[order], 2),
+                   boundary_us=round(diag_only_us[order] - diag_only_us["natural"], 2) if "natural" in diag_only_us else None)
+        curve = {}
+        for wm in [int(c) for c in a.wide_min.split(",") if c]:
+            W = wide_min_handle(A, a.fill, wm)
+            curve[str(wm)] = dict(us=round(timed_us(lambda: W.solve(dx, db), 20, max(a.solves, 200)), 2), wide_launches=W.order_info()["wide_launches"])
+            W.close()
+        if curve:
+            out["wide_min_curve"] = curve
     F.close()
-    A.close()
+    return out
 
 
 if __name__ == "__main__":
