@@ -750,6 +750,31 @@ int mi_bilu4sp_fetch(mi_bilu4_t F, float* val, long long cap_blocks);
  * *copy_bytes of the copy, 64 per factor block (0 until prepared).  Any output may be NULL. */
 int mi_bilu4sp_info(mi_bilu4_t F, int* prepared, int* convert_launches, int* launches_last, long long* copy_bytes);
 
+/* ---- 4x4-block ILU(k): the EXACT solve over the single-precision copy (mi_bilu4spx_*) ----
+ * Under the multicolour ordering the exact solve streams a few wide levels and is bound by what it reads, 128 bytes of values per
+ * block.  mi_bilu4spx_solve* is the level-by-level exact solve reading the copy of mi_bilu4sp_prepare instead: 64 bytes per block,
+ * no new device memory and no new conversion.  Opt-in: nothing chooses it, and mi_bilu4_solve*, mi_bilu4_info, mi_bilu4sw_* and
+ * mi_bilu4sp_* are unchanged by it, bit for bit.
+ * DEFINITION (part of the interface): the definition of mi_bilu4_solve* with v32 = (double)(float)v — the rounding rule of
+ * mi_bilu4sp_* above — in place of EVERY factor value v: L, U and the inverted diagonal blocks.  Vectors, accumulators and a row's
+ * sequence of roundings stay double and unchanged: the fma chain per block, blocks in ascending column order, ONE rounded
+ * subtraction per block, Dinv . s to end a backward row.  Its result therefore equals, BIT FOR BIT, the exact solve of the rounded
+ * factor, which is also what mi_bilu4sp_solve_dev returns with both counts at or above the clamp.
+ * Always enqueued level by level (the launches of form 0, the same folding), whatever mi_bilu4_set_solve_form says: the one-launch
+ * form has no single-precision instantiation.  On an ordered handle the solve keeps the caller's numbering (the gather and the
+ * scatter: two launches, counted in *launches_last), and an unfolded level of at least kBiluWideMin block rows takes the float
+ * instantiation of the wide-level kernel; the same bits either way.
+ * Rules, those of mi_bilu4sp_solve_dev: an unprepared handle is prepared by its first solve, except under stream capture:
+ * MI_ERR_STATE ("not prepared"), nothing enqueued, the capture stays valid; once prepared a solve allocates nothing, copies nothing
+ * to the host and synchronises nothing; d_x == d_b is allowed; vectors need 8-byte alignment only; an overflow in the copy does
+ * not block solves (mi_bilu4sp_status reports it); ONE solve at a time per ordered handle.
+ * MI_ERR_ARG: a null handle or vector — before the device is touched; MI_ERR_NODEVICE: a host-only handle; nbrows == 0: a no-op. */
+int mi_bilu4spx_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s);
+int mi_bilu4spx_solve(mi_bilu4_t F, const double* b, double* x); /* host vectors: copied in and out */
+/* of the last mi_bilu4spx_solve* (0 before the first): *launches_last, the two of an ordered handle included, and how many of them
+ * took the wide-level kernel.  Any output may be NULL. */
+int mi_bilu4spx_info(mi_bilu4_t F, int* launches_last, int* wide_launches_last);
+
 /* ---- 4x4-block ILU(k): an opt-in MULTICOLOUR ORDERING behind the handle (mi_bilu4_create_ordered, mi_bilu4_order_*) ----
  * In the caller's (natural) ordering the exact solve is a chain of dependent levels (2 x (3 nx + 1) on the FE family).  Under a
  * multicolour numbering of the block rows, an exact ILU(0) solve has at most as many levels per sweep as there are colours — about
@@ -839,18 +864,23 @@ int (mi_bilu4_order_probe)(int nbrows, const int* ptrow, const int* indcol, int 
  * The handle owns V (m + 1 rows, even leading dimension), two work vectors, the small state and the two pinned slots; it does
  * NOT own A or F: both must outlive it.  MI_GMRES_PC_EXACT calls mi_bilu4_solve_dev with the handle's current solve form, the
  * two sweep kinds mi_bilu4sw_solve_dev / mi_bilu4sp_solve_dev with the counts given; mi_gmres_set_precond prepares F for them.
+ * MI_GMRES_PC_EXACT_F32 (mi_gmres_set_precond_ex only) calls mi_bilu4spx_solve_dev: the exact solve of the rounded factor.
  * ONE solve at a time per handle.  F's sweep work vectors are F's: two solvers on one F must not overlap.  Vectors need 8-byte
  * alignment only.  Under stream capture mi_gmres_solve_dev returns MI_ERR_STATE (it reads back) and enqueues nothing.
  * MI_ERR_ARG, before the device is touched: a null handle or vector, n < 1, restart outside 1..64, an operator or preconditioner
  * whose row count is not n, a mapped or non-square operator, check_every < 1, maxiter < 0, an unknown kind, a negative count;
  * MI_ERR_STATE: no operator set; MI_ERR_NODEVICE: no GPU (mi_gmres_create): there is no CPU fallback. */
 typedef struct mi_gmres_s* mi_gmres_t;
-enum { MI_GMRES_PC_EXACT = 0, MI_GMRES_PC_SWEEPS = 1, MI_GMRES_PC_SWEEPS_F32 = 2 };
+enum { MI_GMRES_PC_EXACT = 0, MI_GMRES_PC_SWEEPS = 1, MI_GMRES_PC_SWEEPS_F32 = 2, MI_GMRES_PC_EXACT_F32 = 3 };
 int mi_gmres_create(int n, int restart, mi_gmres_t* out);
 int mi_gmres_set_operator_csr(mi_gmres_t G, mi_csr_t A);     /* square, unmapped, n rows: the arithmetic of mi_spmv_dev */
 int mi_gmres_set_operator_bcsr4(mi_gmres_t G, mi_bcsr4_t A); /* 4 nbrows == n: the chain arithmetic of mi_bcsr4_spmv_dev */
 /* F == NULL: no preconditioner (kind and counts ignored) */
 int mi_gmres_set_precond(mi_gmres_t G, mi_bilu4_t F, int kind, int sweeps_fwd, int sweeps_bwd);
+/* the same, and also MI_GMRES_PC_EXACT_F32: the exact solve over the single-precision copy (mi_bilu4spx_solve_dev; the handle is
+ * prepared by mi_bilu4sp_prepare, the counts are ignored).  With F != NULL an unknown kind, and a negative count for the two sweep
+ * kinds, are refused first, before the solver is looked at.  mi_gmres_set_precond keeps refusing kind 3 as unknown. */
+int mi_gmres_set_precond_ex(mi_gmres_t G, mi_bilu4_t F, int kind, int sweeps_fwd, int sweeps_bwd);
 /* d_x holds the initial guess and receives the solution; iterations, reason and history may be NULL */
 int mi_gmres_solve_dev(mi_gmres_t G, const double* d_b, double* d_x, double rtol, int maxiter, int check_every, int* iterations,
                        int* reason, double* history, mi_stream_t s);

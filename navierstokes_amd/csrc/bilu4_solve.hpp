@@ -12,6 +12,17 @@
 // blocks in ascending column order; the backward sweep ends with x = Dinv . s, one chain from a rounded product per entry.
 // A row's result is one fixed sequence of roundings whatever the schedule, the folding or the alignment of the vectors.
 //
+// Stored type: the kernels are templates over the type the VALUES are stored in, as bilu4_sweep is (bilu4_sweep.hpp) — the device
+// factor's doubles (mi_bilu4_solve*), or the opt-in single-precision copy of them (mi_bilu4spx_*: v32 = (double)(float)v for L, U
+// and the inverted diagonal blocks).  Pattern, vectors, look-ahead and arithmetic are the same; a float row of a block is ONE
+// 16-byte load, widened exactly in registers where the chain takes it, so the result is the exact solve of the rounded factor.
+// The type is the VIEW's (Bilu4SweepViewT<T>), not a second kernel argument beside it as in bilu4_sweep: with the values in an
+// argument of their own the compiler's kernel-resource-usage report for the double backward kernels changes (bilu4_level and
+// bilu4_level_wide: 22 SGPRs become 18), and an existing kernel stays the kernel it is.  This way the double instantiations take
+// the argument they always took and their report is unchanged.  The float instantiations (gfx950, the same report, forward /
+// backward, either alignment, no scratch, 8 waves per SIMD): bilu4_level 40 / 44 VGPRs and 18 / 22 SGPRs, bilu4_folded 44 / 48 and
+// 26 / 26 — the double kernels' numbers: one block of look-ahead holds too little for the narrower type to show.
+//
 // The vector x carries t between the sweeps and between the levels.  It is read with plain vector loads and is deliberately
 // NOT const __restrict__: inside the folded kernel other waves of the workgroup write it between two barriers.
 #pragma once
@@ -19,14 +30,19 @@
 
 namespace mi355 {
 
-struct Bilu4SweepView {
+// T: the type the values are stored in.  Bilu4SweepView, the view of the device factor's own doubles, is what every kernel took
+// before there was a second type and is the same kernel argument as before; Bilu4SweepViewT<float> carries the arrays of the
+// single-precision copy in the same two places (Bilu4SweepVals<float>, bilu4_sweep.hpp) and the SAME pattern arrays.
+template <class T>
+struct Bilu4SweepViewT {
     const int* perm;    // [nb] position -> block row
     const int* ptr;     // [nb + 1] by position: first off-diagonal block of the row in this sweep
     const int* col;     // block columns, ascending per row
-    const double* val;  // 16 per block, row-major
-    const double* dinv; // backward sweep: [16 * nb] by position, the inverted diagonal blocks; forward: null
+    const T* val;       // 16 per block, row-major
+    const T* dinv;      // backward sweep: [16 * nb] by position, the inverted diagonal blocks; forward: null
     const int* lev_ptr; // [nlev + 1] first position of each level
 };
+using Bilu4SweepView = Bilu4SweepViewT<double>;
 
 // the four entries of block j of v; AL: v is 16-byte aligned
 template <bool AL>
@@ -50,52 +66,80 @@ __device__ __forceinline__ double bilu4_chain(double2 c01, double2 c23, const do
     return fma(c23.y, t[3], p);
 }
 
+// a quad lane's row of one block as it lies in registers between its load and its chain: two 16-byte loads of doubles, or ONE of
+// floats, widened (exactly) only where the chain takes it, so that a stage of a pipeline holds half the registers
+template <class T>
+struct Bilu4CoefRow;
+template <>
+struct Bilu4CoefRow<double> {
+    double2 a01, a23;
+    __device__ __forceinline__ void load(const double* p)
+    {
+        const double2* r = reinterpret_cast<const double2*>(p);
+        a01 = r[0];
+        a23 = r[1];
+    }
+    __device__ __forceinline__ double2 c01() const { return a01; }
+    __device__ __forceinline__ double2 c23() const { return a23; }
+};
+template <>
+struct Bilu4CoefRow<float> {
+    float4 a;
+    __device__ __forceinline__ void load(const float* p) { a = *reinterpret_cast<const float4*>(p); }
+    __device__ __forceinline__ double2 c01() const { return make_double2((double)a.x, (double)a.y); }
+    __device__ __forceinline__ double2 c23() const { return make_double2((double)a.z, (double)a.w); }
+};
+
+// the end of a backward row: Dinv_pos . s, the quad's four entries of s exchanged
+template <class T>
+__device__ __forceinline__ double bilu4_sweep_dinv(const T* dinv, int pos, int q, double s)
+{
+    const double sv[4] = {quad_bcast<0>(s), quad_bcast<1>(s), quad_bcast<2>(s), quad_bcast<3>(s)};
+    Bilu4CoefRow<T> d;
+    d.load(dinv + 16 * (size_t)pos + 4 * q);
+    return bilu4_chain(d.c01(), d.c23(), sv);
+}
+
 // one block row of one sweep, by the quad's lane q; pos < number of rows.  BWD: src == x (t lies there), else src == b.  The
 // value of entry q of block row `row`: every kernel of the solve stores exactly this.
-template <bool BWD, bool AL>
-__device__ __forceinline__ double bilu4_row_value(const Bilu4SweepView& V, int pos, int row, int q, const double* src, const double* x)
+template <bool BWD, bool AL, class T>
+__device__ __forceinline__ double bilu4_row_value(const Bilu4SweepViewT<T>& V, int pos, int row, int q, const double* src, const double* x)
 {
     const int ia0 = V.ptr[pos], ia1 = V.ptr[pos + 1];
     double s = src[4 * (size_t)row + q];
     if (ia0 < ia1) {
         const int last = ia1 - 1;
-        const double* cq = V.val + 4 * q;
-        const double2* r0 = reinterpret_cast<const double2*>(cq + 16 * (size_t)ia0);
-        double2 a01 = r0[0], a23 = r0[1];
+        const T* cq = V.val + 4 * q;
+        Bilu4CoefRow<T> a;
+        a.load(cq + 16 * (size_t)ia0);
         double t[4];
         bilu4_load4<AL>(x, (unsigned)V.col[ia0], t);
         unsigned cn = (unsigned)V.col[min(ia0 + 1, last)];
         for (int ia = ia0; ia < ia1; ia++) {
-            const double2 c01 = a01, c23 = a23;
+            const double2 c01 = a.c01(), c23 = a.c23();
             const double u[4] = {t[0], t[1], t[2], t[3]};
             // the next block (clamped to the row's last: loads are unconditional) while this one's chain runs
             const int nb = min(ia + 1, last);
-            const double2* nr = reinterpret_cast<const double2*>(cq + 16 * (size_t)nb);
-            a01 = nr[0];
-            a23 = nr[1];
+            a.load(cq + 16 * (size_t)nb);
             bilu4_load4<AL>(x, cn, t);
             cn = (unsigned)V.col[min(ia + 2, last)];
             s = __dsub_rn(s, bilu4_chain(c01, c23, u));
         }
     }
-    if (BWD) {
-        const double sv[4] = {quad_bcast<0>(s), quad_bcast<1>(s), quad_bcast<2>(s), quad_bcast<3>(s)};
-        const double2* d = reinterpret_cast<const double2*>(V.dinv + 16 * (size_t)pos + 4 * q);
-        s = bilu4_chain(d[0], d[1], sv);
-    }
+    if (BWD) s = bilu4_sweep_dinv(V.dinv, pos, q, s);
     return s;
 }
 
-template <bool BWD, bool AL>
-__device__ __forceinline__ void bilu4_row(const Bilu4SweepView& V, int pos, int q, const double* src, double* x)
+template <bool BWD, bool AL, class T>
+__device__ __forceinline__ void bilu4_row(const Bilu4SweepViewT<T>& V, int pos, int q, const double* src, double* x)
 {
     const int row = V.perm[pos];
     x[4 * (size_t)row + q] = bilu4_row_value<BWD, AL>(V, pos, row, q, src, x);
 }
 
 // one level: positions [p0, p1), 64 block rows per workgroup
-template <bool BWD, bool AL>
-__global__ __launch_bounds__(kWG) void bilu4_level(Bilu4SweepView V, int p0, int p1, const double* src, double* x)
+template <bool BWD, bool AL, class T>
+__global__ __launch_bounds__(kWG) void bilu4_level(Bilu4SweepViewT<T> V, int p0, int p1, const double* src, double* x)
 {
     const int g = blockIdx.x * kWG + threadIdx.x;
     const int pos = p0 + (g >> 2);
@@ -105,8 +149,8 @@ __global__ __launch_bounds__(kWG) void bilu4_level(Bilu4SweepView V, int p0, int
 
 // a run of narrow levels [l0, l1) (each fewer than 64 block rows) in ONE workgroup: a workgroup barrier between levels.  The
 // barrier orders the quads' stores to x before the next level's loads of it (same CU, same L1, write-through).
-template <bool BWD, bool AL>
-__global__ __launch_bounds__(kWG) void bilu4_folded(Bilu4SweepView V, int l0, int l1, const double* src, double* x)
+template <bool BWD, bool AL, class T>
+__global__ __launch_bounds__(kWG) void bilu4_folded(Bilu4SweepViewT<T> V, int l0, int l1, const double* src, double* x)
 {
     const int slot = threadIdx.x >> 2, q = threadIdx.x & 3;
     for (int l = l0; l < l1; l++) {

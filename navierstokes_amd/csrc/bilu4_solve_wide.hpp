@@ -17,7 +17,9 @@
 // 16-byte aligned: there is no scalar-load form (the caller's alignment ends at the boundary kernels, bilu4_order_kernels.hpp).
 //
 // Registers at P = 4 (gfx950, the compiler's kernel-resource-usage report): 130 VGPRs forward, 134 backward, no scratch — 3 waves
-// per SIMD, what the double bilu4_sweep it restates gets.
+// per SIMD, what the double bilu4_sweep it restates gets.  The float instantiation (mi_bilu4spx_*, the single-precision copy of the
+// values: Bilu4SweepViewT<float>) at P = 4: 124 VGPRs forward, 128 backward, 18 / 22 SGPRs, no scratch — 4 waves per SIMD, what the
+// float bilu4_sweep gets.
 #pragma once
 #include "bilu4_sweep.hpp"
 
@@ -28,8 +30,17 @@ namespace mi355 {
 // to levels of 64 to 255 block rows (fe_matrix(24) at fill 1), so the threshold is the narrowest level that is not folded.
 constexpr int kBiluWideMin = kBiluRowsPerWG;
 
-template <bool BWD, int P>
-__global__ __launch_bounds__(kWG) void bilu4_level_wide(Bilu4SweepView V, int p0, int p1, const double* src, double* x)
+// P of the float instantiation, a constant of its own: a stage holds 4 VGPRs of coefficients instead of 8, as in the f32 sweeps.
+// 4 and 8 were compared by building each (-DMI355_BILU_WIDE_DEPTH_F32=n) and timing both on the GPU (profiles/NOTES.md R16.1): 8 was
+// slower on every matrix timed (its report: 100 / 104 VGPRs, 4 waves per SIMD — fewer registers than at 4 for twice the stages; why
+// was not analysed).
+#ifndef MI355_BILU_WIDE_DEPTH_F32
+#define MI355_BILU_WIDE_DEPTH_F32 kBiluSweepDepthF32
+#endif
+constexpr int kBiluWideDepthF32 = MI355_BILU_WIDE_DEPTH_F32;
+
+template <bool BWD, int P, class T>
+__global__ __launch_bounds__(kWG) void bilu4_level_wide(Bilu4SweepViewT<T> V, int p0, int p1, const double* src, double* x)
 {
     const int g = blockIdx.x * kWG + threadIdx.x;
     const int pos = p0 + (g >> 2), q = g & 3;
@@ -40,8 +51,8 @@ __global__ __launch_bounds__(kWG) void bilu4_level_wide(Bilu4SweepView V, int p0
     if (ia0 < ia1) {
         const int last = ia1 - 1;
         const unsigned* ucol = reinterpret_cast<const unsigned*>(V.col);
-        const double* cq = V.val + 4 * q;
-        Bilu4CoefRow<double> a[P];
+        const T* cq = V.val + 4 * q;
+        Bilu4CoefRow<T> a[P];
         double t[P][4];
         unsigned cn[P]; // columns of blocks ia+P+k
 #pragma unroll

@@ -41,46 +41,13 @@ constexpr int kBiluSweepDepthF32 = MI355_BILU_SWEEP_DEPTH_F32;
 
 // The values a sweep streams, in the type they are STORED in: the device factor itself (double), or its single-precision copy
 // (float, mi_bilu4sp_*: v32 = (double)(float)v, round to nearest even, subnormals kept).  Pattern, positions and vectors are the
-// view's and double either way; the arithmetic is bilu4_chain in double on the widened values.
+// view's and double either way; the arithmetic is bilu4_chain in double on the widened values.  (A lane's row of a block in
+// registers, Bilu4CoefRow<T>, and the end of a backward row, bilu4_sweep_dinv<T>: bilu4_solve.hpp, shared with the exact solve.)
 template <class T>
 struct Bilu4SweepVals {
     const T* val;  // 16 per block, row-major, in the view's block order
     const T* dinv; // backward sweep: [16 * nb] by position; forward: null
 };
-
-// a quad lane's row of one block as it lies in registers between its load and its chain: two 16-byte loads of doubles, or ONE of
-// floats, widened (exactly) only where the chain takes it, so that a stage of the pipeline holds half the registers
-template <class T>
-struct Bilu4CoefRow;
-template <>
-struct Bilu4CoefRow<double> {
-    double2 a01, a23;
-    __device__ __forceinline__ void load(const double* p)
-    {
-        const double2* r = reinterpret_cast<const double2*>(p);
-        a01 = r[0];
-        a23 = r[1];
-    }
-    __device__ __forceinline__ double2 c01() const { return a01; }
-    __device__ __forceinline__ double2 c23() const { return a23; }
-};
-template <>
-struct Bilu4CoefRow<float> {
-    float4 a;
-    __device__ __forceinline__ void load(const float* p) { a = *reinterpret_cast<const float4*>(p); }
-    __device__ __forceinline__ double2 c01() const { return make_double2((double)a.x, (double)a.y); }
-    __device__ __forceinline__ double2 c23() const { return make_double2((double)a.z, (double)a.w); }
-};
-
-// the end of a backward row: Dinv_pos . s, the quad's four entries of s exchanged
-template <class T>
-__device__ __forceinline__ double bilu4_sweep_dinv(const T* dinv, int pos, int q, double s)
-{
-    const double sv[4] = {quad_bcast<0>(s), quad_bcast<1>(s), quad_bcast<2>(s), quad_bcast<3>(s)};
-    Bilu4CoefRow<T> d;
-    d.load(dinv + 16 * (size_t)pos + 4 * q);
-    return bilu4_chain(d.c01(), d.c23(), sv);
-}
 
 // one sweep: out_i = src_i - sum_k A_ik old_{col k} over the off-diagonal blocks of the view (BWD: then Dinv_i . that)
 template <bool BWD, bool AL, int P, class T>

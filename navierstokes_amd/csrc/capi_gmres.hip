@@ -115,25 +115,35 @@ extern "C" int mi_gmres_set_operator_bcsr4(mi_gmres_t G, mi_bcsr4_t A)
     return MI_OK;
 }
 
-extern "C" int mi_gmres_set_precond(mi_gmres_t G, mi_bilu4_t F, int kind, int sweeps_fwd, int sweeps_bwd)
+// kind and counts are checked first (with a preconditioner they are wrong whatever the solver is), then the handle
+extern "C" int mi_gmres_set_precond_ex(mi_gmres_t G, mi_bilu4_t F, int kind, int sweeps_fwd, int sweeps_bwd)
 {
+    const bool sweeps = kind == MI_GMRES_PC_SWEEPS || kind == MI_GMRES_PC_SWEEPS_F32;
+    CHECK_ARG(!F || sweeps || kind == MI_GMRES_PC_EXACT || kind == MI_GMRES_PC_EXACT_F32, "unknown preconditioner kind");
+    CHECK_ARG(!F || !sweeps || (sweeps_fwd >= 0 && sweeps_bwd >= 0), "negative sweep count");
     CHECK_ARG(G, "null handle");
     if (!F) {
         G->F = nullptr;
         G->gen++;
         return MI_OK;
     }
-    CHECK_ARG(kind == MI_GMRES_PC_EXACT || kind == MI_GMRES_PC_SWEEPS || kind == MI_GMRES_PC_SWEEPS_F32, "unknown preconditioner kind");
-    CHECK_ARG(kind == MI_GMRES_PC_EXACT || (sweeps_fwd >= 0 && sweeps_bwd >= 0), "negative sweep count");
     int nb = 0, rc;
     if ((rc = mi_bilu4_info(F, &nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
     CHECK_ARG(4LL * nb == G->n, "the preconditioner's row count (4 nbrows) is not the solver's n");
     // everything a solve would otherwise allocate on first use
     if (kind == MI_GMRES_PC_SWEEPS && (rc = mi_bilu4sw_prepare(F))) return rc;
-    if (kind == MI_GMRES_PC_SWEEPS_F32 && (rc = mi_bilu4sp_prepare(F))) return rc;
+    if ((kind == MI_GMRES_PC_SWEEPS_F32 || kind == MI_GMRES_PC_EXACT_F32) && (rc = mi_bilu4sp_prepare(F))) return rc;
     G->F = F, G->pc_kind = kind, G->sf = sweeps_fwd, G->sb = sweeps_bwd;
     G->gen++;
     return MI_OK;
+}
+
+// the kinds it has always taken (0..2), refused in the order it has always refused: the handle first
+extern "C" int mi_gmres_set_precond(mi_gmres_t G, mi_bilu4_t F, int kind, int sweeps_fwd, int sweeps_bwd)
+{
+    CHECK_ARG(G, "null handle");
+    CHECK_ARG(!F || (kind >= MI_GMRES_PC_EXACT && kind <= MI_GMRES_PC_SWEEPS_F32), "unknown preconditioner kind");
+    return mi_gmres_set_precond_ex(G, F, kind, sweeps_fwd, sweeps_bwd);
 }
 
 static int gmres_mult(mi_gmres_s* G, const double* x, double* y, mi_stream_t s)
@@ -159,6 +169,7 @@ static int gmres_precond(mi_gmres_s* G, const double* in, double* out, mi_stream
     switch (G->pc_kind) {
     case MI_GMRES_PC_SWEEPS: return mi_bilu4sw_solve_dev(G->F, in, out, G->sf, G->sb, s);
     case MI_GMRES_PC_SWEEPS_F32: return mi_bilu4sp_solve_dev(G->F, in, out, G->sf, G->sb, s);
+    case MI_GMRES_PC_EXACT_F32: return mi_bilu4spx_solve_dev(G->F, in, out, s);
     default: return mi_bilu4_solve_dev(G->F, in, out, s);
     }
 }

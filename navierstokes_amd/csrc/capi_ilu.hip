@@ -4,7 +4,8 @@
 // (bilu4_solve_one.hpp, mi_bilu4one_*); mi_bilu4dev_* refactors on the GPU, into the same device copies, level by level
 // (bilu4_factor.hpp); mi_bilu4sw_* applies the same device factor by a fixed number of Jacobi sweeps per triangle, one launch per
 // sweep (bilu4_sweep.hpp); mi_bilu4sp_* the same sweeps over an opt-in single-precision copy of the factor's values, which every
-// entry point that writes the factor then keeps current.  mi_bilu4_create_ordered puts a multicolour ordering behind the handle
+// entry point that writes the factor then keeps current; mi_bilu4spx_* the exact level-by-level solve over that copy (the float
+// instantiations of the solve's kernels).  mi_bilu4_create_ordered puts a multicolour ordering behind the handle
 // (bilu4_order.hpp): the factor is then that of the permuted matrix, every solve is bracketed by a gather and a scatter
 // (bilu_in_order, the one place), and wide unfolded levels take bilu4_level_wide (bilu4_solve_wide.hpp).
 // No CPU fallback: the solve and the device refactor need a HIP device; the planning and host factorisation entry points need none.
@@ -69,10 +70,12 @@ struct Bilu4SweepWork {
 };
 
 // the single-precision copy of the level-major values (mi_bilu4sp_prepare): L blocks, U blocks, inverted diagonal blocks, in the
-// order of lev[0].val, lev[1].val and lev[1].dinv; rec: what the last conversion found (Bilu4SpRecord)
+// order of lev[0].val, lev[1].val and lev[1].dinv; rec: what the last conversion found (Bilu4SpRecord).  The sweeps (mi_bilu4sp_*)
+// and the exact solve (mi_bilu4spx_*) both stream it; exact_*: launches of the last exact solve over it, and those that were wide
 struct Bilu4SpCopy {
     bool prepared = false;
     int convert_launches = 0, launches_last = 0;
+    int exact_launches_last = 0, exact_wide_last = 0;
     DevArray<float> val[2], dinv;
     DevArray<Bilu4SpRecord> rec;
 };
@@ -218,23 +221,27 @@ static auto bilu_by_alignment(const double* d_x, Fn&& fn)
 // does launch L take the wide-level kernel?  wide_min: the handle's (0 on a natural-order handle: never)
 static bool bilu_wide(const Bilu4Launch& L, int wide_min) { return wide_min > 0 && !L.folded() && L.p1 - L.p0 >= wide_min; }
 
-template <bool BWD, bool AL>
-static void bilu_sweep_launch(const Bilu4Sweep& S, const Bilu4SweepView& V, const double* src, double* x, int wide_min, hipStream_t s)
+// D: the sweep's level-major copy; A: its values in the type they are streamed in — D's own doubles, or the single-precision copy
+// (mi_bilu4spx_*), which take D's places in the view the kernels are handed
+template <bool BWD, bool AL, class T>
+static void bilu_sweep_launch(const Bilu4Sweep& S, const Bilu4SweepView& D, const Bilu4SweepVals<T>& A, const double* src, double* x, int wide_min, hipStream_t s)
 {
+    const Bilu4SweepViewT<T> V{D.perm, D.ptr, D.col, A.val, A.dinv, D.lev_ptr};
+    constexpr int P = std::is_same<T, float>::value ? kBiluWideDepthF32 : kBiluSweepDepth;
     for (int a = 0; a < S.nlaunch(); a++) {
         const Bilu4Launch L = S.launch(a);
         if (L.folded()) {
-            hipLaunchKernelGGL((bilu4_folded<BWD, AL>), dim3(1), dim3(kWG), 0, s, V, L.l0, L.l1, src, x);
+            hipLaunchKernelGGL((bilu4_folded<BWD, AL, T>), dim3(1), dim3(kWG), 0, s, V, L.l0, L.l1, src, x);
             continue;
         }
         const int grid = (L.p1 - L.p0 + kBiluRowsPerWG - 1) / kBiluRowsPerWG;
         if constexpr (AL) { // (the wide kernel runs on an ordered handle's own vectors only: always aligned)
             if (bilu_wide(L, wide_min)) {
-                hipLaunchKernelGGL((bilu4_level_wide<BWD, kBiluSweepDepth>), dim3(grid), dim3(kWG), 0, s, V, L.p0, L.p1, src, x);
+                hipLaunchKernelGGL((bilu4_level_wide<BWD, P, T>), dim3(grid), dim3(kWG), 0, s, V, L.p0, L.p1, src, x);
                 continue;
             }
         }
-        hipLaunchKernelGGL((bilu4_level<BWD, AL>), dim3(grid), dim3(kWG), 0, s, V, L.p0, L.p1, src, x);
+        hipLaunchKernelGGL((bilu4_level<BWD, AL, T>), dim3(grid), dim3(kWG), 0, s, V, L.p0, L.p1, src, x);
     }
 }
 
@@ -277,14 +284,21 @@ static int bilu_in_order(mi_bilu4_s* F, const double* d_b, double* d_x, hipStrea
 }
 
 // form A: one launch per (folded) level, forward then backward, on the caller's stream; nothing allocated or synchronised
-static int bilu_solve_launch(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
+// Lv, Uv: the values of the two triangles in the type they are streamed in (the factor's own, or its single-precision copy)
+template <class T>
+static int bilu_solve_launch(mi_bilu4_s* F, const Bilu4SweepVals<T>& Lv, const Bilu4SweepVals<T>& Uv, const double* d_b, double* d_x, hipStream_t s)
 {
     bilu_by_alignment(d_x, [&](auto al) {
-        bilu_sweep_launch<false, decltype(al)::value>(F->sched.sweep[0], F->lev[0].view(), d_b, d_x, F->ordd.wide_min, s);
-        bilu_sweep_launch<true, decltype(al)::value>(F->sched.sweep[1], F->lev[1].view(), d_x, d_x, F->ordd.wide_min, s);
+        bilu_sweep_launch<false, decltype(al)::value>(F->sched.sweep[0], F->lev[0].view(), Lv, d_b, d_x, F->ordd.wide_min, s);
+        bilu_sweep_launch<true, decltype(al)::value>(F->sched.sweep[1], F->lev[1].view(), Uv, d_x, d_x, F->ordd.wide_min, s);
     });
     HIP_TRY(hipGetLastError());
     return MI_OK;
+}
+
+static int bilu_solve_launch(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
+{
+    return bilu_solve_launch<double>(F, {F->lev[0].val, nullptr}, {F->lev[1].val, F->lev[1].dinv}, d_b, d_x, s);
 }
 
 static const char* const kOneGaveUp =
@@ -1019,5 +1033,49 @@ extern "C" int mi_bilu4sp_info(mi_bilu4_t F, int* prepared, int* convert_launche
     if (convert_launches) *convert_launches = F->sp.convert_launches;
     if (launches_last) *launches_last = F->sp.launches_last;
     if (copy_bytes) *copy_bytes = F->sp.prepared ? (long long)(16 * sizeof(float)) * F->pat().nblocks() : 0;
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------- mi_bilu4spx_*: the EXACT solve over the single-precision copy
+// The level-by-level solve of mi_bilu4_solve* with the copy's floats in place of the factor's doubles: the same schedule, the same
+// launch rule (folded runs, bilu4_level, on an ordered handle bilu4_level_wide), the float instantiations of the same kernels.
+// Always level by level, whatever the handle's form: the one-launch form is not a template over the stored type.
+static int bilu_spx_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
+{
+    if (!F->sp.prepared) {
+        if (stream_is_capturing(s))
+            return fail(MI_ERR_STATE, "mi_bilu4spx_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sp_prepare allocates and converts: call it before the capture)");
+        if (const int rc = mi_bilu4sp_prepare(F)) return rc;
+    }
+    const int rc = bilu_in_order(F, d_b, d_x, s, [&](const double* b, double* x) {
+        return bilu_solve_launch<float>(F, {F->sp.val[0], nullptr}, {F->sp.val[1], F->sp.dinv}, b, x, s);
+    });
+    if (rc) return rc;
+    F->sp.exact_launches_last = F->sched.sweep[0].nlaunch() + F->sched.sweep[1].nlaunch() + (F->ord.on() ? kBiluOrderLaunches : 0);
+    F->sp.exact_wide_last = bilu_wide_launches(F);
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4spx_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s)
+{
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4spx_solve_dev", nullptr, d_b && d_x ? nullptr : "null vector"); rc != kBiluGo) return rc;
+    return bilu_spx_solve_any(F, d_b, d_x, (hipStream_t)s);
+}
+
+extern "C" int mi_bilu4spx_solve(mi_bilu4_t F, const double* b, double* x)
+{
+    if (const int rc = bilu_sw_guard(F, "mi_bilu4spx_solve", nullptr, b && x ? nullptr : "null vector"); rc != kBiluGo) return rc;
+    const size_t bytes = sizeof(double) * 4 * (size_t)F->pat().nb;
+    HIP_TRY(hipMemcpy(F->d_b, b, bytes, hipMemcpyHostToDevice));
+    if (const int rc = bilu_spx_solve_any(F, F->d_b, F->d_x, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(x, F->d_x, bytes, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+extern "C" int mi_bilu4spx_info(mi_bilu4_t F, int* launches_last, int* wide_launches_last)
+{
+    CHECK_ARG(F, "null handle");
+    if (launches_last) *launches_last = F->sp.exact_launches_last;
+    if (wide_launches_last) *wide_launches_last = F->sp.exact_wide_last;
     return MI_OK;
 }

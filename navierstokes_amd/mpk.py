@@ -192,6 +192,9 @@ def lib():
         "mi_bilu4sp_status": [_vp, P(i), P(ll)],
         "mi_bilu4sp_fetch": [_vp, _vp, ll],
         "mi_bilu4sp_info": [_vp, P(i), P(i), P(i), P(ll)],
+        "mi_bilu4spx_solve_dev": [_vp, _vp, _vp, _vp],
+        "mi_bilu4spx_solve": [_vp, _vp, _vp],
+        "mi_bilu4spx_info": [_vp, P(i), P(i)],
         "mi_bilu4_create_ordered": [i, _vp, _vp, _vp, i, i, i, P(_vp)],
         "mi_bilu4_create_host_ordered": [i, _vp, _vp, _vp, i, i, i, P(_vp)],
         "mi_bilu4_order_info": [_vp, P(i), P(i), P(i), _vp],
@@ -200,6 +203,7 @@ def lib():
         "mi_gmres_set_operator_csr": [_vp, _vp],
         "mi_gmres_set_operator_bcsr4": [_vp, _vp],
         "mi_gmres_set_precond": [_vp, _vp, i, i, i],
+        "mi_gmres_set_precond_ex": [_vp, _vp, i, i, i],
         "mi_gmres_solve_dev": [_vp, _vp, _vp, d, i, i, P(i), P(i), _vp, _vp],
         "mi_gmres_solve": [_vp, _vp, _vp, d, i, i, P(i), P(i), _vp],
         "mi_gmres_fetch_cycle": [_vp, P(i), _vp, _vp, P(d)],
@@ -718,6 +722,19 @@ class bilu4:
         single-precision copy of the factor's values (mi_bilu4sp_*); vectors and arithmetic stay double."""
         return bilu4_sweeps(self, fwd, fwd if bwd is None else bwd, precision)
 
+    def exact(self, precision="f64"):
+        """The exact solve as a view with .solve(x, b), which GMRES takes as M like a sweeps() view.  precision="f64": the handle's
+        own solve (the handle itself).  precision="f32": the level-by-level exact solve streaming the single-precision copy of the
+        factor's values (mi_bilu4spx_*) — the exact solve of the rounded factor; vectors and arithmetic stay double.  The view
+        shares this handle and owns nothing."""
+        return bilu4_exact_f32(self) if _sweep_precision(precision) else self
+
+    def exact_info_f32(self):
+        """dict(launches_last, wide_launches_last) of the last single-precision exact solve — mi_bilu4spx_info."""
+        la, wl = _c.c_int(), _c.c_int()
+        check(lib().mi_bilu4spx_info(self.handle, _c.byref(la), _c.byref(wl)))
+        return dict(launches_last=la.value, wide_launches_last=wl.value)
+
     def prepare_sweeps(self, precision="f64"):
         """Allocate the work vectors of the sweep solve (mi_bilu4sw_prepare; idempotent): needed before a graph capture.
         precision="f32": also the single-precision copy of the factor, converted now and kept current by every refactor
@@ -828,6 +845,25 @@ class bilu4_sweeps:
             xx = _host_f64(x, n, "x", writable=True)
             host = L.mi_bilu4sp_solve if self._f32 else L.mi_bilu4sw_solve
             check(host(self.F.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data, self.fwd, self.bwd))
+        return x
+
+
+class bilu4_exact_f32:
+    """bilu4.exact("f32"): the exact solve over the single-precision copy of F's values (mi_bilu4spx_*).  It shares F's handle and
+    owns nothing."""
+
+    def __init__(self, F):
+        self.F = F
+
+    def solve(self, x, b):
+        """x = the exact solve of the rounded factor applied to b.  CUDA tensors: asynchronous on torch's current stream, x may be
+        b; numpy arrays: copied in and out."""
+        n = 4 * self.F.nbrows
+        if _is_torch(b):
+            check(lib().mi_bilu4spx_solve_dev(self.F.handle, _dev_ptr(b, n, "b"), _dev_ptr(x, n, "x"), _stream_ptr()))
+        else:
+            xx = _host_f64(x, n, "x", writable=True)
+            check(lib().mi_bilu4spx_solve(self.F.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data))
         return x
 
 
@@ -1368,7 +1404,7 @@ def GMRES(A, b, x, M=None, restart=30, rtol=1e-8, maxiter=300):
             return its, hist
 
 
-GMRES_PC_EXACT, GMRES_PC_SWEEPS, GMRES_PC_SWEEPS_F32 = 0, 1, 2
+GMRES_PC_EXACT, GMRES_PC_SWEEPS, GMRES_PC_SWEEPS_F32, GMRES_PC_EXACT_F32 = 0, 1, 2, 3
 GMRES_BASIS = {"f64": 0, "f32": 1}  # MI_BASIS_F64, MI_BASIS_F32
 GMRES_CHECK_EVERY = 1  # the default of gmres_solver.solve / GMRES_dev: what tools/bench_gmres.py measured fastest (profiles/NOTES.md R12.1)
 
@@ -1377,7 +1413,7 @@ class gmres_solver:
     """mi_gmres_t: GMRES's definition above with a whole restart cycle enqueued on the device — the products, M, CGS2, the Givens
     rotations, the residual recurrence and the back-substitution — and one small read-back per check_every iterations instead of
     one stream drain per iteration (include/mi355_spmv.h, mi_gmres_*; DESIGN.md 4.6).  A: a bcsr4x4_matrix or a square csrmatrix;
-    M: a bilu4 (the exact solve in the handle's current form), a bilu4_sweeps (either precision) or None.  The solver owns its
+    M: a bilu4 (the exact solve in the handle's current form), a bilu4_sweeps (either precision), a bilu4.exact("f32") view or None.  The solver owns its
     basis and work vectors; A and M must outlive it.  One solve at a time per solver, and per M.
     basis="f32" (MI_BASIS_F32, opt-in): the Krylov basis is stored in single precision, every projection is taken against the
     stored basis, and a converged recurrence is confirmed by the next cycle's true residual (basis_info()).
@@ -1402,6 +1438,8 @@ class gmres_solver:
             check(lib().mi_gmres_set_operator_csr(h, A.handle))
         if isinstance(M, bilu4_sweeps):
             check(lib().mi_gmres_set_precond(h, M.F.handle, GMRES_PC_SWEEPS_F32 if M._f32 else GMRES_PC_SWEEPS, M.fwd, M.bwd))
+        elif isinstance(M, bilu4_exact_f32):
+            check(lib().mi_gmres_set_precond_ex(h, M.F.handle, GMRES_PC_EXACT_F32, 0, 0))
         elif M is not None:
             check(lib().mi_gmres_set_precond(h, M.handle, GMRES_PC_EXACT, 0, 0))
 

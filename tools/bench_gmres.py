@@ -5,7 +5,11 @@ the SAME matrix and factor handles, in one process.  Prints one JSON line per pr
 profiles/gmres_bench.jsonl.
 
     python3 tools/bench_gmres.py [--cells 68] [--fill 0] [--sweeps 3] [--precision f64|f32|both] [--basis f64|f32|both] [--runs 5] [--no-append]
-                                 [--graph SEG[,SEG...]] [--order natural,colour]
+                                 [--graph SEG[,SEG...]] [--order natural,colour] [--exact-precision f64|f32|both]
+
+--exact-precision (default f64): which values the exact-solve rows stream — the double factor ("exact"), its single-precision
+copy ("exact_f32": mpk.bilu4.exact("f32"), MI_GMRES_PC_EXACT_F32), or both on the SAME factor handle in the same process; the
+records carry "exact_precision".
 
 --order natural,colour (default natural): the ordering of the block rows behind the factor handle (mpk.bilu4(order=)); one factor
 handle per ordering on the same matrix handle in one process, the records of each carry "order".
@@ -49,6 +53,7 @@ def main():
     ap.add_argument("--maxiter", type=int, default=300)
     ap.add_argument("--no-append", action="store_true")
     ap.add_argument("--graph", default="", help="segments of the planned solve, e.g. 1,5,30")
+    ap.add_argument("--exact-precision", choices=("f64", "f32", "both"), default="f64", help="the values the exact-solve rows stream")
     ap.add_argument("--order", default="natural", help="comma-separated orderings of the block rows: natural, colour")
     a = ap.parse_args()
     import torch
@@ -68,7 +73,7 @@ def main():
     preconds = []
     for o, F in factors.items():
         preconds += [(o, f"sweeps{a.sweeps}_{p}", F.sweeps(a.sweeps, precision=p)) for p in (("f64", "f32") if a.precision == "both" else (a.precision,))]
-        preconds.append((o, "exact", F))
+        preconds += [(o, "exact" if p == "f64" else "exact_f32", F.exact(p)) for p in (("f64", "f32") if a.exact_precision == "both" else (a.exact_precision,))]
     for order, label, M in preconds:
         if a.basis == "f64":
             S = mpk.gmres_solver(A, M, RESTART)
@@ -117,7 +122,7 @@ def main():
                     last[name].update(readbacks_last=info["readbacks_last"], wasted_steps_last=info["wasted_steps_last"], launches_last=info["launches_last"])
                     if a.basis != "f64":
                         last[name].update(ce[0].basis_info(), device_bytes=info["device_bytes"])
-        out = dict(tool="bench_gmres", cells=a.cells, rows=n, fill=a.fill, order=order, precond=label, restart=RESTART, rtol=RTOL, runs=a.runs,
+        out = dict(tool="bench_gmres", cells=a.cells, rows=n, fill=a.fill, order=order, precond=label, exact_precision=a.exact_precision, restart=RESTART, rtol=RTOL, runs=a.runs,
                    default_check_every=mpk.GMRES_CHECK_EVERY, solvers={})
         for name, _ in solvers:
             med = statistics.median(secs[name])

@@ -35,6 +35,15 @@ further handles created with MI355_BILU_WIDE_MIN set to each value (0: the wide 
 
     python3 tools/bench_ilu.py --order natural,colour [--wide-min 0,64,1024,4096,16384] [--sweeps 3,4] [--cells 68] [--fill 0]
 
+--exact-precision f64|f32|both (default f64): which values the EXACT solve streams — the double factor (the forms above), its
+single-precision copy (mi_bilu4spx_*, mpk.bilu4.exact("f32"): always level by level), or both on the SAME handle in the same
+process.  With f32 the record carries under "exact_f32" the microseconds per solve, its launches and those that were wide, the
+ratio to the double level-by-level solve measured on this handle just before and the ratio of the byte model (68 against 132
+bytes per block, 64 against 128 per inverted diagonal block, the vectors the same), and GMRES(30) with M = F.exact("f32").  Every
+record names what was asked for in "exact_precision".
+
+    python3 tools/bench_ilu.py --order natural,colour --exact-precision both [--cells 68] [--fill 0]
+
 --refactor measures the two refactorisations instead, in one process, and appends one record (tool = "bench_ilu_refactor"): the
 wall time of the host path mi_bilu4_refactor (factor on host threads, wait for the device, upload; median of --host-reps calls),
 the time of mi_bilu4dev_refactor between device events (median of --reps single refactors after warm-ups), launches per refactor,
@@ -215,6 +224,7 @@ def main():
     ap.add_argument("--form", choices=("both", "0", "1"), default="both")
     ap.add_argument("--sweeps", default="", help="comma-separated sweep counts per triangle")
     ap.add_argument("--precision", choices=("f64", "f32", "both"), default="f64", help="with --sweeps: the values the sweeps stream")
+    ap.add_argument("--exact-precision", choices=("f64", "f32", "both"), default="f64", help="the values the exact solve streams")
     ap.add_argument("--order", default="natural", help="comma-separated orderings of the block rows: natural, colour")
     ap.add_argument("--wide-min", default="", help="with the colour order: comma-separated MI355_BILU_WIDE_MIN values to time form 0 at (0: never wide)")
     ap.add_argument("--no-append", action="store_true")
@@ -296,8 +306,26 @@ def order_record(a, A, bv, order, diag_only_us):
                solve_us={names[f]: (None if us[f] is None else round(us[f], 2)) for f in (0, 1)},
                us_per_launch=round(solve_us / max(info["launches"], 1), 3) if forms[0] == 0 else None, bcsr4_spmv_us=round(spmv_us, 2),
                solve_over_spmv=round(solve_us / spmv_us, 2), forms=forms, one_launch_plan=one, one_launch_not_eligible=why_not,
-               one_over_levels=round(us[1] / us[0], 3) if len(forms) == 2 else None, gmres={})
-    for label, M, form in [("ilu" if f == 0 else "ilu_one_launch", F, f) for f in forms] + [("none", None, None)]:
+               one_over_levels=round(us[1] / us[0], 3) if len(forms) == 2 else None, exact_precision=a.exact_precision, gmres={})
+    Mx = None
+    if a.exact_precision != "f64":
+        # the comparison base: the double level-by-level solve on this handle, timed again right beside the f32 one
+        assert F.set_form(0) == 0
+        Mx = F.exact("f32")
+        Mx.solve(dx, db)  # (prepares the copy)
+        F.sweep_status_f32()
+        base_us = timed_us(lambda: F.solve(dx, db), 20, max(a.solves, 200))
+        x32_us = timed_us(lambda: Mx.solve(dx, db), 20, max(a.solves, 200))
+        xinfo = F.exact_info_f32()
+        offdiag = info["nblocks"] - nb
+        model = {prec: offdiag * blk + nb * dia + 2 * 2 * 32 * nb for prec, (blk, dia) in (("f64", (132, 128)), ("f32", (68, 64)))}
+        out["exact_f32"] = dict(us=round(x32_us, 2), f64_levels_us=round(base_us, 2), launches=xinfo["launches_last"], wide_launches=xinfo["wide_launches_last"],
+                                f32_over_f64=round(x32_us / base_us, 3), model_bytes=model, f32_over_f64_model=round(model["f32"] / model["f64"], 3),
+                                model_gb_per_s={"f64": round(model["f64"] / base_us * 1e-3, 1), "f32": round(model["f32"] / x32_us * 1e-3, 1)},
+                                f32_copy_bytes=F.sweep_info_f32()["copy_bytes"])
+        if a.exact_precision == "f32":
+            forms = []
+    for label, M, form in [("ilu" if f == 0 else "ilu_one_launch", F, f) for f in forms] + ([("ilu_exact_f32", Mx, 0)] if Mx else []) + [("none", None, None)]:
         if form is not None:
             assert F.set_form(form) == form
         dx.zero_()
