@@ -6,8 +6,10 @@
 // This kernel computes the positions [p0, p1) of one level with the software pipeline of bilu4_sweep (bilu4_sweep.hpp):
 // coefficients and gathered x blocks P deep, block columns one round ahead, indices clamped to the row's last block,
 // unconditional loads.  (The loop is restated here, not shared with bilu4_sweep: with the loop in a common __device__ function the
-// compiler's resource report for the double sweep kernel changes from 130 / 134 VGPRs and 3 waves per SIMD to 124 / 128 and 4 —
-// other code for an existing kernel, which wants its own measurement of the sweeps before it is taken.)
+// compiler's resource report for both double kernels changes from 130 / 134 VGPRs and 3 waves per SIMD to 124 / 128 and 4 — other
+// code, with the same bits.  Measured, profiles/NOTES.md R18.1: the double sweeps at counts 3 and 4 are then 1.9 % and 1.7 %
+// SLOWER on fe_matrix(24) at fill 1 (41.98 -> 42.76 and 54.38 -> 55.33 us), beyond the run-to-run range, and 2.8 % and 3.0 %
+// faster on fe_matrix(68) at fill 0; this kernel 0.8 % faster on the coloured fe_matrix(68).  Not taken: one case is slower.)
 //
 // Arithmetic: bilu4_row_value's sequence of roundings exactly — blocks ascending, bilu4_chain, one rounded subtraction, backward
 // the Dinv chain — so every bit equals bilu4_level's, and which of the two kernels a launch takes cannot change a result.

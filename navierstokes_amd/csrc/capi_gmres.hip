@@ -20,7 +20,7 @@ struct mi_gmres_s {
     mi_csr_t A_csr = nullptr;       // the operator: one of the two (not owned)
     mi_bcsr4_t A_bcsr = nullptr;
     mi_bilu4_t F = nullptr;         // the preconditioner (not owned), or null
-    int pc_kind = MI_GMRES_PC_EXACT, sf = 0, sb = 0;
+    Bilu4Apply pc{false, false, 0, 0}; // how F is applied (mi_gmres_set_precond*)
     DevArray<double> V;             // (m + 1) rows of ldv (MI_BASIS_F64 only)
     DevArray<float> V32;            // (m + 1) rows of ldv32 (MI_BASIS_F32 only), and q: widen(the newest row), what the next product reads
     DevArray<double> q;
@@ -115,12 +115,18 @@ extern "C" int mi_gmres_set_operator_bcsr4(mi_gmres_t G, mi_bcsr4_t A)
     return MI_OK;
 }
 
+// MI_GMRES_PC_* -> how the factor is applied: what makes a kind valid, and what decides which prepare it needs
+static const Bilu4Apply kGmresPc[] = {{false, false, 0, 0}, {true, false, 0, 0}, {true, true, 0, 0}, {false, true, 0, 0}}; // EXACT, SWEEPS, SWEEPS_F32, EXACT_F32
+static_assert(MI_GMRES_PC_EXACT == 0 && MI_GMRES_PC_SWEEPS == 1 && MI_GMRES_PC_SWEEPS_F32 == 2 && MI_GMRES_PC_EXACT_F32 == 3, "kGmresPc is indexed by kind");
+
 // kind and counts are checked first (with a preconditioner they are wrong whatever the solver is), then the handle
 extern "C" int mi_gmres_set_precond_ex(mi_gmres_t G, mi_bilu4_t F, int kind, int sweeps_fwd, int sweeps_bwd)
 {
-    const bool sweeps = kind == MI_GMRES_PC_SWEEPS || kind == MI_GMRES_PC_SWEEPS_F32;
-    CHECK_ARG(!F || sweeps || kind == MI_GMRES_PC_EXACT || kind == MI_GMRES_PC_EXACT_F32, "unknown preconditioner kind");
-    CHECK_ARG(!F || !sweeps || (sweeps_fwd >= 0 && sweeps_bwd >= 0), "negative sweep count");
+    const bool known = kind >= 0 && kind < (int)(sizeof(kGmresPc) / sizeof(kGmresPc[0]));
+    CHECK_ARG(!F || known, "unknown preconditioner kind");
+    Bilu4Apply how = kGmresPc[known ? kind : 0];
+    how.sf = sweeps_fwd, how.sb = sweeps_bwd;
+    CHECK_ARG(!F || !how.sweeps || (sweeps_fwd >= 0 && sweeps_bwd >= 0), "negative sweep count");
     CHECK_ARG(G, "null handle");
     if (!F) {
         G->F = nullptr;
@@ -130,10 +136,8 @@ extern "C" int mi_gmres_set_precond_ex(mi_gmres_t G, mi_bilu4_t F, int kind, int
     int nb = 0, rc;
     if ((rc = mi_bilu4_info(F, &nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
     CHECK_ARG(4LL * nb == G->n, "the preconditioner's row count (4 nbrows) is not the solver's n");
-    // everything a solve would otherwise allocate on first use
-    if (kind == MI_GMRES_PC_SWEEPS && (rc = mi_bilu4sw_prepare(F))) return rc;
-    if ((kind == MI_GMRES_PC_SWEEPS_F32 || kind == MI_GMRES_PC_EXACT_F32) && (rc = mi_bilu4sp_prepare(F))) return rc;
-    G->F = F, G->pc_kind = kind, G->sf = sweeps_fwd, G->sb = sweeps_bwd;
+    if ((rc = bilu4_apply_prepare(F, how))) return rc; // everything a solve would otherwise allocate on first use
+    G->F = F, G->pc = how;
     G->gen++;
     return MI_OK;
 }
@@ -164,15 +168,7 @@ static int gmres_combine(mi_gmres_s* G, int k, double* out, mi_stream_t s)
                     : mi_maxpy_dev(G->n, k, S.y(), 0, G->Vptr.data(), out, nullptr, s);
 }
 
-static int gmres_precond(mi_gmres_s* G, const double* in, double* out, mi_stream_t s)
-{
-    switch (G->pc_kind) {
-    case MI_GMRES_PC_SWEEPS: return mi_bilu4sw_solve_dev(G->F, in, out, G->sf, G->sb, s);
-    case MI_GMRES_PC_SWEEPS_F32: return mi_bilu4sp_solve_dev(G->F, in, out, G->sf, G->sb, s);
-    case MI_GMRES_PC_EXACT_F32: return mi_bilu4spx_solve_dev(G->F, in, out, s);
-    default: return mi_bilu4_solve_dev(G->F, in, out, s);
-    }
-}
+static int gmres_precond(mi_gmres_s* G, const double* in, double* out, mi_stream_t s) { return bilu4_apply_dev(G->F, G->pc, in, out, (hipStream_t)s); }
 
 static int gmres_need_operator(const mi_gmres_s* G, const char* who)
 {

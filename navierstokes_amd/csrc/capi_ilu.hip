@@ -1,13 +1,13 @@
 // capi_ilu.hip: the 4x4-block ILU(k) preconditioner, mi_bilu4_* — part of libmi355spmv.so (see capi_internal.hpp for the layout of
-// the library).  Factored on the host (bilu4_plan.hpp), solved on the GPU by one launch per (folded) dependency level
-// (bilu4_solve.hpp) or, where the handle was told so (mi_bilu4_set_solve_form), by ONE launch of persistent workgroups
-// (bilu4_solve_one.hpp, mi_bilu4one_*); mi_bilu4dev_* refactors on the GPU, into the same device copies, level by level
-// (bilu4_factor.hpp); mi_bilu4sw_* applies the same device factor by a fixed number of Jacobi sweeps per triangle, one launch per
-// sweep (bilu4_sweep.hpp); mi_bilu4sp_* the same sweeps over an opt-in single-precision copy of the factor's values, which every
-// entry point that writes the factor then keeps current; mi_bilu4spx_* the exact level-by-level solve over that copy (the float
-// instantiations of the solve's kernels).  mi_bilu4_create_ordered puts a multicolour ordering behind the handle
-// (bilu4_order.hpp): the factor is then that of the permuted matrix, every solve is bracketed by a gather and a scatter
-// (bilu_in_order, the one place), and wide unfolded levels take bilu4_level_wide (bilu4_solve_wide.hpp).
+// the library).  Factored on the host (bilu4_plan.hpp) or, into the same device copies, on the GPU level by level (mi_bilu4dev_*,
+// bilu4_factor.hpp).  Applied on the GPU in one of four ways, a Bilu4Apply each, through ONE path (bilu_apply, at the end of the
+// file): exactly — one launch per (folded) dependency level (bilu4_solve.hpp) or, where the handle was told so
+// (mi_bilu4_set_solve_form), one launch of persistent workgroups (bilu4_solve_one.hpp, mi_bilu4one_*) — or by a fixed number of
+// Jacobi sweeps per triangle, one launch per sweep (mi_bilu4sw_*, bilu4_sweep.hpp); either over the factor's doubles or over an
+// opt-in single-precision copy of its values (mi_bilu4sp_* the sweeps, mi_bilu4spx_* the exact solve), which every entry point
+// that writes the factor keeps current.  mi_bilu4_create_ordered puts a multicolour ordering behind the handle (bilu4_order.hpp):
+// the factor is then that of the permuted matrix, every solve is bracketed by a gather and a scatter (bilu_in_order, the one
+// place), and wide unfolded levels take bilu4_level_wide (bilu4_solve_wide.hpp).
 // No CPU fallback: the solve and the device refactor need a HIP device; the planning and host factorisation entry points need none.
 #include "capi_internal.hpp"
 #include "bilu4_plan.hpp"
@@ -137,17 +137,24 @@ static int bilu_check_args(int nbrows, const int* ptrow, const int* indcol, int 
 
 // What the device entry points begin with: MI_ERR_ARG without a handle or with a bad argument (bad_arg: what is wrong with the
 // arguments that are checked even on an empty matrix; bad_data: with those that are not), MI_OK at once on an empty matrix,
-// MI_ERR_STATE on a host-only handle.  kBiluGo: none of these, go on.
+// host_only's status on a host-only handle.  kBiluGo: none of these, go on.
 constexpr int kBiluGo = -1;
-static const char* const kHostOnlyDev = ": a host-only handle (mi_bilu4_create_host) has no device factor";
 
-static int bilu_dev_guard(const mi_bilu4_s* F, const char* name, const char* bad_arg = nullptr, const char* bad_data = nullptr)
+// what a host-only handle gets: MI_ERR_STATE, but MI_ERR_NODEVICE from everything about sweeps and the single-precision copy
+struct BiluHostOnly {
+    int status;
+    const char* tail;
+};
+constexpr BiluHostOnly kHostOnlyDev{MI_ERR_STATE, ": a host-only handle (mi_bilu4_create_host) has no device factor"};
+constexpr BiluHostOnly kHostOnlySweep{MI_ERR_NODEVICE, ": a host-only handle (mi_bilu4_create_host) has no device factor, and the sweep solve has no CPU fallback"};
+
+static int bilu_guard(const mi_bilu4_s* F, const char* name, const BiluHostOnly& host_only, const char* bad_arg = nullptr, const char* bad_data = nullptr)
 {
     CHECK_ARG(F, "null handle");
     CHECK_ARG(!bad_arg, bad_arg);
     if (F->pat().nb == 0) return MI_OK;
     CHECK_ARG(!bad_data, bad_data);
-    if (F->device < 0) return fail(MI_ERR_STATE, std::string(name) + kHostOnlyDev);
+    if (F->device < 0) return fail(host_only.status, std::string(name) + host_only.tail);
     return kBiluGo;
 }
 
@@ -189,12 +196,25 @@ static int bilu_upload_pattern(const mi_bilu4_s* F, int b, Bilu4DevSweep* D)
     return MI_OK;
 }
 
-// the values between the host factor and the level-major device copies — the L blocks, the U blocks, the inverted diagonal blocks by
-// backward position — to the device (create, mi_bilu4_refactor) or back (mi_bilu4dev_fetch)
+// THE ONE LISTING of the factor's three level-major value arrays — the L blocks, the U blocks, the inverted diagonal blocks by
+// backward position: fn(doubles, floats, blocks, host_block) for each in that order, where floats is the array's place in the
+// single-precision copy S (the handle's, or one still being built) and host_block(k) the place of its block k in the host factor
+template <class Fn>
+static int bilu_each_values(const mi_bilu4_s* F, Bilu4SpCopy& S, Fn&& fn)
+{
+    for (int b = 0; b < 2; b++) {
+        const Bilu4DevSweep& D = F->lev[b];
+        if (const int rc = fn((double*)D.val, S.val[b], D.src.size(), [&](size_t k) { return D.src[k]; })) return rc;
+    }
+    return fn((double*)F->lev[1].dinv, S.dinv, (size_t)F->pat().nb, [&](size_t q) { return F->pat().diag[F->sched.sweep[1].perm[q]]; });
+}
+
+// the values between the host factor and the level-major device copies, to the device (create, mi_bilu4_refactor) or back
+// (mi_bilu4dev_fetch)
 static int bilu_move_values(mi_bilu4_s* F, bool to_device)
 {
     std::vector<double> v;
-    auto move = [&](double* dev, size_t n, auto&& host_block) -> int {
+    return bilu_each_values(F, F->sp, [&](double* dev, DevArray<float>&, size_t n, auto&& host_block) -> int {
         if (!n) return MI_OK;
         v.resize(16 * n);
         if (!to_device) HIP_TRY(hipMemcpy(v.data(), dev, sizeof(double) * v.size(), hipMemcpyDeviceToHost));
@@ -204,11 +224,7 @@ static int bilu_move_values(mi_bilu4_s* F, bool to_device)
         }
         if (to_device) HIP_TRY(hipMemcpy(dev, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice));
         return MI_OK;
-    };
-    int rc;
-    for (const Bilu4DevSweep& D : F->lev)
-        if ((rc = move(D.val, D.src.size(), [&](size_t k) { return D.src[k]; }))) return rc;
-    return move(F->lev[1].dinv, (size_t)F->pat().nb, [&](size_t q) { return F->pat().diag[F->sched.sweep[1].perm[q]]; });
+    });
 }
 
 // the kernels' AL: x may be read and written as 16-byte pairs
@@ -332,31 +348,21 @@ static int bilu_solve_one_launch(mi_bilu4_s* F, const double* d_b, double* d_x, 
     return MI_OK;
 }
 
-// what mi_bilu4_solve* enqueue: the handle's form — except under stream capture, where the level-by-level form is recorded (the
-// one-launch form's epoch is a kernel argument: a replayed graph would present it again and every wait would pass at once)
-static int bilu_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
-{
-    if (bilu_one_gave_up(F)) return fail(MI_ERR_HIP, kOneGaveUp);
-    return bilu_in_order(F, d_b, d_x, s, [&](const double* b, double* x) {
-        if (F->form == MI_BILU_FORM_ONE && !stream_is_capturing(s)) return bilu_solve_one_launch(F, b, x, s);
-        return bilu_solve_launch(F, b, x, s);
-    });
-}
-
 // The single-precision copy written from the level-major factor as it lies on the device now, on stream s: two launches (the record
 // of mi_bilu4sp_status cleared, then the values), nothing allocated or synchronised.  S: the copy to write — the handle's, or the
 // one mi_bilu4sp_prepare is still building.
 static int bilu_sp_convert(const mi_bilu4_s* F, Bilu4SpCopy& S, hipStream_t s)
 {
     Bilu4SpConvert C{};
-    const long long nL = (long long)F->lev[0].src.size(), nU = (long long)F->lev[1].src.size(), nb = F->pat().nb;
-    const double* const src[3] = {F->lev[0].val, F->lev[1].val, F->lev[1].dinv};
-    float* const dst[3] = {S.val[0], S.val[1], S.dinv};
-    const long long blocks[3] = {nL, nU, nb};
     long long end = 0;
-    for (int a = 0; a < 3; a++) C.src[a] = src[a], C.dst[a] = dst[a], C.end[a] = (end += 4 * blocks[a]);
+    int a = 0;
+    bilu_each_values(F, S, [&](const double* src, DevArray<float>& dst, size_t blocks, auto&&) {
+        C.src[a] = src, C.dst[a] = dst, C.end[a] = (end += 4 * (long long)blocks);
+        a++;
+        return MI_OK;
+    });
     for (int b = 0; b < 2; b++) C.ptr[b] = F->lev[b].ptr, C.perm[b] = F->lev[b].perm;
-    C.nb = (int)nb;
+    C.nb = F->pat().nb;
     C.rec = S.rec;
     hipLaunchKernelGGL(bilu4sp_reset, dim3(1), dim3(1), 0, s, C.rec);
     hipLaunchKernelGGL(bilu4sp_convert, dim3((unsigned)((end + kWG - 1) / kWG)), dim3(kWG), 0, s, C);
@@ -504,23 +510,6 @@ extern "C" int mi_bilu4_refactor(mi_bilu4_t F, const double* coef, int layout)
     return MI_OK;
 }
 
-extern "C" int mi_bilu4_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s)
-{
-    if (const int rc = bilu_dev_guard(F, "mi_bilu4_solve", nullptr, d_b && d_x ? nullptr : "null vector"); rc != kBiluGo) return rc;
-    return bilu_solve_any(F, d_b, d_x, (hipStream_t)s);
-}
-
-extern "C" int mi_bilu4_solve(mi_bilu4_t F, const double* b, double* x)
-{
-    if (const int rc = bilu_dev_guard(F, "mi_bilu4_solve", nullptr, b && x ? nullptr : "null vector"); rc != kBiluGo) return rc;
-    const size_t bytes = sizeof(double) * 4 * (size_t)F->pat().nb;
-    HIP_TRY(hipMemcpy(F->d_b, b, bytes, hipMemcpyHostToDevice));
-    int rc = bilu_solve_any(F, F->d_b, F->d_x, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(x, F->d_x, bytes, hipMemcpyDeviceToHost));
-    return MI_OK;
-}
-
 extern "C" int mi_bilu4_info(mi_bilu4_t F, int* nbrows, long long* nblocks, int* fwd_levels, int* bwd_levels, int* launches, int* form,
                              double us[2], double* factor_seconds, long long* factor_bytes)
 {
@@ -592,7 +581,7 @@ extern "C" int mi_bilu4dev_plan_probe(int nbrows, const int* ptrow, const int* i
 
 extern "C" int mi_bilu4dev_prepare(mi_bilu4_t F)
 {
-    if (const int rc = bilu_dev_guard(F, "mi_bilu4dev_prepare"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4dev_prepare", kHostOnlyDev); rc != kBiluGo) return rc;
     if (F->dev.prepared) return MI_OK;
     Bilu4DevPlan D;
     bilu4dev_plan(F->sched, F->a_ptr.data(), F->a_col.data(), &D, F->ord.src_or_null());
@@ -609,7 +598,7 @@ extern "C" int mi_bilu4dev_prepare(mi_bilu4_t F)
 
 extern "C" int mi_bilu4dev_refactor(mi_bilu4_t F, const double* d_coef, int layout, mi_stream_t s)
 {
-    if (const int rc = bilu_dev_guard(F, "mi_bilu4dev_refactor", bilu_bad_layout(layout), d_coef ? nullptr : "null coef"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4dev_refactor", kHostOnlyDev, bilu_bad_layout(layout), d_coef ? nullptr : "null coef"); rc != kBiluGo) return rc;
     int rc;
     if (!F->dev.prepared && (rc = mi_bilu4dev_prepare(F))) return rc;
     hipStream_t st = (hipStream_t)s;
@@ -634,7 +623,7 @@ extern "C" int mi_bilu4dev_refactor(mi_bilu4_t F, const double* d_coef, int layo
 extern "C" int mi_bilu4dev_status(mi_bilu4_t F, int* bad_row)
 {
     if (F && bad_row) *bad_row = -1;
-    if (const int rc = bilu_dev_guard(F, "mi_bilu4dev_status"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4dev_status", kHostOnlyDev); rc != kBiluGo) return rc;
     if (!F->dev.prepared) return MI_OK; // no device refactor yet
     HIP_TRY(hipDeviceSynchronize());
     int bad = kBiluBadNone;
@@ -647,7 +636,7 @@ extern "C" int mi_bilu4dev_status(mi_bilu4_t F, int* bad_row)
 
 extern "C" int mi_bilu4dev_fetch(mi_bilu4_t F)
 {
-    if (const int rc = bilu_dev_guard(F, "mi_bilu4dev_fetch"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4dev_fetch", kHostOnlyDev); rc != kBiluGo) return rc;
     HIP_TRY(hipDeviceSynchronize());
     return bilu_move_values(F, false);
 }
@@ -701,7 +690,7 @@ extern "C" int mi_bilu4one_plan_probe(int nbrows, const int* ptrow, const int* i
 
 extern "C" int mi_bilu4one_prepare(mi_bilu4_t F)
 {
-    if (const int rc = bilu_dev_guard(F, "mi_bilu4one_prepare"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4one_prepare", kHostOnlyDev); rc != kBiluGo) return rc;
     if (F->one.state == 1) return MI_OK;
     if (F->one.state < 0) return fail(MI_ERR_UNSUPPORTED, F->one.why);
     Bilu4OnePlan O;
@@ -765,7 +754,7 @@ static int bilu_one_reset(mi_bilu4_s* F)
 extern "C" int mi_bilu4_set_solve_form(mi_bilu4_t F, int form)
 {
     const bool known = form == MI_BILU_FORM_LEVELS || form == MI_BILU_FORM_ONE || form == MI_BILU_FORM_AUTO;
-    if (const int rc = bilu_dev_guard(F, "mi_bilu4_set_solve_form", known ? nullptr : "unknown solve form (0: one launch per level, 1: one launch, -1: measure and choose)"); rc != kBiluGo)
+    if (const int rc = bilu_guard(F, "mi_bilu4_set_solve_form", kHostOnlyDev, known ? nullptr : "unknown solve form (0: one launch per level, 1: one launch, -1: measure and choose)"); rc != kBiluGo)
         return rc;
     int rc;
     if (form == MI_BILU_FORM_LEVELS) {
@@ -805,7 +794,7 @@ extern "C" int mi_bilu4_set_solve_form(mi_bilu4_t F, int form)
 
 extern "C" int mi_bilu4one_status(mi_bilu4_t F)
 {
-    if (const int rc = bilu_dev_guard(F, "mi_bilu4one_status"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4one_status", kHostOnlyDev); rc != kBiluGo) return rc;
     if (bilu_one_gave_up(F)) return fail(MI_ERR_HIP, kOneGaveUp);
     return MI_OK;
 }
@@ -826,19 +815,6 @@ extern "C" int mi_bilu4one_info(mi_bilu4_t F, int* prepared, int* eligible, int*
 }
 
 // ---------------------------------------------------------------- mi_bilu4sw_*: the factor applied by fixed Jacobi sweeps
-static const char* const kHostOnlySweep = ": a host-only handle (mi_bilu4_create_host) has no device factor, and the sweep solve has no CPU fallback";
-
-// What the sweep entry points begin with, in the order of bilu_dev_guard — except that a host-only handle is MI_ERR_NODEVICE here
-static int bilu_sw_guard(const mi_bilu4_s* F, const char* name, const char* bad_arg = nullptr, const char* bad_data = nullptr)
-{
-    CHECK_ARG(F, "null handle");
-    CHECK_ARG(!bad_arg, bad_arg);
-    if (F->pat().nb == 0) return MI_OK;
-    CHECK_ARG(!bad_data, bad_data);
-    if (F->device < 0) return fail(MI_ERR_NODEVICE, std::string(name) + kHostOnlySweep);
-    return kBiluGo;
-}
-
 static const char* bilu_sw_bad_counts(int sf, int sb) { return sf < 0 || sb < 0 ? "negative sweep count" : nullptr; }
 
 // levels - 1 of sweep b: the count at which the sweeps have reached the exact solve's bits, where counts are clamped
@@ -891,41 +867,13 @@ static int bilu_sw_solve_launch(mi_bilu4_s* F, const Bilu4SweepVals<T>& Lv, cons
 
 extern "C" int mi_bilu4sw_prepare(mi_bilu4_t F)
 {
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4sw_prepare"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4sw_prepare", kHostOnlySweep); rc != kBiluGo) return rc;
     if (F->sw.prepared) return MI_OK;
     Bilu4SweepWork W; // moves into the handle once it is complete; a failure on the way frees what there is
     for (DevArray<double>& v : W.w) // (uninitialised: every sweep writes all rows of its output before anything reads them)
         if (const int rc = dev_alloc(v, 4 * (size_t)F->pat().nb, 1)) return rc;
     W.prepared = true;
     F->sw = std::move(W);
-    return MI_OK;
-}
-
-static int bilu_sw_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, int sf, int sb, hipStream_t s)
-{
-    if (!F->sw.prepared) {
-        if (stream_is_capturing(s))
-            return fail(MI_ERR_STATE, "mi_bilu4sw_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sw_prepare allocates: call it before the capture)");
-        if (const int rc = mi_bilu4sw_prepare(F)) return rc;
-    }
-    return bilu_in_order(F, d_b, d_x, s, [&](const double* b, double* x) {
-        return bilu_sw_solve_launch<double>(F, {F->lev[0].val, nullptr}, {F->lev[1].val, F->lev[1].dinv}, &F->sw.launches_last, b, x, sf, sb, s);
-    });
-}
-
-extern "C" int mi_bilu4sw_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s)
-{
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4sw_solve_dev", bilu_sw_bad_counts(sweeps_fwd, sweeps_bwd), d_b && d_x ? nullptr : "null vector"); rc != kBiluGo) return rc;
-    return bilu_sw_solve_any(F, d_b, d_x, sweeps_fwd, sweeps_bwd, (hipStream_t)s);
-}
-
-extern "C" int mi_bilu4sw_solve(mi_bilu4_t F, const double* b, double* x, int sweeps_fwd, int sweeps_bwd)
-{
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4sw_solve", bilu_sw_bad_counts(sweeps_fwd, sweeps_bwd), b && x ? nullptr : "null vector"); rc != kBiluGo) return rc;
-    const size_t bytes = sizeof(double) * 4 * (size_t)F->pat().nb;
-    HIP_TRY(hipMemcpy(F->d_b, b, bytes, hipMemcpyHostToDevice));
-    if (const int rc = bilu_sw_solve_any(F, F->d_b, F->d_x, sweeps_fwd, sweeps_bwd, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(x, F->d_x, bytes, hipMemcpyDeviceToHost));
     return MI_OK;
 }
 
@@ -943,12 +891,12 @@ extern "C" int mi_bilu4sw_info(mi_bilu4_t F, int* prepared, int* max_fwd, int* m
 // ---------------------------------------------------------------- mi_bilu4sp_*: the sweeps over a single-precision copy of the values
 extern "C" int mi_bilu4sp_prepare(mi_bilu4_t F)
 {
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_prepare"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4sp_prepare", kHostOnlySweep); rc != kBiluGo) return rc;
     if (F->sp.prepared) return MI_OK;
     Bilu4SpCopy S; // moves into the handle once it is complete; a failure on the way frees what there is
     int rc;
-    if ((rc = dev_alloc(S.val[0], 16 * std::max<size_t>(F->lev[0].src.size(), 1))) || (rc = dev_alloc(S.val[1], 16 * std::max<size_t>(F->lev[1].src.size(), 1))) ||
-        (rc = dev_alloc(S.dinv, 16 * (size_t)F->pat().nb, 1)) || (rc = dev_alloc(S.rec, 1)))
+    if ((rc = bilu_each_values(F, S, [](const double*, DevArray<float>& copy, size_t blocks, auto&&) { return dev_alloc(copy, 16 * std::max<size_t>(blocks, 1)); })) ||
+        (rc = dev_alloc(S.rec, 1)))
         return rc;
     // the factor as it is now: behind everything that was enqueued to write it, and finished before the first solve on any stream
     HIP_TRY(hipDeviceSynchronize());
@@ -960,39 +908,11 @@ extern "C" int mi_bilu4sp_prepare(mi_bilu4_t F)
     return MI_OK;
 }
 
-static int bilu_sp_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, int sf, int sb, hipStream_t s)
-{
-    if (!F->sp.prepared) {
-        if (stream_is_capturing(s))
-            return fail(MI_ERR_STATE, "mi_bilu4sp_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sp_prepare allocates and converts: call it before the capture)");
-        if (const int rc = mi_bilu4sp_prepare(F)) return rc;
-    }
-    return bilu_in_order(F, d_b, d_x, s, [&](const double* b, double* x) {
-        return bilu_sw_solve_launch<float>(F, {F->sp.val[0], nullptr}, {F->sp.val[1], F->sp.dinv}, &F->sp.launches_last, b, x, sf, sb, s);
-    });
-}
-
-extern "C" int mi_bilu4sp_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s)
-{
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_solve_dev", bilu_sw_bad_counts(sweeps_fwd, sweeps_bwd), d_b && d_x ? nullptr : "null vector"); rc != kBiluGo) return rc;
-    return bilu_sp_solve_any(F, d_b, d_x, sweeps_fwd, sweeps_bwd, (hipStream_t)s);
-}
-
-extern "C" int mi_bilu4sp_solve(mi_bilu4_t F, const double* b, double* x, int sweeps_fwd, int sweeps_bwd)
-{
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_solve", bilu_sw_bad_counts(sweeps_fwd, sweeps_bwd), b && x ? nullptr : "null vector"); rc != kBiluGo) return rc;
-    const size_t bytes = sizeof(double) * 4 * (size_t)F->pat().nb;
-    HIP_TRY(hipMemcpy(F->d_b, b, bytes, hipMemcpyHostToDevice));
-    if (const int rc = bilu_sp_solve_any(F, F->d_b, F->d_x, sweeps_fwd, sweeps_bwd, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(x, F->d_x, bytes, hipMemcpyDeviceToHost));
-    return MI_OK;
-}
-
 extern "C" int mi_bilu4sp_status(mi_bilu4_t F, int* bad_block_row, long long* overflowed)
 {
     if (F && bad_block_row) *bad_block_row = -1;
     if (F && overflowed) *overflowed = 0;
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_status"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4sp_status", kHostOnlySweep); rc != kBiluGo) return rc;
     if (!F->sp.prepared) return MI_OK; // no copy yet
     HIP_TRY(hipDeviceSynchronize());
     Bilu4SpRecord R{};
@@ -1007,23 +927,19 @@ extern "C" int mi_bilu4sp_status(mi_bilu4_t F, int* bad_block_row, long long* ov
 
 extern "C" int mi_bilu4sp_fetch(mi_bilu4_t F, float* val, long long cap_blocks)
 {
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4sp_fetch", nullptr, val ? nullptr : "null val"); rc != kBiluGo) return rc;
+    if (const int rc = bilu_guard(F, "mi_bilu4sp_fetch", kHostOnlySweep, nullptr, val ? nullptr : "null val"); rc != kBiluGo) return rc;
     CHECK_ARG(cap_blocks >= F->pat().nblocks(), "array too short: need mi_bilu4_info's nblocks blocks of 16 floats");
     if (!F->sp.prepared) return fail(MI_ERR_STATE, "mi_bilu4sp_fetch: the handle is not prepared (mi_bilu4sp_prepare)");
     HIP_TRY(hipDeviceSynchronize());
     // as bilu_move_values brings the double factor back: each level-major block to its place in the host factor's order
     std::vector<float> v;
-    auto fetch = [&](const float* dev, size_t n, auto&& host_block) -> int {
+    return bilu_each_values(F, F->sp, [&](const double*, DevArray<float>& copy, size_t n, auto&& host_block) -> int {
         if (!n) return MI_OK;
         v.resize(16 * n);
-        HIP_TRY(hipMemcpy(v.data(), dev, sizeof(float) * v.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(v.data(), copy, sizeof(float) * v.size(), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < n; k++) memcpy(val + 16 * (size_t)host_block(k), &v[16 * k], sizeof(float) * 16);
         return MI_OK;
-    };
-    int rc;
-    for (int b = 0; b < 2; b++)
-        if ((rc = fetch(F->sp.val[b], F->lev[b].src.size(), [&](size_t k) { return F->lev[b].src[k]; }))) return rc;
-    return fetch(F->sp.dinv, (size_t)F->pat().nb, [&](size_t q) { return F->pat().diag[F->sched.sweep[1].perm[q]]; });
+    });
 }
 
 extern "C" int mi_bilu4sp_info(mi_bilu4_t F, int* prepared, int* convert_launches, int* launches_last, long long* copy_bytes)
@@ -1036,41 +952,108 @@ extern "C" int mi_bilu4sp_info(mi_bilu4_t F, int* prepared, int* convert_launche
     return MI_OK;
 }
 
-// ---------------------------------------------------------------- mi_bilu4spx_*: the EXACT solve over the single-precision copy
-// The level-by-level solve of mi_bilu4_solve* with the copy's floats in place of the factor's doubles: the same schedule, the same
-// launch rule (folded runs, bilu4_level, on an ordered handle bilu4_level_wide), the float instantiations of the same kernels.
-// Always level by level, whatever the handle's form: the one-launch form is not a template over the stored type.
-static int bilu_spx_solve_any(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s)
+// ---------------------------------------------------------------- the one apply path: every solve entry point, and GMRES's step
+// A way of applying the factor is a Bilu4Apply (capi_internal.hpp); what differs between the four is this table's row and the
+// launcher bilu_apply picks.  The exact solve over the single-precision copy (mi_bilu4spx_*) is that of mi_bilu4_solve* with the
+// float instantiations of the same kernels — always level by level: the one-launch form is not a template over the stored type.
+struct Bilu4Way {
+    const char *name_dev, *name_host; // as the two entry points report themselves
+    BiluHostOnly host_only;
+    int (*prepare)(mi_bilu4_t);       // what a first solve needs made (null: nothing) ...
+    const char* unprepared_capturing; // ... and cannot make while the stream is capturing
+};
+static const Bilu4Way kBiluWays[2][2] = { // [sweeps][f32]
+    {{"mi_bilu4_solve", "mi_bilu4_solve", kHostOnlyDev, nullptr, nullptr},
+     {"mi_bilu4spx_solve_dev", "mi_bilu4spx_solve", kHostOnlySweep, mi_bilu4sp_prepare,
+      "mi_bilu4spx_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sp_prepare allocates and converts: call it before the capture)"}},
+    {{"mi_bilu4sw_solve_dev", "mi_bilu4sw_solve", kHostOnlySweep, mi_bilu4sw_prepare,
+      "mi_bilu4sw_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sw_prepare allocates: call it before the capture)"},
+     {"mi_bilu4sp_solve_dev", "mi_bilu4sp_solve", kHostOnlySweep, mi_bilu4sp_prepare,
+      "mi_bilu4sp_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sp_prepare allocates and converts: call it before the capture)"}},
+};
+static const Bilu4Way& bilu_way(const Bilu4Apply& how) { return kBiluWays[how.sweeps][how.f32]; }
+
+int bilu4_apply_prepare(mi_bilu4_t F, const Bilu4Apply& how) { return bilu_way(how).prepare ? bilu_way(how).prepare(F) : MI_OK; }
+
+static int bilu_ensure(mi_bilu4_s* F, const Bilu4Apply& how, hipStream_t s)
 {
-    if (!F->sp.prepared) {
-        if (stream_is_capturing(s))
-            return fail(MI_ERR_STATE, "mi_bilu4spx_solve_dev: the handle is not prepared and the stream is capturing (mi_bilu4sp_prepare allocates and converts: call it before the capture)");
-        if (const int rc = mi_bilu4sp_prepare(F)) return rc;
-    }
+    const Bilu4Way& W = bilu_way(how);
+    if (!W.prepare || (how.f32 ? F->sp.prepared : F->sw.prepared)) return MI_OK;
+    if (stream_is_capturing(s)) return fail(MI_ERR_STATE, W.unprepared_capturing);
+    return W.prepare(F);
+}
+
+// d_x = the factor applied to d_b, enqueued on s.  The exact solve in double takes the handle's form — except under stream capture,
+// where the level-by-level form is recorded (the one-launch form's epoch is a kernel argument: a replayed graph would present it
+// again and every wait would pass at once) — and is the one way that refuses once a hand-off wait has given up.
+static int bilu_apply(mi_bilu4_s* F, const Bilu4Apply& how, const double* d_b, double* d_x, hipStream_t s)
+{
+    if (!how.sweeps && !how.f32 && bilu_one_gave_up(F)) return fail(MI_ERR_HIP, kOneGaveUp);
+    if (const int rc = bilu_ensure(F, how, s)) return rc;
+    const Bilu4SweepVals<double> L64{F->lev[0].val, nullptr}, U64{F->lev[1].val, F->lev[1].dinv};
+    const Bilu4SweepVals<float> L32{F->sp.val[0], nullptr}, U32{F->sp.val[1], F->sp.dinv};
     const int rc = bilu_in_order(F, d_b, d_x, s, [&](const double* b, double* x) {
-        return bilu_solve_launch<float>(F, {F->sp.val[0], nullptr}, {F->sp.val[1], F->sp.dinv}, b, x, s);
+        if (how.sweeps)
+            return how.f32 ? bilu_sw_solve_launch(F, L32, U32, &F->sp.launches_last, b, x, how.sf, how.sb, s)
+                           : bilu_sw_solve_launch(F, L64, U64, &F->sw.launches_last, b, x, how.sf, how.sb, s);
+        if (how.f32) return bilu_solve_launch(F, L32, U32, b, x, s);
+        if (F->form == MI_BILU_FORM_ONE && !stream_is_capturing(s)) return bilu_solve_one_launch(F, b, x, s);
+        return bilu_solve_launch(F, L64, U64, b, x, s);
     });
-    if (rc) return rc;
+    if (rc || how.sweeps || !how.f32) return rc;
     F->sp.exact_launches_last = F->sched.sweep[0].nlaunch() + F->sched.sweep[1].nlaunch() + (F->ord.on() ? kBiluOrderLaunches : 0);
     F->sp.exact_wide_last = bilu_wide_launches(F);
     return MI_OK;
 }
 
-extern "C" int mi_bilu4spx_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s)
+// the host-pointer form: through the handle's two scratch vectors, on the null stream
+static int bilu_apply_host(mi_bilu4_s* F, const Bilu4Apply& how, const double* b, double* x)
 {
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4spx_solve_dev", nullptr, d_b && d_x ? nullptr : "null vector"); rc != kBiluGo) return rc;
-    return bilu_spx_solve_any(F, d_b, d_x, (hipStream_t)s);
-}
-
-extern "C" int mi_bilu4spx_solve(mi_bilu4_t F, const double* b, double* x)
-{
-    if (const int rc = bilu_sw_guard(F, "mi_bilu4spx_solve", nullptr, b && x ? nullptr : "null vector"); rc != kBiluGo) return rc;
     const size_t bytes = sizeof(double) * 4 * (size_t)F->pat().nb;
     HIP_TRY(hipMemcpy(F->d_b, b, bytes, hipMemcpyHostToDevice));
-    if (const int rc = bilu_spx_solve_any(F, F->d_b, F->d_x, nullptr)) return rc;
+    if (const int rc = bilu_apply(F, how, F->d_b, F->d_x, nullptr)) return rc;
     HIP_TRY(hipMemcpy(x, F->d_x, bytes, hipMemcpyDeviceToHost));
     return MI_OK;
 }
+
+// a solve entry point: its family's guard, then the one path.  host: b and x are host pointers (and s is not looked at)
+static int bilu_solve_entry(mi_bilu4_s* F, const Bilu4Apply& how, bool host, const double* b, double* x, hipStream_t s)
+{
+    const Bilu4Way& W = bilu_way(how);
+    const char* const bad_counts = how.sweeps ? bilu_sw_bad_counts(how.sf, how.sb) : nullptr;
+    if (const int rc = bilu_guard(F, host ? W.name_host : W.name_dev, W.host_only, bad_counts, b && x ? nullptr : "null vector"); rc != kBiluGo) return rc;
+    return host ? bilu_apply_host(F, how, b, x) : bilu_apply(F, how, b, x, s);
+}
+
+int bilu4_apply_dev(mi_bilu4_t F, const Bilu4Apply& how, const double* d_b, double* d_x, hipStream_t s) { return bilu_solve_entry(F, how, false, d_b, d_x, s); }
+
+extern "C" int mi_bilu4_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s) { return bilu_solve_entry(F, {false, false, 0, 0}, false, d_b, d_x, (hipStream_t)s); }
+
+extern "C" int mi_bilu4_solve(mi_bilu4_t F, const double* b, double* x) { return bilu_solve_entry(F, {false, false, 0, 0}, true, b, x, nullptr); }
+
+extern "C" int mi_bilu4sw_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s)
+{
+    return bilu_solve_entry(F, {true, false, sweeps_fwd, sweeps_bwd}, false, d_b, d_x, (hipStream_t)s);
+}
+
+extern "C" int mi_bilu4sw_solve(mi_bilu4_t F, const double* b, double* x, int sweeps_fwd, int sweeps_bwd)
+{
+    return bilu_solve_entry(F, {true, false, sweeps_fwd, sweeps_bwd}, true, b, x, nullptr);
+}
+
+extern "C" int mi_bilu4sp_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, int sweeps_fwd, int sweeps_bwd, mi_stream_t s)
+{
+    return bilu_solve_entry(F, {true, true, sweeps_fwd, sweeps_bwd}, false, d_b, d_x, (hipStream_t)s);
+}
+
+extern "C" int mi_bilu4sp_solve(mi_bilu4_t F, const double* b, double* x, int sweeps_fwd, int sweeps_bwd)
+{
+    return bilu_solve_entry(F, {true, true, sweeps_fwd, sweeps_bwd}, true, b, x, nullptr);
+}
+
+extern "C" int mi_bilu4spx_solve_dev(mi_bilu4_t F, const double* d_b, double* d_x, mi_stream_t s) { return bilu_solve_entry(F, {false, true, 0, 0}, false, d_b, d_x, (hipStream_t)s); }
+
+extern "C" int mi_bilu4spx_solve(mi_bilu4_t F, const double* b, double* x) { return bilu_solve_entry(F, {false, true, 0, 0}, true, b, x, nullptr); }
 
 extern "C" int mi_bilu4spx_info(mi_bilu4_t F, int* launches_last, int* wide_launches_last)
 {

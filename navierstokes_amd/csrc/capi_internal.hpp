@@ -551,3 +551,11 @@ void bcsr4_drop_sliced(mi_bcsr4_s* A);
 // a CSR handle's blocked copy (blocks + sliced values) from its CSR values d_src, which also go to d_csr_out when that is given: one pass
 int bcsr4_refresh_from_csr(mi_bcsr4_s* A, const int* d_csr_ptrow, const double* d_src, double* d_csr_out, hipStream_t s);
 int launch_bcsr4(mi_bcsr4_t A, const double* d_x, double* d_y, mi_stream_t s, bool use_map);
+// capi_ilu.hip: HOW a block ILU factor is applied — exactly, or by sf forward and sb backward Jacobi sweeps; over the factor's doubles
+// or its single-precision copy.  The four solve families mi_bilu4{,sw,sp,spx}_solve* and GMRES's preconditioner are each one value.
+struct Bilu4Apply {
+    bool sweeps, f32;
+    int sf, sb; // sweeps only
+};
+int bilu4_apply_prepare(mi_bilu4_t F, const Bilu4Apply& how); // the family's public prepare (nothing for exact f64)
+int bilu4_apply_dev(mi_bilu4_t F, const Bilu4Apply& how, const double* d_b, double* d_x, hipStream_t s); // the family's *_solve_dev

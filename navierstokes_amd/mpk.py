@@ -593,6 +593,30 @@ class bcsr4x4_matrix:
             pass
 
 
+GMRES_PC_EXACT, GMRES_PC_SWEEPS, GMRES_PC_SWEEPS_F32, GMRES_PC_EXACT_F32 = 0, 1, 2, 3  # MI_GMRES_PC_*
+
+# the ways a factor is applied, (sweeps, f32) -> the entry point for device vectors, the one for host vectors, the kind GMRES knows it by
+_BILU_APPLY = {
+    (False, False): ("mi_bilu4_solve_dev", "mi_bilu4_solve", GMRES_PC_EXACT),
+    (True, False): ("mi_bilu4sw_solve_dev", "mi_bilu4sw_solve", GMRES_PC_SWEEPS),
+    (True, True): ("mi_bilu4sp_solve_dev", "mi_bilu4sp_solve", GMRES_PC_SWEEPS_F32),
+    (False, True): ("mi_bilu4spx_solve_dev", "mi_bilu4spx_solve", GMRES_PC_EXACT_F32),
+}
+
+
+def _bilu_solve(F, way, counts, x, b):
+    """x = the factor of F (a bilu4) applied to b in that way (a row of _BILU_APPLY); counts: (fwd, bwd) of a sweep solve, else ().
+    CUDA tensors: asynchronous on torch's current stream, x may be b; numpy arrays: copied in and out."""
+    n = 4 * F.nbrows
+    dev, host, _ = way
+    if _is_torch(b):
+        check(getattr(lib(), dev)(F.handle, _dev_ptr(b, n, "b"), _dev_ptr(x, n, "x"), *counts, _stream_ptr()))
+    else:
+        xx = _host_f64(x, n, "x", writable=True)
+        check(getattr(lib(), host)(F.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data, *counts))
+    return x
+
+
 class bilu4:
     """mi_bilu4_t: the incomplete LU factors of a square 4x4-block matrix — PCILU on the BAIJ-4 Jacobian,
     src/solve_newton.c:1156-1164 — factored on the host at construction, solved on the GPU level by level.
@@ -646,13 +670,11 @@ class bilu4:
 
     def solve(self, x, b):
         """x = U^-1 L^-1 b.  CUDA tensors: asynchronous on torch's current stream, x may be b; numpy arrays: copied in and out."""
-        n = 4 * self.nbrows
-        if _is_torch(b):
-            check(lib().mi_bilu4_solve_dev(self.handle, _dev_ptr(b, n, "b"), _dev_ptr(x, n, "x"), _stream_ptr()))
-        else:
-            xx = _host_f64(x, n, "x", writable=True)
-            check(lib().mi_bilu4_solve(self.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data))
-        return x
+        return _bilu_solve(self, _BILU_APPLY[False, False], (), x, b)
+
+    def gmres_args(self):
+        """(handle, MI_GMRES_PC_* kind, sweeps_fwd, sweeps_bwd): what gmres_solver sets this M with."""
+        return self.handle, GMRES_PC_EXACT, 0, 0
 
     def refactor(self, coef):
         """New block values for the same pattern (same layout as at construction)."""
@@ -720,14 +742,14 @@ class bilu4:
         instead of the exact solve (mi_bilu4sw_*): a view with .solve(x, b), which is what GMRES takes as M.  Counts above
         levels - 1 are clamped: there the result is the exact solve's, bit for bit.  precision="f32": the sweeps stream the
         single-precision copy of the factor's values (mi_bilu4sp_*); vectors and arithmetic stay double."""
-        return bilu4_sweeps(self, fwd, fwd if bwd is None else bwd, precision)
+        return bilu4_apply(self, True, precision, fwd, fwd if bwd is None else bwd)
 
     def exact(self, precision="f64"):
         """The exact solve as a view with .solve(x, b), which GMRES takes as M like a sweeps() view.  precision="f64": the handle's
         own solve (the handle itself).  precision="f32": the level-by-level exact solve streaming the single-precision copy of the
         factor's values (mi_bilu4spx_*) — the exact solve of the rounded factor; vectors and arithmetic stay double.  The view
         shares this handle and owns nothing."""
-        return bilu4_exact_f32(self) if _sweep_precision(precision) else self
+        return bilu4_apply(self, False, precision) if _sweep_precision(precision) else self
 
     def exact_info_f32(self):
         """dict(launches_last, wide_launches_last) of the last single-precision exact solve — mi_bilu4spx_info."""
@@ -823,48 +845,32 @@ def _sweep_precision(precision):
     return precision == "f32"
 
 
-class bilu4_sweeps:
-    """bilu4.sweeps(fwd, bwd, precision): the factors of F applied by fixed numbers of Jacobi sweeps.  It shares F's handle and owns
-    nothing."""
+class bilu4_apply:
+    """What bilu4.sweeps(fwd, bwd, precision) and bilu4.exact("f32") return: the factors of F applied by fixed numbers of Jacobi
+    sweeps (sweeps=True) or exactly, over F's values (precision="f64") or their single-precision copy ("f32").  It shares F's handle
+    and owns nothing."""
 
-    def __init__(self, F, fwd, bwd, precision="f64"):
-        self.F, self.fwd, self.bwd, self.precision = F, int(fwd), int(bwd), precision
-        self._f32 = _sweep_precision(precision)
+    def __init__(self, F, sweeps, precision="f64", fwd=0, bwd=0):
+        self.F, self.sweeps, self.fwd, self.bwd, self.precision = F, bool(sweeps), int(fwd), int(bwd), precision
+        self._way = _BILU_APPLY[self.sweeps, _sweep_precision(precision)]
+        self._counts = (self.fwd, self.bwd) if self.sweeps else ()
         if self.fwd < 0 or self.bwd < 0:
             raise ValueError("bilu4.sweeps: negative sweep count")
 
     def solve(self, x, b):
-        """x = the sweep operator applied to b.  CUDA tensors: asynchronous on torch's current stream, x may be b; numpy arrays:
-        copied in and out."""
-        n = 4 * self.F.nbrows
-        L = lib()
-        if _is_torch(b):
-            dev = L.mi_bilu4sp_solve_dev if self._f32 else L.mi_bilu4sw_solve_dev
-            check(dev(self.F.handle, _dev_ptr(b, n, "b"), _dev_ptr(x, n, "x"), self.fwd, self.bwd, _stream_ptr()))
-        else:
-            xx = _host_f64(x, n, "x", writable=True)
-            host = L.mi_bilu4sp_solve if self._f32 else L.mi_bilu4sw_solve
-            check(host(self.F.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data, self.fwd, self.bwd))
-        return x
+        """x = this view's operator applied to b (see _bilu_solve for the vectors it takes)."""
+        return _bilu_solve(self.F, self._way, self._counts, x, b)
+
+    def gmres_args(self):
+        return self.F.handle, self._way[2], self.fwd, self.bwd
 
 
-class bilu4_exact_f32:
-    """bilu4.exact("f32"): the exact solve over the single-precision copy of F's values (mi_bilu4spx_*).  It shares F's handle and
-    owns nothing."""
+def bilu4_sweeps(F, fwd, bwd, precision="f64"):
+    return bilu4_apply(F, True, precision, fwd, bwd)
 
-    def __init__(self, F):
-        self.F = F
 
-    def solve(self, x, b):
-        """x = the exact solve of the rounded factor applied to b.  CUDA tensors: asynchronous on torch's current stream, x may be
-        b; numpy arrays: copied in and out."""
-        n = 4 * self.F.nbrows
-        if _is_torch(b):
-            check(lib().mi_bilu4spx_solve_dev(self.F.handle, _dev_ptr(b, n, "b"), _dev_ptr(x, n, "x"), _stream_ptr()))
-        else:
-            xx = _host_f64(x, n, "x", writable=True)
-            check(lib().mi_bilu4spx_solve(self.F.handle, _host_f64(b, n, "b").ctypes.data, xx.ctypes.data))
-        return x
+def bilu4_exact_f32(F):
+    return bilu4_apply(F, False, "f32")
 
 
 def bilu4_plan_probe(nbrows, ptrow, indcol, fill=0):
@@ -1404,7 +1410,6 @@ def GMRES(A, b, x, M=None, restart=30, rtol=1e-8, maxiter=300):
             return its, hist
 
 
-GMRES_PC_EXACT, GMRES_PC_SWEEPS, GMRES_PC_SWEEPS_F32, GMRES_PC_EXACT_F32 = 0, 1, 2, 3
 GMRES_BASIS = {"f64": 0, "f32": 1}  # MI_BASIS_F64, MI_BASIS_F32
 GMRES_CHECK_EVERY = 1  # the default of gmres_solver.solve / GMRES_dev: what tools/bench_gmres.py measured fastest (profiles/NOTES.md R12.1)
 
@@ -1413,7 +1418,7 @@ class gmres_solver:
     """mi_gmres_t: GMRES's definition above with a whole restart cycle enqueued on the device — the products, M, CGS2, the Givens
     rotations, the residual recurrence and the back-substitution — and one small read-back per check_every iterations instead of
     one stream drain per iteration (include/mi355_spmv.h, mi_gmres_*; DESIGN.md 4.6).  A: a bcsr4x4_matrix or a square csrmatrix;
-    M: a bilu4 (the exact solve in the handle's current form), a bilu4_sweeps (either precision), a bilu4.exact("f32") view or None.  The solver owns its
+    M: a bilu4 (the exact solve in the handle's current form), a bilu4.sweeps(..) view (either precision), a bilu4.exact("f32") view or None.  The solver owns its
     basis and work vectors; A and M must outlive it.  One solve at a time per solver, and per M.
     basis="f32" (MI_BASIS_F32, opt-in): the Krylov basis is stored in single precision, every projection is taken against the
     stored basis, and a converged recurrence is confirmed by the next cycle's true residual (basis_info()).
@@ -1436,12 +1441,10 @@ class gmres_solver:
             check(lib().mi_gmres_set_operator_bcsr4(h, A.handle))
         else:
             check(lib().mi_gmres_set_operator_csr(h, A.handle))
-        if isinstance(M, bilu4_sweeps):
-            check(lib().mi_gmres_set_precond(h, M.F.handle, GMRES_PC_SWEEPS_F32 if M._f32 else GMRES_PC_SWEEPS, M.fwd, M.bwd))
-        elif isinstance(M, bilu4_exact_f32):
-            check(lib().mi_gmres_set_precond_ex(h, M.F.handle, GMRES_PC_EXACT_F32, 0, 0))
-        elif M is not None:
-            check(lib().mi_gmres_set_precond(h, M.handle, GMRES_PC_EXACT, 0, 0))
+        if M is not None:
+            F, kind, fwd, bwd = M.gmres_args()
+            # (the setter each kind has always gone through: the later kind has the later one)
+            check((lib().mi_gmres_set_precond_ex if kind == GMRES_PC_EXACT_F32 else lib().mi_gmres_set_precond)(h, F, kind, fwd, bwd))
 
     @property
     def handle(self):
