@@ -260,6 +260,34 @@ int mi_mring_plan_deal_probe(int n, const int* ptrow, const int* indcol, int* ta
  * inside a run bringing more than T new columns, none holding more than T rows (spmv_ring.hpp)?  The planner cuts its runs
  * at window restarts to make it so; only configuration 4 has the instantiation. */
 int mi_ring_plan_lean(int n, const int* ptrow, const int* indcol, int config_id, int* lean);
+/* host-only: a CENSUS of the ring plan mi_csr_create builds for this matrix under configuration config_id (the same planner call, the
+ * same row alignment rule): which states of the kernel the plan reaches, so that a test can assert that its matrix sits on the limit
+ * it is named for.  counters[cap], cap >= MI_RING_CENSUS_LEN, in this order ("served": a block of the pipelined loop; "PLAIN": a block
+ * computed behind the loop of a kind-3 run; "wide": a block the window cannot serve; "inner": not the first block of its run):
+ *  0 blocks, run table length, blocks per run of the uniform deal, runs of kind 0 / 1 / 3, non-empty runs, idle runs, shortest and longest
+ *    non-empty run, 1 if the deal is the uniform one, 1 if the plan is LEAN (configuration 4), blocks of prefetch by default;
+ * 13 runs of exactly 1, 2, 3, 4, 5 and 9 blocks; 19 runs holding 0, 1, 2, 3, 4 and >= 5 wide blocks, the most in one run;
+ * 26 PLAIN blocks: all, first / last / neither of their run, directly behind another, holding the matrix's last row, a row longer than a
+ *    block, a span wider than the ring; 34 blocks of kind-0 runs: all, wide, a row longer than a block;
+ * 37 served blocks: all, of exactly NNZB and NNZB - 1 nonzeros, of exactly the row limit, of more than T rows, spanning exactly RING columns,
+ *    the widest span; 44 blocks without nonzeros: all, first / last / neither of their run;
+ * 48 window restarts in inner blocks: a jump ahead, a reach back, behind a PLAIN or after only empty blocks;
+ * 51 new columns of inner served blocks: the most, then blocks bringing 1..T-1, T, T+1, T+2..4T-1, 4T, 4T+1, 4T+2..RING-1, RING;
+ * 60 served blocks with a column at or beyond base + RING (slot wrap), inner blocks whose base advanced without a restart. */
+#define MI_RING_CENSUS_LEN 62
+int mi_ring_plan_census(int n, const int* ptrow, const int* indcol, int config_id, long long* counters, int cap);
+/* ... and of the multi-window plan.  counters[cap], cap >= MI_MRING_CENSUS_LEN:
+ *  0 blocks, run table length, runs, empty table entries, runs of kind 0 / 1 / 3, shortest and longest run, blocks of prefetch, forced cuts
+ *    (a block needing more groups than the loop refills); 11 runs holding 0, 1, 2, 3, 4 and >= 5 wide blocks, the most in one run;
+ * 18 PLAIN blocks: all, first / last / neither of their run, by cause: a row longer than a block, more clusters than windows, a cluster
+ *    wider than a window allows; 25 blocks of kind-0 runs;
+ * 26 served blocks: all, with as many clusters as windows, the most clusters, with a cluster of exactly the widest width served, the widest
+ *    cluster; wide blocks one cluster over, and one column over; 33 the smallest gap that split two clusters, the largest that did not;
+ * 35 blocks without nonzeros; 36 groups of inner served blocks: the most in one block, blocks with all of them, groups ending exactly at
+ *    their window's wrap-around, groups continuing across it; served blocks whose columns lie on both sides of it; groups and first
+ *    windows reaching past the last column. */
+#define MI_MRING_CENSUS_LEN 43
+int mi_mring_plan_census(int n, const int* ptrow, const int* indcol, long long* counters, int cap);
 /* host-only: does this CSR pattern have the exact 4x4 node-block structure mi_csr_create looks for (n % 4 == 0,
  * the four rows of a block row hold the same columns, in aligned groups {4j..4j+3}) — i.e. will a blocked copy be
  * built and the BCSR kernel become an AUTO candidate?  *nblocks = number of 4x4 blocks if so. */

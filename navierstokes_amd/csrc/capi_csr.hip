@@ -180,7 +180,7 @@ static int build_mring(mi_csr_t A, const int* indcol, int row_align = 0)
     M.bad_runs = P.bad_runs;
     M.restarts = P.restarts;
     M.ok_fraction = 1.0 - (double)P.bad_nnz / (double)A->nnz;
-    M.depth = P.bpw >= 40 ? 4 : 2; // as for the single ring (tools/depth_ab.py)
+    M.depth = mring_default_depth(P);
     M.skew = ring_wants_skew(A->n, A->h_ptrow.data());
     M.nt = beyond_infinity_cache(10.0, A->nnz, A->n);
     A->mring = std::move(M);
@@ -231,7 +231,7 @@ static int fill_ring_table(RingTable& R, const RingPlanHost& best, int n, const 
     // the HBM latency — same handle, same box, back to back 172.8 / 168.8 / 167.5 us at depth 2 / 3 / 4, cold caches
     // 198.2 / 194.2 / 191.9 us; with short runs (1 M rows: 14 blocks) the longer pipeline fill costs more than it hides:
     // 34.7 / 35.1 / 37.3 us (tools/depth_ab.py, profiles/r02_ring_depth_ab.txt).  Configuration 4 only.
-    if (best.cfg.id == 4 && best.bpw >= 40) R.cfg.depth = 4;
+    R.cfg.depth = ring_default_depth(best);
     if (const char* e = getenv("MI355_RING_DEPTH")) {
         const int d = atoi(e);
         if (best.cfg.id == 4 && d >= 2 && d <= 4) R.cfg.depth = d;
@@ -1074,6 +1074,19 @@ extern "C" int mi_csr_tune_detail(mi_csr_t A, double us[5], int* ring_nt, int* s
     if (stream_nt) *stream_nt = A->stream_nt ? 1 : 0;
     return MI_OK;
 }
+
+// smallest / largest column of every row (row_min > row_max for an empty row): the ring planner's input, for the host-only probes
+static void row_ranges(int n, const int* ptrow, const int* indcol, std::vector<int>& row_min, std::vector<int>& row_max)
+{
+    row_min.assign((size_t)n, 0x7fffffff);
+    row_max.assign((size_t)n, -1);
+    for (int i = 0; i < n; i++)
+        for (int k = ptrow[i]; k < ptrow[i + 1]; k++) {
+            row_min[i] = std::min(row_min[i], indcol[k]);
+            row_max[i] = std::max(row_max[i], indcol[k]);
+        }
+}
+
 // host-only: build the ring plan and the 16-bit column stream for one configuration exactly as
 // mi_csr_create would, and check their invariants (every block of a served run keeps its columns
 // inside one window of at most RING entries, distinct columns of a block get distinct slots, slots
@@ -1084,16 +1097,8 @@ extern "C" int mi_ring_plan_probe(int n, const int* ptrow, const int* indcol, in
     CHECK_ARG(n >= 0 && ptrow && config_id >= 1 && config_id <= kNumRingConfigs, "bad argument");
     const long long nnz = ptrow[n];
     CHECK_ARG(nnz == 0 || indcol, "indcol is null");
-    std::vector<int> row_min((size_t)n), row_max((size_t)n);
-    for (int i = 0; i < n; i++) {
-        int lo = 0x7fffffff, hi = -1;
-        for (int k = ptrow[i]; k < ptrow[i + 1]; k++) {
-            lo = std::min(lo, indcol[k]);
-            hi = std::max(hi, indcol[k]);
-        }
-        row_min[i] = lo;
-        row_max[i] = hi;
-    }
+    std::vector<int> row_min, row_max;
+    row_ranges(n, ptrow, indcol, row_min, row_max);
     RingPlanHost P;
     build_ring_plan(kRingConfigs[config_id - 1], n, ptrow, row_min.data(), row_max.data(), P);
     std::vector<unsigned short> slots;
@@ -1571,19 +1576,40 @@ extern "C" int mi_tile_plan_probe(int n, const int* ptrow, const int* indcol, in
 extern "C" int mi_ring_plan_lean(int n, const int* ptrow, const int* indcol, int config_id, int* lean)
 {
     CHECK_ARG(n >= 0 && ptrow && lean && config_id >= 1 && config_id <= kNumRingConfigs, "bad argument");
-    std::vector<int> row_min((size_t)n), row_max((size_t)n);
-    for (int i = 0; i < n; i++) {
-        int lo = 0x7fffffff, hi = -1;
-        for (int k = ptrow[i]; k < ptrow[i + 1]; k++) {
-            lo = std::min(lo, indcol[k]);
-            hi = std::max(hi, indcol[k]);
-        }
-        row_min[i] = lo;
-        row_max[i] = hi;
-    }
+    std::vector<int> row_min, row_max;
+    row_ranges(n, ptrow, indcol, row_min, row_max);
     RingPlanHost P;
     build_ring_plan(kRingConfigs[config_id - 1], n, ptrow, row_min.data(), row_max.data(), P);
     *lean = P.lean && P.cfg.id == 4 && P.bad_runs == 0;
+    return MI_OK;
+}
+
+// host-only: the census of the plan mi_csr_create builds for this matrix and configuration (ring_plan.hpp: ring_plan_census) — the
+// same planner call, the same row alignment rule (large_row_align)
+static_assert(kRingCensusLen == MI_RING_CENSUS_LEN && kMringCensusLen == MI_MRING_CENSUS_LEN, "include/mi355_spmv.h lists the counters");
+extern "C" int mi_ring_plan_census(int n, const int* ptrow, const int* indcol, int config_id, long long* counters, int cap)
+{
+    CHECK_ARG(n >= 0 && ptrow && ptrow[0] == 0 && config_id >= 1 && config_id <= kNumRingConfigs && counters, "bad argument");
+    CHECK_ARG(cap >= kRingCensusLen, "counters holds fewer than MI_RING_CENSUS_LEN entries");
+    const long long nnz = ptrow[n];
+    CHECK_ARG(nnz == 0 || indcol, "indcol is null");
+    std::vector<int> row_min, row_max;
+    row_ranges(n, ptrow, indcol, row_min, row_max);
+    RingPlanHost P;
+    build_ring_plan(kRingConfigs[config_id - 1], n, ptrow, row_min.data(), row_max.data(), P, 0, 0, large_row_align(nnz));
+    ring_plan_census(P, indcol, counters);
+    return MI_OK;
+}
+
+// ... and of the multi-window plan (mring_plan.hpp: mring_plan_census)
+extern "C" int mi_mring_plan_census(int n, const int* ptrow, const int* indcol, long long* counters, int cap)
+{
+    CHECK_ARG(n >= 0 && ptrow && ptrow[0] == 0 && counters, "bad argument");
+    CHECK_ARG(cap >= kMringCensusLen, "counters holds fewer than MI_MRING_CENSUS_LEN entries");
+    CHECK_ARG(ptrow[n] == 0 || indcol, "indcol is null");
+    MringPlanHost P;
+    build_mring_plan(n, ptrow, indcol, P, large_row_align(ptrow[n]));
+    mring_plan_census(P, n, indcol, counters);
     return MI_OK;
 }
 

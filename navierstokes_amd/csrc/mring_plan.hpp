@@ -334,6 +334,7 @@ inline void build_mring_plan(int n, const int* ptrow, const int* indcol, MringPl
             if (count_long() <= kMringWgUnit || target >= kMringMaxB) break;
         }
         pass(0, &planned, true);
+        forced += (int)seg.size() - 2; // the segment boundaries ARE forced cuts (found by the first pass); the final pass meets them as planned ones
     }
     const int nruns = (int)cuts.size();
     // dispatch order: per XCD its long runs, then its short ones
@@ -470,6 +471,115 @@ inline const char* check_mring_plan(const MringPlanHost& P, int n, const int* pt
     }
     if (next_row != n || next_nz != ptrow[n]) return "plan does not cover the matrix";
     return nullptr;
+}
+
+inline int mring_default_depth(const MringPlanHost& P) { return P.bpw >= 40 ? 4 : 2; } // as for the single ring (tools/depth_ab.py)
+
+// Census of a plan (mi_mring_plan_census; ring_plan.hpp: ring_plan_census has the vocabulary).  The clusters are recounted from
+// the matrix with the planner's rule, the groups and slots are read from the records as the kernel reads them.  The order of the
+// counters is part of the C interface (include/mi355_spmv.h lists them).
+enum MringCensus {
+    kMcBlocks, kMcTableLen, kMcRuns, kMcTablePadded, kMcRunsKind0, kMcRunsKind1, kMcRunsKind3, kMcRunMin, kMcRunMax, kMcDepth, kMcForcedCuts,
+    kMcRunsWide0, kMcRunsWide1, kMcRunsWide2, kMcRunsWide3, kMcRunsWide4, kMcRunsWide5Up, kMcWideMaxPerRun,
+    kMcPlain, kMcPlainFirst, kMcPlainLast, kMcPlainMiddle, kMcPlainLongRow, kMcPlainClusters, kMcPlainWidth, kMcKind0Blocks,
+    kMcServed, kMcServedClustersK, kMcClustersMax, kMcServedWidthLimit, kMcWidthMax, kMcWideClustersK1, kMcWideWidthLimit1,
+    kMcGapMinSplit, kMcGapMaxJoined, kMcEmpty,
+    kMcGroupsMax, kMcGroupsFull, kMcGroupEndsAtWrap, kMcGroupStartsAtWrap, kMcBlockAcrossWrap, kMcGroupPastEnd, kMcFirstPastEnd,
+    kMringCensusLen
+};
+
+inline void mring_plan_census(const MringPlanHost& P, int n, const int* indcol, long long* out)
+{
+    std::fill(out, out + kMringCensusLen, 0LL);
+    const int K = kMringK, W = kMringW, T = kMringThreads, nnzb = kMringNnzb, per = nnzb / T, G = kMringGroups;
+    out[kMcBlocks] = P.nblk;
+    out[kMcTableLen] = P.wgs;
+    out[kMcRuns] = P.nruns;
+    out[kMcDepth] = mring_default_depth(P);
+    out[kMcForcedCuts] = P.restarts;
+    out[kMcRunMin] = P.nblk > 0 ? 0x7fffffff : 0;
+    out[kMcGapMinSplit] = 0x7fffffff;
+    std::vector<int> u;
+    for (int g = 0; g < P.wgs; g++) {
+        const int b0 = P.run_rng[2 * g], b1 = P.run_rng[2 * g + 1], nb = b1 - b0, kind = P.run_ok[g];
+        if (nb <= 0) { out[kMcTablePadded]++; continue; }
+        out[kind == 0 ? kMcRunsKind0 : kind == 3 ? kMcRunsKind3 : kMcRunsKind1]++;
+        out[kMcRunMin] = std::min<long long>(out[kMcRunMin], nb);
+        out[kMcRunMax] = std::max<long long>(out[kMcRunMax], nb);
+        const int* F = &P.first[(size_t)kMringFirst * g];
+        for (int w = 0; w < K; w++) out[kMcFirstPastEnd] += F[5 + w] > 0 && F[w] + F[5 + w] > n;
+        int nwide = 0;
+        for (int b = b0; b < b1; b++) {
+            const int* Q = &P.plan[(size_t)kMringRec * b];
+            const int nn = Q[3];
+            const bool first = b == b0, last = b == b1 - 1;
+            if (kind == 0) out[kMcKind0Blocks]++;
+            if (nn == 0) { out[kMcEmpty]++; continue; }
+            int nc = 0, width = 0;
+            if (nn <= nnzb) { // the planner's clusters: distinct columns sorted, cut at gaps >= kMringGap
+                u.assign(indcol + Q[1], indcol + Q[1] + nn);
+                std::sort(u.begin(), u.end());
+                u.erase(std::unique(u.begin(), u.end()), u.end());
+                nc = 1;
+                int lo = u[0];
+                for (size_t i = 1; i < u.size(); i++) {
+                    const int gap = u[i] - u[i - 1];
+                    if (gap >= kMringGap) {
+                        out[kMcGapMinSplit] = std::min<long long>(out[kMcGapMinSplit], gap);
+                        width = std::max(width, u[i - 1] - lo + 1);
+                        lo = u[i];
+                        nc++;
+                    } else out[kMcGapMaxJoined] = std::max<long long>(out[kMcGapMaxJoined], gap);
+                }
+                width = std::max(width, u.back() - lo + 1);
+            }
+            const bool wide = nn > nnzb || nc > K || width > W - 64;
+            if (wide) {
+                nwide++;
+                out[kMcWideClustersK1] += nn <= nnzb && nc == K + 1;
+                out[kMcWideWidthLimit1] += nn <= nnzb && nc <= K && width == W - 63;
+                if (kind != 0) {
+                    out[kMcPlain]++;
+                    out[kMcPlainFirst] += first;
+                    out[kMcPlainLast] += last;
+                    out[kMcPlainMiddle] += !first && !last;
+                    out[nn > nnzb ? kMcPlainLongRow : nc > K ? kMcPlainClusters : kMcPlainWidth]++;
+                }
+                continue;
+            }
+            if (kind == 0) continue;
+            out[kMcServed]++;
+            out[kMcServedClustersK] += nc == K;
+            out[kMcClustersMax] = std::max<long long>(out[kMcClustersMax], nc);
+            out[kMcServedWidthLimit] += width == W - 64;
+            out[kMcWidthMax] = std::max<long long>(out[kMcWidthMax], width);
+            if (!first) {
+                out[kMcGroupsMax] = std::max<long long>(out[kMcGroupsMax], Q[5]);
+                out[kMcGroupsFull] += Q[5] == G;
+                for (int q = 0; q < Q[5]; q++) {
+                    const unsigned sl = ((unsigned)Q[16 + q / 2] >> (16 * (q & 1))) & 0xffffu;
+                    out[kMcGroupEndsAtWrap] += sl % W == (unsigned)(W - 64);
+                    // a group at a window's first slot that continues the group before it: the window slid across its wrap-around
+                    if (sl % W == 0 && q > 0 && Q[8 + q] == Q[8 + q - 1] + 64) out[kMcGroupStartsAtWrap]++;
+                    out[kMcGroupPastEnd] += Q[8 + q] + 64 > n;
+                }
+            }
+            // a window whose columns of this block lie on both sides of its wrap-around: the smallest column's slot above the largest's
+            int cmin[kMringK], cmax[kMringK], smin[kMringK], smax[kMringK];
+            for (int w = 0; w < K; w++) { cmin[w] = 0x7fffffff; cmax[w] = -1; smin[w] = smax[w] = 0; }
+            for (int k = 0; k < nn; k++) {
+                const int s = P.slots[(size_t)b * nnzb + (size_t)ring_slot_pos(T, per, k)], w = s / W, c = indcol[Q[1] + k];
+                if (w >= K) continue;
+                if (c < cmin[w]) { cmin[w] = c; smin[w] = s; }
+                if (c > cmax[w]) { cmax[w] = c; smax[w] = s; }
+            }
+            bool across = false;
+            for (int w = 0; w < K; w++) across = across || (cmax[w] >= 0 && smin[w] > smax[w]);
+            out[kMcBlockAcrossWrap] += across;
+        }
+        out[kMcRunsWide0 + std::min(nwide, 5)]++;
+        out[kMcWideMaxPerRun] = std::max<long long>(out[kMcWideMaxPerRun], nwide);
+    }
 }
 
 } // namespace mi355

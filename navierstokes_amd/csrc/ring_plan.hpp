@@ -380,6 +380,115 @@ inline void build_run_deps(const RingPlanHost& P, int n, std::vector<int>& dep_p
     dep_ptr[W] = (int)dep_run.size();
 }
 
+// Blocks of prefetch a plan runs with unless MI355_RING_DEPTH says otherwise (capi_csr.hip: fill_ring_table has the measurements)
+inline int ring_default_depth(const RingPlanHost& P) { return P.cfg.id == 4 && P.bpw >= 40 ? 4 : P.cfg.depth; }
+
+// Census of a plan (mi_ring_plan_census): which of the kernel's states the plan of a matrix reaches.  Counted from the plan
+// records as the kernel replays them (the window is followed through every run), so that a test can assert that its matrix
+// sits on the limit it is named for.  "served" = a block of the pipelined loop (flags 1); "PLAIN" = flags 2, behind the loop of
+// a kind-3 run; "wide" = a block the window cannot serve (a PLAIN block, or one of a kind-0 run); "inner" = not the first
+// block of its run.  The order of the counters is part of the C interface (include/mi355_spmv.h lists them).
+enum RingCensus {
+    kRcBlocks, kRcTableLen, kRcBpw, kRcRunsKind0, kRcRunsKind1, kRcRunsKind3, kRcRunsNonEmpty, kRcRunsIdle, kRcRunMin, kRcRunMax,
+    kRcUniform, kRcLean, kRcDepth, kRcRunsLen1, kRcRunsLen2, kRcRunsLen3, kRcRunsLen4, kRcRunsLen5, kRcRunsLen9,
+    kRcRunsWide0, kRcRunsWide1, kRcRunsWide2, kRcRunsWide3, kRcRunsWide4, kRcRunsWide5Up, kRcWideMaxPerRun,
+    kRcPlain, kRcPlainFirst, kRcPlainLast, kRcPlainMiddle, kRcPlainAfterPlain, kRcPlainEndsMatrix, kRcPlainLongRow, kRcPlainSpan,
+    kRcKind0Blocks, kRcKind0Wide, kRcKind0LongRow,
+    kRcServed, kRcServedFull, kRcServedFullLess1, kRcServedRowLimit, kRcServedRowsOverT, kRcServedSpanRing, kRcServedSpanMax,
+    kRcEmpty, kRcEmptyFirst, kRcEmptyLast, kRcEmptyMiddle,
+    kRcRestartAhead, kRcRestartBack, kRcRestartCold,
+    kRcNewMax, kRcNewBelowT, kRcNewT, kRcNewT1, kRcNewMid, kRcNew4T, kRcNew4T1, kRcNewHigh, kRcNewRing,
+    kRcSlotWrap, kRcBaseAdvance,
+    kRingCensusLen
+};
+
+inline void ring_plan_census(const RingPlanHost& P, const int* indcol, long long* out)
+{
+    std::fill(out, out + kRingCensusLen, 0LL);
+    const int T = P.cfg.threads, nnzb = P.cfg.nnzb, ring = P.cfg.ring, max_rows = P.cfg.id == 4 ? T : 2 * T;
+    out[kRcBlocks] = P.nblk;
+    out[kRcTableLen] = P.wgs;
+    out[kRcBpw] = P.bpw;
+    out[kRcLean] = P.lean && P.cfg.id == 4;
+    out[kRcDepth] = ring_default_depth(P);
+    out[kRcUniform] = 1;
+    out[kRcRunMin] = P.nblk > 0 ? 0x7fffffff : 0;
+    for (int g = 0; g < P.wgs; g++) {
+        const int b0 = P.run_rng[2 * g], b1 = P.run_rng[2 * g + 1], nb = b1 - b0, kind = P.run_ok[g];
+        if (b0 != std::min(P.nblk, g * P.bpw) || b1 != std::min(P.nblk, (g + 1) * P.bpw)) out[kRcUniform] = 0;
+        if (nb <= 0) { out[kRcRunsIdle]++; continue; }
+        out[kRcRunsNonEmpty]++;
+        out[kind == 0 ? kRcRunsKind0 : kind == 3 ? kRcRunsKind3 : kRcRunsKind1]++;
+        out[kRcRunMin] = std::min<long long>(out[kRcRunMin], nb);
+        out[kRcRunMax] = std::max<long long>(out[kRcRunMax], nb);
+        if (nb <= 5) out[kRcRunsLen1 + nb - 1]++;
+        if (nb == 9) out[kRcRunsLen9]++;
+        int nwide = 0, wlo = 0, whi = 0, pbase = 0;
+        bool live = false, prev_wide = false;
+        for (int b = b0; b < b1; b++) {
+            const int* Q = &P.plan[(size_t)8 * b];
+            const int nn = Q[3], rows = Q[7] == 2 ? Q[4] : Q[2];
+            const bool first = b == b0, last = b == b1 - 1;
+            if (kind == 0) out[kRcKind0Blocks]++;
+            if (nn == 0) {
+                out[kRcEmpty]++;
+                out[first ? kRcEmptyFirst : last ? kRcEmptyLast : kRcEmptyMiddle]++;
+                prev_wide = false;
+                continue;
+            }
+            int cmin = 0x7fffffff, cmax = -1;
+            for (long long k = Q[1]; k < (long long)Q[1] + nn; k++) { cmin = std::min(cmin, indcol[k]); cmax = std::max(cmax, indcol[k]); }
+            const int span = cmax - cmin + 1;
+            const bool wide = kind == 0 ? (nn > nnzb || span > ring) : Q[7] == 2;
+            if (wide) {
+                nwide++;
+                if (kind == 0) {
+                    out[kRcKind0Wide]++;
+                    out[kRcKind0LongRow] += nn > nnzb;
+                } else {
+                    out[kRcPlain]++;
+                    out[kRcPlainFirst] += first;
+                    out[kRcPlainLast] += last;
+                    out[kRcPlainMiddle] += !first && !last;
+                    out[kRcPlainAfterPlain] += prev_wide;
+                    out[kRcPlainEndsMatrix] += b == P.nblk - 1;
+                    out[nn > nnzb ? kRcPlainLongRow : kRcPlainSpan]++;
+                }
+                live = false;
+                prev_wide = true;
+                continue;
+            }
+            prev_wide = false;
+            if (kind == 0) continue; // computed by the plain path: no window
+            out[kRcServed]++;
+            out[kRcServedFull] += nn == nnzb;
+            out[kRcServedFullLess1] += nn == nnzb - 1;
+            out[kRcServedRowLimit] += rows == max_rows;
+            out[kRcServedRowsOverT] += rows > T;
+            out[kRcServedSpanRing] += span == ring;
+            out[kRcServedSpanMax] = std::max<long long>(out[kRcServedSpanMax], span);
+            const bool restart = !live || Q[4] != whi;
+            if (!first) {
+                if (restart) out[!live ? kRcRestartCold : cmin > whi ? kRcRestartAhead : kRcRestartBack]++;
+                else out[kRcBaseAdvance] += Q[6] != pbase;
+                const int cnt = Q[5];
+                out[kRcNewMax] = std::max<long long>(out[kRcNewMax], cnt);
+                if (cnt > 0)
+                    out[cnt < T ? kRcNewBelowT : cnt == T ? kRcNewT : cnt == T + 1 ? kRcNewT1 : cnt < 4 * T ? kRcNewMid : cnt == 4 * T ? kRcNew4T
+                        : cnt == 4 * T + 1 ? kRcNew4T1 : cnt < ring ? kRcNewHigh : kRcNewRing]++;
+            }
+            out[kRcSlotWrap] += cmax - Q[6] >= ring;
+            const int lo = restart ? Q[4] : wlo;
+            whi = Q[4] + Q[5];
+            wlo = std::max(lo, whi - ring);
+            pbase = Q[6];
+            live = true;
+        }
+        out[kRcRunsWide0 + std::min(nwide, 5)]++;
+        out[kRcWideMaxPerRun] = std::max<long long>(out[kRcWideMaxPerRun], nwide);
+    }
+}
+
 // The 16-bit column stream of the ring kernel: for block b, thread t, i < PER the
 // ring slot of nonzero k = t + i*T of the block (the last nonzero again for k >= nnz of the
 // block) at out[(b*T + t)*PER + i] — configuration 4: of nonzero k = 2(t + (i/2)T) + (i & 1), see ring_pairs().  Blocks the

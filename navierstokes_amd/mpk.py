@@ -114,6 +114,8 @@ def lib():
         "mi_csr_block4_structure": [i, _vp, _vp, P(i), P(_c.c_longlong)],
         "mi_ring_plan_probe": [i, _vp, _vp, i, P(i), P(i), P(i), P(d), P(i)],
         "mi_ring_plan_lean": [i, _vp, _vp, i, P(i)],
+        "mi_ring_plan_census": [i, _vp, _vp, i, _vp, i],
+        "mi_mring_plan_census": [i, _vp, _vp, _vp, i],
         "mi_csr_tile_info": [_vp, P(i), P(i), P(d), P(d), P(i)],
         "mi_bcsr4_tile_info": [_vp, P(i), P(i), P(d), P(d)],
         "mi_bcsr4_sell_info": [_vp, P(i), P(i), P(ll), P(d), P(d)],
@@ -927,6 +929,40 @@ def bilu4one_plan_probe(nbrows, ptrow, indcol, fill=0, workgroups=0):
     return dict(eligible=bool(el.value), why=why, nchunks=(nch[0], nch[1]), max_deps=(md[0], md[1]), plan_bytes=by.value,
                 chunk_pos=tuple(tabs[0]), chunk_lev=tuple(tabs[1]), dep_ptr=tuple(tabs[2]),
                 dep=tuple(dep[b][: int(tabs[2][b][-1])] for b in range(2)))
+
+
+RING_CENSUS = ("blocks table_len bpw runs_kind0 runs_kind1 runs_kind3 runs_nonempty runs_idle run_min run_max uniform lean depth "
+               "runs_len1 runs_len2 runs_len3 runs_len4 runs_len5 runs_len9 "
+               "runs_wide0 runs_wide1 runs_wide2 runs_wide3 runs_wide4 runs_wide5up wide_max_per_run "
+               "plain plain_first plain_last plain_middle plain_after_plain plain_ends_matrix plain_long_row plain_span "
+               "kind0_blocks kind0_wide kind0_long_row "
+               "served served_full served_full_less1 served_row_limit served_rows_over_t served_span_ring served_span_max "
+               "empty empty_first empty_last empty_middle restart_ahead restart_back restart_cold "
+               "new_max new_below_t new_t new_t1 new_mid new_4t new_4t1 new_high new_ring slot_wrap base_advance").split()
+MRING_CENSUS = ("blocks table_len runs table_padded runs_kind0 runs_kind1 runs_kind3 run_min run_max depth forced_cuts "
+                "runs_wide0 runs_wide1 runs_wide2 runs_wide3 runs_wide4 runs_wide5up wide_max_per_run "
+                "plain plain_first plain_last plain_middle plain_long_row plain_clusters plain_width kind0_blocks "
+                "served served_clusters_k clusters_max served_width_limit width_max wide_clusters_k1 wide_width_limit1 "
+                "gap_min_split gap_max_joined empty "
+                "groups_max groups_full group_ends_at_wrap group_starts_at_wrap block_across_wrap group_past_end first_past_end").split()
+
+
+def ring_plan_census(n, ptrow, indcol, config_id):
+    """mi_ring_plan_census (no GPU): dict of the counters include/mi355_spmv.h lists, by the names of RING_CENSUS."""
+    ptrow = np.ascontiguousarray(ptrow, np.int32)
+    indcol = np.ascontiguousarray(indcol, np.int32)
+    out = np.zeros(len(RING_CENSUS), np.int64)
+    check(lib().mi_ring_plan_census(int(n), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, int(config_id), out.ctypes.data, out.size))
+    return dict(zip(RING_CENSUS, out.tolist()))
+
+
+def mring_plan_census(n, ptrow, indcol):
+    """mi_mring_plan_census (no GPU): dict of the counters include/mi355_spmv.h lists, by the names of MRING_CENSUS."""
+    ptrow = np.ascontiguousarray(ptrow, np.int32)
+    indcol = np.ascontiguousarray(indcol, np.int32)
+    out = np.zeros(len(MRING_CENSUS), np.int64)
+    check(lib().mi_mring_plan_census(int(n), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, out.ctypes.data, out.size))
+    return dict(zip(MRING_CENSUS, out.tolist()))
 
 
 def spmk_plan_probe(n, ptrow, indcol):
