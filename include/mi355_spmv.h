@@ -288,6 +288,30 @@ int mi_ring_plan_census(int n, const int* ptrow, const int* indcol, int config_i
  *    windows reaching past the last column. */
 #define MI_MRING_CENSUS_LEN 43
 int mi_mring_plan_census(int n, const int* ptrow, const int* indcol, long long* counters, int cap);
+/* host-only: a CENSUS of the row blocks of the stream kernel (which = MI_KERNEL_STREAM: blocks of 1024 nonzeros, T = 256 threads,
+ * the table every CSR handle falls back to) or of the tile kernel's plan (which = MI_KERNEL_TILE: blocks of 2048 nonzeros, T = 256;
+ * built as mi_csr_set_kernel builds it and checked like mi_tile_plan_probe, MI_ERR_STATE names a violation), under the row-alignment
+ * rule of the handle (blocks end on multiples of 64 rows below 20 M nonzeros where that keeps 7/8 of the block; MI355_STREAM_ROW_ALIGN
+ * is not looked at).  counters[cap], cap >= MI_ROWBLOCK_CENSUS_LEN, in this order ("listed": a block of 1..NNZB nonzeros, computed by the
+ * one-thread-per-row phase; "long": a single row of more than NNZB nonzeros, chunked through thread 0):
+ *  0 blocks, the row alignment used, idle workgroups of the launch grid (8 * ceil(blocks / 8) - blocks);
+ *  3 blocks without nonzeros: all, the first block of the matrix, the last, neither;
+ *  7 listed blocks of exactly NNZB and NNZB - 1 nonzeros, with nonzeros % 8 == 1 and == 7, of exactly 1 nonzero;
+ * 12 listed blocks of exactly 1, T, T + 1 and 4 T (the row cap) rows, the most rows in a listed block; blocks ended by the row cap and
+ *    not by the nonzero limit; blocks whose end the alignment rule pulled back;
+ * 19 listed blocks whose first row is empty, whose last row is empty; rows of exactly 1, 8 and 9 nonzeros in listed blocks;
+ * 24 long blocks: all, of exactly NNZB + 1, 2 NNZB and 2 NNZB + 1 nonzeros, as the matrix's first row, as its last row, directly behind
+ *    another long block;
+ * tile only (0 for the stream kernel), U = distinct columns of a listed block:
+ * 31 blocks by R = ceil(U / 256) = 1 .. 8 (the kernel's eight instantiations of tile_block);
+ * 39 blocks with U == 1, U a multiple of 256, U == 256 k + 1 for a k >= 1, U == nonzeros; the largest U; 1 if the handle runs the SKEW
+ *    instantiation (more than a tenth of the rows a multiple of 8 long).
+ * With cap >= MI_ROWBLOCK_CENSUS_LEN + blocks + 1 the first row of every block, then n, follow the counters. */
+#define MI_ROWBLOCK_CENSUS_LEN 45
+int mi_rowblock_census(int n, const int* ptrow, const int* indcol, int which, long long* counters, int cap);
+/* The handle's table for the stream kernel (blocks of 1024 nonzeros), built now if no product has needed it yet: its blocks and the row
+ * alignment it was cut with (MI355_STREAM_ROW_ALIGN included).  mi_csr_tile_info reports the same for the tile kernel's plan. */
+int mi_csr_stream_info(mi_csr_t A, int* nblk, int* row_align);
 /* host-only: does this CSR pattern have the exact 4x4 node-block structure mi_csr_create looks for (n % 4 == 0,
  * the four rows of a block row hold the same columns, in aligned groups {4j..4j+3}) — i.e. will a blocked copy be
  * built and the BCSR kernel become an AUTO candidate?  *nblocks = number of 4x4 blocks if so. */
@@ -467,6 +491,12 @@ int mi_bcsr4_update_values_layout_dev(mi_bcsr4_t A, const double* d_coef, int la
  * block rows touches more than 1024 block columns).  mi_bcsr4_create times both and keeps the faster; same bits.
  * MI355_BCSR_TILE=0|1 forces. */
 int mi_bcsr4_tile_info(mi_bcsr4_t A, int* built, int* in_use, double* us_plain, double* us_tile);
+/* host-only: the lists of that x tile as mi_bcsr4_create would build them for this block pattern (the same builder,
+ * bcsr4_tile_plan.hpp).  *would_build = 0 for a pattern of fewer than 4096 blocks (nothing is listed then: *max_nodes and
+ * *groups_at_cap are 0) or with a group of more than 1024 distinct block columns (MI355_BCSR_TILE is not looked at);
+ * *groups = groups of 64 block rows; *max_nodes = the longest list among the groups listed; *groups_at_cap = groups of exactly 1024. */
+int mi_bcsr4_tile_probe(int nbrows, const int* ptrow, const int* indcol, int* would_build, int* groups, int* max_nodes,
+                        int* groups_at_cap);
 /* Third form (round 4, spmv_bcsr_sell.hpp): a SLICED copy of the block values made at mi_bcsr4_create for matrices of >= 100 000 blocks
  * — 16 consecutive block rows per slice, padded to the slice's longest row, step j of a slice = the j-th block of each of its rows as
  * two contiguous kilobytes — streamed by persistent waves, each over one contiguous range of slices, with unconditional counted loads

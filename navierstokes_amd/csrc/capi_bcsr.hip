@@ -4,6 +4,7 @@
 #include "blas1_kernels.hpp"
 #include "spmv_bcsr_sell.hpp"
 #include "spmm_tile_plan.hpp"
+#include "bcsr4_tile_plan.hpp"
 
 static int sell_fill(mi_bcsr4_t A, hipStream_t s);
 
@@ -36,34 +37,18 @@ static bool bcsr4_race(mi_bcsr4_t A, int ncand, Select select, double* us)
 // faster is kept (MI355_BCSR_TILE=0 never builds it, =1 takes it unmeasured).
 static int build_bcsr4_tile(mi_bcsr4_t A, const int* ptrow, const int* indcol)
 {
-    const int nbrows = A->nbrows;
     const long long nb = A->nblocks;
-    if (nb < 4096 || env_is("MI355_BCSR_TILE", "0")) return MI_OK;
-    const int per = kWG / 4, nwg = (nbrows + per - 1) / per;
-    std::vector<int> wg_ptr((size_t)nwg + 1, 0);
-    std::vector<unsigned> nodes;
-    std::vector<unsigned short> slots((size_t)nb + 1, 0);
-    std::vector<unsigned> u;
-    bool fits = true;
-    for (int w = 0; w < nwg && fits; w++) {
-        const int b0 = ptrow[(size_t)w * per], b1 = ptrow[std::min<long long>((long long)(w + 1) * per, nbrows)];
-        u.assign(indcol + b0, indcol + b1);
-        std::sort(u.begin(), u.end());
-        u.erase(std::unique(u.begin(), u.end()), u.end());
-        fits = (int)u.size() <= kBtileNodes;
-        for (int k = b0; k < b1 && fits; k++) slots[k] = (unsigned short)(std::lower_bound(u.begin(), u.end(), (unsigned)indcol[k]) - u.begin());
-        nodes.insert(nodes.end(), u.begin(), u.end());
-        wg_ptr[w + 1] = (int)nodes.size();
-    }
-    if (!fits) return MI_OK;
-    nodes.push_back(0);
+    if (nb < kBtileMinBlocks || env_is("MI355_BCSR_TILE", "0")) return MI_OK;
+    Bcsr4TileListsHost H; // the lists themselves: bcsr4_tile_plan.hpp (host only; mi_bcsr4_tile_probe below reports the same call)
+    build_bcsr4_tile_lists(A->nbrows, ptrow, indcol, kWG / 4, kBtileNodes, H);
+    if (!H.built) return MI_OK;
     Bcsr4TileLists T;
-    HIP_TRY(T.ptr.alloc(wg_ptr.size()));
-    HIP_TRY(T.nodes.alloc(nodes.size()));
-    HIP_TRY(T.slots.alloc(slots.size()));
-    HIP_TRY(T.ptr.fill(wg_ptr));
-    HIP_TRY(T.nodes.fill(nodes));
-    HIP_TRY(T.slots.fill(slots));
+    HIP_TRY(T.ptr.alloc(H.wg_ptr.size()));
+    HIP_TRY(T.nodes.alloc(H.nodes.size()));
+    HIP_TRY(T.slots.alloc(H.slots.size()));
+    HIP_TRY(T.ptr.fill(H.wg_ptr));
+    HIP_TRY(T.nodes.fill(H.nodes));
+    HIP_TRY(T.slots.fill(H.slots));
     A->tl = std::move(T);
     if (env_is("MI355_BCSR_TILE", "1")) A->use_tile = true;
     else if (!env_is("MI355_SPMV_AUTOTUNE", "0") && nb >= 100000) {
@@ -74,6 +59,23 @@ static int build_bcsr4_tile(mi_bcsr4_t A, const int* ptrow, const int* indcol)
             A->use_tile = us[1] > 0 && us[1] < us[0];
         }
     }
+    return MI_OK;
+}
+
+// host-only: the list-building half of build_bcsr4_tile for this block pattern — would the handle hold the x tile, and how full is it
+extern "C" int mi_bcsr4_tile_probe(int nbrows, const int* ptrow, const int* indcol, int* would_build, int* groups, int* max_nodes, int* groups_at_cap)
+{
+    CHECK_ARG(nbrows >= 0 && ptrow && ptrow[0] == 0, "bad argument");
+    for (int i = 0; i < nbrows; i++) CHECK_ARG(ptrow[i] <= ptrow[i + 1], "ptrow must be non-decreasing");
+    const long long nb = ptrow[nbrows];
+    CHECK_ARG(nb == 0 || indcol, "indcol is null");
+    for (long long k = 0; k < nb; k++) CHECK_ARG(indcol[k] >= 0, "negative block column");
+    Bcsr4TileListsHost H;
+    build_bcsr4_tile_lists(nbrows, ptrow, indcol, kWG / 4, kBtileNodes, H);
+    if (would_build) *would_build = H.built;
+    if (groups) *groups = H.groups;
+    if (max_nodes) *max_nodes = H.max_nodes;
+    if (groups_at_cap) *groups_at_cap = H.groups_at_cap;
     return MI_OK;
 }
 

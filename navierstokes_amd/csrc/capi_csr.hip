@@ -4,6 +4,7 @@
 #include "reorder.hpp"
 #include "mring_plan.hpp"
 #include "tile_plan.hpp"
+#include "rowblock_census.hpp"
 
 // ---------------------------------------------------------------- CSR create
 int get_table(mi_csr_t A, int nnzb, BlockTable** out)
@@ -11,15 +12,14 @@ int get_table(mi_csr_t A, int nnzb, BlockTable** out)
     auto it = A->tables.find(nnzb);
     if (it == A->tables.end()) {
         std::vector<int> rows, ptrs;
-        // whole waves of rows for the one-thread-per-row chain phase where that keeps 7/8 of the block (ring_plan.hpp) — for
-        // matrices that live in the Infinity Cache: S15 1 M rows 61 -> 56 us, but the 5 M-row mesh 180 -> 193 us
-        // (tools/stream_align_ab.py); MI355_STREAM_ROW_ALIGN=1|64 forces (A/B)
-        int row_align = A->nnz < 20000000 ? 64 : 1;
+        // the row-alignment rule of partition.hpp (row_block_align); MI355_STREAM_ROW_ALIGN=1|64 forces (A/B)
+        int row_align = row_block_align(A->nnz);
         if (const char* e = getenv("MI355_STREAM_ROW_ALIGN")) row_align = std::max(1, atoi(e));
-        build_row_blocks(A->n, A->h_ptrow.data(), nnzb, 4 * kWG, rows, ptrs, row_align, 7);
+        build_row_blocks(A->n, A->h_ptrow.data(), nnzb, 4 * kWG, rows, ptrs, row_align, kRowBlockKeepEighths);
         BlockTable T;
         T.nnzb = nnzb;
         T.nblk = (int)rows.size() - 1;
+        T.row_align = row_align;
         std::vector<int2> h(rows.size());
         for (size_t i = 0; i < rows.size(); i++) h[i] = make_int2(rows[i], ptrs[i]);
         HIP_TRY(T.d_blk.upload(h));
@@ -200,7 +200,7 @@ static int build_tile(mi_csr_t A, const int* indcol)
         indcol = back.data();
     }
     TilePlanHost P;
-    build_tile_plan(A->n, A->h_ptrow.data(), indcol, P, kTileNnzb, 0, A->nnz < 20000000 ? 64 : 1);
+    build_tile_plan(A->n, A->h_ptrow.data(), indcol, P, kTileNnzb, 0, row_block_align(A->nnz));
     TileTable T;
     HIP_TRY(T.d_desc.alloc(P.desc.size()));
     HIP_TRY(T.d_ulist.alloc(P.ulist.size()));
@@ -210,12 +210,7 @@ static int build_tile(mi_csr_t A, const int* indcol)
     HIP_TRY(T.d_slots.fill(P.slots));
     T.nblk = P.nblk;
     T.unique_per_nnz = (double)(P.ulist.size() - kTileThreads) / (double)A->nnz;
-    long long mult8 = 0;
-    for (int i = 0; i < A->n; i++) {
-        const int len = A->h_ptrow[i + 1] - A->h_ptrow[i];
-        mult8 += len > 0 && len % 8 == 0;
-    }
-    T.skew = 10 * mult8 > A->n;
+    T.skew = tile_wants_skew(A->n, A->h_ptrow.data());
     T.nt = beyond_infinity_cache(10.0, A->nnz, A->n);
     A->tile = std::move(T);
     return MI_OK;
@@ -1610,6 +1605,50 @@ extern "C" int mi_mring_plan_census(int n, const int* ptrow, const int* indcol, 
     MringPlanHost P;
     build_mring_plan(n, ptrow, indcol, P, large_row_align(ptrow[n]));
     mring_plan_census(P, n, indcol, counters);
+    return MI_OK;
+}
+
+// ... and of the row blocks of the stream kernel (get_table's call) or the tile kernel (build_tile's call): rowblock_census.hpp
+static_assert(kRowblockCensusLen == MI_ROWBLOCK_CENSUS_LEN, "include/mi355_spmv.h lists the counters");
+extern "C" int mi_rowblock_census(int n, const int* ptrow, const int* indcol, int which, long long* counters, int cap)
+{
+    CHECK_ARG(n >= 0 && ptrow && ptrow[0] == 0 && counters && (which == MI_KERNEL_STREAM || which == MI_KERNEL_TILE), "bad argument");
+    CHECK_ARG(cap >= kRowblockCensusLen, "counters holds fewer than MI_ROWBLOCK_CENSUS_LEN entries");
+    for (int i = 0; i < n; i++) CHECK_ARG(ptrow[i] <= ptrow[i + 1], "ptrow must be non-decreasing");
+    const long long nnz = ptrow[n];
+    CHECK_ARG(nnz == 0 || indcol, "indcol is null");
+    const bool tile = which == MI_KERNEL_TILE;
+    const int nnzb = tile ? kTileNnzb : 1024, threads = tile ? kTileThreads : kWG, row_align = row_block_align(nnz);
+    std::vector<int> rows, ptrs, ucount;
+    std::vector<char> why;
+    build_row_blocks(n, ptrow, nnzb, 4 * threads, rows, ptrs, row_align, kRowBlockKeepEighths, &why);
+    const int nblk = (int)rows.size() - 1;
+    if (tile) {
+        TilePlanHost P;
+        build_tile_plan(n, ptrow, indcol, P, kTileNnzb, 0, row_align);
+        if (const char* bad = check_tile_plan(P, n, ptrow, indcol)) return fail(MI_ERR_STATE, std::string("tile plan: ") + bad);
+        if (P.nblk != nblk) return fail(MI_ERR_STATE, "tile plan: its blocks are not those of build_row_blocks");
+        ucount.resize((size_t)nblk);
+        for (int b = 0; b < nblk; b++) {
+            if (P.desc[(size_t)4 * b] != rows[b] || P.desc[(size_t)4 * b + 1] != ptrs[b]) return fail(MI_ERR_STATE, "tile plan: its blocks are not those of build_row_blocks");
+            ucount[b] = P.desc[(size_t)4 * (b + 1) + 2] - P.desc[(size_t)4 * b + 2];
+        }
+    }
+    rowblock_census(n, ptrow, nnzb, threads, row_align, rows, ptrs, why, tile ? ucount.data() : nullptr, tile && tile_wants_skew(n, ptrow), counters);
+    if ((long long)cap >= (long long)kRowblockCensusLen + nblk + 1) // room for the row starts: blocks + 1 entries behind the counters
+        for (int b = 0; b <= nblk; b++) counters[kRowblockCensusLen + b] = rows[b];
+    return MI_OK;
+}
+
+extern "C" int mi_csr_stream_info(mi_csr_t A, int* nblk, int* row_align)
+{
+    CHECK_ARG(A, "null handle");
+    if (A->inner) A = A->inner;
+    BlockTable* T = nullptr;
+    int rc = need_device();
+    if (rc || (rc = get_table(A, 1024, &T))) return rc;
+    if (nblk) *nblk = T->nblk;
+    if (row_align) *row_align = T->row_align;
     return MI_OK;
 }
 

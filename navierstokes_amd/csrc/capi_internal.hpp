@@ -150,6 +150,7 @@ static inline bool stream_is_capturing(hipStream_t s)
 struct BlockTable {
     int nnzb = 0;
     int nblk = 0;
+    int row_align = 1;     // what the table was cut with (mi_csr_stream_info)
     DevArray<int2> d_blk;  // [nblk+1]
 };
 

@@ -249,21 +249,30 @@ struct PartPlan {
 // so that the y segment a block writes starts on a 128-byte line (row_align = 16).
 // row_align > 1: blocks end on multiples of row_align rows; keep_eighths > 0: only where the shortened block keeps at least that
 // many eighths of its nonzeros (the one-thread-per-row kernels want whole waves of rows, but not half-empty blocks)
+// why (optional, one entry per block): what ended the block — kBlockEndRowCap: the row cap, not the nonzero limit;
+// kBlockEndPulledBack: the alignment rule moved its end (the census of rowblock_census.hpp counts both)
+enum { kBlockEndRowCap = 1, kBlockEndPulledBack = 2 };
 inline void build_row_blocks(int n, const int* ptrow, int nnzb, int max_rows, std::vector<int>& out_rows,
-                             std::vector<int>& out_ptr, int row_align = 1, int keep_eighths = 0)
+                             std::vector<int>& out_ptr, int row_align = 1, int keep_eighths = 0, std::vector<char>* why = nullptr)
 {
     out_rows.clear();
     out_ptr.clear();
+    if (why) why->clear();
     int r = 0;
     while (r < n) {
         const int start = r;
         const int p0 = ptrow[r];
         int e = r + 1; // a block always takes at least one row
         while (e < n && (e - start) < max_rows && (long long)ptrow[e + 1] - p0 <= nnzb) e++;
+        char w = e < n && (e - start) == max_rows && (long long)ptrow[e + 1] - p0 <= nnzb ? kBlockEndRowCap : 0;
         if (row_align > 1 && e < n) {
             const int ea = (e / row_align) * row_align;
-            if (ea > start && 8 * (long long)(ptrow[ea] - p0) >= (long long)keep_eighths * (ptrow[e] - p0)) e = ea;
+            if (ea > start && ea < e && 8 * (long long)(ptrow[ea] - p0) >= (long long)keep_eighths * (ptrow[e] - p0)) {
+                e = ea;
+                w = kBlockEndPulledBack;
+            }
         }
+        if (why) why->push_back(w);
         out_rows.push_back(start);
         out_ptr.push_back(p0);
         r = e;
@@ -271,6 +280,14 @@ inline void build_row_blocks(int n, const int* ptrow, int nnzb, int max_rows, st
     out_rows.push_back(n);
     out_ptr.push_back(n > 0 ? ptrow[n] : 0);
 }
+
+// The row-alignment rule of the row-block kernels (the stream kernel's table, the tile kernel's plan): blocks of whole waves of rows
+// for the one-thread-per-row chain phase where the shortened block keeps 7/8 of its nonzeros — for matrices that live in the
+// Infinity Cache: S15 1 M rows 61 -> 56 us, but the 5 M-row mesh 180 -> 193 us (tools/stream_align_ab.py).  One place: get_table,
+// build_tile and the census (mi_rowblock_census) call it.
+constexpr long long kRowBlockAlignMaxNnz = 20000000;
+constexpr int kRowBlockKeepEighths = 7;
+inline int row_block_align(long long nnz) { return nnz < kRowBlockAlignMaxNnz ? 64 : 1; }
 
 // CSR with 4x4 node-block structure (what the reference's FE assembly produces:
 // src/benchmark_spmv.c:104-118 inserts whole 4x4 blocks) -> BCSR 4x4 with row-major blocks

@@ -43,8 +43,8 @@ inline void build_tile_plan(int n, const int* ptrow, const int* indcol, TilePlan
     out = TilePlanHost();
     out.nnzb = nnzb;
     std::vector<int> rows, ptrs;
-    build_row_blocks(n, ptrow, nnzb, 4 * kTileThreads, rows, ptrs, row_align, 7); // whole waves of rows for the row-chain phase
-                                                                                   // (ring_plan.hpp; the caller decides by matrix size)
+    build_row_blocks(n, ptrow, nnzb, 4 * kTileThreads, rows, ptrs, row_align, kRowBlockKeepEighths); // whole waves of rows for the row-chain
+                                                                                   // phase (partition.hpp: the caller passes row_block_align)
     const int nblk = (int)rows.size() - 1;
     out.nblk = nblk;
     out.desc.assign((size_t)4 * (nblk + 1), 0);
@@ -110,6 +110,18 @@ inline void build_tile_plan(int n, const int* ptrow, const int* indcol, TilePlan
             if (ucount[b] > 0) out.listed += ptrs[b + 1] - ptrs[b];
         }
     }
+}
+
+// Staging layout of the kernel's value array (its SKEW template argument, cf. ring_wants_skew): the pad slot per 32 staged values
+// pays once more than a tenth of the rows are a multiple of 8 long (a wave's row chains then start on the same banks).
+inline bool tile_wants_skew(int n, const int* ptrow)
+{
+    long long mult8 = 0;
+    for (int i = 0; i < n; i++) {
+        const int len = ptrow[i + 1] - ptrow[i];
+        mult8 += len > 0 && len % 8 == 0;
+    }
+    return 10 * mult8 > n;
 }
 
 // invariants of a plan against the matrix it was built from; returns nullptr or the first violation

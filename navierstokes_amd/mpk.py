@@ -116,8 +116,11 @@ def lib():
         "mi_ring_plan_lean": [i, _vp, _vp, i, P(i)],
         "mi_ring_plan_census": [i, _vp, _vp, i, _vp, i],
         "mi_mring_plan_census": [i, _vp, _vp, _vp, i],
+        "mi_rowblock_census": [i, _vp, _vp, i, _vp, i],
+        "mi_csr_stream_info": [_vp, P(i), P(i)],
         "mi_csr_tile_info": [_vp, P(i), P(i), P(d), P(d), P(i)],
         "mi_bcsr4_tile_info": [_vp, P(i), P(i), P(d), P(d)],
+        "mi_bcsr4_tile_probe": [i, _vp, _vp, P(i), P(i), P(i), P(i)],
         "mi_bcsr4_sell_info": [_vp, P(i), P(i), P(ll), P(d), P(d)],
         "mi_bcsr4_sell_plan_probe": [i, _vp, _vp, i, P(i), P(ll), P(i), _vp, _vp, _vp],
         "mi_bcsr4_spmm_plan_probe": [i, _vp, _vp, i, i, P(i), P(i), P(i), P(d), _vp, ll, _vp, ll, _vp, ll, _vp, ll],
@@ -468,6 +471,12 @@ class csrmatrix:
         us = (_c.c_double * 2)()
         check(lib().mi_csr_tile_info(self.handle, _c.byref(b), _c.byref(nb), _c.byref(u), us, _c.byref(nt)))
         return dict(built=bool(b.value), nblk=nb.value, unique_per_nnz=u.value, us=us[0], us_nt=us[1], nt=bool(nt.value))
+
+    def stream_info(self):
+        """dict(nblk, row_align) — mi_csr_stream_info (the handle's table for the stream kernel, built if no product needed it yet)."""
+        nb, al = _c.c_int(), _c.c_int()
+        check(lib().mi_csr_stream_info(self.handle, _c.byref(nb), _c.byref(al)))
+        return dict(nblk=nb.value, row_align=al.value)
 
     def reorder_info(self):
         """dict(reordered, block, spread_before, spread_after, us_natural, us_reordered) — mi_csr_reorder_info."""
@@ -963,6 +972,36 @@ def mring_plan_census(n, ptrow, indcol):
     out = np.zeros(len(MRING_CENSUS), np.int64)
     check(lib().mi_mring_plan_census(int(n), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, out.ctypes.data, out.size))
     return dict(zip(MRING_CENSUS, out.tolist()))
+
+
+ROWBLOCK_CENSUS = ("blocks row_align idle_wgs empty empty_first empty_last empty_middle "
+                   "full full_less1 nn_mod8_1 nn_mod8_7 nn_1 "
+                   "rows_1 rows_t rows_t1 rows_cap rows_max ended_by_cap pulled_back "
+                   "first_row_empty last_row_empty rowlen_1 rowlen_8 rowlen_9 "
+                   "long long_plus1 long_2x long_2x1 long_first_row long_last_row long_after_long "
+                   "r1 r2 r3 r4 r5 r6 r7 r8 u_1 u_mult u_mult1 u_eq_nn u_max skew").split()
+
+
+def rowblock_census(n, ptrow, indcol, which, starts=False):
+    """mi_rowblock_census (no GPU): dict of the counters include/mi355_spmv.h lists, by the names of ROWBLOCK_CENSUS, for the row
+    blocks of the stream kernel (which = "stream") or the tile kernel's plan ("tile").  starts=True: (dict, first row of every
+    block followed by n)."""
+    ptrow = np.ascontiguousarray(ptrow, np.int32)
+    indcol = np.ascontiguousarray(indcol, np.int32)
+    k = len(ROWBLOCK_CENSUS)
+    out = np.zeros(k + (int(n) + 1 if starts else 0), np.int64)
+    check(lib().mi_rowblock_census(int(n), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, KERNELS[which], out.ctypes.data, out.size))
+    S = dict(zip(ROWBLOCK_CENSUS, out[:k].tolist()))
+    return (S, out[k:k + S["blocks"] + 1].copy()) if starts else S
+
+
+def bcsr4_tile_probe(nbrows, ptrow, indcol):
+    """mi_bcsr4_tile_probe (no GPU): dict(would_build, groups, max_nodes, groups_at_cap) — the x-tile lists of the blocked kernel."""
+    ptrow = np.ascontiguousarray(ptrow, np.int32)
+    indcol = np.ascontiguousarray(indcol, np.int32)
+    v = [_c.c_int() for _ in range(4)]
+    check(lib().mi_bcsr4_tile_probe(int(nbrows), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, *[_c.byref(t) for t in v]))
+    return dict(would_build=bool(v[0].value), groups=v[1].value, max_nodes=v[2].value, groups_at_cap=v[3].value)
 
 
 def spmk_plan_probe(n, ptrow, indcol):

@@ -2,9 +2,13 @@
 // and undefined-behaviour sanitizers.  The pattern families of tests/spmm_tile_cases.py are regenerated here and every plan — 128 and 64
 // rows per tile, the default caps and small ones, rows sorted and in growth order — is checked by brute force: every block row once, shadows
 // naming a live row of their own tile, lists strictly ascending and equal to the set of their rows' columns, every slot naming its block's
-// column, umax the longest list, over-cap lists on single rows only, the 16-bit refusal and the empty matrices:
+// column, umax the longest list, over-cap lists on single rows only, the 16-bit refusal and the empty matrices.  Also here: the x-tile
+// lists of the single-vector blocked kernel (bcsr4_tile_plan.hpp) and the row-block table with its census (partition.hpp,
+// rowblock_census.hpp) on random patterns:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -Inavierstokes_amd/csrc -o /tmp/spmm_plan_asan tools/spmm_plan_asan.cpp && /tmp/spmm_plan_asan
 #include "spmm_tile_plan.hpp"
+#include "bcsr4_tile_plan.hpp"
+#include "rowblock_census.hpp"
 #include <cstdio>
 #include <random>
 #include <set>
@@ -116,8 +120,89 @@ static void check(const std::string& nm, const Rows& rows, bool small_caps = fal
     }
 }
 
+// The x-tile lists of the single-vector blocked kernel (bcsr4_tile_plan.hpp) and the row-block table with its census
+// (partition.hpp: build_row_blocks, rowblock_census.hpp), on exactly-sized arrays, against brute force.
+static void check_bcsr4_tile_lists(std::mt19937& rng, int nbr, int width, int cap)
+{
+    std::vector<int> ptr(1, 0), col;
+    for (int r = 0; r < nbr; r++) {
+        const int len = rng() % 5 == 0 ? 0 : 10 + (int)(rng() % 12);
+        for (int j = 0; j < len; j++) col.push_back((int)((r / 64 * 64 + rng() % width) % (nbr + 50)));
+        ptr.push_back((int)col.size());
+    }
+    Bcsr4TileListsHost H;
+    build_bcsr4_tile_lists(nbr, ptr.data(), col.data(), 64, cap, H);
+    plans++;
+    const int groups = (nbr + 63) / 64;
+    int longest = 0, at_cap = 0;
+    bool fits = true;
+    for (int g = 0; g < groups && fits; g++) {
+        std::set<int> cols(col.begin() + ptr[64 * g], col.begin() + ptr[std::min(nbr, 64 * g + 64)]);
+        longest = std::max(longest, (int)cols.size());
+        at_cap += (int)cols.size() == cap;
+        fits = (int)cols.size() <= cap;
+        if (!fits || (long long)col.size() < kBtileMinBlocks) continue;
+        int k = H.wg_ptr[g];
+        for (int c : cols) bad += H.nodes[k++] != (unsigned)c;
+        bad += k != H.wg_ptr[g + 1];
+        for (int b = ptr[64 * g]; b < ptr[std::min(nbr, 64 * g + 64)]; b++) bad += H.nodes[H.wg_ptr[g] + H.slots[b]] != (unsigned)col[b];
+    }
+    const bool listed = (long long)col.size() >= kBtileMinBlocks;
+    if (H.groups != groups || H.built != (listed && fits) || H.max_nodes != (listed ? longest : 0) || H.groups_at_cap != (listed ? at_cap : 0) ||
+        (H.built && (H.slots.size() != col.size() + 1 || (int)H.nodes.size() != H.wg_ptr[groups] + 1))) {
+        printf("bcsr4 tile lists: %d block rows, width %d, cap %d: wrong answer\n", nbr, width, cap);
+        bad++;
+    }
+}
+
+static void check_row_blocks(std::mt19937& rng, int n, int nnzb, int max_rows, int align)
+{
+    std::vector<int> ptr(1, 0);
+    for (int r = 0; r < n; r++) {
+        const unsigned kind = rng() % 16;
+        ptr.push_back(ptr.back() + (kind == 0 ? nnzb + (int)(rng() % (2 * nnzb + 2)) : kind < 4 ? 0 : (int)(rng() % 9)));
+    }
+    std::vector<int> rows, ptrs;
+    std::vector<char> why;
+    build_row_blocks(n, ptr.data(), nnzb, max_rows, rows, ptrs, align, kRowBlockKeepEighths, &why);
+    plans++;
+    const int nblk = (int)rows.size() - 1;
+    bool ok = (int)why.size() == nblk && rows[0] == 0 && rows[nblk] == n && ptrs[nblk] == (n ? ptr[n] : 0);
+    for (int b = 0; b < nblk && ok; b++) {
+        const int r0 = rows[b], r1 = rows[b + 1], nn = ptr[r1] - ptr[r0];
+        ok = r1 > r0 && r1 - r0 <= max_rows && ptrs[b] == ptr[r0] && (nn <= nnzb || r1 == r0 + 1);
+        // a block that was not pulled back could not have taken its next row; one that was ends on a multiple of `align`
+        if (ok && !(why[b] & kBlockEndPulledBack) && r1 < n) ok = r1 - r0 == max_rows || ptr[r1 + 1] - ptr[r0] > nnzb;
+        if (ok && (why[b] & kBlockEndPulledBack)) ok = r1 % align == 0;
+    }
+    std::vector<long long> c((size_t)kRowblockCensusLen);
+    rowblock_census(n, ptr.data(), nnzb, max_rows / 4, align, rows, ptrs, why, nullptr, false, c.data());
+    long long empty = 0, longs = 0;
+    for (int b = 0; b < nblk; b++) {
+        empty += ptrs[b + 1] == ptrs[b];
+        longs += ptrs[b + 1] - ptrs[b] > nnzb;
+    }
+    if (!ok || c[kRbBlocks] != nblk || c[kRbEmpty] != empty || c[kRbLong] != longs || c[kRbIdleWgs] != 8LL * ((nblk + 7) / 8) - nblk) {
+        printf("row blocks: n %d nnzb %d cap %d align %d: wrong table or census\n", n, nnzb, max_rows, align);
+        bad++;
+    }
+}
+
 int main()
 {
+    {
+        std::mt19937 rng(777);
+        for (int nbr : {0, 1, 63, 64, 65, 300, 401}) {
+            check_bcsr4_tile_lists(rng, nbr, 20, 1024);
+            check_bcsr4_tile_lists(rng, nbr, 200, 64);
+            check_bcsr4_tile_lists(rng, nbr, 65, 65);
+        }
+        for (int trial = 0; trial < 60; trial++) {
+            const int n = (int)(rng() % 3000);
+            check_row_blocks(rng, n, trial % 2 ? 1024 : 2048, 1024, trial % 3 ? 64 : 1);
+            check_row_blocks(rng, n, 16, 8, 4);
+        }
+    }
     { // grid: 3-D 7-point, 11 x 10 x 9
         const int nx = 11, ny = 10, nz = 9;
         Rows rows;
