@@ -1,6 +1,7 @@
-// bilu4_factor.hpp — the numeric 4x4-block ILU(k) factorisation on the GPU (mi_bilu4dev_refactor): what
-// src/kernels/baij4_factor_avx2.c:114-170 computes, row by row, IKJ, written in place into the level-major device copies the
-// solve reads (bilu4_solve.hpp).  Bit for bit the host factorisation of bilu4_plan.hpp ("ARITHMETIC" there): every product
+// bilu4_factor.hpp — the numeric 4x4-block ILU(k) factorisation on the GPU (mi_bilu4dev_refactor): the IKJ factorisation that
+// PETSc performs for the reference, in the row loop src/kernels/baij4_factor_avx2.c:114-170 is laid out as (that file is not run by
+// the reference — nothing installs it — and does not compute it: its line 141 drops L . Dinv), written in place into the level-major
+// device copies the solve reads (bilu4_solve.hpp).  Bit for bit the host factorisation of bilu4_plan.hpp ("ARITHMETIC" there): every product
 // entry one chain from a rounded product, every update one rounded subtraction, pivots in ascending column order, an L block
 // whose 16 entries all == 0.0 at its turn skipped, the Gauss-Jordan inverse in the order fixed there (rounded product, then
 // rounded subtraction; 1/d a correctly rounded division; |d| < 1e-12 refused).  Compiled with -ffp-contract=off.

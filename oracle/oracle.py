@@ -3,7 +3,9 @@
 ctypes loaders for
   * ``libcpu_ref.so``  — our plain-C restatement (oracle/cpu_ref.c), always built;
   * ``_ref/libref_*.so`` — the REAL reference kernels compiled from
-    /root/reference/mpk by oracle/Makefile (present only where they were built).
+    /root/reference/mpk by oracle/Makefile (present only where they were built);
+    ``_ref/libref_baij_*.so`` are the solver's PETSc-bound kernels (src/kernels/*.c)
+    compiled against oracle/petsc_stub and reached through oracle/ref_glue_baij.c.
 
 Only tests/, ``__graft_entry__.smoke()`` and bench.py's ``cpu_baseline`` leg
 import this module.
@@ -465,6 +467,13 @@ def ref(which):
             L.ref_orthogonalize3.argtypes = [_c.c_int, _f64, _f64, _f64, _c.c_double]
         elif which == "multi1":
             L.ref_multi1_spm4v_avx2.argtypes = [_c.c_int, _c.c_int, _i32, _i32, _f64, _f64, _f64]
+        elif which == "baij_solve":
+            L.ref_baij_solve.argtypes = [_c.c_int, _c.c_int, _i32, _i32, _i32, _f64, _c.c_int, _f64, _f64, _c.c_int]
+        elif which in ("baij_mult", "baij_mad"):
+            L.ref_baij_mult.argtypes = [_c.c_int, _c.c_int, _c.c_int, _i32, _i32, _f64, _f64, _f64, _c.c_int]
+            L.ref_aij_mult.argtypes = [_c.c_int, _c.c_int, _c.c_int, _i32, _i32, _f64, _f64, _f64]
+            if which == "baij_mult":
+                L.ref_baij_spmm.argtypes = [_c.c_int, _i32, _i32, _f64, _f64, _f64, _c.c_int, _c.c_int]
         _REF[which] = L
     return _REF[which]
 
@@ -599,3 +608,64 @@ def ref_spm4v_avx2(ptrow, indcol, coef, x):
     rc = ref("multi1").ref_multi1_spm4v_avx2(n, len(indcol), ptrow, indcol, coef, x, Y.reshape(-1))
     assert rc == 0
     return Y
+
+
+# ---- the solver's PETSc-bound kernels, src/kernels/*.c (oracle/ref_glue_baij.c over oracle/petsc_stub)
+
+def have_ref_baij():
+    return all(os.path.exists(os.path.join(_HERE, "_ref", f"libref_baij_{s}.so")) for s in ("solve", "mult", "mad"))
+
+
+BAIJ_SOLVE_KINDS = {"scalar": 0, "avx2": 1}        # MatSolve_SeqBAIJ_4, MatSolve_SeqBAIJ_4_AVX2
+BAIJ_MULT_KINDS = {"mad": 0, "fma": 1, "avx2": 2}  # MatMult_SeqBAIJ_4, ..._FMA, ..._AVX2
+AIJ_MULT_KINDS = {"mad": 0, "fma": 1}              # MatMult_SeqAIJ, MatMult_SeqAIJ_FMA
+
+
+def ref_baij_solve(kind, bi, bj, bdiag, ba, b, inplace=False):
+    """x = U^-1 L^-1 b by the reference's MATOP_SOLVE function over PETSc's factored BAIJ arrays (tests/petsc_layout.py:
+    to_petsc_factor); inplace: the kernel gets one vector as b and x."""
+    bi, bj, bdiag, ba, b = _as_i32(bi), _as_i32(bj), _as_i32(bdiag), _as_f64(ba).reshape(-1), _as_f64(b)
+    nb = len(bi) - 1
+    assert len(bdiag) == nb + 1 and len(ba) == 16 * len(bj) and len(b) == 4 * nb
+    x = np.full(4 * nb, np.nan)
+    rc = ref("baij_solve").ref_baij_solve(BAIJ_SOLVE_KINDS[kind], nb, bi, bj, bdiag, ba, len(bj), b, x, 1 if inplace else 0)
+    assert rc == 0, rc
+    return x
+
+
+def ref_baij_mult(kind, ai, aj, aa, x, compressed=False):
+    """y = A x by one of the reference's MATOP_MULT functions; aa: COLUMN-major 4x4 blocks, the bytes of Mat_SeqBAIJ::a.
+    compressed: the matrix is presented with compressedrow.use set (the empty block rows left out of the row loop)."""
+    ai, aj, aa, x = _as_i32(ai), _as_i32(aj), _as_f64(aa).reshape(-1), _as_f64(x)
+    nb = len(ai) - 1
+    assert len(aa) == 16 * len(aj) and len(x) % 4 == 0 and (len(aj) == 0 or 4 * (int(aj.max()) + 1) <= len(x))
+    y = np.full(4 * nb, np.nan)
+    lib = ref("baij_mad" if kind == "mad" else "baij_mult")
+    rc = lib.ref_baij_mult(BAIJ_MULT_KINDS[kind], nb, len(x) // 4, ai, aj, aa, x, y, 1 if compressed else 0)
+    assert rc == 0, rc
+    return y
+
+
+def ref_baij_spmm(ai, aj, aa, X, compressed=False):
+    """MatMatMult_SeqBAIJ_4_AVX2 on a square matrix: X (s, 4 nb), one vector per row (= PETSc's column-major dense 4 nb x s);
+    returns Y of the same shape.  aa reaches the kernel byte for byte."""
+    ai, aj, aa, X = _as_i32(ai), _as_i32(aj), _as_f64(aa).reshape(-1), _as_f64(X)
+    nb = len(ai) - 1
+    s = X.shape[0]
+    assert X.shape == (s, 4 * nb) and len(aa) == 16 * len(aj)
+    Y = np.full((s, 4 * nb), np.nan)
+    rc = ref("baij_mult").ref_baij_spmm(nb, ai, aj, aa, X.reshape(-1), Y.reshape(-1), s, 1 if compressed else 0)
+    assert rc == 0, rc
+    return Y
+
+
+def ref_aij_mult(kind, ai, aj, aa, x):
+    """y = A x by MatMult_SeqAIJ ('mad') or MatMult_SeqAIJ_FMA ('fma')."""
+    ai, aj, aa, x = _as_i32(ai), _as_i32(aj), _as_f64(aa), _as_f64(x)
+    n = len(ai) - 1
+    assert len(aa) == len(aj) and (len(aj) == 0 or int(aj.max()) < len(x))
+    y = np.full(n, np.nan)
+    lib = ref("baij_mad" if kind == "mad" else "baij_mult")
+    rc = lib.ref_aij_mult(AIJ_MULT_KINDS[kind], n, len(x), ai, aj, aa, x, y)
+    assert rc == 0, rc
+    return y

@@ -4,7 +4,8 @@
 Run in a container that has /root/reference and a built oracle/_ref/
 (`make -C oracle`).  Every expected output below is produced by the
 reference's own object code (mpk/SpMV.cpp, utils.cpp, SpM2V.cpp,
-SpMVmulti0.cpp compiled where they lie); the inputs are seeded synthetic
+SpMVmulti0.cpp compiled where they lie; for ref_baij.npz the solver's
+src/kernels/*.c compiled against oracle/petsc_stub); the inputs are seeded synthetic
 matrices (navierstokes_amd/synth.py) or hand-made COO edge cases.  The .npz
 files hold DATA only: inputs and expected outputs as raw float64/int32.
 
@@ -177,9 +178,46 @@ def ref_symbols():
     print("ref_symbols", {k: len(v) for k, v in d.items()})
 
 
+def write_npz(path, arrays):
+    """np.savez_compressed with nothing of the day in it: entries in sorted order, the zip's earliest timestamp on each, so that the
+    same arrays give the same bytes on every run."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for key in sorted(arrays):
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.ascontiguousarray(arrays[key]), allow_pickle=False)
+
+
+def ref_baij():
+    """tests/test_gpu_petsc_seam.py: what the reference's PETSc-bound kernels (src/kernels/*.c, oracle/_ref/libref_baij_*.so)
+    return on the cases of tests/ref_baij_cases.py — x of MatSolve_SeqBAIJ_4 and MatSolve_SeqBAIJ_4_AVX2 with the
+    extended-precision yardstick, the model's solve and the three errors; y of MatMult_SeqBAIJ_4{,_FMA,_AVX2}; Y of
+    MatMatMult_SeqBAIJ_4_AVX2.  Results only (tests/test_ref_baij.py computes them)."""
+    import ref_baij_cases as R
+    import test_ref_baij as T
+    d = {}
+    for case in R.SOLVE_CASES:
+        if case[0] in R.GOLDEN_SKIP:
+            continue
+        for kind, rec in T.solve_record(*case).items():
+            d.update(R.pack_solve(case, kind, rec))
+    for name in R.PRODUCT_MATRICES:
+        if name not in R.GOLDEN_SKIP:
+            d.update(R.pack_product(name, T.product_record(name)))
+    path = os.path.join(OUT, "ref_baij.npz")
+    write_npz(path, d)
+    print("ref_baij", len(d), "arrays,", os.path.getsize(path), "bytes")
+
+
 def main():
-    if not O.have_ref():
+    if not O.have_ref() or not O.have_ref_baij():
         sys.exit("oracle/_ref is not built: run `make -C oracle` where /root/reference exists")
+    if sys.argv[1:] == ["ref_baij"]:  # that recording alone
+        return ref_baij()
+    ref_baij()
     ref_digests()
     fe_ref_blocks()
     ref_symbols()

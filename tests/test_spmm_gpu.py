@@ -1,8 +1,10 @@
 """Multi-vector products and the s-step Krylov basis (src/kernels/spmm_avx2.c:7-168) on the GPU.
 Oracle: per column, orc_spmv_bcsr4_fma (bit-pinned to SpMV_BCSR_FMA) for MI_ARITH_CHAIN and orc_spmv_bcsr4_blockacc
 (bit-pinned to SpM2V_BCSR_OPT, the same association spmm_avx2.c:77-88 uses) for MI_ARITH_BLOCKACC.
-The arithmetic of spmm_avx2.c itself cannot be run here (PETSc is absent: SURVEY F6) — for that file parity is
-UNPINNED; what is pinned is the association it shares with SpM2V_BCSR_OPT, and its x4 defect is documented, not copied."""
+spmm_avx2.c itself runs without PETSc since oracle/petsc_stub: tests/test_ref_baij.py holds MatMatMult_SeqBAIJ_4_AVX2 (fed the
+row-major bytes it indexes) BIT-equal to 4 x orc_spmv_bcsr4_blockacc at s = 1, 3, 4, 5, 8, and tests/test_gpu_petsc_seam.py holds
+mi_bcsr4_spmm{,_dev}(MI_ARITH_BLOCKACC) to its recorded output the same way.  Its x4 defect (the horizontal add sums four lanes that
+hold the same value) is measured there and documented, not copied."""
 import numpy as np
 import pytest
 import torch
