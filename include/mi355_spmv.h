@@ -1067,6 +1067,66 @@ int mi_gmres_plan_solve(mi_gmres_plan_t P, int* iterations, int* reason, double*
 int mi_gmres_plan_info(mi_gmres_plan_t P, int* graphs, int* segment, int* replays_last, int* readbacks_last, int* wasted_steps_last);
 int mi_gmres_plan_destroy(mi_gmres_plan_t P);
 
+/* ---- 4x4-block DILU applied with EISENSTAT'S TRICK: a GMRES step with no separate product (mi_dilu4_*, opt-in) ----
+ * A preconditioned GMRES step reads the matrix twice: once for the product, once (as many bytes again) for the ILU(0) factor.
+ * For a preconditioner whose off-diagonal blocks are the matrix's OWN the second reading can be had for free.  Write
+ * B = L + D + U (strict block triangles, block diagonal) and M = (E + L) E^-1 (E + U) with the block DILU pivots E.  Then
+ * B = (E + L) + (E + U) - (2E - D), and the split-preconditioned operator A^ = (E + L)^-1 B (E + U)^-1 E costs ONE backward
+ * and ONE forward triangular sweep over B's blocks — one preconditioner application, and no product.  The handle keeps B's strict
+ * triangles level-major, and Einv = E^-1 and K = 2E - D per block row: no factor, no fill.
+ * Ordering: MI_BILU_ORDER_NATURAL or MI_BILU_ORDER_COLOUR — the rule, perm and the two boundary launches of ordered mi_bilu4
+ * handles: B = Q A Q^T, and EVERY call keeps the caller's numbering (vectors, coef, the block row a refused pivot names, the
+ * rows mi_dilu4_fetch returns).  DILU of B is not DILU of A; in the colour order it measured as good as ILU(0) there, in the
+ * natural order about half as good (profiles/NOTES.md R21.1).  Nothing chooses this preconditioner: it is opt-in.
+ * Schedule: the dependency levels and the folding of mi_bilu4 at fill 0 on B's pattern: one launch per level, a run of levels of
+ * fewer than 64 block rows folded into one workgroup.
+ * PIVOTS (part of the interface; chain, the 4x4 product of sixteen chains and the Gauss-Jordan inverse with its 1e-12 refusal are
+ * those of mi_bilu4 above): block rows i of B ascending: E_i = D_i; for every j < i ascending with BOTH blocks (i, j) and (j, i) in
+ * the pattern: T = B_ij . Einv_j, P = T . B_ji, E_i = E_i - P, one rounded subtraction per entry; Einv_i = inverse(E_i);
+ * K_i = (2 E_i) - D_i per entry: an exact doubling, then one rounded subtraction.  The rows of a level are computed by several host
+ * threads (MI355_BILU_THREADS); the bits do not depend on the count.  A refused pivot: MI_ERR_ARG with the caller's block row.
+ * THE THREE OPERATIONS (chain(a, t) = fma(a3,t3, fma(a2,t2, fma(a1,t1, a0*t0))); every + and - below is one rounded operation;
+ * blocks of a row in ascending column of B; rows in level order):
+ *   to_hat     b^ = (E + L)^-1 r.        forward:  a = 0; a_q = a_q + chain(L_ij row q, b^_j); s_q = r_iq - a_q;
+ *                                                  b^_iq = chain(Einv_i row q, s)
+ *   from_hat   x = (E + U)^-1 E u.       backward: a = 0; a_q = a_q + chain(U_ij row q, x_j); c_q = chain(Einv_i row q, a);
+ *                                                  x_iq = u_iq - c_q
+ *   apply_hat  w = A^ u.                 t = from_hat(u) into a work vector of the handle; forward: a_q = chain(K_i row q, t_i);
+ *                                                  a_q = a_q + chain(L_ij row q, y_j); c_q = chain(Einv_i row q, a);
+ *                                                  y_iq = u_iq - c_q; w_iq = t_iq + y_iq   (y: a second work vector)
+ * Every row is ONE fixed sequence of roundings, independent of the schedule, the folding and the alignment.  Each operation is
+ * enqueued on the caller's stream, allocates nothing, synchronises nothing and can be captured into a graph; output == input is
+ * allowed; vectors need 8-byte alignment only.  ONE operation at a time per handle (the work vectors are the handle's).
+ * SOLVING WITH IT: the caller composes  r = b - A x0 (the one true product);  b^ = to_hat(r);  u^ = 0, GMRES on A^ u^ = b^
+ * (mi_gmres_set_operator_dilu4);  x = x0 + from_hat(u^).  rtol AND THE HISTORY OF THAT SOLVE ARE IN THE HAT NORM,
+ * ||(E + L)^-1 r|| / ||b^||, not in the norm of r: compare solves by their true residuals.
+ * mi_dilu4_refactor: new values, same pattern; runs on the host, waits for the device, uploads (as mi_bilu4_refactor).
+ * mi_dilu4_fetch: Einv and K, 16 doubles per block row, row-major, by the CALLER's block row (either may be NULL).
+ * mi_dilu4_info: *nblocks of B, *ordering, *ncolours (0 in natural order), levels of the two sweeps, *launches of one apply_hat
+ * (both sweeps after folding, + 2 on an ordered handle), *factor_seconds of the last host computation of the pivots, *device_bytes
+ * the handle owns on the device (0 on a host-only handle), perm [nbrows] (perm[caller's row] = B's).  Any output may be NULL.
+ * mi_dilu4_create_host: no device (refactor, fetch, info work; the three operations return MI_ERR_STATE).
+ * MI_ERR_ARG: what mi_bilu4_create refuses in a pattern, an unknown layout or ordering, a null argument, a refused pivot.
+ * nbrows == 0: every call is a no-op.  NOT built: a refactorisation on the device, a single-precision copy, Jacobi sweeps, a
+ * one-launch form, an automatic choice, mi_dist. */
+typedef struct mi_dilu4_s* mi_dilu4_t;
+int mi_dilu4_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout /* MI_BLOCK_* */,
+                    int ordering /* MI_BILU_ORDER_* */, mi_dilu4_t* out);
+int mi_dilu4_create_host(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int ordering, mi_dilu4_t* out);
+int mi_dilu4_destroy(mi_dilu4_t E);
+int mi_dilu4_refactor(mi_dilu4_t E, const double* coef, int layout);
+int mi_dilu4_fetch(mi_dilu4_t E, double* einv, double* k);
+int mi_dilu4_info(mi_dilu4_t E, int* nbrows, long long* nblocks, int* ordering, int* ncolours, int* fwd_levels, int* bwd_levels,
+                  int* launches, double* factor_seconds, long long* device_bytes, int* perm);
+int mi_dilu4_to_hat_dev(mi_dilu4_t E, const double* d_r, double* d_bhat, mi_stream_t s);
+int mi_dilu4_from_hat_dev(mi_dilu4_t E, const double* d_u, double* d_x, mi_stream_t s);
+int mi_dilu4_apply_hat_dev(mi_dilu4_t E, const double* d_u, double* d_w, mi_stream_t s);
+/* The operator of mi_gmres_*'s DEFINITION becomes A^: every "A x" there is mi_dilu4_apply_hat_dev(E, x, .) — the eager solve, the
+ * float basis, mi_gmres_cycle_dev and the plans alike; everything else in the DEFINITION is untouched.  4 nbrows == n.  The
+ * preconditioner must be NULL (M is inside A^): MI_ERR_STATE otherwise, and mi_gmres_set_precond* with F != NULL is refused with
+ * MI_ERR_STATE while this operator is set.  E is not owned and must outlive G; one solve at a time per E. */
+int mi_gmres_set_operator_dilu4(mi_gmres_t G, mi_dilu4_t E);
+
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r
  * owns global rows [row_starts[r], row_starts[r+1]) and the matching slice of

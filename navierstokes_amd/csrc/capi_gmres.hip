@@ -17,8 +17,9 @@ struct mi_gmres_s {
     long long ldv = 0;      // n rounded up to even: every row of V is 16-byte aligned
     int basis = MI_BASIS_F64;
     long long ldv32 = 0;    // MI_BASIS_F32: n rounded up to a multiple of 4: every row of V32 is 16-byte aligned
-    mi_csr_t A_csr = nullptr;       // the operator: one of the two (not owned)
+    mi_csr_t A_csr = nullptr;       // the operator: one of these (not owned)
     mi_bcsr4_t A_bcsr = nullptr;
+    mi_dilu4_t A_dilu = nullptr;    // ... or the split-preconditioned operator of a block DILU handle (mi_gmres_set_operator_dilu4)
     mi_bilu4_t F = nullptr;         // the preconditioner (not owned), or null
     Bilu4Apply pc{false, false, 0, 0}; // how F is applied (mi_gmres_set_precond*)
     DevArray<double> V;             // (m + 1) rows of ldv (MI_BASIS_F64 only)
@@ -100,7 +101,7 @@ extern "C" int mi_gmres_set_operator_csr(mi_gmres_t G, mi_csr_t A)
     CHECK_ARG(G && A, "null handle");
     CHECK_ARG(A->n == A->ncols && !A->mapped, "the operator must be a square, unmapped matrix");
     CHECK_ARG(A->n == G->n, "the operator's row count is not the solver's n");
-    G->A_csr = A, G->A_bcsr = nullptr;
+    G->A_csr = A, G->A_bcsr = nullptr, G->A_dilu = nullptr;
     G->gen++, G->prepared.clear();
     return MI_OK;
 }
@@ -110,7 +111,19 @@ extern "C" int mi_gmres_set_operator_bcsr4(mi_gmres_t G, mi_bcsr4_t A)
     CHECK_ARG(G && A, "null handle");
     CHECK_ARG(A->nbrows == A->nbcols, "the operator must be square");
     CHECK_ARG(4LL * A->nbrows == G->n, "the operator's row count (4 nbrows) is not the solver's n");
-    G->A_bcsr = A, G->A_csr = nullptr;
+    G->A_bcsr = A, G->A_csr = nullptr, G->A_dilu = nullptr;
+    G->gen++, G->prepared.clear();
+    return MI_OK;
+}
+
+extern "C" int mi_gmres_set_operator_dilu4(mi_gmres_t G, mi_dilu4_t E)
+{
+    CHECK_ARG(G && E, "null handle");
+    int nb = 0, rc;
+    if ((rc = mi_dilu4_info(E, &nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
+    CHECK_ARG(4LL * nb == G->n, "the operator's row count (4 nbrows) is not the solver's n");
+    if (G->F) return fail(MI_ERR_STATE, "mi_gmres_set_operator_dilu4: a preconditioner is set; the DILU operator has its preconditioner inside (mi_gmres_set_precond(G, NULL, ..) first)");
+    G->A_dilu = E, G->A_csr = nullptr, G->A_bcsr = nullptr;
     G->gen++, G->prepared.clear();
     return MI_OK;
 }
@@ -133,6 +146,7 @@ extern "C" int mi_gmres_set_precond_ex(mi_gmres_t G, mi_bilu4_t F, int kind, int
         G->gen++;
         return MI_OK;
     }
+    if (G->A_dilu) return fail(MI_ERR_STATE, "mi_gmres_set_precond: the operator is a DILU handle's, which has its preconditioner inside");
     int nb = 0, rc;
     if ((rc = mi_bilu4_info(F, &nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
     CHECK_ARG(4LL * nb == G->n, "the preconditioner's row count (4 nbrows) is not the solver's n");
@@ -152,6 +166,7 @@ extern "C" int mi_gmres_set_precond(mi_gmres_t G, mi_bilu4_t F, int kind, int sw
 
 static int gmres_mult(mi_gmres_s* G, const double* x, double* y, mi_stream_t s)
 {
+    if (G->A_dilu) return mi_dilu4_apply_hat_dev(G->A_dilu, x, y, s);
     return G->A_csr ? mi_spmv_dev(G->A_csr, x, y, s) : mi_bcsr4_spmv_dev(G->A_bcsr, x, y, s);
 }
 
@@ -172,7 +187,7 @@ static int gmres_precond(mi_gmres_s* G, const double* in, double* out, mi_stream
 
 static int gmres_need_operator(const mi_gmres_s* G, const char* who)
 {
-    return G->A_csr || G->A_bcsr ? MI_OK : fail(MI_ERR_STATE, std::string(who) + ": no operator set (mi_gmres_set_operator_*)");
+    return G->A_csr || G->A_bcsr || G->A_dilu ? MI_OK : fail(MI_ERR_STATE, std::string(who) + ": no operator set (mi_gmres_set_operator_*)");
 }
 
 // The enqueue helpers add what they enqueued to `launches`, by the rule of mi_gmres_info (kernels of this file and library calls, each

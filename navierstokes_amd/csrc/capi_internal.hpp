@@ -2,7 +2,7 @@
 // error helpers, the handle structs, and the few functions one unit needs from another.  The library is
 // built from capi_lib.hip (library / device / cache flush), capi_csr.hip (CSR handles: create, plans,
 // autotuner, products), launch_csr.hip (the CSR kernels' instantiations and launch_spmv), capi_blas1.hip,
-// capi_bcsr.hip (BCSR 4x4, multi-vector products, Krylov basis), capi_ilu.hip (block ILU preconditioner), capi_gmres.hip (restarted GMRES) and capi_part.hip
+// capi_bcsr.hip (BCSR 4x4, multi-vector products, Krylov basis), capi_ilu.hip (block ILU preconditioner), capi_dilu.hip (block DILU with Eisenstat's trick), capi_gmres.hip (restarted GMRES) and capi_part.hip
 // (partition, RCCL and peer-push exchange); devtools.hip (mi355_devtools.h) is linked into libmi355spmv_dev.so only.
 #pragma once
 #include "mi355_spmv.h"

@@ -229,6 +229,16 @@ def lib():
         "mi_gmres_plan_solve": [_vp, P(i), P(i), _vp, _vp],
         "mi_gmres_plan_info": [_vp, P(i), P(i), P(i), P(i), P(i)],
         "mi_gmres_plan_destroy": [_vp],
+        "mi_dilu4_create": [i, _vp, _vp, _vp, i, i, P(_vp)],
+        "mi_dilu4_create_host": [i, _vp, _vp, _vp, i, i, P(_vp)],
+        "mi_dilu4_destroy": [_vp],
+        "mi_dilu4_refactor": [_vp, _vp, i],
+        "mi_dilu4_fetch": [_vp, _vp, _vp],
+        "mi_dilu4_info": [_vp, P(i), P(ll), P(i), P(i), P(i), P(i), P(i), P(d), P(ll), _vp],
+        "mi_dilu4_to_hat_dev": [_vp, _vp, _vp, _vp],
+        "mi_dilu4_from_hat_dev": [_vp, _vp, _vp, _vp],
+        "mi_dilu4_apply_hat_dev": [_vp, _vp, _vp, _vp],
+        "mi_gmres_set_operator_dilu4": [_vp, _vp],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -1073,6 +1083,122 @@ def MatSolve_SeqBAIJ_4(F, b, x):
     return F.solve(x, b)
 
 
+class dilu4:
+    """mi_dilu4_t: the block DILU preconditioner M = (E + L) E^-1 (E + U) of a square 4x4-block matrix B = L + D + U, applied with
+    Eisenstat's trick: apply_hat is the split-preconditioned operator A^ = (E + L)^-1 B (E + U)^-1 E at the cost of ONE backward and
+    ONE forward triangular sweep, with no separate product (include/mi355_spmv.h, mi_dilu4_*).  dilu4(A, order="colour") takes a
+    bcsr4x4_matrix's host arrays (and its block layout); dilu4(nbrows, ptrow, indcol, coef, layout="row") the arrays themselves.
+    order: "colour" (the multicolour ordering of bilu4, where DILU measured as good as ILU(0)) or "natural"; every method keeps the
+    caller's numbering.  host_only=True: no device copy (refactor, fetch, info only).  Opt-in: nothing chooses it.  The three
+    operations take CUDA tensors, run asynchronously on torch's current stream, allocate nothing and may run in place; one operation
+    at a time per handle."""
+
+    def __init__(self, A, ptrow=None, indcol=None, coef=None, layout="row", host_only=False, order="colour"):
+        if isinstance(A, bcsr4x4_matrix):
+            nbrows, ptrow, indcol, coef, lay = A.nrows, A.ptrow, A.indcol, A.coef, A.layout
+        else:
+            nbrows, lay = int(A), {"row": 0, "col": 1}[layout]
+        self.nbrows = int(nbrows)
+        self.layout = lay
+        self.order = order
+        ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+        indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+        coef = _host_f64(coef, None, "coef")
+        if len(ptrow) != self.nbrows + 1:
+            raise ValueError("ptrow must have nbrows+1 entries")
+        if coef.size < 16 * len(indcol):
+            raise ValueError("coef: 16 values per block")
+        self._nblocks_in = len(indcol)
+        self._h = None
+        h = _vp()
+        make = lib().mi_dilu4_create_host if host_only else lib().mi_dilu4_create
+        check(make(self.nbrows, ptrow.ctypes.data, indcol.ctypes.data, coef.ctypes.data, lay, _bilu_order(order), _c.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("dilu4: closed")
+        return self._h
+
+    def _sweep(self, fn, out, src):
+        n = 4 * self.nbrows
+        check(fn(self.handle, _dev_ptr(src, n, "input"), _dev_ptr(out, n, "output"), _stream_ptr()))
+        return out
+
+    def to_hat(self, bhat, r):
+        """bhat = (E + L)^-1 r (mi_dilu4_to_hat_dev); bhat may be r."""
+        return self._sweep(lib().mi_dilu4_to_hat_dev, bhat, r)
+
+    def from_hat(self, x, u):
+        """x = (E + U)^-1 E u (mi_dilu4_from_hat_dev); x may be u."""
+        return self._sweep(lib().mi_dilu4_from_hat_dev, x, u)
+
+    def apply_hat(self, w, u):
+        """w = A^ u = (E + L)^-1 B (E + U)^-1 E u (mi_dilu4_apply_hat_dev); w may be u."""
+        return self._sweep(lib().mi_dilu4_apply_hat_dev, w, u)
+
+    def refactor(self, coef):
+        """New values on the same pattern (host array, the layout of construction): the pivots are recomputed on the host and
+        uploaded (mi_dilu4_refactor; waits for the device)."""
+        coef = _host_f64(coef, 16 * self._nblocks_in, "coef")
+        check(lib().mi_dilu4_refactor(self.handle, coef.ctypes.data, self.layout))
+        return self
+
+    def fetch(self):
+        """(Einv, K), each (nbrows, 4, 4) row-major by the caller's block row (mi_dilu4_fetch): the inverted pivots and 2E - D."""
+        einv = np.zeros((max(self.nbrows, 1), 4, 4))
+        k = np.zeros((max(self.nbrows, 1), 4, 4))
+        check(lib().mi_dilu4_fetch(self.handle, einv.ctypes.data, k.ctypes.data))
+        return einv[: self.nbrows], k[: self.nbrows]
+
+    def info(self):
+        """dict(nbrows, nblocks, order, ncolours, fwd_levels, bwd_levels, launches, factor_seconds, device_bytes, perm) —
+        mi_dilu4_info; launches: of one apply_hat; perm[caller's block row] = the row of B."""
+        nb, o, nc, fl, bl, la = (_c.c_int() for _ in range(6))
+        nblk, by = _c.c_longlong(), _c.c_longlong()
+        fs = _c.c_double()
+        perm = np.zeros(max(self.nbrows, 1), np.int32)
+        check(lib().mi_dilu4_info(self.handle, _c.byref(nb), _c.byref(nblk), _c.byref(o), _c.byref(nc), _c.byref(fl), _c.byref(bl), _c.byref(la),
+                                  _c.byref(fs), _c.byref(by), perm.ctypes.data))
+        return dict(nbrows=nb.value, nblocks=nblk.value, order=BILU_ORDERS[o.value], ncolours=nc.value, fwd_levels=fl.value,
+                    bwd_levels=bl.value, launches=la.value, factor_seconds=fs.value, device_bytes=by.value, perm=perm[: self.nbrows])
+
+    def gmres(self, A, b, x, restart=30, rtol=1e-8, maxiter=300, check_every=None, basis="f64"):
+        """Solve A x = b (A: the bcsr4x4_matrix this handle was made from; b, x CUDA tensors, x the initial guess, then the solution)
+        by GMRES on the split-preconditioned system: r = b - A x0 (the one true product), b^ = to_hat(r), u^ = 0, A^ u^ = b^ with
+        gmres_solver(self), x = x0 + from_hat(u^).  (iterations, history, reason) of that solve: rtol AND THE HISTORY ARE IN THE HAT
+        NORM, ||(E + L)^-1 r|| / ||b^||, not in the norm of b - A x."""
+        import torch
+
+        w = torch.empty_like(b)
+        SpMV_BCSR(w, x, A)
+        r = b.clone()
+        axpy(-1.0, w, r)
+        self.to_hat(r, r)
+        u = torch.zeros_like(b)
+        S = gmres_solver(self, None, restart, basis)
+        try:
+            out = S.solve(r, u, rtol=rtol, maxiter=maxiter, check_every=GMRES_CHECK_EVERY if check_every is None else check_every)
+            self.from_hat(u, u)
+            axpy(1.0, u, x)
+            torch.cuda.current_stream().synchronize()  # (the solver and the work vectors go out of scope)
+        finally:
+            S.close()
+        return out
+
+    def close(self):
+        if self._h is not None:
+            lib().mi_dilu4_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DistVector:
     """mi_dist_vec_t: a vector distributed like the rows of a DistMatrix (per rank [owned | halo] on the rank's device)."""
 
@@ -1492,7 +1618,8 @@ GMRES_CHECK_EVERY = 1  # the default of gmres_solver.solve / GMRES_dev: what too
 class gmres_solver:
     """mi_gmres_t: GMRES's definition above with a whole restart cycle enqueued on the device — the products, M, CGS2, the Givens
     rotations, the residual recurrence and the back-substitution — and one small read-back per check_every iterations instead of
-    one stream drain per iteration (include/mi355_spmv.h, mi_gmres_*; DESIGN.md 4.6).  A: a bcsr4x4_matrix or a square csrmatrix;
+    one stream drain per iteration (include/mi355_spmv.h, mi_gmres_*).  A: a bcsr4x4_matrix, a square csrmatrix or a
+    dilu4 (the operator is then its apply_hat, M must be None, and the solve is in the hat variables: dilu4.gmres composes it);
     M: a bilu4 (the exact solve in the handle's current form), a bilu4.sweeps(..) view (either precision), a bilu4.exact("f32") view or None.  The solver owns its
     basis and work vectors; A and M must outlive it.  One solve at a time per solver, and per M.
     basis="f32" (MI_BASIS_F32, opt-in): the Krylov basis is stored in single precision, every projection is taken against the
@@ -1507,13 +1634,17 @@ class gmres_solver:
             raise ValueError(f"basis: expected 'f64' or 'f32', got {basis!r}")
         self.basis = basis
         self.A, self.M = A, M
-        self.n = 4 * A.nrows if isinstance(A, bcsr4x4_matrix) else A.n
+        self.n = 4 * A.nrows if isinstance(A, bcsr4x4_matrix) else 4 * A.nbrows if isinstance(A, dilu4) else A.n
         self.restart = int(restart)
         h = _vp()
         check(lib().mi_gmres_create_ex(self.n, self.restart, GMRES_BASIS[basis], _c.byref(h)))
         self._h = h
         if isinstance(A, bcsr4x4_matrix):
             check(lib().mi_gmres_set_operator_bcsr4(h, A.handle))
+        elif isinstance(A, dilu4):  # the operator is A^ = apply_hat; M must be None (it is inside)
+            if M is not None:
+                raise ValueError("gmres_solver: a dilu4 operator takes no M (the preconditioner is inside apply_hat)")
+            check(lib().mi_gmres_set_operator_dilu4(h, A.handle))
         else:
             check(lib().mi_gmres_set_operator_csr(h, A.handle))
         if M is not None:
