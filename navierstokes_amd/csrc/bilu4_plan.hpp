@@ -230,6 +230,16 @@ static inline bool bilu4_invert(double* a)
     return true;
 }
 
+// one block of the caller's into row-major: transposed where the caller's blocks are column-major
+static inline void bilu4_block_in(const double* from, bool colmajor, double* dst)
+{
+    if (colmajor)
+        for (int r = 0; r < 4; r++)
+            for (int q = 0; q < 4; q++) dst[4 * r + q] = from[4 * q + r];
+    else
+        std::memcpy(dst, from, sizeof(double) * 16);
+}
+
 // one row of the IKJ factorisation (baij4_factor_avx2.c:114-170) into val; pos: a per-thread map block column -> place in the
 // row, all -1 on entry and on return.  false: zero pivot in this row.  src: null, or the caller's index of every block of
 // (ptrow, indcol) — an ordered handle's pattern is the permuted one (bilu4_order.hpp), coef stays the caller's.
@@ -240,15 +250,7 @@ static inline bool bilu4_factor_row(const Bilu4Pattern& P, int i, const int* ptr
     double* w = val + 16 * (size_t)k0;
     std::memset(w, 0, sizeof(double) * 16 * (size_t)(k1 - k0));
     for (int k = k0; k < k1; k++) pos[P.col[k]] = k - k0;
-    for (int k = ptrow[i]; k < ptrow[i + 1]; k++) {
-        double* dst = w + 16 * (size_t)pos[indcol[k]];
-        const double* from = coef + 16 * (size_t)(src ? src[k] : k);
-        if (colmajor)
-            for (int r = 0; r < 4; r++)
-                for (int q = 0; q < 4; q++) dst[4 * r + q] = from[4 * q + r];
-        else
-            std::memcpy(dst, from, sizeof(double) * 16);
-    }
+    for (int k = ptrow[i]; k < ptrow[i + 1]; k++) bilu4_block_in(coef + 16 * (size_t)(src ? src[k] : k), colmajor, w + 16 * (size_t)pos[indcol[k]]);
     double m[16], pr[16];
     for (int k = k0; k < P.diag[i]; k++) {
         double* wk = w + 16 * (size_t)(k - k0);
@@ -270,15 +272,18 @@ static inline bool bilu4_factor_row(const Bilu4Pattern& P, int i, const int* ptr
     return bilu4_invert(val + 16 * (size_t)P.diag[i]);
 }
 
-// The numeric factorisation over the forward schedule F: the rows of a level are independent, so wide levels are dealt to
-// `threads` threads (contiguous shares); every row is computed by one thread in one fixed order, so the bits do not depend on
-// the thread count.  Returns -1, or the lowest block row whose pivot was refused (rows behind it are then not meaningful).
-inline int bilu4_factor(const Bilu4Pattern& P, const Bilu4Sweep& F, const int* ptrow, const int* indcol, const double* coef, bool colmajor,
-                        int threads, double* val, const int* src = nullptr)
+// THE LEVEL LOOP of the host numerics (the factorisation below, the DILU pivots of dilu4_plan.hpp): over the forward schedule F,
+// level by level.  The rows of a level are independent, so a level of at least kBiluRowsPerWG rows is dealt to the threads in
+// contiguous shares; every row is computed by one thread in one fixed order — row_fn(block row, thread index), false: its pivot
+// was refused — so the bits do not depend on the thread count.  Returns -1, or the lowest block row that was refused; the loop
+// stops behind the first level with a refusal (later rows would use what was refused), and rows behind it are not meaningful.
+inline int bilu4_level_threads(int threads) { return std::max(1, std::min(threads, 64)); }
+
+template <class RowFn>
+inline int bilu4_for_level_rows(const Bilu4Sweep& F, int threads, RowFn&& row_fn)
 {
-    const int nb = P.nb;
-    threads = std::max(1, std::min(threads, 64));
-    std::vector<std::vector<int>> pos(threads, std::vector<int>(nb, -1));
+    const int nb = (int)F.perm.size();
+    threads = bilu4_level_threads(threads);
     std::atomic<int> bad(nb);
     auto note = [&](int i) {
         int cur = bad.load();
@@ -290,7 +295,7 @@ inline int bilu4_factor(const Bilu4Pattern& P, const Bilu4Sweep& F, const int* p
         auto share = [&](int t) {
             const int a = p0 + (int)((long long)(p1 - p0) * t / T), b = p0 + (int)((long long)(p1 - p0) * (t + 1) / T);
             for (int q = a; q < b; q++)
-                if (!bilu4_factor_row(P, F.perm[q], ptrow, indcol, coef, colmajor, val, pos[t].data(), src)) note(F.perm[q]);
+                if (!row_fn(F.perm[q], t)) note(F.perm[q]);
         };
         if (T == 1) {
             share(0);
@@ -300,9 +305,18 @@ inline int bilu4_factor(const Bilu4Pattern& P, const Bilu4Sweep& F, const int* p
             share(0);
             for (auto& x : th) x.join();
         }
-        if (bad.load() < nb) break; // later rows would divide by what was refused
+        if (bad.load() < nb) break;
     }
     return bad.load() < nb ? bad.load() : -1;
+}
+
+// The numeric factorisation over the forward schedule F (bilu4_for_level_rows; a per-thread pos table for bilu4_factor_row).
+// Returns -1, or the lowest block row whose pivot was refused (rows behind it are then not meaningful).
+inline int bilu4_factor(const Bilu4Pattern& P, const Bilu4Sweep& F, const int* ptrow, const int* indcol, const double* coef, bool colmajor,
+                        int threads, double* val, const int* src = nullptr)
+{
+    std::vector<std::vector<int>> pos(bilu4_level_threads(threads), std::vector<int>(P.nb, -1));
+    return bilu4_for_level_rows(F, threads, [&](int i, int t) { return bilu4_factor_row(P, i, ptrow, indcol, coef, colmajor, val, pos[t].data(), src); });
 }
 
 // ---------------------------------------------------------------- the device refactor's plan (mi_bilu4dev_*)

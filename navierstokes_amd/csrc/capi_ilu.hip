@@ -8,30 +8,20 @@
 // that writes the factor keeps current.  mi_bilu4_create_ordered puts a multicolour ordering behind the handle (bilu4_order.hpp):
 // the factor is then that of the permuted matrix, every solve is bracketed by a gather and a scatter (bilu_in_order, the one
 // place), and wide unfolded levels take bilu4_level_wide (bilu4_solve_wide.hpp).
+// What the handle has in common with a block DILU handle (capi_dilu.hip) is capi_bilu_common.hpp's: the argument rules, the host
+// part of the handle (ordering, pattern, schedule), the level-major device copy and how values move into it, the guard, the steps
+// of a refactor, and bilu_in_order.
 // No CPU fallback: the solve and the device refactor need a HIP device; the planning and host factorisation entry points need none.
-#include "capi_internal.hpp"
-#include "bilu4_plan.hpp"
+#include "capi_bilu_common.hpp"
 #include "bilu4_solve.hpp"
 #include "bilu4_solve_one.hpp"
 #include "bilu4_factor.hpp"
 #include "bilu4_sweep.hpp"
-#include "bilu4_order.hpp"
-#include "bilu4_order_kernels.hpp"
 #include "bilu4_solve_wide.hpp"
 
-// ---------------------------------------------------------------- ownership
-// Every device array of this file is a DevArray, the give-up word a MappedWord (dev_array.hpp, the types all handles of the library
-// own their device memory with): member destructors are the only release path.  This file floors every allocation at ONE entry
-// (an empty level or list still gets an address the kernels may be handed), which the shared type leaves to the caller: hence the 1s.
+// (ownership: DevArray and the floor of one entry, capi_bilu_common.hpp; the give-up word is a MappedWord)
 
-// the level-major copy of one sweep (bilu4_solve.hpp)
-struct Bilu4DevSweep {
-    DevArray<int> perm, ptr, col;
-    DevArray<double> val, dinv; // dinv: the backward sweep only
-    DevArray<int> lev_ptr;
-    std::vector<long long> src; // per device block: its place in the host factor (values move through it, both ways)
-    Bilu4SweepView view() const { return Bilu4SweepView{perm, ptr, col, val, dinv, lev_ptr}; }
-};
+static Bilu4SweepView bilu_view(const Bilu4DevSweep& D) { return Bilu4SweepView{D.perm, D.ptr, D.col, D.val, D.dinv, D.lev_ptr}; }
 
 // the device refactor (mi_bilu4dev_prepare): pattern-only tables, see Bilu4DevPlan
 struct Bilu4DevTables {
@@ -80,34 +70,25 @@ struct Bilu4SpCopy {
     DevArray<Bilu4SpRecord> rec;
 };
 
-// what an ordered handle (mi_bilu4_create_ordered) owns on the device: the numbering and the two vectors in it that every solve
-// passes through — allocated at create, so that a solve allocates nothing and stays capturable; hence one solve at a time per handle
+// what an ordered handle (mi_bilu4_create_ordered) owns on the device besides the numbering (d_perm): the two vectors in it that every
+// solve passes through — allocated at create, so that a solve allocates nothing and stays capturable; hence one solve at a time per handle
 struct Bilu4OrderDev {
-    DevArray<int> perm;    // [nb] the caller's block row -> the factor's
     DevArray<double> b, x; // [4 nb] right-hand side and solution in the factor's numbering
     int wide_min = 0;      // block rows from which an unfolded level takes bilu4_level_wide; 0: never (natural order)
 };
 
-struct mi_bilu4_s {
-    int device = -1; // -1: host-only handle (mi_bilu4_create_host)
+struct mi_bilu4_s : Bilu4Handle { // a_ptr, a_col: the pattern that is factored (refactor scatters new values through it)
     int fill = 0;
-    Bilu4Order ord;                // the ordering behind the handle (natural: empty tables)
-    std::vector<int> a_ptr, a_col; // the pattern that is factored (refactor scatters new values through it): the caller's, or on an
-                                   // ordered handle that of the permuted matrix, whose blocks ord.src maps back to the caller's
-    Bilu4Schedule sched;
     std::vector<double> val;       // host factor, row order, row-major blocks
-    double factor_seconds = 0.0;
     double us_form[2] = {0.0, 0.0}; // [0] one launch per level, measured at create; [1] one launch, once mi_bilu4_set_solve_form(F, -1) has measured it
     int form = MI_BILU_FORM_LEVELS;
-    Bilu4DevSweep lev[2];          // forward, backward
     DevArray<double> d_b, d_x;     // scratch of the host-pointer solve
     Bilu4DevTables dev;
     Bilu4OneTables one;
     Bilu4SweepWork sw;
     Bilu4SpCopy sp;
     Bilu4OrderDev ordd;
-    ~mi_bilu4_s() { ordd = {}, sp = {}, sw = {}, one = {}, lev[0] = {}, lev[1] = {}, d_b = {}, d_x = {}, dev = {}; } // the order the handle has always been freed in (newest first)
-    const Bilu4Pattern& pat() const { return sched.pat; }
+    ~mi_bilu4_s() { d_perm = {}, ordd = {}, sp = {}, sw = {}, one = {}, lev[0] = {}, lev[1] = {}, d_b = {}, d_x = {}, dev = {}; } // the order the handle has always been freed in (newest first)
     Bilu4FactorView factor_view() const
     {
         return Bilu4FactorView{lev[0].perm, lev[0].ptr, lev[0].col, lev[1].ptr, lev[0].lev_ptr, dev.fpos, dev.bpos, dev.upd_ptr, dev.upd,
@@ -115,50 +96,9 @@ struct mi_bilu4_s {
     }
 };
 
-static int bilu_threads()
-{
-    const char* e = getenv("MI355_BILU_THREADS");
-    if (e && atoi(e) > 0) return atoi(e);
-    const unsigned hw = std::thread::hardware_concurrency();
-    return (int)std::max(1u, std::min(hw, 16u));
-}
-
-static int bilu_check_args(int nbrows, const int* ptrow, const int* indcol, int fill)
-{
-    CHECK_ARG(nbrows >= 0, "negative nbrows");
-    CHECK_ARG(fill >= 0, "fill must be >= 0");
-    if (nbrows == 0) return MI_OK;
-    CHECK_ARG(ptrow, "null ptrow");
-    CHECK_ARG(ptrow[nbrows] <= 0 || indcol, "null indcol");
-    const std::string why = bilu4_check_pattern(nbrows, ptrow, indcol);
-    if (!why.empty()) return fail(MI_ERR_ARG, "mi_bilu4: " + why);
-    return MI_OK;
-}
-
-// What the device entry points begin with: MI_ERR_ARG without a handle or with a bad argument (bad_arg: what is wrong with the
-// arguments that are checked even on an empty matrix; bad_data: with those that are not), MI_OK at once on an empty matrix,
-// host_only's status on a host-only handle.  kBiluGo: none of these, go on.
-constexpr int kBiluGo = -1;
-
 // what a host-only handle gets: MI_ERR_STATE, but MI_ERR_NODEVICE from everything about sweeps and the single-precision copy
-struct BiluHostOnly {
-    int status;
-    const char* tail;
-};
 constexpr BiluHostOnly kHostOnlyDev{MI_ERR_STATE, ": a host-only handle (mi_bilu4_create_host) has no device factor"};
 constexpr BiluHostOnly kHostOnlySweep{MI_ERR_NODEVICE, ": a host-only handle (mi_bilu4_create_host) has no device factor, and the sweep solve has no CPU fallback"};
-
-static int bilu_guard(const mi_bilu4_s* F, const char* name, const BiluHostOnly& host_only, const char* bad_arg = nullptr, const char* bad_data = nullptr)
-{
-    CHECK_ARG(F, "null handle");
-    CHECK_ARG(!bad_arg, bad_arg);
-    if (F->pat().nb == 0) return MI_OK;
-    CHECK_ARG(!bad_data, bad_data);
-    if (F->device < 0) return fail(host_only.status, std::string(name) + host_only.tail);
-    return kBiluGo;
-}
-
-static const char* bilu_bad_layout(int layout) { return layout == MI_BLOCK_ROWMAJOR || layout == MI_BLOCK_COLMAJOR ? nullptr : "unknown block layout"; }
 
 static int bilu_zero_pivot(int row)
 {
@@ -172,28 +112,6 @@ static int bilu_factor(mi_bilu4_s* F, const double* coef, int layout)
                                  F->ord.src_or_null());
     F->factor_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return bad >= 0 ? bilu_zero_pivot(F->ord.caller_row(bad)) : MI_OK;
-}
-
-// the level-major copy of sweep b: its pattern, and room for its values
-static int bilu_upload_pattern(const mi_bilu4_s* F, int b, Bilu4DevSweep* D)
-{
-    const Bilu4Pattern& P = F->pat();
-    const Bilu4Sweep& S = F->sched.sweep[b];
-    std::vector<int> ptr(P.nb + 1, 0), col;
-    D->src.clear();
-    for (int q = 0; q < P.nb; q++) {
-        const auto [k0, k1] = P.offdiag(S.perm[q], b == 1);
-        for (int k = k0; k < k1; k++) {
-            col.push_back(P.col[k]);
-            D->src.push_back(k);
-        }
-        ptr[q + 1] = (int)col.size();
-    }
-    int rc;
-    if ((rc = dev_upload(D->perm, S.perm, 1)) || (rc = dev_upload(D->ptr, ptr, 1)) || (rc = dev_upload(D->col, col, 1)) || (rc = dev_alloc(D->val, 16 * std::max<size_t>(col.size(), 1))) ||
-        (rc = dev_upload(D->lev_ptr, S.lev_ptr, 1)) || (b == 1 && (rc = dev_alloc(D->dinv, 16 * (size_t)P.nb, 1))))
-        return rc;
-    return MI_OK;
 }
 
 // THE ONE LISTING of the factor's three level-major value arrays — the L blocks, the U blocks, the inverted diagonal blocks by
@@ -214,24 +132,7 @@ static int bilu_each_values(const mi_bilu4_s* F, Bilu4SpCopy& S, Fn&& fn)
 static int bilu_move_values(mi_bilu4_s* F, bool to_device)
 {
     std::vector<double> v;
-    return bilu_each_values(F, F->sp, [&](double* dev, DevArray<float>&, size_t n, auto&& host_block) -> int {
-        if (!n) return MI_OK;
-        v.resize(16 * n);
-        if (!to_device) HIP_TRY(hipMemcpy(v.data(), dev, sizeof(double) * v.size(), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < n; k++) {
-            double *h = &F->val[16 * (size_t)host_block(k)], *d = &v[16 * k];
-            memcpy(to_device ? d : h, to_device ? h : d, sizeof(double) * 16);
-        }
-        if (to_device) HIP_TRY(hipMemcpy(dev, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice));
-        return MI_OK;
-    });
-}
-
-// the kernels' AL: x may be read and written as 16-byte pairs
-template <class Fn>
-static auto bilu_by_alignment(const double* d_x, Fn&& fn)
-{
-    return pick(fn, (((uintptr_t)d_x) & 15) == 0);
+    return bilu_each_values(F, F->sp, [&](double* dev, DevArray<float>&, size_t n, auto&& host_block) { return bilu_move_blocks(dev, n, F->val.data(), host_block, to_device, v); });
 }
 
 // does launch L take the wide-level kernel?  wide_min: the handle's (0 on a natural-order handle: never)
@@ -270,43 +171,14 @@ static int bilu_wide_launches(const mi_bilu4_s* F)
     return n;
 }
 
-// THE ONE PLACE an ordering meets the caller's vectors: whatever applies the factor (levels, one launch, sweeps, sweeps in f32)
-// runs as inner(b, x) on vectors in the factor's numbering.  Natural order: the caller's own.  Ordered: the handle's two vectors,
-// with a gather in front and a scatter behind, on the same stream — two launches, nothing allocated or synchronised.  d_x may be d_b:
-// the gather has read all of it before the scatter writes.
-constexpr int kBiluOrderLaunches = 2;
-
-template <bool IN>
-static void bilu_order_move(const mi_bilu4_s* F, const double* from, double* to, const double* user, hipStream_t s)
-{
-    const int nb = F->pat().nb;
-    bilu_by_alignment(user, [&](auto al) {
-        constexpr bool AL = decltype(al)::value;
-        const int grid = launch_grid((long long)nb * kBiluOrderLanes<AL>, kWG, INT_MAX, 1);
-        hipLaunchKernelGGL((bilu4_order_move<IN, AL>), dim3(grid), dim3(kWG), 0, s, F->ordd.perm, nb, from, to);
-        return 0;
-    });
-}
-
-template <class Fn>
-static int bilu_in_order(mi_bilu4_s* F, const double* d_b, double* d_x, hipStream_t s, Fn&& inner)
-{
-    if (!F->ord.on()) return inner(d_b, d_x);
-    bilu_order_move<true>(F, d_b, F->ordd.b, d_b, s);
-    if (const int rc = inner((const double*)F->ordd.b, (double*)F->ordd.x)) return rc;
-    bilu_order_move<false>(F, F->ordd.x, d_x, d_x, s);
-    HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
 // form A: one launch per (folded) level, forward then backward, on the caller's stream; nothing allocated or synchronised
 // Lv, Uv: the values of the two triangles in the type they are streamed in (the factor's own, or its single-precision copy)
 template <class T>
 static int bilu_solve_launch(mi_bilu4_s* F, const Bilu4SweepVals<T>& Lv, const Bilu4SweepVals<T>& Uv, const double* d_b, double* d_x, hipStream_t s)
 {
     bilu_by_alignment(d_x, [&](auto al) {
-        bilu_sweep_launch<false, decltype(al)::value>(F->sched.sweep[0], F->lev[0].view(), Lv, d_b, d_x, F->ordd.wide_min, s);
-        bilu_sweep_launch<true, decltype(al)::value>(F->sched.sweep[1], F->lev[1].view(), Uv, d_x, d_x, F->ordd.wide_min, s);
+        bilu_sweep_launch<false, decltype(al)::value>(F->sched.sweep[0], bilu_view(F->lev[0]), Lv, d_b, d_x, F->ordd.wide_min, s);
+        bilu_sweep_launch<true, decltype(al)::value>(F->sched.sweep[1], bilu_view(F->lev[1]), Uv, d_x, d_x, F->ordd.wide_min, s);
     });
     HIP_TRY(hipGetLastError());
     return MI_OK;
@@ -328,7 +200,7 @@ static hipError_t bilu_one_launch_t(const mi_bilu4_s* F, const Bilu4OneArgs& A, 
 {
     auto kern = bilu4_solve_one<AL>;
     if (query) return hipOccupancyMaxActiveBlocksPerMultiprocessor(max_blocks, kern, kWG, 0);
-    hipLaunchKernelGGL(kern, dim3(F->one.wgs), dim3(kWG), 0, s, F->lev[0].view(), F->lev[1].view(), A, d_b, d_x);
+    hipLaunchKernelGGL(kern, dim3(F->one.wgs), dim3(kWG), 0, s, bilu_view(F->lev[0]), bilu_view(F->lev[1]), A, d_b, d_x);
     return hipGetLastError();
 }
 
@@ -371,31 +243,10 @@ static int bilu_sp_convert(const mi_bilu4_s* F, Bilu4SpCopy& S, hipStream_t s)
     return MI_OK;
 }
 
-static const char* bilu_bad_ordering(int ordering)
-{
-    return ordering == MI_BILU_ORDER_NATURAL || ordering == MI_BILU_ORDER_COLOUR ? nullptr : "unknown ordering (0: natural, 1: multicolour)";
-}
-
-// the ordering of a pattern that bilu_check_args has accepted, checked (bilu4_order_check) before anything relies on it
-static int bilu_order(int nbrows, const int* ptrow, const int* indcol, int ordering, const char* who, Bilu4Order* O)
-{
-    *O = Bilu4Order{};
-    if (ordering == MI_BILU_ORDER_NATURAL) return MI_OK;
-    bilu4_colour(nbrows, ptrow, indcol, O);
-    const std::string bad = bilu4_order_check(nbrows, ptrow, indcol, *O);
-    if (!bad.empty()) return fail(MI_ERR_STATE, std::string(who) + ": " + bad);
-    return MI_OK;
-}
-
 static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout, int fill, int ordering, bool device, mi_bilu4_t* out)
 {
-    CHECK_ARG(out, "null output handle");
-    *out = nullptr;
-    CHECK_ARG(!bilu_bad_layout(layout), bilu_bad_layout(layout));
-    CHECK_ARG(!bilu_bad_ordering(ordering), bilu_bad_ordering(ordering));
-    int rc = bilu_check_args(nbrows, ptrow, indcol, fill);
-    if (rc) return rc;
-    CHECK_ARG(nbrows == 0 || coef, "null coef");
+    int rc;
+    if ((rc = bilu_check_create("mi_bilu4: ", nbrows, ptrow, indcol, coef, layout, fill, ordering, out))) return rc;
     if (const char* e = getenv("MI355_BILU_FORM")) {
         CHECK_ARG(!strcmp(e, "0") || !strcmp(e, "1"), "MI355_BILU_FORM must be 0 or 1");
         if (!strcmp(e, "1"))
@@ -405,30 +256,22 @@ static int bilu_create(int nbrows, const int* ptrow, const int* indcol, const do
     std::unique_ptr<mi_bilu4_s> F(new (std::nothrow) mi_bilu4_s);
     if (!F) return fail(MI_ERR_ALLOC, "host allocation failed");
     F->fill = fill;
-    if (nbrows == 0) F->ord.ordering = ordering; // (an empty matrix: no tables, but the handle says what it was asked for)
-    if (nbrows > 0 && ordering != MI_BILU_ORDER_NATURAL) {
-        if ((rc = bilu_order(nbrows, ptrow, indcol, ordering, "mi_bilu4_create_ordered", &F->ord))) return rc;
-        bilu4_permute_pattern(nbrows, ptrow, indcol, &F->ord, &F->a_ptr, &F->a_col);
+    if ((rc = bilu_plan_host(F.get(), nbrows, ptrow, indcol, fill, ordering, "mi_bilu4_create_ordered"))) return rc;
+    if (nbrows > 0 && F->ord.on()) {
         F->ordd.wide_min = kBiluWideMin;
         if (const char* e = getenv("MI355_BILU_WIDE_MIN")) {
             CHECK_ARG(atoi(e) >= 1, "MI355_BILU_WIDE_MIN must be >= 1 (block rows)");
             F->ordd.wide_min = atoi(e);
         }
-    } else if (nbrows > 0) {
-        F->a_ptr.assign(ptrow, ptrow + nbrows + 1);
-        F->a_col.assign(indcol, indcol + ptrow[nbrows]);
-    } else {
-        F->a_ptr.assign(1, 0);
     }
-    bilu4_schedule(nbrows, F->a_ptr.data(), F->a_col.data(), fill, &F->sched);
     F->val.assign(16 * (size_t)F->pat().nblocks(), 0.0);
     if ((rc = bilu_factor(F.get(), coef, layout))) return rc;
     if (device && nbrows > 0) {
         HIP_TRY(hipGetDevice(&F->device));
-        if ((rc = bilu_upload_pattern(F.get(), 0, &F->lev[0])) || (rc = bilu_upload_pattern(F.get(), 1, &F->lev[1])) || (rc = bilu_move_values(F.get(), true)) ||
+        if ((rc = bilu_upload_pattern(F.get())) || (rc = dev_alloc(F->lev[1].dinv, 16 * (size_t)nbrows, 1)) || (rc = bilu_move_values(F.get(), true)) ||
             (rc = dev_alloc(F->d_b, 4 * (size_t)nbrows, 1)) || (rc = dev_alloc(F->d_x, 4 * (size_t)nbrows, 1)))
             return rc;
-        if (F->ord.on() && ((rc = dev_upload(F->ordd.perm, F->ord.perm, 1)) || (rc = dev_alloc(F->ordd.b, 4 * (size_t)nbrows, 1)) || (rc = dev_alloc(F->ordd.x, 4 * (size_t)nbrows, 1))))
+        if (F->ord.on() && ((rc = dev_upload(F->d_perm, F->ord.perm, 1)) || (rc = dev_alloc(F->ordd.b, 4 * (size_t)nbrows, 1)) || (rc = dev_alloc(F->ordd.x, 4 * (size_t)nbrows, 1))))
             return rc;
         HIP_TRY(hipMemset(F->d_b, 0, sizeof(double) * 4 * nbrows));
         // the solve's time, through the library's one timing helper (zero right-hand side: the time does not depend on values)
@@ -475,7 +318,7 @@ extern "C" int mi_bilu4_order_info(mi_bilu4_t F, int* ordering, int* ncolours, i
 extern "C" int mi_bilu4_order_probe(int nbrows, const int* ptrow, const int* indcol, int ordering, int* perm, int* ncolours, int* colour_sizes, int cap)
 {
     CHECK_ARG(!bilu_bad_ordering(ordering), bilu_bad_ordering(ordering));
-    int rc = bilu_check_args(nbrows, ptrow, indcol, 0);
+    int rc = bilu_check_args("mi_bilu4: ", nbrows, ptrow, indcol, 0);
     if (rc) return rc;
     Bilu4Order O;
     if ((rc = bilu_order(nbrows, ptrow, indcol, ordering, "mi_bilu4_order_probe", &O))) return rc;
@@ -494,20 +337,14 @@ extern "C" int mi_bilu4_destroy(mi_bilu4_t F)
 
 extern "C" int mi_bilu4_refactor(mi_bilu4_t F, const double* coef, int layout)
 {
-    CHECK_ARG(F, "null handle");
-    CHECK_ARG(!bilu_bad_layout(layout), bilu_bad_layout(layout));
-    if (F->pat().nb == 0) return MI_OK;
-    CHECK_ARG(coef, "null coef");
-    int rc = bilu_factor(F, coef, layout);
-    if (rc) return rc;
-    if (F->device < 0) return MI_OK;
-    // solves already enqueued read the old values: wait for them, then replace (a Newton step refactors between solves)
-    HIP_TRY(hipDeviceSynchronize());
-    if ((rc = bilu_move_values(F, true)) || !F->sp.prepared) return rc;
-    // the single-precision copy follows the factor before the call returns
-    if ((rc = bilu_sp_convert(F, F->sp, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return MI_OK;
+    return bilu_refactor(F, coef, layout, [&] { return bilu_factor(F, coef, layout); }, [&]() -> int {
+        int rc;
+        if ((rc = bilu_move_values(F, true)) || !F->sp.prepared) return rc;
+        // the single-precision copy follows the factor before the call returns
+        if ((rc = bilu_sp_convert(F, F->sp, nullptr))) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return MI_OK;
+    });
 }
 
 extern "C" int mi_bilu4_info(mi_bilu4_t F, int* nbrows, long long* nblocks, int* fwd_levels, int* bwd_levels, int* launches, int* form,
@@ -545,7 +382,7 @@ extern "C" int mi_bilu4_factor_host(mi_bilu4_t F, int* ptr, int* col, int* diag,
 extern "C" int mi_bilu4_plan_probe(int nbrows, const int* ptrow, const int* indcol, int fill, long long* nblocks, int* fwd_levels,
                                    int* bwd_levels, int* fwd_launches, int* bwd_launches, int* fwd_sizes, int* bwd_sizes, int cap_levels)
 {
-    int rc = bilu_check_args(nbrows, ptrow, indcol, fill);
+    int rc = bilu_check_args("mi_bilu4: ", nbrows, ptrow, indcol, fill);
     if (rc) return rc;
     Bilu4Schedule S;
     bilu4_schedule(nbrows, ptrow, indcol, fill, &S);
@@ -567,7 +404,7 @@ extern "C" int mi_bilu4_plan_probe(int nbrows, const int* ptrow, const int* indc
 extern "C" int mi_bilu4dev_plan_probe(int nbrows, const int* ptrow, const int* indcol, int fill, long long* update_pairs, int* launches,
                                       long long* plan_bytes)
 {
-    int rc = bilu_check_args(nbrows, ptrow, indcol, fill);
+    int rc = bilu_check_args("mi_bilu4: ", nbrows, ptrow, indcol, fill);
     if (rc) return rc;
     Bilu4Schedule S;
     Bilu4DevPlan D;
@@ -665,7 +502,7 @@ extern "C" int mi_bilu4one_plan_probe(int nbrows, const int* ptrow, const int* i
                                       int max_deps[2], long long* plan_bytes, int* const chunk_pos[2], int* const chunk_lev[2],
                                       int* const dep_ptr[2], int* const dep[2])
 {
-    int rc = bilu_check_args(nbrows, ptrow, indcol, fill);
+    int rc = bilu_check_args("mi_bilu4: ", nbrows, ptrow, indcol, fill);
     if (rc) return rc;
     CHECK_ARG(workgroups >= 0, "negative workgroups");
     Bilu4Schedule S;
@@ -846,7 +683,7 @@ static int bilu_sw_solve_launch(mi_bilu4_s* F, const Bilu4SweepVals<T>& Lv, cons
     sf = std::min(sf, bilu_sw_max(F, 0));
     sb = std::min(sb, bilu_sw_max(F, 1));
     double* const w[3] = {F->sw.w[0], F->sw.w[1], F->sw.w[2]};
-    const Bilu4SweepView L = F->lev[0].view(), U = F->lev[1].view();
+    const Bilu4SweepView L = bilu_view(F->lev[0]), U = bilu_view(F->lev[1]);
     const double* t = d_b; // t^0
     for (int k = 0; k < sf; k++) {
         bilu_sw_launch<false>(L, Lv, nb, d_b, t, w[k & 1], s);
@@ -992,7 +829,7 @@ static int bilu_apply(mi_bilu4_s* F, const Bilu4Apply& how, const double* d_b, d
     if (const int rc = bilu_ensure(F, how, s)) return rc;
     const Bilu4SweepVals<double> L64{F->lev[0].val, nullptr}, U64{F->lev[1].val, F->lev[1].dinv};
     const Bilu4SweepVals<float> L32{F->sp.val[0], nullptr}, U32{F->sp.val[1], F->sp.dinv};
-    const int rc = bilu_in_order(F, d_b, d_x, s, [&](const double* b, double* x) {
+    const int rc = bilu_in_order(F, d_b, d_x, F->ordd.b, F->ordd.x, s, [&](const double* b, double* x) {
         if (how.sweeps)
             return how.f32 ? bilu_sw_solve_launch(F, L32, U32, &F->sp.launches_last, b, x, how.sf, how.sb, s)
                            : bilu_sw_solve_launch(F, L64, U64, &F->sw.launches_last, b, x, how.sf, how.sb, s);

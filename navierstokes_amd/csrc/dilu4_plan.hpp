@@ -1,6 +1,7 @@
 // dilu4_plan.hpp — host side of the 4x4-block DILU preconditioner applied with Eisenstat's trick (mi_dilu4_*, include/mi355_spmv.h):
 // the values of B in the factor's numbering and the pivots E, their inverses and K = 2E - D.  Plain C++ (no HIP), like
-// bilu4_plan.hpp, whose pattern, levels, folding rule and 4x4 primitives it reuses; the ordering is bilu4_order.hpp's.
+// bilu4_plan.hpp, whose pattern, levels, folding rule, 4x4 primitives, block intake (bilu4_block_in) and level loop
+// (bilu4_for_level_rows) it reuses; the ordering is bilu4_order.hpp's.
 //
 // B = Q A Q^T = L + D + U (strict block triangles, block diagonal), NO fill: the pattern is B's own, so Bilu4Pattern at fill 0 lists
 // B's blocks in B's order and block k of the pattern is block k of the permuted matrix.  M = (E + L) E^-1 (E + U).
@@ -25,15 +26,7 @@ namespace mi355 {
 // the caller's values into B's block order, row-major; src: null, or the caller's index of every block of B (bilu4_order.hpp)
 inline void dilu4_values(long long nblocks, const double* coef, bool colmajor, const int* src, double* val)
 {
-    for (long long k = 0; k < nblocks; k++) {
-        const double* from = coef + 16 * (size_t)(src ? src[k] : k);
-        double* dst = val + 16 * (size_t)k;
-        if (colmajor)
-            for (int r = 0; r < 4; r++)
-                for (int q = 0; q < 4; q++) dst[4 * r + q] = from[4 * q + r];
-        else
-            std::memcpy(dst, from, sizeof(double) * 16);
-    }
+    for (long long k = 0; k < nblocks; k++) bilu4_block_in(coef + 16 * (size_t)(src ? src[k] : k), colmajor, val + 16 * (size_t)k);
 }
 
 // Einv_i and K_i of block row i (16 doubles each, by block row); false: a refused pivot in this row
@@ -62,37 +55,11 @@ static inline bool dilu4_pivot_row(const Bilu4Pattern& P, int i, const double* v
     return bilu4_invert(e);
 }
 
-// All pivots over the forward schedule F: wide levels are dealt to `threads` threads in contiguous shares, every row is computed by
-// one thread in one fixed order, so the bits do not depend on the thread count (bilu4_factor's scheme).  Returns -1, or the lowest
-// block row (B's numbering) whose pivot was refused; rows behind it are then not meaningful.
+// All pivots over the forward schedule F, by bilu4_for_level_rows: the bits do not depend on the thread count.  Returns -1, or the
+// lowest block row (B's numbering) whose pivot was refused; rows behind it are then not meaningful.
 inline int dilu4_pivots(const Bilu4Pattern& P, const Bilu4Sweep& F, const double* val, int threads, double* einv, double* kmat)
 {
-    const int nb = P.nb;
-    threads = std::max(1, std::min(threads, 64));
-    std::atomic<int> bad(nb);
-    auto note = [&](int i) {
-        int cur = bad.load();
-        while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
-    };
-    for (int l = 0; l < F.nlev(); l++) {
-        const int p0 = F.lev_ptr[l], p1 = F.lev_ptr[l + 1];
-        const int T = (p1 - p0 >= kBiluRowsPerWG) ? threads : 1;
-        auto share = [&](int t) {
-            const int a = p0 + (int)((long long)(p1 - p0) * t / T), b = p0 + (int)((long long)(p1 - p0) * (t + 1) / T);
-            for (int q = a; q < b; q++)
-                if (!dilu4_pivot_row(P, F.perm[q], val, einv, kmat)) note(F.perm[q]);
-        };
-        if (T == 1) {
-            share(0);
-        } else {
-            std::vector<std::thread> th;
-            for (int t = 1; t < T; t++) th.emplace_back(share, t);
-            share(0);
-            for (auto& x : th) x.join();
-        }
-        if (bad.load() < nb) break; // later rows would multiply by what was refused
-    }
-    return bad.load() < nb ? bad.load() : -1;
+    return bilu4_for_level_rows(F, threads, [&](int i, int) { return dilu4_pivot_row(P, i, val, einv, kmat); });
 }
 
 } // namespace mi355

@@ -638,7 +638,46 @@ def _bilu_solve(F, way, counts, x, b):
     return x
 
 
-class bilu4:
+def _block_pattern(A, ptrow, indcol, coef, layout):
+    """What bilu4 and dilu4 are made from, checked: (nbrows, ptrow, indcol, coef, lay) of a bcsr4x4_matrix A (its host arrays and
+    block layout), or of the arrays themselves with A the number of block rows."""
+    if isinstance(A, bcsr4x4_matrix):
+        nbrows, ptrow, indcol, coef, lay = A.nrows, A.ptrow, A.indcol, A.coef, A.layout
+    else:
+        nbrows, lay = int(A), {"row": 0, "col": 1}[layout]
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    coef = _host_f64(coef, None, "coef")
+    if len(ptrow) != int(nbrows) + 1:
+        raise ValueError("ptrow must have nbrows+1 entries")
+    if coef.size < 16 * len(indcol):
+        raise ValueError("coef: 16 values per block")
+    return int(nbrows), ptrow, indcol, coef, lay
+
+
+class _OwnsHandle:
+    """The C handle self._h of a bilu4 or a dilu4: refused once closed, destroyed (by the class's _destroy symbol) exactly once."""
+    _h, _destroy = None, None
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError(f"{type(self).__name__}: closed")
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class bilu4(_OwnsHandle):
     """mi_bilu4_t: the incomplete LU factors of a square 4x4-block matrix — PCILU on the BAIJ-4 Jacobian,
     src/solve_newton.c:1156-1164 — factored on the host at construction, solved on the GPU level by level.
     bilu4(A, fill=0) takes a bcsr4x4_matrix's host arrays (and its block layout); bilu4(nbrows, ptrow, indcol, coef, fill=0,
@@ -648,23 +687,13 @@ class bilu4:
     you.  Every method keeps the caller's numbering except factor_host() and fetch_f32(), which return the permuted matrix's
     factor; one solve at a time per ordered handle."""
 
+    _destroy = "mi_bilu4_destroy"
+
     def __init__(self, A, ptrow=None, indcol=None, coef=None, fill=0, layout="row", host_only=False, order="natural"):
-        if isinstance(A, bcsr4x4_matrix):
-            nbrows, ptrow, indcol, coef, lay = A.nrows, A.ptrow, A.indcol, A.coef, A.layout
-        else:
-            nbrows, lay = int(A), {"row": 0, "col": 1}[layout]
-        self.nbrows = int(nbrows)
+        self.nbrows, ptrow, indcol, coef, lay = _block_pattern(A, ptrow, indcol, coef, layout)
         self.layout = lay
         self.fill = int(fill)
-        ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
-        indcol = np.ascontiguousarray(indcol, dtype=np.int32)
-        coef = _host_f64(coef, None, "coef")
-        if len(ptrow) != self.nbrows + 1:
-            raise ValueError("ptrow must have nbrows+1 entries")
-        if coef.size < 16 * len(indcol):
-            raise ValueError("coef: 16 values per block")
         self._nblocks_in = len(indcol)
-        self._h = None
         h = _vp()
         self.order = order
         if order == "natural":  # the entry points natural-order handles have always been made by
@@ -682,12 +711,6 @@ class bilu4:
         perm = np.zeros(max(self.nbrows, 1), np.int32)
         check(lib().mi_bilu4_order_info(self.handle, _c.byref(o), _c.byref(nc), _c.byref(wl), perm.ctypes.data))
         return dict(order=BILU_ORDERS[o.value], ncolours=nc.value, wide_launches=wl.value, perm=perm[: self.nbrows])
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise ValueError("bilu4: closed")
-        return self._h
 
     def solve(self, x, b):
         """x = U^-1 L^-1 b.  CUDA tensors: asynchronous on torch's current stream, x may be b; numpy arrays: copied in and out."""
@@ -837,18 +860,6 @@ class bilu4:
         val = np.zeros((max(nblk, 1), 4, 4), np.float64)
         check(lib().mi_bilu4_factor_host(self.handle, ptr.ctypes.data, col.ctypes.data, diag.ctypes.data, val.ctypes.data, max(nblk, 1)))
         return ptr, col[:nblk], diag[: self.nbrows], val[:nblk]
-
-    def close(self):
-        if self._h is not None:
-            lib().mi_bilu4_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 BILU_ORDERS = ("natural", "colour")  # MI_BILU_ORDER_*
 
@@ -1083,7 +1094,7 @@ def MatSolve_SeqBAIJ_4(F, b, x):
     return F.solve(x, b)
 
 
-class dilu4:
+class dilu4(_OwnsHandle):
     """mi_dilu4_t: the block DILU preconditioner M = (E + L) E^-1 (E + U) of a square 4x4-block matrix B = L + D + U, applied with
     Eisenstat's trick: apply_hat is the split-preconditioned operator A^ = (E + L)^-1 B (E + U)^-1 E at the cost of ONE backward and
     ONE forward triangular sweep, with no separate product (include/mi355_spmv.h, mi_dilu4_*).  dilu4(A, order="colour") takes a
@@ -1093,33 +1104,17 @@ class dilu4:
     operations take CUDA tensors, run asynchronously on torch's current stream, allocate nothing and may run in place; one operation
     at a time per handle."""
 
+    _destroy = "mi_dilu4_destroy"
+
     def __init__(self, A, ptrow=None, indcol=None, coef=None, layout="row", host_only=False, order="colour"):
-        if isinstance(A, bcsr4x4_matrix):
-            nbrows, ptrow, indcol, coef, lay = A.nrows, A.ptrow, A.indcol, A.coef, A.layout
-        else:
-            nbrows, lay = int(A), {"row": 0, "col": 1}[layout]
-        self.nbrows = int(nbrows)
+        self.nbrows, ptrow, indcol, coef, lay = _block_pattern(A, ptrow, indcol, coef, layout)
         self.layout = lay
         self.order = order
-        ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
-        indcol = np.ascontiguousarray(indcol, dtype=np.int32)
-        coef = _host_f64(coef, None, "coef")
-        if len(ptrow) != self.nbrows + 1:
-            raise ValueError("ptrow must have nbrows+1 entries")
-        if coef.size < 16 * len(indcol):
-            raise ValueError("coef: 16 values per block")
         self._nblocks_in = len(indcol)
-        self._h = None
         h = _vp()
         make = lib().mi_dilu4_create_host if host_only else lib().mi_dilu4_create
         check(make(self.nbrows, ptrow.ctypes.data, indcol.ctypes.data, coef.ctypes.data, lay, _bilu_order(order), _c.byref(h)))
         self._h = h
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise ValueError("dilu4: closed")
-        return self._h
 
     def _sweep(self, fn, out, src):
         n = 4 * self.nbrows
@@ -1186,18 +1181,6 @@ class dilu4:
         finally:
             S.close()
         return out
-
-    def close(self):
-        if self._h is not None:
-            lib().mi_dilu4_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class DistVector:
     """mi_dist_vec_t: a vector distributed like the rows of a DistMatrix (per rank [owned | halo] on the rank's device)."""

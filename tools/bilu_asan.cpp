@@ -1,9 +1,12 @@
 // tools/bilu_asan.cpp — dev tool: bilu4_plan.hpp (the schedule of the block ILU, its host factorisation, the device refactor's plan, the
-// one-launch solve's plan) under the host address and undefined-behaviour sanitizers, every table checked by brute force on the empty
-// matrix, a diagonal one, a chain, random banded and random unsymmetric patterns at fill 0 to 3, and layered patterns whose levels
-// have 1, 63, 64, 65 and 129 rows (either side of the folding rule):
+// one-launch solve's plan) and dilu4_plan.hpp (the block DILU's pivots) under the host address and undefined-behaviour sanitizers,
+// every table checked by brute force on the empty matrix, a diagonal one, a chain, random banded and random unsymmetric patterns at
+// fill 0 to 3, and layered patterns whose levels have 1, 63, 64, 65 and 129 rows (either side of the folding rule).  The level loop
+// the factorisation and the pivots share (bilu4_for_level_rows) through both: the same bits at 1, 3, 4 and 16 threads, and of several
+// refused pivots planted in one wide and in one narrow level the lowest block row is the one returned:
 //   g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -Inavierstokes_amd/csrc -o /tmp/bilu_asan tools/bilu_asan.cpp && /tmp/bilu_asan
 #include "bilu4_plan.hpp"
+#include "dilu4_plan.hpp"
 #include <cstdio>
 #include <random>
 using namespace mi355;
@@ -38,6 +41,49 @@ static Rows layered(const std::vector<int>& widths, int extra, std::mt19937& rng
         for (int r = 0; r < widths[l]; r++)
             for (int e = 0; e < extra; e++) link(first[l] + r, (int)(rng() % first[l - 1]));
     return rows;
+}
+
+// fill 0, where the factor's pattern is the matrix's own: the DILU pivots with the same bits whatever the thread count, and a refused
+// pivot — every block of a block row zeroed, so that nothing is subtracted from its zero diagonal block — planted in two rows of a
+// level: both users of the shared level loop return the lower one.  widths: as for check (the levels of a layered pattern)
+static void check_dilu(const char* name, const Bilu4Schedule& S, const std::vector<int>& ptr, const std::vector<int>& col, const std::vector<double>& coef,
+                       const std::vector<int>& widths)
+{
+    const int fill = 0;
+    const Bilu4Pattern& P = S.pat;
+    const Bilu4Sweep& F = S.sweep[0];
+    const int nb = P.nb;
+    EXPECT(P.col == col && (int)P.ptr.size() == (int)ptr.size(), "the pattern at fill 0 is not the matrix's");
+    const size_t nv = 16 * (size_t)P.nblocks(), nd = 16 * (size_t)nb;
+    std::vector<double> val(nv, -1.0), e1(nd, -1.0), k1(nd, -1.0), et(nd), kt(nd);
+    dilu4_values(P.nblocks(), coef.data(), false, nullptr, val.data());
+    EXPECT(nv == 0 || !memcmp(val.data(), coef.data(), sizeof(double) * nv), "dilu4_values without a src table is not a copy");
+    const int r1 = dilu4_pivots(P, F, val.data(), 1, e1.data(), k1.data());
+    EXPECT(r1 == -1, "a DILU pivot was refused (row %d)", r1);
+    for (int threads : {3, 16}) {
+        std::fill(et.begin(), et.end(), -2.0), std::fill(kt.begin(), kt.end(), -2.0);
+        const int rt = dilu4_pivots(P, F, val.data(), threads, et.data(), kt.data());
+        EXPECT(rt == -1, "a DILU pivot was refused with %d threads (row %d)", threads, rt);
+        EXPECT(nd == 0 || (!memcmp(e1.data(), et.data(), sizeof(double) * nd) && !memcmp(k1.data(), kt.data(), sizeof(double) * nd)), "the DILU pivots differ between 1 and %d threads", threads);
+    }
+    if (widths.empty()) return;
+    for (bool wide : {true, false}) {
+        int l = 0; // the first level of that kind
+        while (l < F.nlev() && (F.lev_ptr[l + 1] - F.lev_ptr[l] >= kBiluRowsPerWG) != wide) l++;
+        if (l == F.nlev()) continue;
+        const int p0 = F.lev_ptr[l], p1 = F.lev_ptr[l + 1];
+        const int rows[2] = {F.perm[p1 - 1], F.perm[p0 + (p1 - p0) / 2]}; // the last share's last row, and a lower one from the middle (the same one in a level of one row)
+        const int want = std::min(rows[0], rows[1]);
+        std::vector<double> cz(coef);
+        for (int i : rows) std::fill(cz.begin() + 16 * (size_t)ptr[i], cz.begin() + 16 * (size_t)ptr[i + 1], 0.0);
+        dilu4_values(P.nblocks(), cz.data(), false, nullptr, val.data());
+        for (int threads : {1, 3, 16}) {
+            std::vector<double> v(nv, -3.0);
+            const int rf = bilu4_factor(P, F, ptr.data(), col.data(), cz.data(), false, threads, v.data());
+            const int rd = dilu4_pivots(P, F, val.data(), threads, et.data(), kt.data());
+            EXPECT(rf == want && rd == want, "%s level %d, %d threads: refused rows %d and %d planted, factor says %d, pivots say %d", wide ? "wide" : "narrow", l, threads, rows[0], rows[1], rf, rd);
+        }
+    }
 }
 
 // widths: the level sizes the pattern must have at fill 0 (forward; reversed backward), or empty
@@ -101,18 +147,23 @@ static void check(const char* name, Rows rows, int fill, const std::vector<int>&
         EXPECT(lev == W.nlev() && pos == nb, "sweep %d: the launches end at level %d, position %d", b, lev, pos);
     }
 
-    // the factorisation: the same bits with 1 and with 4 threads
+    // the factorisation: the same bits whatever the thread count
     std::mt19937 rng(7 + nb);
     std::vector<double> coef(16 * col.size());
     for (int i = 0; i < nb; i++)
         for (int k = ptr[i]; k < ptr[i + 1]; k++)
             for (int e = 0; e < 16; e++)
                 coef[16 * (size_t)k + e] = ((int)(rng() % 2001) - 1000) / (col[k] == i ? 20000.0 : 4000.0 * (ptr[i + 1] - ptr[i])) + (col[k] == i && e % 5 == 0 ? 4.0 : 0.0);
-    std::vector<double> v1(16 * (size_t)P.nblocks(), -1.0), v4(v1.size(), -2.0);
+    std::vector<double> v1(16 * (size_t)P.nblocks(), -1.0), vt(v1.size());
     const int r1 = bilu4_factor(P, S.sweep[0], ptr.data(), col.data(), coef.data(), false, 1, v1.data());
-    const int r4 = bilu4_factor(P, S.sweep[0], ptr.data(), col.data(), coef.data(), false, 4, v4.data());
-    EXPECT(r1 == -1 && r4 == -1, "a pivot was refused (rows %d, %d)", r1, r4);
-    EXPECT(v1.empty() || !memcmp(v1.data(), v4.data(), sizeof(double) * v1.size()), "the factor differs between 1 and 4 threads");
+    EXPECT(r1 == -1, "a pivot was refused (row %d)", r1);
+    for (int threads : {3, 4, 16}) {
+        std::fill(vt.begin(), vt.end(), -2.0);
+        const int rt = bilu4_factor(P, S.sweep[0], ptr.data(), col.data(), coef.data(), false, threads, vt.data());
+        EXPECT(rt == -1, "a pivot was refused with %d threads (row %d)", threads, rt);
+        EXPECT(v1.empty() || !memcmp(v1.data(), vt.data(), sizeof(double) * v1.size()), "the factor differs between 1 and %d threads", threads);
+    }
+    if (fill == 0) check_dilu(name, S, ptr, col, coef, widths);
 
     // the device refactor's plan
     Bilu4DevPlan D;
