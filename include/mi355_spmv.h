@@ -38,7 +38,8 @@ extern "C" {
 #define MI355_SPMV_VERSION 501 /* 0.5.1: mi_bcsr4_spmm_info writes us[5] since 0.4 (it was us[4] in 0.3: a caller built against 0.3 must be rebuilt); 0.5 adds
                                 * mi_sstream_plan_probe_ex, mi_part_kernel_name, mi_part_sends_contiguous and refills sliced copies inside mi_*_update_values*;
                                 * 0.5.1 adds mi_sstream_mw_plan_probe (nothing changed for a caller built against 0.5.0); mi_bilu4dev_* (the
-                                * device refactor of the block ILU) was added without a version change: nothing existing changed */
+                                * device refactor of the block ILU) and mi_dilu4dev_* (the device refactor of the block DILU) were added
+                                * without a version change: nothing existing changed */
 
 enum {
     MI_OK = 0,
@@ -1107,8 +1108,8 @@ int mi_gmres_plan_destroy(mi_gmres_plan_t P);
  * the handle owns on the device (0 on a host-only handle), perm [nbrows] (perm[caller's row] = B's).  Any output may be NULL.
  * mi_dilu4_create_host: no device (refactor, fetch, info work; the three operations return MI_ERR_STATE).
  * MI_ERR_ARG: what mi_bilu4_create refuses in a pattern, an unknown layout or ordering, a null argument, a refused pivot.
- * nbrows == 0: every call is a no-op.  NOT built: a refactorisation on the device, a single-precision copy, Jacobi sweeps, a
- * one-launch form, an automatic choice, mi_dist. */
+ * nbrows == 0: every call is a no-op.  NOT built: a single-precision copy, Jacobi sweeps, a one-launch form, an automatic
+ * choice, mi_dist, a symbolic phase on the device.  The refactorisation on the device is mi_dilu4dev_*, below. */
 typedef struct mi_dilu4_s* mi_dilu4_t;
 int mi_dilu4_create(int nbrows, const int* ptrow, const int* indcol, const double* coef, int layout /* MI_BLOCK_* */,
                     int ordering /* MI_BILU_ORDER_* */, mi_dilu4_t* out);
@@ -1126,6 +1127,51 @@ int mi_dilu4_apply_hat_dev(mi_dilu4_t E, const double* d_u, double* d_w, mi_stre
  * preconditioner must be NULL (M is inside A^): MI_ERR_STATE otherwise, and mi_gmres_set_precond* with F != NULL is refused with
  * MI_ERR_STATE while this operator is set.  E is not owned and must outlive G; one solve at a time per E. */
 int mi_gmres_set_operator_dilu4(mi_gmres_t G, mi_dilu4_t E);
+
+/* ---- 4x4-block DILU: the pivots recomputed on the GPU from values on the device (mi_dilu4dev_*) ----
+ * A Newton step re-assembles the Jacobian and refactors before every linear solve (src/solve_newton.c:1245-1265);
+ * mi_dilu4_refactor does that on host threads, waits for the device and uploads both triangles, Einv and K.
+ * mi_dilu4dev_refactor computes the same state (the PIVOTS above, operation for operation: after it the device holds, bit for
+ * bit, what mi_dilu4_refactor would have uploaded for the same values — both triangles level-major, Einv, K) on the GPU, on the
+ * caller's stream, from block values that already lie on the device, in place into the arrays the three operations read.
+ * Schedule: the forward sweep's levels and launches (row i needs Einv_j only of the rows j it has an L block to), after ONE
+ * launch that scatters the values into both triangles, puts D_i into Einv_i and K_i and resets the refusal word: launches per
+ * refactor = forward launches + 1.  Sixteen lanes per block row, one per entry of a block; the block (j, i) of every L block
+ * (i, j) is looked up once per handle, not once per refactor.
+ * ORDERING is the caller's business, as it is for the operations: a refactor on stream s is ordered with operations on s only.
+ * An operation running on another stream during a refactor reads half-written pivots.
+ * Refused pivot: the refactor itself cannot report it (nothing is copied back); mi_dilu4dev_status does.  As on the host, the
+ * rows of later levels are then not computed and the handle must be refactored, by either path, before it is used.
+ * The host copies (what mi_dilu4_fetch returns) are NOT updated by a device refactor until mi_dilu4dev_fetch copies them back;
+ * mi_dilu4_refactor replaces host and device state as before.  Creation still computes the pivots on the host.
+ * mi_dilu4_info and its device_bytes are unchanged; the tables of the device refactor are counted by mi_dilu4dev_info.
+ * MI_ERR_ARG: a null handle, null d_coef, an unknown layout; MI_ERR_STATE: a host-only handle (_prepare, _refactor, _status,
+ * _fetch).  nbrows == 0: every call is a no-op. */
+/* host-only: the device refactor's plan for a pattern under `ordering` (MI_BILU_ORDER_*), built exactly as mi_dilu4dev_prepare
+ * builds it AND replayed against the pattern (MI_ERR_STATE naming the first violation): *pivot_pairs = the updates
+ * E_i -= (B_ij Einv_j) B_ji of one refactor (once per Newton step, src/solve_newton.c:1245-1265), *launches per refactor,
+ * *plan_bytes of its tables (below).  Refuses what mi_dilu4_create refuses in a pattern or an ordering, with its messages */
+int mi_dilu4dev_plan_probe(int nbrows, const int* ptrow, const int* indcol, int ordering, long long* pivot_pairs, int* launches,
+                           long long* plan_bytes);
+/* build, check and upload the pattern-only tables of the device refactor (idempotent; allocates, may synchronise: not
+ * capturable): every block row's position in the forward sweep, per block of the device state the caller's block that lands
+ * there, and per L block (i, j) the place of block (j, i) or that there is none.  Pattern-only: once per handle, not once per
+ * Newton step (src/solve_newton.c:1245-1265) */
+int mi_dilu4dev_prepare(mi_dilu4_t E);
+/* new values, same pattern (src/solve_newton.c:1245-1265), d_coef on the device in the CALLER's block order, as the arrays given at
+ * create (16 per block, `layout`; 8-byte alignment suffices); asynchronous on s: nothing allocated, copied or synchronised once
+ * prepared (so it can be captured into a graph); calls mi_dilu4dev_prepare itself when needed (that first call is not capturable) */
+int mi_dilu4dev_refactor(mi_dilu4_t E, const double* d_coef, int layout, mi_stream_t s);
+/* waits for the device, hence for the last mi_dilu4dev_refactor (src/solve_newton.c:1245-1265); *bad_row = -1 and MI_OK, or the
+ * CALLER's block row of the refused pivot and MI_ERR_ARG with the same message mi_dilu4_refactor gives (|d| < 1e-12); MI_OK before
+ * any device refactor */
+int mi_dilu4dev_status(mi_dilu4_t E, int* bad_row);
+/* waits, then copies the device's triangles, Einv and K back into the host copies, so that mi_dilu4_fetch returns what the device
+ * holds (the pivots after the refactor of src/solve_newton.c:1245-1265) */
+int mi_dilu4dev_fetch(mi_dilu4_t E);
+/* *prepared, *launches per refactor, *plan_bytes of device tables beyond what mi_dilu4_info counts (0 until prepared); any output
+ * may be NULL (src/solve_newton.c:1245-1265: the cost of refactoring per Newton step) */
+int mi_dilu4dev_info(mi_dilu4_t E, int* prepared, int* launches, long long* plan_bytes);
 
 /* ---- row-range partition of one matrix over the GPUs of a node ----------
  * New design (the reference has no distributed code).  Rank r

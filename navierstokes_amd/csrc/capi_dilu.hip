@@ -1,13 +1,22 @@
 // capi_dilu.hip: the 4x4-block DILU preconditioner applied with Eisenstat's trick, mi_dilu4_* — part of libmi355spmv.so (see
-// capi_internal.hpp for the layout of the library).  Pivots on the host (dilu4_plan.hpp); the three sweeps on the GPU
+// capi_internal.hpp for the layout of the library).  Pivots on the host (dilu4_plan.hpp) or, into the same device arrays, on the
+// GPU level by level from values that lie on the device (mi_dilu4dev_*, dilu4_factor.hpp); the three sweeps on the GPU
 // (dilu4_kernels.hpp), one launch per (folded) dependency level of the schedule bilu4_plan.hpp computes on the pattern of B.
 // Everything a DILU handle has in common with a block ILU handle is capi_bilu_common.hpp's: the argument rules, the host part of
 // the handle (ordering, pattern, schedule), the level-major copy of the two triangles, the guard, the steps of a refactor and the
 // gather and scatter that bracket every call on an ordered handle (MI_BILU_ORDER_COLOUR).  This file holds what is DILU's own.
-// No CPU fallback: the sweeps need a HIP device; create_host, refactor, fetch and info need none.
+// No CPU fallback: the sweeps and the device refactor need a HIP device; create_host, refactor, fetch, info and the plan probe need none.
 #include "capi_bilu_common.hpp"
 #include "dilu4_plan.hpp"
 #include "dilu4_kernels.hpp"
+#include "dilu4_factor.hpp"
+
+// the device refactor (mi_dilu4dev_prepare): pattern-only tables, see Dilu4DevPlan
+struct Dilu4DevTables {
+    bool prepared = false;
+    long long nL = 0, nU = 0, plan_bytes = 0;
+    DevArray<int> fpos, gather, mate, bad;
+};
 
 struct mi_dilu4_s : Bilu4Handle { // sched: fill 0, the pattern is B's own
     std::vector<double> val;        // B's values, B's block order, row-major
@@ -15,8 +24,13 @@ struct mi_dilu4_s : Bilu4Handle { // sched: fill 0, the pattern is B's own
     DevArray<double> d_einv, d_kmat;
     DevArray<double> d_t, d_y;      // the work vectors of apply_hat, B's numbering
     DevArray<double> d_v;           // ordered: the vector every call passes through, B's numbering
-    ~mi_dilu4_s() { d_v = {}, d_perm = {}, d_y = {}, d_t = {}, d_kmat = {}, d_einv = {}; } // the order the handle has always been freed in; the two triangles follow
+    Dilu4DevTables dev;
+    ~mi_dilu4_s() { dev = {}, d_v = {}, d_perm = {}, d_y = {}, d_t = {}, d_kmat = {}, d_einv = {}; } // newest first, then the order the handle has always been freed in; the two triangles follow
     Dilu4View view(int b) const { return Dilu4View{lev[b].perm, lev[b].ptr, lev[b].col, lev[b].val, d_einv, d_kmat, lev[b].lev_ptr}; }
+    Dilu4FactorView factor_view() const
+    {
+        return Dilu4FactorView{lev[0].perm, lev[0].ptr, lev[0].col, lev[0].lev_ptr, dev.fpos, dev.mate, lev[0].val, lev[1].val, d_einv, d_kmat, (int)dev.nL, (int)dev.nU, dev.bad};
+    }
     long long device_bytes() const
     {
         if (device < 0 || pat().nb == 0) return 0;
@@ -32,6 +46,11 @@ struct mi_dilu4_s : Bilu4Handle { // sched: fill 0, the pattern is B's own
 
 constexpr BiluHostOnly kDiluHostOnly{MI_ERR_STATE, ": a host-only handle (mi_dilu4_create_host) has no device copy"};
 
+static int dilu_zero_pivot(int row)
+{
+    return fail(MI_ERR_ARG, "mi_dilu4: zero pivot (|d| < 1e-12) in the pivot block E of block row " + std::to_string(row));
+}
+
 // B's values and the pivots from the caller's coef
 static int dilu_factor(mi_dilu4_s* E, const double* coef, int layout)
 {
@@ -39,8 +58,7 @@ static int dilu_factor(mi_dilu4_s* E, const double* coef, int layout)
     dilu4_values(E->pat().nblocks(), coef, layout == MI_BLOCK_COLMAJOR, E->ord.src_or_null(), E->val.data());
     const int bad = dilu4_pivots(E->pat(), E->sched.sweep[0], E->val.data(), bilu_threads(), E->einv.data(), E->kmat.data());
     E->factor_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (bad >= 0) return fail(MI_ERR_ARG, "mi_dilu4: zero pivot (|d| < 1e-12) in the pivot block E of block row " + std::to_string(E->ord.caller_row(bad)));
-    return MI_OK;
+    return bad >= 0 ? dilu_zero_pivot(E->ord.caller_row(bad)) : MI_OK;
 }
 
 // the host values to the device copies: both triangles level-major, Einv and K by block row
@@ -126,6 +144,105 @@ extern "C" int mi_dilu4_info(mi_dilu4_t E, int* nbrows, long long* nblocks, int*
     if (factor_seconds) *factor_seconds = E->factor_seconds;
     if (device_bytes) *device_bytes = E->device_bytes();
     for (int i = 0; perm && i < E->pat().nb; i++) perm[i] = E->ord.on() ? E->ord.perm[i] : i;
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------- mi_dilu4dev_*: the pivots on the GPU
+// the plan of a schedule, checked (dilu4dev_check) before anything relies on it; who: the entry point, for the message
+static int dilu_dev_plan(const Bilu4Handle* H, const char* who, Dilu4DevPlan* D)
+{
+    dilu4dev_plan(H->sched, H->a_ptr.data(), H->a_col.data(), D, H->ord.src_or_null());
+    const std::string bad = dilu4dev_check(H->sched, *D, H->ord.src_or_null());
+    if (!bad.empty()) return fail(MI_ERR_STATE, std::string(who) + ": " + bad);
+    return MI_OK;
+}
+
+extern "C" int mi_dilu4dev_plan_probe(int nbrows, const int* ptrow, const int* indcol, int ordering, long long* pivot_pairs, int* launches, long long* plan_bytes)
+{
+    CHECK_ARG(!bilu_bad_ordering(ordering), bilu_bad_ordering(ordering));
+    int rc;
+    if ((rc = bilu_check_args("mi_dilu4: ", nbrows, ptrow, indcol, 0))) return rc;
+    Bilu4Handle H; // the host part only: nothing of it reaches a device
+    Dilu4DevPlan D;
+    if ((rc = bilu_plan_host(&H, nbrows, ptrow, indcol, 0, ordering, "mi_dilu4dev_plan_probe")) || (rc = dilu_dev_plan(&H, "mi_dilu4dev_plan_probe", &D))) return rc;
+    if (pivot_pairs) *pivot_pairs = D.pivot_pairs;
+    if (launches) *launches = H.sched.sweep[0].nlaunch() + kDiluDevFixedLaunches;
+    if (plan_bytes) *plan_bytes = D.bytes();
+    return MI_OK;
+}
+
+extern "C" int mi_dilu4dev_prepare(mi_dilu4_t E)
+{
+    if (const int rc = bilu_guard(E, "mi_dilu4dev_prepare", kDiluHostOnly); rc != kBiluGo) return rc;
+    if (E->dev.prepared) return MI_OK;
+    Dilu4DevPlan D;
+    int rc;
+    if ((rc = dilu_dev_plan(E, "mi_dilu4dev_prepare", &D))) return rc;
+    Dilu4DevTables T; // moves into the handle once it is complete; a failure on the way frees what there is
+    if ((rc = dev_upload(T.fpos, D.fpos, 1)) || (rc = dev_upload(T.gather, D.gather, 1)) || (rc = dev_upload(T.mate, D.mate, 1)) ||
+        (rc = dev_upload(T.bad, std::vector<int>(1, kDiluBadNone), 1)))
+        return rc;
+    T.nL = D.nL, T.nU = D.nU, T.plan_bytes = D.bytes();
+    T.prepared = true;
+    E->dev = std::move(T);
+    return MI_OK;
+}
+
+extern "C" int mi_dilu4dev_refactor(mi_dilu4_t E, const double* d_coef, int layout, mi_stream_t s)
+{
+    if (const int rc = bilu_guard(E, "mi_dilu4dev_refactor", kDiluHostOnly, bilu_bad_layout(layout), d_coef ? nullptr : "null coef"); rc != kBiluGo) return rc;
+    int rc;
+    if (!E->dev.prepared && (rc = mi_dilu4dev_prepare(E))) return rc;
+    hipStream_t st = (hipStream_t)s;
+    const Dilu4FactorView V = E->factor_view();
+    const long long total = E->pat().nblocks();
+    hipLaunchKernelGGL(dilu4f_gather, dim3((unsigned)((total * 16 + kWG - 1) / kWG)), dim3(kWG), 0, st, V, E->dev.gather, total, d_coef, (int)(layout == MI_BLOCK_COLMAJOR));
+    const Bilu4Sweep& S = E->sched.sweep[0]; // the pivots follow the forward sweep's launches
+    for (int a = 0; a < S.nlaunch(); a++) {
+        const Bilu4Launch L = S.launch(a);
+        if (L.folded()) {
+            hipLaunchKernelGGL(dilu4f_folded, dim3(1), dim3(kDiluFactorFoldedWG), 0, st, V, L.l0, L.l1);
+        } else {
+            const int grid = (int)(((long long)(L.p1 - L.p0) * 16 + kWG - 1) / kWG);
+            hipLaunchKernelGGL(dilu4f_level, dim3(grid), dim3(kWG), 0, st, V, L.p0, L.p1);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+extern "C" int mi_dilu4dev_status(mi_dilu4_t E, int* bad_row)
+{
+    if (E && bad_row) *bad_row = -1;
+    if (const int rc = bilu_guard(E, "mi_dilu4dev_status", kDiluHostOnly); rc != kBiluGo) return rc;
+    if (!E->dev.prepared) return MI_OK; // no device refactor yet
+    HIP_TRY(hipDeviceSynchronize());
+    int bad = kDiluBadNone;
+    HIP_TRY(hipMemcpy(&bad, E->dev.bad, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad == kDiluBadNone) return MI_OK;
+    bad = E->ord.caller_row(bad);
+    if (bad_row) *bad_row = bad;
+    return dilu_zero_pivot(bad);
+}
+
+// the device's triangles, Einv and K into the host copies; B's diagonal blocks are not kept on the device (Einv and K start from
+// them), so those of the host's val stay as the last host refactor left them — nothing reads them but that refactor, which rewrites them
+extern "C" int mi_dilu4dev_fetch(mi_dilu4_t E)
+{
+    if (const int rc = bilu_guard(E, "mi_dilu4dev_fetch", kDiluHostOnly); rc != kBiluGo) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (const int rc = bilu_move_offdiag(E, E->val.data(), false)) return rc;
+    HIP_TRY(hipMemcpy(E->einv.data(), E->d_einv, sizeof(double) * E->einv.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(E->kmat.data(), E->d_kmat, sizeof(double) * E->kmat.size(), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+extern "C" int mi_dilu4dev_info(mi_dilu4_t E, int* prepared, int* launches, long long* plan_bytes)
+{
+    CHECK_ARG(E, "null handle");
+    if (prepared) *prepared = E->dev.prepared ? 1 : 0;
+    if (launches) *launches = E->sched.sweep[0].nlaunch() + kDiluDevFixedLaunches;
+    if (plan_bytes) *plan_bytes = E->dev.plan_bytes;
     return MI_OK;
 }
 

@@ -239,6 +239,12 @@ def lib():
         "mi_dilu4_from_hat_dev": [_vp, _vp, _vp, _vp],
         "mi_dilu4_apply_hat_dev": [_vp, _vp, _vp, _vp],
         "mi_gmres_set_operator_dilu4": [_vp, _vp],
+        "mi_dilu4dev_plan_probe": [i, _vp, _vp, i, P(ll), P(i), P(ll)],
+        "mi_dilu4dev_prepare": [_vp],
+        "mi_dilu4dev_refactor": [_vp, _vp, i, _vp],
+        "mi_dilu4dev_status": [_vp, P(i)],
+        "mi_dilu4dev_fetch": [_vp],
+        "mi_dilu4dev_info": [_vp, P(i), P(i), P(ll)],
         "mi_part_create": [i, i, _vp, _vp, _vp, _vp, P(_vp)],
         "mi_part_destroy": [_vp],
         "mi_part_sizes": [_vp, P(i), P(i), P(i), P(i)],
@@ -940,6 +946,17 @@ def bilu4dev_plan_probe(nbrows, ptrow, indcol, fill=0):
     return dict(update_pairs=up.value, launches=la.value, plan_bytes=by.value)
 
 
+def dilu4dev_plan_probe(nbrows, ptrow, indcol, order="colour"):
+    """mi_dilu4dev_plan_probe (no GPU): dict(pivot_pairs, launches, plan_bytes) of the block DILU's device refactor under `order`,
+    built and checked by the library (MiError, status 6, naming the first violation)."""
+    ptrow = np.ascontiguousarray(ptrow, dtype=np.int32)
+    indcol = np.ascontiguousarray(indcol, dtype=np.int32)
+    pp, by, la = _c.c_longlong(), _c.c_longlong(), _c.c_int()
+    check(lib().mi_dilu4dev_plan_probe(int(nbrows), ptrow.ctypes.data, indcol.ctypes.data if indcol.size else None, _bilu_order(order), _c.byref(pp),
+                                       _c.byref(la), _c.byref(by)))
+    return dict(pivot_pairs=pp.value, launches=la.value, plan_bytes=by.value)
+
+
 def bilu4one_plan_probe(nbrows, ptrow, indcol, fill=0, workgroups=0):
     """mi_bilu4one_plan_probe (no GPU): dict(eligible, why, nchunks, max_deps, plan_bytes, chunk_pos, chunk_lev, dep_ptr, dep) of the
     one-launch solve's plan, replayed for `workgroups` (0: 256); the last six are (forward, backward) pairs."""
@@ -1102,7 +1119,8 @@ class dilu4(_OwnsHandle):
     order: "colour" (the multicolour ordering of bilu4, where DILU measured as good as ILU(0)) or "natural"; every method keeps the
     caller's numbering.  host_only=True: no device copy (refactor, fetch, info only).  Opt-in: nothing chooses it.  The three
     operations take CUDA tensors, run asynchronously on torch's current stream, allocate nothing and may run in place; one operation
-    at a time per handle."""
+    at a time per handle.  New values on the same pattern: refactor(coef) from the host (waits, uploads) or refactor_dev(coef) from a
+    CUDA tensor, on the GPU and on the current stream (mi_dilu4dev_*; the same bits)."""
 
     _destroy = "mi_dilu4_destroy"
 
@@ -1139,6 +1157,36 @@ class dilu4(_OwnsHandle):
         coef = _host_f64(coef, 16 * self._nblocks_in, "coef")
         check(lib().mi_dilu4_refactor(self.handle, coef.ctypes.data, self.layout))
         return self
+
+    def prepare_dev(self):
+        """Build, check and upload the pattern-only tables of the device refactor (mi_dilu4dev_prepare; idempotent)."""
+        check(lib().mi_dilu4dev_prepare(self.handle))
+        return self
+
+    def refactor_dev(self, coef):
+        """New values on the same pattern from a CUDA tensor (the block order and layout of construction): both triangles, Einv
+        and K are rewritten on the GPU, asynchronously on torch's current stream (mi_dilu4dev_refactor; capturable once prepared).
+        A refused pivot shows in factor_status(); fetch() follows only after fetch_dev()."""
+        check(lib().mi_dilu4dev_refactor(self.handle, _dev_ptr(coef, 16 * self._nblocks_in, "coef"), self.layout, _stream_ptr()))
+        return self
+
+    def factor_status(self):
+        """Wait for the last refactor_dev; MiError (MI_ERR_ARG, naming the caller's block row) when it refused a pivot."""
+        bad = _c.c_int()
+        check(lib().mi_dilu4dev_status(self.handle, _c.byref(bad)))
+        return self
+
+    def fetch_dev(self):
+        """Copy the device's triangles, Einv and K back into the host copies, so that fetch() returns what the device holds
+        (mi_dilu4dev_fetch; waits)."""
+        check(lib().mi_dilu4dev_fetch(self.handle))
+        return self
+
+    def info_dev(self):
+        """dict(prepared, launches, plan_bytes) — mi_dilu4dev_info; launches: of one refactor_dev."""
+        pr, la, by = _c.c_int(), _c.c_int(), _c.c_longlong()
+        check(lib().mi_dilu4dev_info(self.handle, _c.byref(pr), _c.byref(la), _c.byref(by)))
+        return dict(prepared=bool(pr.value), launches=la.value, plan_bytes=by.value)
 
     def fetch(self):
         """(Einv, K), each (nbrows, 4, 4) row-major by the caller's block row (mi_dilu4_fetch): the inverted pivots and 2E - D."""

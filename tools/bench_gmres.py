@@ -6,7 +6,7 @@ profiles/gmres_bench.jsonl.
 
     python3 tools/bench_gmres.py [--cells 68] [--fill 0] [--sweeps 3] [--precision f64|f32|both] [--basis f64|f32|both] [--runs 5] [--no-append]
                                  [--graph SEG[,SEG...]] [--order natural,colour] [--exact-precision f64|f32|both]
-    python3 tools/bench_gmres.py --precond dilu [--cells 68] [--order colour,natural] [--sweeps 3] [--runs 5] [--no-append]
+    python3 tools/bench_gmres.py --precond dilu [--cells 68] [--order colour,natural] [--sweeps 3] [--runs 5] [--no-append] [--refactor]
 
 --exact-precision (default f64): which values the exact-solve rows stream — the double factor ("exact"), its single-precision
 copy ("exact_f32": mpk.bilu4.exact("f32"), MI_GMRES_PC_EXACT_F32), or both on the SAME factor handle in the same process; the
@@ -34,6 +34,14 @@ against block ILU(0) on the SAME matrix handle in one process.  One record (tool
              --runs, the solvers alternating inside every run), microseconds per iteration and the TRUE residual ||b - A x|| / ||b||.
              THE TWO TOLERANCES ARE IN DIFFERENT NORMS: DILU's rtol is on ||(E + L)^-1 r|| / ||b^||, ILU's on the residual of the
              right-preconditioned system, which is the true one; compare the solves by true_residual.
+
+--precond dilu --refactor adds to that record, per ordering and on the handles it already builds,
+  refactor   mi_dilu4dev_refactor (mpk.dilu4.refactor_dev: events around 20 refactors after 3 warm-ups, values on the device) against
+             mi_dilu4_refactor, the host path (median wall seconds of 3, values on the host: pivots on host threads, a wait, the upload),
+             in the same process: device_us, host_seconds, their ratio, the launches per refactor, plan_bytes, pivot_pairs, and the
+             byte model — scatter: every block read and written once, its gather index, D_i written twice; pivots: per L block itself,
+             Einv_j, its mate and two indices, per block row Einv and K read and written — with its time at this box's
+             mi_stream_read_probe rate and the fraction of that rate the device refactor reaches.
 
 Preconditioners per process: the sweeps (--sweeps per triangle) in each precision asked for, and the exact solve.  For each one a
 record (tool = "bench_gmres") with, per solver: iterations, wall seconds (median of --runs runs; the solvers ALTERNATE inside every
@@ -101,6 +109,32 @@ def dilu_mode(a):
                                   ncolours=info["ncolours"], device_bytes=info["device_bytes"], pivots_host_seconds=round(dilu_create[o], 3),
                                   # both sweeps: every off-diagonal block once, Einv twice and K once per block row, u twice, t three times, y and w
                                   model_bytes=(nblk - nb) * blk + 3 * nb * 128 + 8 * vec)
+    refactor = {}
+    if a.refactor:
+        dcoef = torch.from_numpy(np.ascontiguousarray(bv, dtype=np.float64)).cuda()
+        hbm = (1 << 30) / mpk.stream_read_us(1 << 30)  # bytes per microsecond of a plain read sweep
+        rows = np.repeat(np.arange(nb), np.diff(bp))
+        for o, E in dilus.items():
+            perm = E.info()["perm"].astype(np.int64)
+            n_l = int((perm[np.asarray(bc)] < perm[rows]).sum())
+            E.prepare_dev()
+            dev_us = timed(lambda: E.refactor_dev(dcoef), warm=3, reps=20)
+            E.factor_status()
+            host = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                E.refactor(bv)
+                host.append(time.perf_counter() - t0)
+            E.refactor_dev(dcoef).factor_status()  # the solves below run on what the device refactor left
+            probe = mpk.dilu4dev_plan_probe(nb, bp, bc, o)
+            scatter = nblk * (2 * 128 + 4) + nb * 128
+            pivots = n_l * (3 * 128 + 8) + nb * (4 * 128 + 8)
+            model_us = (scatter + pivots) / hbm
+            refactor[o] = dict(device_us=dev_us, host_seconds=round(statistics.median(host), 4), host_over_device=round(statistics.median(host) * 1e6 / dev_us, 1),
+                               launches=E.info_dev()["launches"], plan_bytes=E.info_dev()["plan_bytes"], pivot_pairs=probe["pivot_pairs"],
+                               model_bytes=dict(scatter=scatter, pivots=pivots), read_probe_bytes_per_us=round(hbm, 1), model_us=round(model_us, 2),
+                               fraction_of_model=round(model_us / dev_us, 3))
+        del dcoef
     solvers = {}
     for o, E in dilus.items():
         S = mpk.gmres_solver(E, None, RESTART)
@@ -140,6 +174,8 @@ def dilu_mode(a):
             secs[k].append(sec)
             last[k] = dict(iterations=its, true_residual=true, recurrence_residual=rec, norm="hat" if k.startswith("dilu") else "true")
     out = dict(tool="bench_gmres_dilu", cells=a.cells, rows=n, blocks=nblk, restart=RESTART, rtol=RTOL, runs=a.runs, apply=apply, solvers={})
+    if a.refactor:
+        out["refactor"] = refactor
     for k in solvers:
         med = statistics.median(secs[k])
         out["solvers"][k] = dict(last[k], seconds=round(med, 6), spread_seconds=round(max(secs[k]) - min(secs[k]), 6),
@@ -168,6 +204,7 @@ def main():
     ap.add_argument("--no-append", action="store_true")
     ap.add_argument("--graph", default="", help="segments of the planned solve, e.g. 1,5,30")
     ap.add_argument("--exact-precision", choices=("f64", "f32", "both"), default="f64", help="the values the exact-solve rows stream")
+    ap.add_argument("--refactor", action="store_true", help="with --precond dilu: the device refactor against the host path (module docstring)")
     ap.add_argument("--order", default="natural", help="comma-separated orderings of the block rows: natural, colour")
     a = ap.parse_args()
     if a.precond == "dilu":
