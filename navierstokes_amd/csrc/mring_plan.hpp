@@ -416,6 +416,8 @@ inline const char* check_mring_plan(const MringPlanHost& P, int n, const int* pt
             run_of[b] = g;
         }
     }
+    int cend = std::max(n, 64); // one past the last column of x: a partition's piece names ghost columns beyond its rows
+    for (long long k = 0; k < ptrow[n]; k++) cend = std::max(cend, indcol[k] + 1);
     std::vector<int> content((size_t)K * W, -1);
     int next_row = 0, cur_run = -1;
     long long next_nz = 0;
@@ -439,7 +441,7 @@ inline const char* check_mring_plan(const MringPlanHost& P, int n, const int* pt
             }
         }
         for (int g = 0; g < G; g++)
-            if (Q[8 + g] < 0 || Q[8 + g] > std::max(n, 64)) return "a group's first column is out of range";
+            if (Q[8 + g] < 0 || Q[8 + g] > cend) return "a group's first column is out of range";
         if (!P.run_ok[run]) {
             if (Q[4] != 0) return "flags of a block in a plain run";
             continue;

@@ -3,7 +3,11 @@
 // every table checked by brute force on the empty matrix, a diagonal one, a chain, random banded and random unsymmetric patterns at
 // fill 0 to 3, and layered patterns whose levels have 1, 63, 64, 65 and 129 rows (either side of the folding rule).  The level loop
 // the factorisation and the pivots share (bilu4_for_level_rows) through both: the same bits at 1, 3, 4 and 16 threads, and of several
-// refused pivots planted in one wide and in one narrow level the lowest block row is the one returned:
+// refused pivots planted in one wide and in one narrow level the lowest block row is the one returned.  The device refactor's plan of the
+// DILU pivots (dilu4dev_plan, dilu4dev_check) at fill 0 on all of these, on patterns that lost some of their (j, i) blocks and on a
+// strictly lower one (no U block at all), without and with a src table: the index stream of dilu4f_row replayed, and corruptions planted
+// that dilu4dev_check must report.  Address and undefined behaviour, then (a second binary) threads:
+//   g++ -O1 -g -std=c++17 -pthread -fsanitize=thread -Inavierstokes_amd/csrc -o /tmp/bilu_tsan tools/bilu_asan.cpp && /tmp/bilu_tsan
 //   g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -Inavierstokes_amd/csrc -o /tmp/bilu_asan tools/bilu_asan.cpp && /tmp/bilu_asan
 #include "bilu4_plan.hpp"
 #include "dilu4_plan.hpp"
@@ -86,6 +90,76 @@ static void check_dilu(const char* name, const Bilu4Schedule& S, const std::vect
     }
 }
 
+// The device plan of the DILU pivots at fill 0, without a src table and with one (a random permutation of the caller's blocks:
+// the caller then stores block k of the pattern at src[k]).  The index stream of dilu4f_row (dilu4_factor.hpp), which reads
+//     m = V.mate[k0];  V.fcol[k0];  kn = min(k0 + 1, last): V.fcol[kn], V.mate[kn];  in the loop kn = min(lk + 2, last): V.fcol[kn], V.mate[kn]
+//     load: V.L[16 lk + e], V.einv + 16 j + c, V.U + 16 max(m, 0) + c
+// over fptr / fcol, the forward sweep's level-major row starts and columns, replayed for every forward position.
+static int dilu_plans = 0, planted = 0, caught = 0;
+static void check_dilu_dev(const char* name, const Bilu4Schedule& S, const std::vector<int>& ptr, const std::vector<int>& col, std::mt19937& rng)
+{
+    const int fill = 0;
+    const Bilu4Pattern& P = S.pat;
+    const int nb = P.nb;
+    const long long total = P.nblocks();
+    std::vector<int> perm((size_t)total);
+    for (long long k = 0; k < total; k++) perm[k] = (int)k;
+    std::shuffle(perm.begin(), perm.end(), rng);
+    for (const int* src : {(const int*)nullptr, (const int*)perm.data()}) {
+        dilu_plans++;
+        Dilu4DevPlan D;
+        dilu4dev_plan(S, ptr.data(), col.data(), &D, src);
+        const std::string why = dilu4dev_check(S, D, src);
+        EXPECT(why.empty(), "%s src: %s", src ? "with" : "without", why.c_str());
+        std::vector<int> fptr(1, 0), fcol;
+        for (int q = 0; q < nb; q++) {
+            const auto [k0, k1] = P.offdiag(S.sweep[0].perm[q], false);
+            for (int k = k0; k < k1; k++) fcol.push_back(P.col[k]);
+            fptr.push_back((int)fcol.size());
+        }
+        const long long nL = D.nL, nU = D.nU;
+        EXPECT((long long)fcol.size() == nL && (long long)D.mate.size() == nL && (long long)D.gather.size() == nL + nU + nb, "table lengths");
+        long long pairs = 0;
+        for (int q = 0; q < nb; q++) {
+            const int k0 = fptr[q], k1 = fptr[q + 1];
+            if (k0 >= k1) continue;
+            const int last = k1 - 1;
+            auto touch = [&](long long at) { // one read of fcol[at] and mate[at], and the loads they lead to
+                if (at < 0 || at >= nL) return false;
+                const int j = fcol[at], m = D.mate[at];
+                return j >= 0 && j < nb && m >= -1 && std::max(m, 0) < std::max<long long>(nU, 1);
+            };
+            EXPECT(touch(k0) && touch(std::min(k0 + 1, last)), "position %d: the reads ahead of the loop leave the tables", q);
+            for (int lk = k0; lk < k1; lk++) {
+                EXPECT(touch(std::min(lk + 2, last)), "position %d: the read two blocks ahead of block %d leaves the tables", q, lk);
+                pairs += D.mate[lk] >= 0;
+            }
+        }
+        EXPECT(pairs == D.pivot_pairs, "pivot_pairs");
+        std::vector<char> seen((size_t)total, 0);
+        for (int h : D.gather) EXPECT(h >= 0 && h < total && !seen[h]++, "gather names block %d twice, or no block of the caller's", h);
+        // teeth
+        long long km = -1;
+        for (long long k = 0; k < nL && km < 0; k++)
+            if (D.mate[k] >= 0) km = k;
+        if (km >= 0 && nU >= 2) {
+            Dilu4DevPlan C(D);
+            C.mate[km] += C.mate[km] + 1 < nU ? 1 : -1;
+            planted++, caught += !dilu4dev_check(S, C, src).empty();
+        }
+        if (total >= 2) {
+            Dilu4DevPlan C(D);
+            C.gather[total - 1] = C.gather[0];
+            planted++, caught += !dilu4dev_check(S, C, src).empty();
+        }
+        if (nb >= 2) {
+            Dilu4DevPlan C(D);
+            std::swap(C.fpos[0], C.fpos[nb - 1]);
+            planted++, caught += !dilu4dev_check(S, C, src).empty();
+        }
+    }
+}
+
 // widths: the level sizes the pattern must have at fill 0 (forward; reversed backward), or empty
 static void check(const char* name, Rows rows, int fill, const std::vector<int>& widths = {})
 {
@@ -164,6 +238,7 @@ static void check(const char* name, Rows rows, int fill, const std::vector<int>&
         EXPECT(v1.empty() || !memcmp(v1.data(), vt.data(), sizeof(double) * v1.size()), "the factor differs between 1 and %d threads", threads);
     }
     if (fill == 0) check_dilu(name, S, ptr, col, coef, widths);
+    if (fill == 0) check_dilu_dev(name, S, ptr, col, rng);
 
     // the device refactor's plan
     Bilu4DevPlan D;
@@ -238,6 +313,27 @@ int main()
     const std::vector<std::vector<int>> layers = {{1}, {63}, {64}, {65}, {129}, {1, 63, 64, 65, 1, 1, 128, 129, 2, 63, 64, 200, 1}, {63, 64, 63, 64, 65, 63}, {129, 1, 129}};
     for (const std::vector<int>& w : layers)
         for (int extra : {0, 3}) check("layered", layered(w, extra, rng), 0, w), patterns++;
+    // fill 0 only, for the DILU device plan: a strictly lower pattern (L blocks, no U block), and symmetric patterns that lost a fifth of
+    // their off-diagonal blocks one by one, so that some (i, j) have no (j, i)
+    Rows lower(150);
+    for (int i = 1; i < 150; i++)
+        for (int e = 0; e < 3; e++) lower[i].push_back((int)(rng() % i));
+    check("lower only", lower, 0), patterns++;
+    for (int it = 0; it < 12; it++, patterns++) {
+        const int nb = 2 + (int)(rng() % 300), band = 1 + (int)(rng() % 12);
+        std::vector<std::pair<int, int>> blocks;
+        for (int i = 0; i < nb; i++)
+            for (int e = 0; e < 3; e++) {
+                const int j = i - band + (int)(rng() % (2 * band + 1));
+                if (j >= 0 && j < nb && j != i) blocks.push_back({i, j}), blocks.push_back({j, i});
+            }
+        Rows rows(nb);
+        for (const auto& b : blocks)
+            if (rng() % 5) rows[b.first].push_back(b.second);
+        check("dropped mates", rows, 0);
+    }
+    if (planted != caught) bad++;
+    printf("DILU device plans %d teeth planted %d caught %d\n", dilu_plans, planted, caught);
     printf("block ILU plans: patterns %d bad %d\n", patterns, bad);
     return bad != 0;
 }
